@@ -12,6 +12,11 @@ protocol, one host sync per iteration for the loss dict).
 
 metric: env-steps/s for the whole job = n_gpus * N * T * steps / wall time (max over ranks).
 Prints ONE JSON line on rank 0 (see the contract in the task statement).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (value, ms_per_step, the phase times).
+--full adds what the headline does not need: per-kernel event times and the roofline, the all-reduce times and replica
+checksums at N > 1, the asynchronous / ingest / nav legs and the CPU baseline.  --dump-outputs DIR writes the results of
+the last timed step as .npy files (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -944,6 +949,31 @@ def build_net(n_envs, horizon, iters, max_batch=None):
                       max_batch=max_batch if max_batch is not None else n_envs * horizon), config_nn
 
 
+DUMP_CAP = {"params": 1 << 22}   # elements per dumped array (default 1 << 20): the whole dump stays under 64 MB at any --envs / --horizon
+
+
+def dump_outputs(out_dir, hp, ro):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (float32, the dtype the path computes in).
+    The rollout: `values` [T+1, N] (row T = the bootstrap forward), `actions` and `logps` [T+1, N], `probs` [N, A] of the bootstrap
+    forward; GAE: `advantages` and `returns` [T, N]; the PPO update: `params` (the flat parameter arena after the last Adam step) and
+    the statistics of its last iteration (`ActorLoss`, `VLoss`, `EntLoss`, `PpoTotalLoss`, `GradNorm`, `ClipCoef`, one element each).
+    An array with more elements than its DUMP_CAP is cut to a fixed sample of its flattened elements (seeded: the same indices for
+    the same shape), and the file is then named <name>_sample.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"values": ro.values, "actions": ro._actions, "logps": ro._logps, "probs": ro._probs,
+              "advantages": ro.adv, "returns": ro.ret, "params": hp.params}
+    stats = hp.grads[hp.n_params:hp.n_params + 6]
+    for i, k in enumerate(("ActorLoss", "VLoss", "EntLoss", "PpoTotalLoss", "GradNorm", "ClipCoef")):   # HotPath.stats() order
+        arrays[k] = stats[i:i + 1]
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        cap = DUMP_CAP.get(name, 1 << 20)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start N rank processes -- fresh interpreters, one per GPU, RCCL ("nccl")
     between them -- BEFORE this process makes any GPU call (it never does: a process that has initialised the GPU must not be
@@ -1037,10 +1067,16 @@ def main():
     ap.add_argument("--envs", type=int, default=256, help="envs per GPU (BASELINE config 2/3)")
     ap.add_argument("--horizon", type=int, default=256, help="TIME_MAX")
     ap.add_argument("--iters", type=int, default=10, help="TRAINING_ITER_TIME")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-async", action="store_true", help="skip the asynchronous actor/learner leg")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the leg that feeds the frames through the pinned-host ring")
-    ap.add_argument("--no-nav", action="store_true", help="skip the robot_nav (BASELINE config 4 network) sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel HIP-event times and the roofline (event "
+                         "records around every training launch in the timed steps, a separate pass for the acting launches), the "
+                         "all-reduce times and replica checksums (N > 1), the asynchronous / ingest / nav legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-async", action="store_true", help="--full without the asynchronous actor/learner leg")
+    ap.add_argument("--no-ingest", action="store_true", help="--full without the leg that feeds the frames through the pinned-host ring")
+    ap.add_argument("--no-nav", action="store_true", help="--full without the robot_nav (BASELINE config 4 network) sub-record")
     ap.add_argument("--no-nav-loop", action="store_true", help="nav sub-record without the whole loop at config 4's size (about 10 s)")
     ap.add_argument("--ingest-memcpy", action="store_true", help="ingest leg: the producer also copies 7.2 MB per step into the slot")
     ap.add_argument("--preflight", action="store_true",
@@ -1083,7 +1119,9 @@ def main():
     hp = net.hot_path
     broadcast_params(hp.params)
     hp.params_changed()
-    hp.profile(True)
+    full = args.full
+    if full:
+        hp.profile(True)
 
     # ---- synthetic rollout inputs, resident in HBM before the timed region ----
     ro = DeviceRollout(net, N, horizon=T, gamma=config_nn.EXTRINSIC_DISCOUNT, landa=config_nn.LANDA, seed=rank * 1000003)
@@ -1120,14 +1158,16 @@ def main():
     for _ in range(args.warmup):
         one_step(False)
     torch.cuda.synchronize()
-    hp.profile(False)
-    hp.profile_read()
-    # Reset the accumulators: per-kernel times cover the timed region only.  The training kernels (ms each) are
-    # timed live; the acting launches (10-40 us each, 1,285 per rollout) are NOT -- event records around them cost
-    # about as much as they do (measured: 44.5 -> 34.6 ms per rollout without) -- they get their own pass below.
-    hp.profile(True, acting=False)
+    if full:
+        hp.profile(False)
+        hp.profile_read()
+        # Reset the accumulators: per-kernel times cover the timed region only.  The training kernels (ms each) are
+        # timed live; the acting launches (10-40 us each, 1,285 per rollout) are NOT -- event records around them cost
+        # about as much as they do (measured: 44.5 -> 34.6 ms per rollout without) -- they get their own pass below.
+        hp.profile(True, acting=False)
+        if world > 1:
+            hp.time_allreduce(True)
     if world > 1:
-        hp.time_allreduce(True)
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -1149,117 +1189,120 @@ def main():
         per_rank = [float(t.item()) for t in allr]
         elapsed = max(per_rank)
     stats = hp.stats()
-    # N > 1: the run proves its own replicas.  Every rank's parameters after the timed updates as a 64-bit checksum (the fp32 bit
-    # patterns summed as integers) and its step count, gathered on all ranks: clip + Adam run on every rank from the SAME reduced
-    # gradient, so the replicas must be bit-identical (the reference has no multi-GPU path to compare with,
-    # server/backward.py:167).  A collective that dropped or re-ordered a contribution on one rank shows up here.
-    replicas = None
-    if world > 1:
-        on_dev = dist.get_backend() == "nccl"
-        mine = torch.stack([hp.params.view(torch.int32).to(torch.int64).sum(), torch.tensor(hp.step, dtype=torch.int64, device=dev)])
-        mine = mine if on_dev else mine.cpu()
-        allc = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allc, mine)
-        sums, stepsr = [int(t[0].item()) for t in allc], [int(t[1].item()) for t in allc]
-        replicas = {"identical": len(set(sums)) == 1 and len(set(stepsr)) == 1, "param_checksums": ["%016x" % (c & (2 ** 64 - 1)) for c in sums],
-                    "optimizer_steps": stepsr}
-    ar_ms = hp.allreduce_ms() if world > 1 else []
-    hp.time_allreduce(False)
-    prof = hp.profile_read()
-    # per-kernel times of the acting launches: a separate, untimed pass of 64 forwards with events around them
-    hp.profile(False)
-    hp.profile(True, acting=True)
-    for t in range(min(T, 64)):
-        ro.act(t)
-    torch.cuda.synchronize()
-    hp.profile(False)
-    for k, v in hp.profile_read().items():
-        prof.setdefault(k, v)
+    if args.dump_outputs and rank == 0:   # before anything else runs on the rollout / arena: the last timed step's results
+        dump_outputs(args.dump_outputs, hp, ro)
+    replicas, ar_ms, prof = None, [], {}
+    if full:
+        # N > 1: the run proves its own replicas.  Every rank's parameters after the timed updates as a 64-bit checksum (the fp32 bit
+        # patterns summed as integers) and its step count, gathered on all ranks: clip + Adam run on every rank from the SAME reduced
+        # gradient, so the replicas must be bit-identical (the reference has no multi-GPU path to compare with,
+        # server/backward.py:167).  A collective that dropped or re-ordered a contribution on one rank shows up here.
+        if world > 1:
+            on_dev = dist.get_backend() == "nccl"
+            mine = torch.stack([hp.params.view(torch.int32).to(torch.int64).sum(), torch.tensor(hp.step, dtype=torch.int64, device=dev)])
+            mine = mine if on_dev else mine.cpu()
+            allc = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allc, mine)
+            sums, stepsr = [int(t[0].item()) for t in allc], [int(t[1].item()) for t in allc]
+            replicas = {"identical": len(set(sums)) == 1 and len(set(stepsr)) == 1, "param_checksums": ["%016x" % (c & (2 ** 64 - 1)) for c in sums],
+                        "optimizer_steps": stepsr}
+        ar_ms = hp.allreduce_ms() if world > 1 else []
+        hp.time_allreduce(False)
+        prof = hp.profile_read()
+        # per-kernel times of the acting launches: a separate, untimed pass of 64 forwards with events around them
+        hp.profile(False)
+        hp.profile(True, acting=True)
+        for t in range(min(T, 64)):
+            ro.act(t)
+        torch.cuda.synchronize()
+        hp.profile(False)
+        for k, v in hp.profile_read().items():
+            prof.setdefault(k, v)
 
     if rank == 0:
         steps = args.steps
         env_steps = world * N * T * steps
         value = env_steps / elapsed
-        kernels = {}
-        for k, (ms, calls) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
-            ent = {"ms_total": round(ms, 3), "calls": calls, "ms_avg": round(ms / max(calls, 1), 4)}
-            base = k[:-4] if k.endswith(".act") else k
-            if base in MAC:
-                # training launches process B samples each, acting launches (".act", FcFwdSplit) N samples
-                per_launch = 2 * 2 * MAC[base] * (N if k.endswith(".act") else B)
-                ent["tflops"] = round(per_launch * calls / (ms * 1e-3) / 1e12, 2)
-                ent["flop_per_launch"] = per_launch
-                if k in PIPE:
-                    pipe, products = PIPE[k]
-                    ent["pipe"] = pipe
-                    ent["pipe_ceiling_tflops"] = round(PEAK_BF16_MFMA_TFLOPS / products, 1)
-                    ent["frac_of_pipe_ceiling"] = round(ent["tflops"] / (PEAK_BF16_MFMA_TFLOPS / products), 4)
-                    ent["executed_over_algorithmic"] = executed_over_algorithmic(k)
-            elif k == "ActConvs":
-                # conv1 + conv2 + conv3 of an acting forward in one launch (csrc/act.hip), N samples
-                per_launch = 2 * 2 * (MAC["ConvFwd1"] + MAC["ConvFwd2"] + MAC["ConvFwd3"]) * N
-                ent["tflops"] = round(per_launch * calls / (ms * 1e-3) / 1e12, 2)
-                ent["flop_per_launch"] = per_launch
-            elif k in HBM_BYTES:
-                # HBM-bound kernels: algorithmic bytes per launch / launch time
-                per_launch = HBM_BYTES[k](N, B, hp.n_params)
-                ent["gbps"] = round(per_launch * calls / (ms * 1e-3) / 1e9, 1)
-                ent["bytes_per_launch"] = per_launch
-                ent["frac_of_hbm_peak"] = round(ent["gbps"] / PEAK_HBM_GBPS, 4)
-            kernels[k] = ent
-        # dominant kernel = largest accumulated time among the GEMM-shaped kernels
-        gemm = {k: v for k, v in kernels.items() if k in MAC}
-        roofline = None
-        if gemm:
-            dom = max(gemm, key=lambda k: gemm[k]["ms_total"])
-            d = gemm[dom]
-            pipe, products = PIPE.get(dom, ("f32", None))
-            peak = PEAK_BF16_MFMA_TFLOPS / products if products else PEAK_F32_MFMA_TFLOPS
-            td = pmc_traffic(dom)
-            # the committed PMC passes ran at their own batch (65,536); a run at another B scales the per-launch bytes linearly
-            tscale = (B / float(td["measured_on"]["batch"])) if td else 1.0
-            tbytes = td["hbm_bytes_per_launch_corrected"] * tscale if td else None
-            roofline = {"kernel": dom, "bound": "mfma", "achieved": d["tflops"], "peak": round(peak, 1),
-                        "unit": "TFLOP/s", "frac": round(d["tflops"] / peak, 4),
-                        # HBM bytes per launch from the PMC passes WITH the guide's gfx950 correction (FETCH_SIZE counts wide streaming
-                        # reads at half their bytes: 2 x FETCH_SIZE + WRITE_SIZE); the uncorrected sum is in traffic_detail
-                        "traffic": tbytes, "traffic_scaled_by_batch": round(tscale, 6),
-                        # traffic is NOT measured by this run (bench.py never profiles): it is the newest committed PMC summary that holds
-                        # the kernel, dated here -- its build, and whether the kernel's source file has changed since (evidence_age)
-                        "traffic_build": td["traffic_build"] if td else None, "traffic_stale": td["traffic_stale"] if td else None,
-                        "traffic_detail": td,
-                        # what actually binds the update: the socket's power cap (committed hwmon trace of a bench run)
-                        "power": power_evidence(),
-                        "mix_model": mix_model(dom, d["ms_avg"] / tscale),
-                        "avg_launch_ms": d["ms_avg"], "launches": d["calls"],
-                        # the HBM side of the same kernel (north_star asks for the HBM fraction): corrected PMC bytes per launch /
-                        # this run's launch time / 8 TB/s
-                        "hbm_bytes_per_launch_corrected": tbytes,
-                        "hbm_frac": round(tbytes / (d["ms_avg"] * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4) if td else None,
-                        "algorithmic_bytes_per_launch": ALG_BYTES[dom](B) if dom in ALG_BYTES else None,
-                        "algorithmic_flop_per_launch": d["flop_per_launch"], "pipe": pipe,
-                        "executed_over_algorithmic": executed_over_algorithmic(dom),
-                        "note": "dominant training kernel (largest accumulated time).  achieved = ALGORITHMIC fp32 FLOP (2*2*MAC per "
-                                "sample, both encoders, x B) / launch time from HIP events on the launch stream; peak = the ceiling of the "
-                                "pipe the kernel runs on: dense 16-bit MFMA 2.5 PFLOP/s / plane products (3 for two fp32 operands as two "
-                                "scaled fp16 planes each, 2 when one operand -- the pixels -- is exact in fp16), or the "
-                                "f32-input MFMA peak 157.3"}
-            # every GEMM kernel against ITS pipe's ceiling, and the time-weighted mean over the training kernels
-            tw = sum(v["ms_total"] for k, v in gemm.items() if "frac_of_pipe_ceiling" in v)
-            if tw > 0:
-                roofline["time_weighted_frac_all_gemm_kernels"] = round(
-                    sum(v["ms_total"] * v["frac_of_pipe_ceiling"] for v in gemm.values() if "frac_of_pipe_ceiling" in v) / tw, 4)
         upd_ms = phase["update_ms"] / steps
-        it_bytes = iteration_traffic()
-        if roofline is not None and it_bytes:
-            it_bytes *= roofline["traffic_scaled_by_batch"]
-            roofline["iteration_hbm_bytes_corrected"] = round(it_bytes)
-            roofline["iteration_hbm_frac"] = round(it_bytes / (upd_ms / ITERS * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4)
-            roofline["iteration_algorithmic_bytes"] = 28296 * B     # frames re-read + loss operands per sample
+        kernels, roofline = {}, None
+        if full:   # per-kernel figures from the events of the timed steps and the acting pass, priced against their roofline
+            for k, (ms, calls) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
+                ent = {"ms_total": round(ms, 3), "calls": calls, "ms_avg": round(ms / max(calls, 1), 4)}
+                base = k[:-4] if k.endswith(".act") else k
+                if base in MAC:
+                    # training launches process B samples each, acting launches (".act", FcFwdSplit) N samples
+                    per_launch = 2 * 2 * MAC[base] * (N if k.endswith(".act") else B)
+                    ent["tflops"] = round(per_launch * calls / (ms * 1e-3) / 1e12, 2)
+                    ent["flop_per_launch"] = per_launch
+                    if k in PIPE:
+                        pipe, products = PIPE[k]
+                        ent["pipe"] = pipe
+                        ent["pipe_ceiling_tflops"] = round(PEAK_BF16_MFMA_TFLOPS / products, 1)
+                        ent["frac_of_pipe_ceiling"] = round(ent["tflops"] / (PEAK_BF16_MFMA_TFLOPS / products), 4)
+                        ent["executed_over_algorithmic"] = executed_over_algorithmic(k)
+                elif k == "ActConvs":
+                    # conv1 + conv2 + conv3 of an acting forward in one launch (csrc/act.hip), N samples
+                    per_launch = 2 * 2 * (MAC["ConvFwd1"] + MAC["ConvFwd2"] + MAC["ConvFwd3"]) * N
+                    ent["tflops"] = round(per_launch * calls / (ms * 1e-3) / 1e12, 2)
+                    ent["flop_per_launch"] = per_launch
+                elif k in HBM_BYTES:
+                    # HBM-bound kernels: algorithmic bytes per launch / launch time
+                    per_launch = HBM_BYTES[k](N, B, hp.n_params)
+                    ent["gbps"] = round(per_launch * calls / (ms * 1e-3) / 1e9, 1)
+                    ent["bytes_per_launch"] = per_launch
+                    ent["frac_of_hbm_peak"] = round(ent["gbps"] / PEAK_HBM_GBPS, 4)
+                kernels[k] = ent
+            # dominant kernel = largest accumulated time among the GEMM-shaped kernels
+            gemm = {k: v for k, v in kernels.items() if k in MAC}
+            if gemm:
+                dom = max(gemm, key=lambda k: gemm[k]["ms_total"])
+                d = gemm[dom]
+                pipe, products = PIPE.get(dom, ("f32", None))
+                peak = PEAK_BF16_MFMA_TFLOPS / products if products else PEAK_F32_MFMA_TFLOPS
+                td = pmc_traffic(dom)
+                # the committed PMC passes ran at their own batch (65,536); a run at another B scales the per-launch bytes linearly
+                tscale = (B / float(td["measured_on"]["batch"])) if td else 1.0
+                tbytes = td["hbm_bytes_per_launch_corrected"] * tscale if td else None
+                roofline = {"kernel": dom, "bound": "mfma", "achieved": d["tflops"], "peak": round(peak, 1),
+                            "unit": "TFLOP/s", "frac": round(d["tflops"] / peak, 4),
+                            # HBM bytes per launch from the PMC passes WITH the guide's gfx950 correction (FETCH_SIZE counts wide streaming
+                            # reads at half their bytes: 2 x FETCH_SIZE + WRITE_SIZE); the uncorrected sum is in traffic_detail
+                            "traffic": tbytes, "traffic_scaled_by_batch": round(tscale, 6),
+                            # traffic is NOT measured by this run (bench.py never profiles): it is the newest committed PMC summary that holds
+                            # the kernel, dated here -- its build, and whether the kernel's source file has changed since (evidence_age)
+                            "traffic_build": td["traffic_build"] if td else None, "traffic_stale": td["traffic_stale"] if td else None,
+                            "traffic_detail": td,
+                            # what actually binds the update: the socket's power cap (committed hwmon trace of a bench run)
+                            "power": power_evidence(),
+                            "mix_model": mix_model(dom, d["ms_avg"] / tscale),
+                            "avg_launch_ms": d["ms_avg"], "launches": d["calls"],
+                            # the HBM side of the same kernel (north_star asks for the HBM fraction): corrected PMC bytes per launch /
+                            # this run's launch time / 8 TB/s
+                            "hbm_bytes_per_launch_corrected": tbytes,
+                            "hbm_frac": round(tbytes / (d["ms_avg"] * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4) if td else None,
+                            "algorithmic_bytes_per_launch": ALG_BYTES[dom](B) if dom in ALG_BYTES else None,
+                            "algorithmic_flop_per_launch": d["flop_per_launch"], "pipe": pipe,
+                            "executed_over_algorithmic": executed_over_algorithmic(dom),
+                            "note": "dominant training kernel (largest accumulated time).  achieved = ALGORITHMIC fp32 FLOP (2*2*MAC per "
+                                    "sample, both encoders, x B) / launch time from HIP events on the launch stream; peak = the ceiling of the "
+                                    "pipe the kernel runs on: dense 16-bit MFMA 2.5 PFLOP/s / plane products (3 for two fp32 operands as two "
+                                    "scaled fp16 planes each, 2 when one operand -- the pixels -- is exact in fp16), or the "
+                                    "f32-input MFMA peak 157.3"}
+                # every GEMM kernel against ITS pipe's ceiling, and the time-weighted mean over the training kernels
+                tw = sum(v["ms_total"] for k, v in gemm.items() if "frac_of_pipe_ceiling" in v)
+                if tw > 0:
+                    roofline["time_weighted_frac_all_gemm_kernels"] = round(
+                        sum(v["ms_total"] * v["frac_of_pipe_ceiling"] for v in gemm.values() if "frac_of_pipe_ceiling" in v) / tw, 4)
+            it_bytes = iteration_traffic()
+            if roofline is not None and it_bytes:
+                it_bytes *= roofline["traffic_scaled_by_batch"]
+                roofline["iteration_hbm_bytes_corrected"] = round(it_bytes)
+                roofline["iteration_hbm_frac"] = round(it_bytes / (upd_ms / ITERS * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4)
+                roofline["iteration_algorithmic_bytes"] = 28296 * B     # frames re-read + loss operands per sample
         total_flop = env_steps / world * (FLOP_ACT_PER_STEP + ITERS * FLOP_TRAIN_PER_SAMPLE)
         out = {
             "metric": "env-steps/sec (whole node) + PPO update ms, Pong 256 envs at 1/2/4/8 GPUs",
-            "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
+            "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": args.warmup, "full": full,
             "ms_per_step": round(elapsed / steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
             # median + p95 over the timed steps (rank 0's own steps; `value` stays total work / total time)
             "step_ms": {"median": round(float(np.median(step_ms)), 3), "p95": round(float(np.percentile(step_ms, 95)), 3),
@@ -1283,22 +1326,9 @@ def main():
             "acting_ms_per_rollout": round(phase["act_ms"] / steps, 2), "gae_ms": round(phase["gae_ms"] / steps, 4),
             "acting_env_steps_per_s_per_gpu": round(N * (T + 1) / (phase["act_ms"] / steps * 1e-3), 1),
             # fp32-equivalent (algorithmic) work of the whole step per second.  NOT a roofline fraction: the GEMM kernels run on
-            # the bf16 matrix pipe (fp32-accurate plane products); each kernel's fraction of its pipe's ceiling is in `kernels`
+            # the bf16 matrix pipe (fp32-accurate plane products); each kernel's fraction of its pipe's ceiling is in `kernels` (--full)
             "whole_step_tflops_per_gpu": round(total_flop / elapsed / 1e12, 2),
-            # section 8e: one SUM all-reduce of the 13,487,420-byte gradient arena (+ loss tail) per PPO iteration, bracketed by
-            # events on the compute stream of rank 0 (includes waiting for the slowest rank to arrive)
-            "allreduce": None if world == 1 else {
-                "bytes": int(hp.grads.numel() * 4), "calls": len(ar_ms), "ms_avg": round(float(np.mean(ar_ms)), 4),
-                "ms_p50": round(float(np.median(ar_ms)), 4), "ms_max": round(float(np.max(ar_ms)), 4),
-                "ms_per_update": round(float(np.sum(ar_ms)) / steps, 3), "backend": dist.get_backend(),
-                "rccl_version": _rccl_version(), "path": ("ddrl_comm (C ABI, csrc/comm.cpp)" if hp.comm is not None else "torch.distributed"),
-                # overlapped = layer buckets reduced on a second stream under the rest of the backward: the span above is then the
-                # EXPOSED part (what the compute stream waited for before clip + Adam)
-                "overlapped_with_backward": bool(hp._overlap), "exposed_ms_per_iteration": round(float(np.mean(ar_ms)), 4),
-                "algbw_gbps": round(hp.grads.numel() * 4 / (float(np.median(ar_ms)) * 1e-3) / 1e9, 2)},
-            "replicas_identical": None if replicas is None else replicas["identical"], "replicas": replicas,
             "last_losses": dict(stats, **{k: v for k, v in last.items() if k != "PpoBackUpTime"}),
-            "roofline": roofline, "kernels": kernels,
             "dtype_note": "fp32 operands in HBM, fp32 accumulation; every operand enters the 16-bit MFMA as TWO scaled fp16 planes (22 bits, not "
                           "24) and the three plane products that matter are summed in fp32 (f16x3; conv1's forward and weight gradient: "
                           "exact-fp16 pixels 0..255 x two planes of the other operand, f16x2).  Measured against float64: every parameter "
@@ -1309,16 +1339,32 @@ def main():
                           "a float64 step by 1.1-2 x what an fp32 evaluation's does (tests/golden/margins.json __vs_onednn_only: up to "
                           "1.74).  'tflops' is fp32-equivalent (algorithmic) work; acting launches of at most 512 envs run conv1-conv3 in "
                           "one kernel (csrc/act.hip), same arithmetic",
-            "kernel_timing": "training kernels: HIP events around every launch inside the timed region; acting launches "
-                             "(ActConvs, FcFwdSplit, heads_act): a separate, untimed pass of 64 forwards after it",
         }
-        if world == 1 and not args.no_async:
+        if full:
+            out.update({
+                # section 8e: one SUM all-reduce of the 13,487,420-byte gradient arena (+ loss tail) per PPO iteration, bracketed by
+                # events on the compute stream of rank 0 (includes waiting for the slowest rank to arrive)
+                "allreduce": None if world == 1 else {
+                    "bytes": int(hp.grads.numel() * 4), "calls": len(ar_ms), "ms_avg": round(float(np.mean(ar_ms)), 4),
+                    "ms_p50": round(float(np.median(ar_ms)), 4), "ms_max": round(float(np.max(ar_ms)), 4),
+                    "ms_per_update": round(float(np.sum(ar_ms)) / steps, 3), "backend": dist.get_backend(),
+                    "rccl_version": _rccl_version(), "path": ("ddrl_comm (C ABI, csrc/comm.cpp)" if hp.comm is not None else "torch.distributed"),
+                    # overlapped = layer buckets reduced on a second stream under the rest of the backward: the span above is then the
+                    # EXPOSED part (what the compute stream waited for before clip + Adam)
+                    "overlapped_with_backward": bool(hp._overlap), "exposed_ms_per_iteration": round(float(np.mean(ar_ms)), 4),
+                    "algbw_gbps": round(hp.grads.numel() * 4 / (float(np.median(ar_ms)) * 1e-3) / 1e9, 2)},
+                "replicas_identical": None if replicas is None else replicas["identical"], "replicas": replicas,
+                "roofline": roofline, "kernels": kernels,
+                "kernel_timing": "training kernels: HIP events around every launch inside the timed region; acting launches "
+                                 "(ActConvs, FcFwdSplit, heads_act): a separate, untimed pass of 64 forwards after it",
+            })
+        if full and world == 1 and not args.no_async:
             hp.profile(False)
             try:
                 out["async_actor_learner"] = async_actor_leg(net, config_nn, N, T, ITERS, dev)
             except Exception as e:  # an extra, never allowed to take the headline line down
                 out["async_actor_learner"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_ingest:
+        if full and world == 1 and not args.no_ingest:
             hp.profile(False)
             try:
                 # the section-8d(i)/(iv) figure: H2D of every acting step inside the timed region, overlapped with the learner
@@ -1334,7 +1380,7 @@ def main():
                 out["with_ingest_serial"] = ingest_leg(net, ro, N, T, host_memcpy=args.ingest_memcpy)
             except Exception as e:
                 out["with_ingest_serial"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_nav:
+        if full and world == 1 and not args.no_nav:
             try:
                 out["nav"] = nav_leg(whole_loop=not args.no_nav_loop)
                 out["config"].update(nav_ppo_iter_ms=out["nav"]["ppo_iter_ms"], nav_samples_per_s=out["nav"]["samples_per_s"],
@@ -1343,7 +1389,7 @@ def main():
                                      nav_whole_loop_env_steps_per_s=(out["nav"]["whole_loop"] or {}).get("env_steps_per_s"))
             except Exception as e:
                 out["nav"] = {"error": repr(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     hp.close()

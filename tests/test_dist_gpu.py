@@ -196,7 +196,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "1",
-                          "--envs", "32", "--horizon", "16", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--envs", "32", "--horizon", "16", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -223,7 +223,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it():
     env.update(DDRL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--envs", "32", "--horizon", "16", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--envs", "32", "--horizon", "16", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -292,7 +292,7 @@ def test_bench_single_gpu_line_has_its_legs():
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--envs", "32", "--horizon", "16",
-                          "--no-cpu-baseline", "--no-nav"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-nav"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -319,6 +319,40 @@ def test_bench_single_gpu_line_has_its_legs():
     assert isinstance(r["mix_model"], dict) and "error" not in r["mix_model"] and r["mix_model"]["model_ms"] > 0
     sm = d["step_ms"]
     assert sm["n"] == 2 and 0 < sm["min"] <= sm["median"] <= sm["p95"] <= sm["max"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line only, with K timed steps, and --dump-outputs writes the last timed
+    step's results as float32 .npy files; a second run with the same arguments starts from identical inputs (same actions sampled in
+    the same rollout, same parameters before the update), so every dumped array agrees to the rounding of reordered sums."""
+    import json
+    root = os.path.dirname(HERE)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    N, T = 32, 16
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / ("out%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--envs", str(N),
+                              "--horizon", str(T), "--dump-outputs", str(d_out)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["step_ms"]["n"] == 3 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in d, k
+        for k in ("kernels", "roofline", "with_ingest", "async_actor_learner", "nav", "cpu_baseline"):
+            assert k not in d, k
+        got = {p.stem: np.load(p) for p in d_out.glob("*.npy")}
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 for a in got.values())
+        assert got["values"].shape == (T + 1, N) and got["advantages"].shape == (T, N) and got["probs"].shape == (N, 6)
+        assert got["params"].ndim == 1 and np.isfinite(got["params"]).all() and got["PpoTotalLoss"].shape == (1,)
+        dumps.append(got)
+    assert dumps[0].keys() == dumps[1].keys()
+    assert np.array_equal(dumps[0]["actions"], dumps[1]["actions"])
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-4, atol=1e-5, err_msg=k)
 
 
 @pytest.mark.parametrize("gpus", [1, 2])

@@ -1,6 +1,6 @@
 """Same-box A/B of whole bench steps with a given build of the library:
     python tools/ab_bench.py tools/_scratch_abl/<name>.so
-runs `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-async` on that build and prints one line (env-steps/s,
+runs `bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-async` on that build and prints one line (env-steps/s,
 ms per PPO iteration, acting ms per rollout, per-kernel ms).  Alternate builds in one gpurun call (A B A B):
 profiles/r01_v7_same_box_ab.txt and r01_v8_same_box_ab.txt were made this way."""
 import contextlib
@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddrl4nav_amd import _lib  # noqa: E402
 
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
-sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-async"]
+sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-async"]
 import bench  # noqa: E402
 
 buf = io.StringIO()
