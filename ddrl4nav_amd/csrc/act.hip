@@ -1,4 +1,4 @@
-// The three convolutions of an ACTING forward (ddrl_forward, n <= DDRL_ACT_FUSED_MAX) in ONE launch.
+// The three convolutions of an ACTING forward (ddrl_forward, n <= ACT_FUSED_MAX) in ONE launch.
 //
 // Reference: AtariPreNet.forward (nn/atari_encoder.py:25-32) inside ForwardThread.run (server/forward.py:128-149): a few hundred
 // samples per call, latency-bound.  The training kernels of conv2.hip tile the BATCH (3-5 samples per workgroup, k loop of 8-16
@@ -33,16 +33,7 @@
 // stores them for the tests that look at them.
 #include "engine2.h"
 
-#ifndef DDRL_ACT_STOP
-#define DDRL_ACT_STOP 0  // timing-only: 1 = return after the staging barrier, 2 = after conv1, 3 = after conv2 (results are WRONG)
-#endif
-
 namespace ddrl {
-
-#ifdef DDRL_PLANES_BF16
-// three bf16 planes per operand do not fit this kernel's LDS budget: DDRL_ACT_FUSED_MAX is 0 in that build (kernels.h) and nothing calls in here
-void launch_act_convs(const EncCall&, hipStream_t) { abort(); }
-#else
 
 using u4a = __attribute__((ext_vector_type(4))) unsigned;
 struct __attribute__((packed, aligned(4))) lds_pair {
@@ -150,11 +141,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
   for (int ch = 0; ch < 4; ++ch) *(u4a*)(lds + K::W1_OFF + (ch * 512 + tid) * 16) = w1r[ch];
   __syncthreads();
-  if (DDRL_ACT_STOP == 1) {
-    if (lds[tid] == 77 && w2f[0][0][0][0][0] == (_Float16)3.0f) A.a3max[0] = 1.0f;
-    return;
-  }
-
   // ---------------- phase 1: conv1.  wave w: pixel tiles w and w + 8 (13 tiles of 32 cover the 400 output pixels)
   {
     f32x16 acc[2];
@@ -210,11 +196,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
   }
   __syncthreads();  // a1 planes complete
-  if (DDRL_ACT_STOP == 2) {
-    if (lds[K::A1_OFF + tid] == 77 && w2f[0][0][0][0][0] == (_Float16)3.0f) A.a3max[0] = 1.0f;
-    return;
-  }
-
   // conv3 weights wp3b[e][k-block][tap pair 5][plane][oc][tap parity][8 channels]: k-step s of the wave = (k-block pair 2 kh + s / 5,
   // tap pair s % 5); lane chunk q4 = (k-block parity, tap parity)
   const unsigned short* w3 = A.wp3b + (size_t)e * (8 * 5 * NPL * 64 * 16) + (size_t)(((q4 >> 1) * 5 * NPL * 64 + 32 * mp + l15) * 16 + (q4 & 1) * 8);
@@ -255,7 +236,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const lds_pair lo = *(const lds_pair*)q, up = *(const lds_pair*)(q + K::A1_ROW);
             bq[j][p] = __builtin_bit_cast(frag8, (u4a){lo.x, lo.y, up.x, up.y});
           }
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -327,11 +307,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
   }
   __syncthreads();
-  if (DDRL_ACT_STOP == 3) {
-    if (lds[tid] == 77 && w3f[0][0][0][0][0] == (_Float16)3.0f) A.a3max[0] = 1.0f;
-    return;
-  }
-
   // ---------------- phase 3: conv3.  wave = output channels 32 mp .. (two tiles), k-blocks 4 kh .. 4 kh + 3, column tiles 2 nh, 2 nh + 1
   {
     f4 acc[2][2];
@@ -353,7 +328,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int p = 0; p < NPL; ++p) bq[j][p] = *(const frag8*)(lds + bB[j] + toff + p * K::A2_PLANE);
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -426,14 +400,12 @@ void launch_act_convs(const EncCall& c, hipStream_t st) {
             {L.enc_base[0] + L.enc.c1b, L.enc_base[L.NE - 1] + L.enc.c1b},
             {L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b},
             {L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b},
-            w.a1, w.a2, w.a3, MB * 12800, MB * 5184, MB * FLAT, w.actmax, DDRL_ACT_FUSED_MAX, c.n, L.C, L.NE};
+            w.a1, w.a2, w.a3, MB * 12800, MB * 5184, MB * FLAT, w.actmax, ACT_FUSED_MAX, c.n, L.C, L.NE};
   ProfRange pr(c.prof, "ActConvs", st);
   if (c.keep_acts)
     hipLaunchKernelGGL(act_convs_kernel<true>, dim3((unsigned)c.n, (unsigned)L.NE), dim3(K::THREADS), K::LDS_BYTES, st, a);
   else
     hipLaunchKernelGGL(act_convs_kernel<false>, dim3((unsigned)c.n, (unsigned)L.NE), dim3(K::THREADS), K::LDS_BYTES, st, a);
 }
-
-#endif  // DDRL_PLANES_BF16
 
 }  // namespace ddrl

@@ -222,7 +222,7 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
   Profiler* prof = ctx->profile && ctx->profile_acting ? ctx : nullptr;
   EncCall ec{prof, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n, ctx->cfg.max_batch};
   ec.keep_acts = ctx->keep_acts;
-  ctx->acts_stored = ctx->keep_acts || n > DDRL_ACT_FUSED_MAX;
+  ctx->acts_stored = ctx->keep_acts || n > ACT_FUSED_MAX;
   launch_encoder_forward(ec, true, st);
   HeadsCall hc{&ctx->ws, &ctx->L, &ctx->cfg, ctx->params, n, ctx->cfg.max_batch};
   {

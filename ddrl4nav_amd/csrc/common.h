@@ -151,39 +151,26 @@ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 __host__ __device__ inline int64_t m1_words(int64_t max_batch) { return max_batch * 400; }
 __host__ __device__ inline int m1_bit(int oc) { return ((oc >> 2) & 1) * 16 + 15 - ((oc & 3) + 4 * (oc >> 3)); }
 
-#ifdef DDRL_PLANES_BF16
-#define DDRL_ACT_FUSED_MAX 0    // three bf16 planes do not fit the fused kernel's LDS budget: every acting launch takes the batch-tiled kernels
-#elif !defined(DDRL_ACT_FUSED_MAX)
-#define DDRL_ACT_FUSED_MAX 512  // acting launches of at most this many samples (Workspace::actmax is carved for it)
-#endif
-// split counts for the weight-gradient GEMMs (fixed per context -> deterministic sums)
-#ifndef DDRL_FC_ACT_SPLITS
-#define DDRL_FC_ACT_SPLITS 14  // split-K factor of the dense layer's forward in acting launches: a divisor of its 98 k-blocks
-#endif
+constexpr int ACT_FUSED_MAX = 512;  // acting launches of at most this many samples take the fused kernel (Workspace::actmax is carved for it)
+constexpr int FC_ACT_SPLITS = 14;  // split-K factor of the dense layer's forward in acting launches: a divisor of its 98 k-blocks
 // the fused acting kernel (act.hip) leaves a3's scale as per-sample maxima in Workspace::actmax, which only the SPLIT launch of the
 // dense forward reads (fc2.hip); an unsplit acting launch would read a stale AMAX_A3 slot
-static_assert(DDRL_FC_ACT_SPLITS > 1 && 98 % DDRL_FC_ACT_SPLITS == 0, "DDRL_FC_ACT_SPLITS: a divisor of 98 larger than 1");
-#ifndef DDRL_C1_SPLITS
-#define DDRL_C1_SPLITS 512  // two workgroups per CU in ONE round: 3.37 ms against 3.66 at 768 / 1024 / 1536, 4.1 at 256 / 384 / 640 (profiles/README.md)
-#endif
-#ifndef DDRL_C2_SPLITS
-#define DDRL_C2_SPLITS 256
-#endif
-#ifndef DDRL_C3_SPLITS
-#define DDRL_C3_SPLITS 256
-#endif
+static_assert(FC_ACT_SPLITS > 1 && 98 % FC_ACT_SPLITS == 0, "FC_ACT_SPLITS: a divisor of 98 larger than 1");
+// split counts for the weight-gradient GEMMs (fixed per context -> deterministic sums)
 struct Splits {
   int c1, c2, c3, fc;
 };
 inline Splits choose_splits(int max_batch, int NE = 2) {
+  // conv1: two workgroups per CU in ONE round: 3.37 ms against 3.66 at 768 / 1024 / 1536, 4.1 at 256 / 384 / 640 (profiles/README.md)
+  constexpr int C1_SPLITS = 512, C2_SPLITS = 256, C3_SPLITS = 256;
   // ~1024 workgroups per weight-gradient launch (2 resident per CU x 256 CUs x 2 rounds)
   const int pairs = (max_batch + 1) / 2;
   auto cap = [&](int want, int limit) { return want < limit ? (want < 1 ? 1 : want) : (limit < 1 ? 1 : limit); };
   Splits s;
-  s.c1 = cap(DDRL_C1_SPLITS, pairs);      // 1 column tile, encoders fused
+  s.c1 = cap(C1_SPLITS, pairs);      // 1 column tile, encoders fused
   const int k = 2 / NE;         // one encoder: twice the splits keep the same number of workgroups
-  s.c2 = cap(DDRL_C2_SPLITS * k, pairs);   // 2 column tiles x 2 encoders
-  s.c3 = cap(DDRL_C3_SPLITS * k, pairs);   // conv_wgrad3_planes_kernel: one workgroup per (split, encoder), up to two per CU
+  s.c2 = cap(C2_SPLITS * k, pairs);   // 2 column tiles x 2 encoders
+  s.c3 = cap(C3_SPLITS * k, pairs);   // conv_wgrad3_pipe_kernel: one workgroup per (split, encoder)
   s.fc = cap(5 * k, (max_batch + 31) / 32);  // 25 x 4 tiles x 2 encoders
   return s;
 }
@@ -202,7 +189,7 @@ inline int64_t carve(Workspace& w, const ddrl_config& c, void* base) {
   w.wlb = (unsigned short*)take(2 * 3 * (int64_t)FLAT * FEAT / 2);
   w.wdlb = (unsigned short*)take(2 * 3 * (int64_t)FLAT * FEAT / 2);
   w.amax = take(64);
-  w.actmax = take(2 * (DDRL_ACT_FUSED_MAX > 512 ? DDRL_ACT_FUSED_MAX : 512));  // [2 encoders][DDRL_ACT_FUSED_MAX]
+  w.actmax = take(2 * ACT_FUSED_MAX);  // [2 encoders][ACT_FUSED_MAX]
   w.wp2b = (unsigned short*)take(2 * 32 * 3 * 64 * 16 / 2);
   w.wp3b = (unsigned short*)take(2 * 8 * 5 * 3 * 64 * 16 / 2);
   w.wd2b = (unsigned short*)take(2 * 2 * 4 * 4 * 3 * 64 * 16 / 2);
@@ -232,7 +219,7 @@ inline int64_t carve(Workspace& w, const ddrl_config& c, void* base) {
   if (p3 > pm) pm = p3;
   if (pf > pm) pm = pf;
   // the acting path parks the split-K partial sums of the FC forward here (fc_forward_splits)
-  const int64_t pact = (int64_t)DDRL_FC_ACT_SPLITS * 2 * (MB < 1024 ? MB : 1024) * FEAT;
+  const int64_t pact = (int64_t)FC_ACT_SPLITS * 2 * (MB < 1024 ? MB : 1024) * FEAT;
   if (pact > pm) pm = pact;
   w.wpart_floats = pm;
   w.wpart = take(pm);

@@ -9,7 +9,7 @@
 // Weights arrive pre-split into planes, in exactly the order the k index walks (optim.hip).
 //
 // Reference arithmetic: F.conv2d + F.leaky_relu (USTC_lab/nn/atari_encoder.py:26-28) and the autograd data-gradients of conv3 /
-// conv2 (ppo.py:122-123).  Acting launches of at most DDRL_ACT_FUSED_MAX samples do not come here: act.hip.
+// conv2 (ppo.py:122-123).  Acting launches of at most ACT_FUSED_MAX samples do not come here: act.hip.
 #include "engine2.h"
 
 namespace ddrl {
@@ -17,8 +17,8 @@ namespace ddrl {
 
 // ================================================================================================
 // conv1 forward on the 16-bit matrix pipe, fp32-accurate.  The input pixels are integers 0..255 and therefore EXACT in
-// fp16 (and bf16); the weights come as NPL planes from optim.hip (two scaled fp16 planes whose sum reproduces them to 22
-// bits; -DDDRL_PLANES_BF16: three bf16 planes, 24 bits).  Every product plane x pixel is exact in fp32, the MFMA
+// fp16; the weights come as NPL planes from optim.hip (two scaled fp16 planes whose sum reproduces them to 22
+// bits).  Every product plane x pixel is exact in fp32, the MFMA
 // accumulates in fp32, and the 1/255 of the reference's frame normalisation (and the planes' scale) is applied once to the
 // sum:  z = (sum_k (W0 + W1)[k] x[k]) / (255 S) + b.  Two v_mfma_f32_32x32x16_f16 (32 cycles each) replace eight
 // v_mfma_f32_32x32x2_f32 (64 cycles each).
@@ -27,31 +27,19 @@ namespace ddrl {
 //   pixels of that row (stride-4 convolution: x = 4 ox + kx), i.e. one 16-byte LDS read per operand.
 // The image is kept as 16-bit rows (pitch 176 B) in natural pixel order.
 // ================================================================================================
-using bf8 = __attribute__((ext_vector_type(8))) __bf16;
 using u4v = __attribute__((ext_vector_type(4))) unsigned;
-using bf4 = __attribute__((ext_vector_type(4))) __bf16;
 
-// Timing-only knock-outs (-DDDRL_F1_KO=bits; results are WRONG): 1 no a1 stores, 2 no epilogue at all, 4 no MFMAs, 8 no image
-// conversion / LDS writes, 16 no weight copies
-#ifndef DDRL_F1_KO
-#define DDRL_F1_KO 0
-#endif
-#ifndef DDRL_F1_LDS_PAD
-#define DDRL_F1_LDS_PAD 0  // A/B: 256 restores the two-workgroups-per-CU footprint
-#endif
-#ifndef DDRL_F1_PITCH
-#define DDRL_F1_PITCH 168
-#endif
+// image row pitch 168 B = the 84 pixels of a row, no pad: a 32-pixel column tile reads 20 pixels of one row and 12 of the row 4 below,
+// whose banks (4 x 168 B = 40 words further) follow the first 20 pixels without overlap, and 2 x (16 KB + 10.5 KB) lets THREE workgroups
+// share a CU (at pitch 176 the third missed by 1.4 KB)
+constexpr int F1_PITCH = 168;
 template <int NE>
 struct Fwd1B {
-  // image row pitch 168 B = the 84 pixels of a row, no pad: a 32-pixel column tile reads 20 pixels of one row and 12 of the row 4 below,
-  // whose banks (4 x 168 B = 40 words further) follow the first 20 pixels without overlap, and 2 x (16 KB + 10.5 KB) lets THREE workgroups
-  // share a CU (at pitch 176 the third missed by 1.4 KB)
-  static constexpr int ROWS = 32 * NE, A_BYTES = 4 * NPL * 2 * ROWS * 16, PITCH = DDRL_F1_PITCH, IMG_BYTES = 64 * PITCH;
+  static constexpr int ROWS = 32 * NE, A_BYTES = 4 * NPL * 2 * ROWS * 16, PITCH = F1_PITCH, IMG_BYTES = 64 * PITCH;
   static constexpr int STAGE_BYTES = A_BYTES + IMG_BYTES, AQ = A_BYTES / 16, NAJ = AQ / 256;  // weight quads per thread
   // 54,272 B = 106 allocation units of 512 B: THREE workgroups share a CU's 160 KB (the bias used to sit behind the stages: 54,528 B
   // -> 107 units -> two workgroups).  The epilogue reads the bias from stage 0, which is free by then.
-  static constexpr size_t LDS_BYTES = 2 * STAGE_BYTES + DDRL_F1_LDS_PAD;
+  static constexpr size_t LDS_BYTES = 2 * STAGE_BYTES;
 };
 
 template <int NE>
@@ -109,11 +97,9 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
 #pragma unroll
   for (int j = 0; j < K::NAJ; ++j) woff[j] = (uint32_t)((tid + 256 * j) * 16);
   auto stage_w = [&](int ch, char* st) {
-    if (DDRL_F1_KO & 16) return;
     direct_copy((const char*)wp1b + (size_t)ch * K::A_BYTES, woff, (float*)st, wave, tid, K::AQ);
   };
   auto commit_img = [&](char* st, int ch) {
-    if (DDRL_F1_KO & 8) return;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       if (tid + 256 * j < nd_total) {
@@ -156,10 +142,7 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
 #pragma unroll
         for (int i = 0; i < NE; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (DDRL_F1_KO & 4) acc[i][j][0] += (float)a[i][0] + (float)b[j][0];
-            else acc[i][j] = mfma_planes(a[i], b[j], acc[i][j]);
-          }
+          for (int j = 0; j < 2; ++j) acc[i][j] = mfma_planes(a[i], b[j], acc[i][j]);
       }
     }
     if (ch + 1 < C) {
@@ -175,12 +158,6 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
 #pragma unroll
   for (int i = 0; i < NE; ++i) r255[i] = PIXEL_UNIT / (255.0f * plane_scale(amax[amax_idx(AMAX_W1, i)]));
   // (the scale of a1's planes comes from a bound that pack_weights derives from the weights, common.h AMAX_A1: no maximum here)
-  if (DDRL_F1_KO & 2) {
-    float sum = 0.0f;
-    for (int i = 0; i < NE; ++i) for (int j = 0; j < 2; ++j) for (int r = 0; r < 16; ++r) sum += acc[i][j][r];
-    if (sum == 1.2345f) out[tid] = sum;
-    return;
-  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int c = c0 + wc * 64 + j * 32 + l31;
@@ -197,7 +174,7 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
       for (int r = 0; r < 16; ++r) {
         const int oc = acc_row(r, hi);
         const float y = leaky_f(__builtin_fmaf(acc[i][j][r], r255[i], bias[i * 32 + oc]));  // one rounding less than mul + add
-        if (!(DDRL_F1_KO & 1) || y == 1.2345f) st1_so(base + acc_row(r, 0) * 400, lanep, y);
+        st1_so(base + acc_row(r, 0) * 400, lanep, y);
         // y > 0 <=> its bit pattern, as a signed integer, is >= 1 <=> (pattern -sat 1) has a clear sign; alignbit shifts that sign
         // in: two VALU instructions per output (compare + select + or: three and two s_nop)
         bits = __builtin_amdgcn_alignbit(bits, (unsigned)__builtin_elementwise_sub_sat((int)__float_as_uint(y), 1), 31);
@@ -208,27 +185,20 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv1 forward of a TRAINING launch with the weight planes resident in LDS (-DDDRL_F1_RESIDENT=0: the kernel above for every launch).
+// conv1 forward of a TRAINING launch with the weight planes resident in LDS.
 // conv_fwd1_planes_kernel copies a stacked frame's planes (16 KB) from L2 into LDS for every 256 output pixels: 6.5 GB per launch at
-// B = 65,536, and its timing knock-outs put 0.6 of the kernel's 2.7 ms there.  Here one workgroup per CU keeps all four frames' planes
+// B = 65,536, and timing knock-outs put 0.6 of the kernel's 2.7 ms there.  Here one workgroup per CU keeps all four frames' planes
 // (64 KB) for the whole launch and walks over the tiles: eight waves = two groups of four, each group with the tile geometry, image
 // rows (4 x 10.5 KB, all four stacked frames staged at once) and epilogue of the kernel above; the groups share the barriers (they
 // run the same phases), the next tile's frame bytes are in flight while the present one feeds the matrix pipe.
 // ------------------------------------------------------------------------------------------------
-#ifndef DDRL_F1_RESIDENT
-#ifdef DDRL_PLANES_BF16
-#define DDRL_F1_RESIDENT 0  // three planes per operand: the resident weights (96 KB) and two image groups exceed the LDS
-#else
-#define DDRL_F1_RESIDENT 1
-#endif
-#endif
 template <int NE>
 struct Fwd1R {
-  static constexpr int ROWS = 32 * NE, A_BYTES = 4 * NPL * 2 * ROWS * 16, PITCH = DDRL_F1_PITCH, IMG_BYTES = 64 * PITCH;
+  static constexpr int ROWS = 32 * NE, A_BYTES = 4 * NPL * 2 * ROWS * 16, PITCH = F1_PITCH, IMG_BYTES = 64 * PITCH;
   static constexpr int W_BYTES = 4 * A_BYTES, IMG_OFF = W_BYTES, GROUP_IMG = 4 * IMG_BYTES;   // per group: four stacked frames
   static constexpr int BIAS_OFF = IMG_OFF + 2 * GROUP_IMG;
   static constexpr size_t LDS_BYTES = BIAS_OFF + ROWS * 4;
-  static_assert(!DDRL_F1_RESIDENT || LDS_BYTES <= 160 * 1024, "one workgroup per CU");
+  static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 };
 
 template <int NE>
@@ -380,7 +350,7 @@ template <int NE>
 static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
-  if (DDRL_F1_RESIDENT != 0 && !acting && (int64_t)c.n * 400 >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
+  if (!acting && (int64_t)c.n * 400 >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
     using R = Fwd1R<NE>;
     static bool configured_r = false;
     static int cus = 256;
@@ -412,51 +382,36 @@ static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
 // six plane products that reach 2^-18 of the largest are accumulated in fp32.  One MFMA k-group (16) = the 4 x 4 taps
 // of ONE input channel: lane (pixel, h) holds taps (ky = 2h, kx = 0..3) and (ky = 2h + 1, kx = 0..3) = two runs of four
 // consecutive 16-bit values in the staged image (4-byte aligned 8-byte LDS reads), so the im2col stays implicit.
-// Tile = 64 output channels x 3 whole samples (243 columns in 8 column tiles of 32), k-block = 2 input channels (DDRL_F2B_KC);
+// Tile = 64 output channels x 3 whole samples (243 columns in 8 column tiles of 32), k-block = 2 input channels (KC);
 // LDS holds ONE stage (image planes [plane][sample][channel][20 rows of pitch 26] 16-bit + weight planes [channel][plane][oc][16]):
 // the next k-block waits in registers and is split / committed between two barriers while the CU's other
 // workgroups compute.
 // ================================================================================================
-// Build knobs (A/B and timing-only knock-outs, see profiles/README.md v16): DDRL_F2B_ROW = image row pitch in bytes (40 = dense,
-// 52 = bank-conflict free), DDRL_F2B_KO = 1 drops the residual-plane arithmetic, 2 the global loads inside the k loop
-// (both give WRONG results, only their kernel times mean something).
-#ifndef DDRL_F2B_ROW
-#define DDRL_F2B_ROW 52
-#endif
-#ifndef DDRL_F2B_KO
-#define DDRL_F2B_KO 0
-#endif
-#ifndef DDRL_F2B_KC
-#define DDRL_F2B_KC 2  // input channels per k-block: 2 -> 146 VGPRs and 31 KB of LDS, three workgroups per CU (3.66 vs 3.83 ms at 4 / two)
-#endif
-#ifndef DDRL_F2B_WPE
-#define DDRL_F2B_WPE 3  // waves per SIMD the register budget is cut for
-#endif
-#ifndef DDRL_F2B_STAGES
-#define DDRL_F2B_STAGES 1  // 2 = double-buffered LDS, one barrier per k-block: measured 2.40 against 2.335 ms (same box, f16 planes)
-#endif
 struct Fwd2B {
-  static constexpr int SPT = 3, KC = DDRL_F2B_KC;                 // samples per tile, input channels per k-block
+  // samples per tile, input channels per k-block: KC = 2 -> 146 VGPRs and 31 KB of LDS, three workgroups per CU (3.66 vs 3.83 ms at 4 / two)
+  static constexpr int SPT = 3, KC = 2;
+  static constexpr int WPE = 3;  // waves per SIMD the register budget is cut for
   // image row pitch 26 halfwords (13 words): the 5 input-row pairs a 32-pixel column tile reads in one instruction start
-  // 26 words apart = banks {0, 26, 52, 14, 40} + c, ten words each, disjoint (pitch 20: 2-way conflicts, 46 % of LDS cycles)
-  static constexpr int ROW = DDRL_F2B_ROW, CH = 20 * ROW, IMG_PLANE = SPT * KC * CH;  // 12,480 B at KC = 4
+  // 26 words apart = banks {0, 26, 52, 14, 40} + c, ten words each, disjoint (pitch 20: 2-way conflicts, 46 % of LDS cycles;
+  // profiles/README.md v16)
+  static constexpr int ROW = 52, CH = 20 * ROW, IMG_PLANE = SPT * KC * CH;  // 12,480 B at KC = 4
   static constexpr int W_OFF = NPL * IMG_PLANE, W_BYTES = KC * NPL * 64 * 32;
   static constexpr int BIAS_OFF = W_OFF + W_BYTES;
   static constexpr int NIU = SPT * KC * 100, NIJ = (NIU + 255) / 256;      // image units of 4 pixels, per thread
   static constexpr int NWJ = W_BYTES / 16 / 256;                          // weight quads per thread (6)
-  // ONE LDS stage, the next k-block committed between two barriers while the CU's other workgroups compute.  With two planes
-  // instead of three a second stage fits (2 x 20.7 KB, still three workgroups per CU; -DDDRL_F2B_STAGES=2: the next k-block is
-  // committed into the other stage while this one feeds the matrix pipe, one barrier per k-block) -- and loses 3 %: vector-ALU
-  // work does not overlap the matrix pipe of its own SIMD (tools/mfma16_peak.hip), so the commit costs the same either way and
-  // the second stage only takes LDS from the neighbours.
-  static constexpr int STAGES = DDRL_F2B_STAGES, STAGE_BYTES = BIAS_OFF;
-  static constexpr size_t LDS_BYTES = STAGES * STAGE_BYTES + 64 * 4;
+  // ONE LDS stage, the next k-block committed between two barriers while the CU's other workgroups compute.  Two stages fit
+  // (2 x 20.7 KB, still three workgroups per CU: the next k-block committed into the other stage while this one feeds the matrix
+  // pipe, one barrier per k-block) and measured 2.40 vs 2.335 ms (round 5), not kept: vector-ALU work does not overlap the matrix
+  // pipe of its own SIMD (tools/mfma16_peak.hip), so the commit costs the same either way and the second stage only takes LDS
+  // from the neighbours.
+  static constexpr int STAGE_BYTES = BIAS_OFF;
+  static constexpr size_t LDS_BYTES = STAGE_BYTES + 64 * 4;
 };
 struct __attribute__((packed, aligned(4))) lds_u2 {
   unsigned x, y;
 };
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F2B_WPE, DDRL_F2B_WPE))) void conv_fwd2_planes_kernel(const float* __restrict__ a1, int64_t a1_es, const unsigned short* __restrict__ wp2b,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2B::WPE, Fwd2B::WPE))) void conv_fwd2_planes_kernel(const float* __restrict__ a1, int64_t a1_es, const unsigned short* __restrict__ wp2b,
                                                                float* __restrict__ amax, const float* __restrict__ params, int64_t bias_off0,
                                                                int64_t bias_off1, float* __restrict__ out, int64_t out_es, int n,
                                                                unsigned* __restrict__ m2) {
@@ -465,7 +420,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F2B_WP
   const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int e = blockIdx.z, b0 = blockIdx.x * K::SPT;
   const float sa = plane_scale(amax[amax_idx(AMAX_A1, e)]), inv = 1.0f / (sa * plane_scale(amax[amax_idx(AMAX_W2, e)]));
-  if (tid < 64) ((float*)(ldsc2 + K::STAGES * K::STAGE_BYTES))[tid] = params[(e ? bias_off1 : bias_off0) + tid];
+  if (tid < 64) ((float*)(ldsc2 + K::STAGE_BYTES))[tid] = params[(e ? bias_off1 : bias_off0) + tid];
   // ---- staging maps.  image unit u = tid + 256 j: sample u / 400, channel (u % 400) / 100, pixel quad u % 100
   // (row q / 5, quad q % 5).  Missing samples of the last tile read the last sample.
   const float* isrc[K::NIJ];
@@ -536,7 +491,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F2B_WP
         }
       }
       // smallest products first
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -549,32 +503,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F2B_WP
   commit(ldsc2);
   fetch(1);
   __syncthreads();
-  if (K::STAGES == 1) {
-    for (int kb = 0; kb < NKB; ++kb) {
-      compute(ldsc2);
-      __syncthreads();  // every wave is done with the stage
-      if (kb + 1 < NKB) {
-        commit(ldsc2);
-        if (kb + 2 < NKB) fetch(kb + 2);
-      }
-      __syncthreads();
-    }
-  } else {
-    static_assert(NKB % 2 == 0, "unrolled by the two stages: every LDS address stays register + immediate");
-    for (int kb = 0; kb < NKB; kb += 2) {
-      compute(ldsc2);                      // stage 0; stage 1 was last read before the previous barrier
-      commit(ldsc2 + K::STAGE_BYTES);      // k-block kb + 1 (always exists)
+  for (int kb = 0; kb < NKB; ++kb) {
+    compute(ldsc2);
+    __syncthreads();  // every wave is done with the stage
+    if (kb + 1 < NKB) {
+      commit(ldsc2);
       if (kb + 2 < NKB) fetch(kb + 2);
-      __syncthreads();
-      compute(ldsc2 + K::STAGE_BYTES);
-      if (kb + 2 < NKB) {
-        commit(ldsc2);
-        if (kb + 3 < NKB) fetch(kb + 3);
-      }
-      __syncthreads();
     }
+    __syncthreads();
   }
-  const float* bias = (const float*)(ldsc2 + K::STAGES * K::STAGE_BYTES);
+  const float* bias = (const float*)(ldsc2 + K::STAGE_BYTES);
   float big = 0.0f;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -621,15 +559,10 @@ static void launch_fwd2_planes(const EncCall& c, bool acting, hipStream_t st) {
 // whole samples (245 columns in 8 column tiles), k-block = 8 input channels = 5 k-groups; one LDS stage, the next
 // k-block waits in registers.  Weights: wp3b[e][k-block 8][k-group 5][plane 3][oc 64][h 2][8 channels] (optim.hip).
 // ================================================================================================
-#ifndef DDRL_F3B_TN
-#define DDRL_F3B_TN 2
-#endif
-#ifndef DDRL_F3B_WPE
-#define DDRL_F3B_WPE 3  // waves per SIMD the register budget is cut for: 162 VGPRs, three 50 KB workgroups per CU (2.57 vs 2.69 ms at 2)
-#endif
 struct Fwd3B {
+  static constexpr int WPE = 3;  // waves per SIMD the register budget is cut for: 162 VGPRs, three 50 KB workgroups per CU (2.57 vs 2.69 ms at 2)
   // column tiles per wave (2 x 4 fragment tiles = 10 samples per tile measured 3.00 vs 2.70 ms: not a general win); whole samples per tile
-  static constexpr int TN = DDRL_F3B_TN, SPT = (128 * TN) / 49, NPX = SPT * 81;
+  static constexpr int TN = 2, SPT = (128 * TN) / 49, NPX = SPT * 81;
   static constexpr int IMG_PLANE = NPX * 16;                      // 6,480 B
   static constexpr int W_OFF = NPL * IMG_PLANE, W_BYTES = 5 * NPL * 64 * 32;
   static constexpr int BIAS_OFF = W_OFF + W_BYTES;
@@ -638,7 +571,7 @@ struct Fwd3B {
   static constexpr size_t LDS_BYTES = BIAS_OFF + 64 * 4;
 };
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F3B_WPE, DDRL_F3B_WPE))) void conv_fwd3_planes_kernel(const float* __restrict__ a2, int64_t a2_es, const unsigned short* __restrict__ wp3b,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd3B::WPE, Fwd3B::WPE))) void conv_fwd3_planes_kernel(const float* __restrict__ a2, int64_t a2_es, const unsigned short* __restrict__ wp3b,
                                                                float* __restrict__ amax, const float* __restrict__ params, int64_t bias_off0,
                                                                int64_t bias_off1, float* __restrict__ out, int64_t out_es, int n,
                                                                unsigned* __restrict__ m3) {
@@ -724,7 +657,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DDRL_F3B_WP
 #pragma unroll
         for (int j = 0; j < K::TN; ++j) b[p][j] = *(const frag8*)(ldsc3 + bB[j] + tapoff[kg] + p * K::IMG_PLANE);
       }
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -780,7 +712,7 @@ static void launch_fwd3_planes(const EncCall& c, bool acting, hipStream_t st) {
 
 // ================================================================================================
 
-// Training launches, and acting launches of more than DDRL_ACT_FUSED_MAX samples (they skip the sign masks only the backward reads)
+// Training launches, and acting launches of more than ACT_FUSED_MAX samples (they skip the sign masks only the backward reads)
 void launch_conv_forward2(const EncCall& c, bool acting, hipStream_t st) {
   {
     ProfRange pr(c.prof, acting ? "ConvFwd1.act" : "ConvFwd1", st);
@@ -811,19 +743,14 @@ void launch_conv_forward2(const EncCall& c, bool acting, hipStream_t st) {
 // not) and still wins: 192 instead of 512 matrix-pipe cycles per 16 k.
 // Weights: wd3b[e][k-block 4][tap 9][plane][ic 64][oc half 2][oc 8] (optim.hip).
 // ================================================================================================
-#ifndef DDRL_D3B_THREADS
-#define DDRL_D3B_THREADS 256  // 512 (eight waves, 6 samples share one copy of the weights): 2.52 vs 2.43 ms -- unlike conv2's data gradient
-#endif
-#ifndef DDRL_D3B_TN
-#define DDRL_D3B_TN 2  // 2 x 2 fragment tiles, 3 samples per tile: 4.19 vs 4.27 ms for 2 x 4 / 6 samples (re-measured under f16 planes: 2.54 vs 2.60)
-#endif
 struct Dgrad3B {
   // one MFMA k-group = ONE tap x 16 oc (lane half h = oc 8 h .. 8 h + 7): nine k-groups per k-block of 16 oc, no padded tenth tap
   // (tap pairs x 8 oc walked ten: executed / algorithmic 1.84 -> 1.65), the tap shift is a compile-time LDS offset, four k-blocks
   // instead of eight.  Weights: wd3b[e][k-block 4][tap 9][plane NPL][ic 64][oc half 2][oc 8] (optim.hip pack_dgrad3_planes_kernel).
-  // four waves / 3 samples per workgroup, two workgroups per CU.  (-DDDRL_D3B_THREADS=512: eight waves / 6 samples share one copy of
-  // the k-block's 37 KB of weights, one workgroup per CU: measured slower.)
-  static constexpr int THREADS = DDRL_D3B_THREADS, TN = DDRL_D3B_TN, SPT = ((THREADS / 64) * 32 * TN) / 81;  // column tiles per wave, whole samples per tile
+  // four waves / 3 samples per workgroup, two workgroups per CU.  Eight waves / 6 samples sharing one copy of the k-block's 37 KB of
+  // weights (one workgroup per CU) measured 2.52 vs 2.43 ms, not kept -- unlike conv2's data gradient.
+  // 2 x 2 fragment tiles, 3 samples per tile: 4.19 vs 4.27 ms for 2 x 4 / 6 samples (re-measured under f16 planes: 2.54 vs 2.60)
+  static constexpr int THREADS = 256, TN = 2, SPT = ((THREADS / 64) * 32 * TN) / 81;  // column tiles per wave, whole samples per tile
   static constexpr int KOC = 16, NKB = 64 / KOC, PIXB = 2 * KOC;  // oc per k-block, k-blocks, bytes per pixel and plane
   static constexpr int IMG_PLANE = SPT * 121 * PIXB;              // 11,616 B
   static constexpr int W_OFF = NPL * IMG_PLANE, W_BYTES = 9 * NPL * 64 * 32;
@@ -918,7 +845,6 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
         for (int j = 0; j < K::TN; ++j) bfr[p][j] = *(const frag8*)(ldsd3 + bB[j] - toff + p * K::IMG_PLANE);
       }
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -985,11 +911,6 @@ void launch_conv_dgrad3_2(const EncCall& c, hipStream_t st) {
 // (A first version with 5-wave workgroups of 3 samples kept only ONE workgroup resident per CU -- SQ_WAVE_CYCLES -- and
 // ran at 6.7 ms.)
 // ================================================================================================
-// Timing-only knock-outs (-DDDRL_D2_KO=bits; results are WRONG): 1 no dz1 stores, 2 no MFMAs, 4 no dz2 loads, 8 no weight loads,
-// 16 no dz2 split / LDS writes
-#ifndef DDRL_D2_KO
-#define DDRL_D2_KO 0
-#endif
 // ------------------------------------------------------------------------------------------------
 // The kernel: ONE workgroup per tile for BOTH row parities: eight waves, rows = (a, c, ic) = 128
 // (four 32-row fragment tiles), wave w = columns 64 w .. 64 w + 63 (4 x 2 fragment tiles: the same LDS bytes per MFMA), dz2
@@ -1080,7 +1001,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int j = 0; j < K::TN; ++j) bfr[p][j] = *(const frag8*)(ldsd2 + bB[j] + p * K::IMG_PLANE - kg * (11 * 16));
       }
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int t = 0; t < NPROD; ++t)
 #pragma unroll

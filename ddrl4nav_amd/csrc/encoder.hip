@@ -53,7 +53,7 @@ static void launch_backward_amax(const EncCall& c, hipStream_t st) {
 }
 
 void launch_encoder_forward(const EncCall& c, bool acting, hipStream_t st) {
-  if (acting && c.n <= DDRL_ACT_FUSED_MAX) {  // latency-bound: one launch for the three convolutions (act.hip), then the batched dense layer
+  if (acting && c.n <= ACT_FUSED_MAX) {  // latency-bound: one launch for the three convolutions (act.hip), then the batched dense layer
     launch_act_convs(c, st);
     launch_fc_forward2(c, true, st, true);
     return;
@@ -66,12 +66,11 @@ void launch_encoder_forward(const EncCall& c, bool acting, hipStream_t st) {
 // kernel leaves split-K partial slabs that reduce_partials sums into the grad arena.
 // Order: the data-gradient chain first (dense, conv3, conv2: kernels on the bf16 matrix pipe, then conv1's weight
 // gradient, also on it), the three fp32-MFMA weight gradients last.  Every buffer a weight gradient reads (dh, dz3, dz2
-// and the activations) is still intact then.  The layer-by-layer order (-DDDRL_BWD_LAYERWISE) alternates bf16-pipe and
-// fp32-pipe kernels, and each fp32 kernel that follows a bf16 one starts at the lower clock the denser pipe leaves
-// behind: 42.07 vs 41.84 ms per PPO iteration on one box.
+// and the activations) is still intact then.  The layer-by-layer order measured 42.07 vs 41.84 ms per PPO iteration on one
+// box, not kept: it alternates bf16-pipe and fp32-pipe kernels, and each fp32 kernel that follows a bf16 one starts at the
+// lower clock the denser pipe leaves behind.
 void launch_encoder_backward(const EncCall& c, float* grads, hipStream_t st, bool dh_normalised) {
   if (!dh_normalised) launch_backward_amax(c, st);  // dh from heads_loss arrives normalised (heads.hip); anyone else's is normalised here
-#ifndef DDRL_BWD_LAYERWISE
   launch_fc_backward2(c, grads, st, 1);
   launch_conv_dgrad3_2(c, st);
   launch_conv_dgrad2_2(c, st);
@@ -83,18 +82,6 @@ void launch_encoder_backward(const EncCall& c, float* grads, hipStream_t st, boo
   bucket_done(c, BUCKET_CONV3, st);
   launch_conv_wgrad2_2(c, grads, st);
   bucket_done(c, BUCKET_CONV2, st);
-#else
-  launch_fc_backward2(c, grads, st);
-  bucket_done(c, BUCKET_FC, st);
-  launch_conv_wgrad3_2(c, grads, st);
-  bucket_done(c, BUCKET_CONV3, st);
-  launch_conv_dgrad3_2(c, st);
-  launch_conv_wgrad2_2(c, grads, st);
-  bucket_done(c, BUCKET_CONV2, st);
-  launch_conv_dgrad2_2(c, st);
-  launch_conv_wgrad1_2(c, grads, st);
-  bucket_done(c, BUCKET_CONV1, st);
-#endif
 }
 
 }  // namespace ddrl

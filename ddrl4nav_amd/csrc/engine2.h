@@ -83,20 +83,10 @@ __device__ __forceinline__ void pin_offsets(uint32_t (&off)[N]) {
 __device__ __forceinline__ f4 ld4_so(const void* uniform_base, uint32_t lane_bytes) {
   return *(const f4*)((const char*)uniform_base + lane_bytes);
 }
-#ifndef DDRL_ST_SBASE
-#define DDRL_ST_SBASE 0  // measured: 61 fewer vector instructions per ConvFwd1 workgroup, ConvFwd2 2.36 -> 2.51 ms, iteration 25.18 -> 25.40: off
-#endif
+// a store written out in the scalar-base form (global_store_dword v_off, v_data, s[base]) measured 61 fewer vector instructions per
+// ConvFwd1 workgroup but ConvFwd2 2.36 -> 2.51 ms, iteration 25.18 -> 25.40 ms: not kept
 __device__ __forceinline__ void st1_so(void* uniform_base, uint32_t lane_bytes, float v) {
-#if DDRL_ST_SBASE
-  // the row offset that callers fold into `uniform_base` (k x 1,600 B, k x 324 B ...) fits the store's 12-bit immediate only for the
-  // first few rows of an epilogue; beyond that the compiler rebuilds a 64-bit VECTOR address per store (v_add_co + v_addc, or
-  // v_lshl_add_u64 when the base is merely opaque).  Written out, the sum stays on the scalar ALU:
-  //   global_store_dword v_off, v_data, s[base:base+1]
-  // (a dword store reads its data register at issue: no hazard the compiler would have to know about)
-  asm volatile("global_store_dword %0, %1, %2" ::"v"(lane_bytes), "v"(v), "s"(uniform_base) : "memory");
-#else
   *(float*)((char*)uniform_base + lane_bytes) = v;
-#endif
 }
 __device__ __forceinline__ float ld1f_so(const void* uniform_base, uint32_t lane_bytes) {
   return *(const float*)((const char*)uniform_base + lane_bytes);
@@ -134,20 +124,12 @@ struct IglpOf {
 };
 template <class Op>
 struct IglpOf<Op, decltype((void)Op::IGLP)> {
-#ifdef DDRL_NO_IGLP  // A/B switch for tools/ablate_iter.py
-  static constexpr bool v = false;
-#else
   static constexpr bool v = Op::IGLP != 0;
-#endif
 };
 
 template <class Op>
 __device__ __forceinline__ void compute_block(const Op& op, const float* __restrict__ cur, const float* lds_base,
                                               f32x16 (&acc)[Op::TM][Op::TN]) {
-#ifdef DDRL_SETPRIO
-  __builtin_amdgcn_s_setprio(DDRL_SETPRIO);
-#endif
-#ifndef DDRL_NO_LDS_PREFETCH
   // Operand pointers of this k-block.  When the two stage buffers together exceed the 64 KB reach of the
   // DS immediate offset, the (compile-time) offset of the second buffer is folded into the lane registers
   // here, once per k-block, and hidden from the compiler; otherwise it would re-base the address with a
@@ -212,24 +194,6 @@ __device__ __forceinline__ void compute_block(const Op& op, const float* __restr
       __builtin_amdgcn_sched_group_barrier(0x008, Op::TM * Op::TN, 0);
     }
   }
-#else
-#pragma unroll
-  for (int s = 0; s < Op::KSTEPS; ++s) {
-    float a[Op::TM], b[Op::TN];
-#pragma unroll
-    for (int i = 0; i < Op::TM; ++i) a[i] = cur[op.abase[i] + Op::aoff(s)];
-#pragma unroll
-    for (int j = 0; j < Op::TN; ++j) b[j] = cur[op.bbase[j] + Op::boff(s)];
-#pragma unroll
-    for (int i = 0; i < Op::TM; ++i)
-#pragma unroll
-      for (int j = 0; j < Op::TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-  }
-#endif
-#ifdef DDRL_SETPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Ops may declare `static constexpr int OCC` = waves per SIMD the register allocator must leave
@@ -252,11 +216,7 @@ struct CommitFirstOf {
 };
 template <class Op>
 struct CommitFirstOf<Op, decltype((void)Op::COMMIT_FIRST)> {
-#ifdef DDRL_NO_COMMIT_FIRST  // A/B switch for tools/ablate_iter.py
-  static constexpr bool v = false;
-#else
   static constexpr bool v = Op::COMMIT_FIRST != 0;
-#endif
 };
 
 // Ops may stage (part of) a k-block with LDS-direct loads: `static constexpr int DIRECT_PENDING` = number of
@@ -312,38 +272,26 @@ __device__ __forceinline__ void engine2_step(Op& op, const typename Op::Params& 
     // before the last k-block, so their latency hides under its MFMAs instead of being exposed
     if (kb == kbe - 1) op.pre_epilogue(P);
   }
-  // DDRL_ABL_* are timing-only knock-outs for tools/ablate_engine.sh (results are WRONG with any of
-  // them set): they show what each phase of the loop costs on top of the bare LDS->MFMA stream.
   if constexpr (CommitFirstOf<Op>::v) {
     // ops with a VALU-heavy commit (masks, u8 conversion): write the NEXT stage and issue the
     // following fetch before this block's MFMAs, so the scheduler can run them under the MFMAs
     if (kb + 1 < kbe) {
-#ifndef DDRL_ABL_NOCOMMIT
       op.commit(regs, nxt);
-#endif
-#ifndef DDRL_ABL_NOFETCH
       if (kb + 2 < kbe) op.fetch(P, kb + 2, regs);
-#endif
     }
     compute_block<Op>(op, cur, lds2, acc);
   } else {
     compute_block<Op>(op, cur, lds2, acc);
     if (kb + 1 < kbe) {
-#ifndef DDRL_ABL_NOCOMMIT
       op.commit(regs, nxt);
-#endif
-#ifndef DDRL_ABL_NOFETCH
       if (kb + 2 < kbe) op.fetch(P, kb + 2, regs);
-#endif
     }
   }
   wait_direct<Op>(kb + 2 < kbe);
   if constexpr (HasDirect<Op>::v) {
     if (kb + 1 < kbe) op.direct_done(P, kb + 1, nxt);  // e.g. zero-fill of a ragged last k-block
   }
-#ifndef DDRL_ABL_NOBARRIER
   __syncthreads();
-#endif
 }
 
 template <class Op>
@@ -351,9 +299,6 @@ __global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(type
   extern __shared__ __attribute__((aligned(16))) float lds2[];
   Op op;
   const int tid = threadIdx.x;
-#ifdef DDRL_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(DDRL_EDGE_PRIO);
-#endif
   op.init(P, tid, lds2);
   typename Op::Regs regs;
   f32x16 acc[Op::TM][Op::TN];
@@ -375,9 +320,6 @@ __global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(type
     if constexpr (HasDirect<Op>::v) op.direct_done(P, kb, lds2);
   }
   __syncthreads();
-#ifdef DDRL_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
   // The loop is unrolled by the two LDS buffers (engine2_step) and leaves the last one or two k-blocks to a
   // tail with a run-time buffer index (an exit in the middle of the unrolled loop would cost a copy of every
   // accumulator register per iteration; the tail also keeps the pre-epilogue registers out of the loop).
@@ -386,21 +328,7 @@ __global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(type
     engine2_step<Op, 1>(op, P, kb + 1, kbe, regs, acc, lds2);
   }
   for (int rbuf = 0; kb < kbe; ++kb, rbuf ^= 1) engine2_step<Op, -1>(op, P, kb, kbe, regs, acc, lds2, rbuf);
-#ifdef DDRL_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(DDRL_EDGE_PRIO);
-#endif
-#ifndef DDRL_ABL_NOEPILOGUE
   op.epilogue(P, acc, lds2);
-#else
-  float sink = 0.0f;
-#pragma unroll
-  for (int i = 0; i < Op::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < Op::TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sink += acc[i][j][r];
-  if (sink == 123.456f) lds2[0] = sink;  // keeps the accumulators live without an epilogue
-#endif
 }
 
 // Ops may declare `static constexpr int EXTRA` = floats of LDS behind the two stage buffers that
@@ -426,50 +354,31 @@ inline void launch_engine2(dim3 grid, const typename Op::Params& p, hipStream_t 
   hipLaunchKernelGGL(engine2_kernel<Op>, grid, dim3(Op::THREADS), bytes, st, p);
 }
 
-// accumulator element r of tile (i,j) of this lane -> (row, col) inside the wave tile
-// ---- fp32 -> three bf16 planes (only the -DDDRL_PLANES_BF16 build uses them; the default planes are fp16, below) ------
-// x = p0 + p1 + p2 to 24 bits: p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), round-to-nearest-even
-// (v_cvt_pk_bf16_f32); the two subtractions are exact in fp32.  Two values per dword: x in the low half, y in the high.
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2_t = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ unsigned pack_bf16x2(float x, float y) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){x, y}, bf16x2_t));
-}
-__device__ __forceinline__ void split_bf16x3(float x, float y, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = pack_bf16x2(x, y);
-  const float r1x = x - __uint_as_float(p0 << 16), r1y = y - __uint_as_float(p0 & 0xFFFF0000u);
-  p1 = pack_bf16x2(r1x, r1y);
-  const float r2x = r1x - __uint_as_float(p1 << 16), r2y = r1y - __uint_as_float(p1 & 0xFFFF0000u);
-  p2 = pack_bf16x2(r2x, r2y);
-}
-// the six plane products of a k-group under three bf16 planes per operand, smallest first: (a plane, b plane)
-#define DDRL_BF16X6_PRODUCTS constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0}
-
 // the value the neighbouring lane (lane ^ 1) holds: one DPP move (quad_perm [1, 0, 3, 2]), no LDS traffic
 __device__ __forceinline__ float lane_swap1(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
 }
 
+// accumulator element r of tile (i,j) of this lane -> (row, col) inside the wave tile
 __device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // ---- plane scheme of the kernels with TWO fp32 operands -----------------------------------------------------------
-// Default "f16x3": every operand as TWO scaled fp16 planes, x S = h0 + h1 to 22 bits (h0 = fp16(x S), h1 = fp16(x S - h0),
+// "f16x3": every operand as TWO scaled fp16 planes, x S = h0 + h1 to 22 bits (h0 = fp16(x S), h1 = fp16(x S - h0),
 // round-to-nearest-even; S = f16_scale(largest magnitude of the tensor), a power of two, so scaling and un-scaling are
 // exact), and the three products h0 g0, h0 g1, h1 g0 on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  What is left out
 // (h1 g1 and the representation error) is <= 3 x 2^-22 |a b| per term with zero mean; measured against float64 it does not
 // show next to the rounding of the fp32 accumulation itself (tests/test_gpu_parity.py::*_is_at_least_fp32_accurate).  Half the
-// matrix instructions and two thirds of the LDS planes of "bf16x6" (three bf16 planes per operand, six products), which
-// -DDDRL_PLANES_BF16 keeps: bf16 has fp32's exponent range and needs no scale.
+// matrix instructions and two thirds of the LDS planes of "bf16x6" (three bf16 planes per operand, six products; bf16 has
+// fp32's exponent range and needs no scale), which was kept for accuracy attribution only and is no longer built.
 // Range: with the tensor's maximum at [2^12, 2^13) every element down to 2^-16 of it keeps its 22 bits (fp16 normal range
 // 2^-14), below that the absolute error stays <= 2^-25 / S, i.e. <= 2^-38 of the maximum -- far below 2^-24 of any sum that
 // the large elements take part in.
 using f16x2_t = __attribute__((ext_vector_type(2))) _Float16;
 using h8v = __attribute__((ext_vector_type(8))) _Float16;
-using b8v = __attribute__((ext_vector_type(8))) __bf16;
-#ifndef DDRL_PLANES_BF16
 constexpr int NPL = 2, NPROD = 3;
 using frag8 = h8v;
-#define DDRL_PLANE_PRODUCTS constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0} /* smallest first: h1 g0, h0 g1, h0 g0 */
+// the plane products of a k-group, smallest first: h1 g0, h0 g1, h0 g0 (A plane PA[m] times B plane PB[m])
+constexpr int PA[NPROD] = {1, 0, 0}, PB[NPROD] = {0, 1, 0};
 // FOUR VALU instructions per PAIR: v_fma_mixlo_f16 / v_fma_mixhi_f16 compute fma(x, S, c) in fp32 and write the result as fp16 into
 // the low / high half of the destination, with c an fp32 or (op_sel_hi) an fp16 source: h0 = fp16(x S + 0), h1 = fp16(x S - h0)
 // straight from the h0 halves.  x S and x S - h0 are exact in fp32, so each value is rounded once, as in the plain form
@@ -478,7 +387,7 @@ using frag8 = h8v;
 // instructions per MFMA, most of them this split.
 using f32x2_t = __attribute__((ext_vector_type(2))) float;
 // the plain form (six instructions, but visible to the scheduler): same-box A/B of the two forms per kernel -- the dense forward /
-// data gradient and the conv2 weight gradient are 1-3 % faster with it, the other six with the four-instruction form
+// data gradient and the one-stage conv2 weight gradient of round 5 were 1-3 % faster with it, the other six with the four-instruction form
 __device__ __forceinline__ void split_planes_c(float x, float y, float scale, unsigned (&p)[NPL]) {
   const f32x2_t xs = {x * scale, y * scale};
   const f16x2_t a = __builtin_convertvector(xs, f16x2_t);
@@ -488,7 +397,6 @@ __device__ __forceinline__ void split_planes_c(float x, float y, float scale, un
   p[1] = __builtin_bit_cast(unsigned, b);
 }
 __device__ __forceinline__ void split_planes(float x, float y, float scale, unsigned (&p)[NPL]) {
-#ifndef DDRL_SPLIT_PLAIN
   unsigned h0, h1;
   asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h0) : "v"(x), "v"(scale));
   asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h0) : "v"(y), "v"(scale));
@@ -496,37 +404,15 @@ __device__ __forceinline__ void split_planes(float x, float y, float scale, unsi
   asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(h1) : "v"(y), "v"(scale), "v"(h0));
   p[0] = h0;
   p[1] = h1;
-#else
-  const f32x2_t xs = {x * scale, y * scale};
-  const f16x2_t a = __builtin_convertvector(xs, f16x2_t);
-  const f32x2_t r = {__builtin_fmaf(x, scale, -(float)a[0]), __builtin_fmaf(y, scale, -(float)a[1])};
-  const f16x2_t b = __builtin_convertvector(r, f16x2_t);
-  p[0] = __builtin_bit_cast(unsigned, a);
-  p[1] = __builtin_bit_cast(unsigned, b);
-#endif
 }
 __device__ __forceinline__ f32x16 mfma_planes(frag8 a, frag8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 __host__ __device__ inline float plane_scale(float amax) { return f16_scale(amax); }
-// frame bytes 0..255 are exact in fp16 (and in bf16): the pixel operand of conv1 is ONE plane, "f16x2" = NPL products.
-// -DDDRL_PIX_SUBNORMAL=1 (measured, NOT used) feeds them as fp16 SUBNORMALS: the 16-bit pattern 0x00bb is the fp16 value b x 2^-24, so
-// a byte becomes an operand by zero extension -- one v_perm_b32 per pair of pixels instead of two byte->float conversions and a
-// pack, with 2^24 (PIXEL_UNIT) folded into the epilogue's scale.  Same-box A/B: 110 M fewer vector-ALU instructions per iteration
-// (4 %), ConvWgrad1 2.83 -> 2.78 ms, the PPO iteration 25.43 -> 25.37 ms (0.2 %) -- and the results are NOT the same bits: the matrix
-// pipe takes subnormal operands, but the conv1 weight gradient's mean error against float64 grows from 1.0 x to 1.6 x that of an
-// fp32 evaluation (products of a subnormal pixel with the small plane of dz1 lose bits inside the pipe), which breaks
-// tests/test_gpu_parity.py::test_conv1_weight_gradient_is_at_least_fp32_accurate.  Vector-ALU count is not what bounds these kernels.
-#ifndef DDRL_PIX_SUBNORMAL
-#define DDRL_PIX_SUBNORMAL 0
-#endif
-#if DDRL_PIX_SUBNORMAL
-constexpr float PIXEL_UNIT = 16777216.0f;
-// [byte QA of a][0][byte QB of b][0] = the two pixels as 16-bit operands
-template <int QA, int QB>
-__device__ __forceinline__ unsigned pixel_pair_sel(unsigned a, unsigned b) {
-  return __builtin_amdgcn_perm(b, a, 0x0c040c00u + (unsigned)QA + ((unsigned)QB << 16));
-}
-__device__ __forceinline__ unsigned short pixel_one(unsigned a) { return (unsigned short)a; }
-#else
+// frame bytes 0..255 are exact in fp16: the pixel operand of conv1 is ONE plane, "f16x2" = NPL products.
+// Feeding them as fp16 SUBNORMALS (0x00bb = b x 2^-24: one v_perm_b32 per pair of pixels, 2^24 folded into the epilogue's scale) was
+// measured and not kept: 110 M fewer vector-ALU instructions per iteration (4 %), ConvWgrad1 2.83 -> 2.78 ms, the PPO iteration
+// 25.43 -> 25.37 ms (0.2 %) -- and the results are NOT the same bits: the conv1 weight gradient's mean error against float64 grows from
+// 1.0 x to 1.6 x that of an fp32 evaluation (products of a subnormal pixel with the small plane of dz1 lose bits inside the pipe), which
+// breaks tests/test_gpu_parity.py::test_conv1_weight_gradient_is_at_least_fp32_accurate.  Vector-ALU count is not what bounds these kernels.
 constexpr float PIXEL_UNIT = 1.0f;
 __device__ __forceinline__ unsigned pixel_pair(unsigned a, unsigned b) {
   const f16x2_t v = {(_Float16)(float)a, (_Float16)(float)b};
@@ -535,7 +421,6 @@ __device__ __forceinline__ unsigned pixel_pair(unsigned a, unsigned b) {
 template <int QA, int QB>
 __device__ __forceinline__ unsigned pixel_pair_sel(unsigned a, unsigned b) { return pixel_pair((a >> (8 * QA)) & 255u, (b >> (8 * QB)) & 255u); }
 __device__ __forceinline__ unsigned short pixel_one(unsigned a) { return __builtin_bit_cast(unsigned short, (_Float16)(float)a); }
-#endif
 // the four pixels of one dword as two operand pairs
 __device__ __forceinline__ uint2 pixel_quad(unsigned v) { return make_uint2(pixel_pair_sel<0, 1>(v, v), pixel_pair_sel<2, 3>(v, v)); }
 __host__ __device__ inline void planes_of(float w, float scale, unsigned short (&p)[NPL]) {
@@ -545,31 +430,6 @@ __host__ __device__ inline void planes_of(float w, float scale, unsigned short (
   p[0] = __builtin_bit_cast(unsigned short, h0);
   p[1] = __builtin_bit_cast(unsigned short, h1);
 }
-#else
-constexpr int NPL = 3, NPROD = 6;
-using frag8 = b8v;
-#define DDRL_PLANE_PRODUCTS constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0}
-__device__ __forceinline__ void split_planes(float x, float y, float, unsigned (&p)[NPL]) { split_bf16x3(x, y, p[0], p[1], p[2]); }
-__device__ __forceinline__ void split_planes_c(float x, float y, float s, unsigned (&p)[NPL]) { split_planes(x, y, s, p); }
-__device__ __forceinline__ f32x16 mfma_planes(frag8 a, frag8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__host__ __device__ inline float plane_scale(float) { return 1.0f; }
-// float(byte) has at most 8 significant bits: its upper 16 bits ARE the bf16 value
-constexpr float PIXEL_UNIT = 1.0f;
-__device__ __forceinline__ unsigned pixel_pair(unsigned a, unsigned b) {
-  return (__float_as_uint((float)a) >> 16) | (__float_as_uint((float)b) & 0xFFFF0000u);
-}
-template <int QA, int QB>
-__device__ __forceinline__ unsigned pixel_pair_sel(unsigned a, unsigned b) { return pixel_pair((a >> (8 * QA)) & 255u, (b >> (8 * QB)) & 255u); }
-__device__ __forceinline__ unsigned short pixel_one(unsigned a) { return (unsigned short)(__float_as_uint((float)a) >> 16); }
-__device__ __forceinline__ uint2 pixel_quad(unsigned v) { return make_uint2(pixel_pair_sel<0, 1>(v, v), pixel_pair_sel<2, 3>(v, v)); }
-__host__ __device__ inline void planes_of(float w, float, unsigned short (&p)[NPL]) {
-  auto rne = [](float v) { unsigned u = __builtin_bit_cast(unsigned, v); return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
-  p[0] = rne(w);
-  const float r1 = w - __builtin_bit_cast(float, (unsigned)p[0] << 16);
-  p[1] = rne(r1);
-  p[2] = rne(r1 - __builtin_bit_cast(float, (unsigned)p[1] << 16));
-}
-#endif
 // largest magnitude of the values a thread wrote -> the tensor's running maximum (float bits of non-negative values order like
 // unsigned integers; the maximum does not depend on the order of the atomics, so the result is deterministic).
 // One atomic per wave on ONE address serialises in the memory system (25,600 of them cost conv1's forward 6 ms): a wave

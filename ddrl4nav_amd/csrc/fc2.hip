@@ -12,18 +12,14 @@ namespace ddrl {
 // ([plane][row][32 k] 16-bit, row pitch 80 B so that 16 lanes' 16-byte fragments hit distinct banks): the next
 // k-block waits in registers and is committed between two barriers while the CU's other workgroup computes.
 // ------------------------------------------------------------------------------------------------
-using bf8f = __attribute__((ext_vector_type(8))) __bf16;
 
-// xcd_note: XCD-aware tile order of the three dense-layer kernels (-DDDRL_FC_SWZ=0 switches it off).  The hardware deals
+// xcd_note: XCD-aware tile order of the three dense-layer kernels.  The hardware deals
 // workgroups to the chip's 8 XCDs round-robin by linear id and an XCD runs about 64 of them at a time; each XCD has its own
 // 4 MB L2.  In launch order the workgroups that share an operand tile land on different XCDs and every L2 fetches its own copy
 // (FETCH_SIZE 2-3 x the algorithmic bytes, profiles/r02_v27_pmc_traffic.json).  The kernels therefore derive their tile from
 // (xcd = id mod 8, position = id / 8) so that sharers sit next to each other on one XCD.  FETCH_SIZE per launch at B = 65,536,
 // off -> on: forward 3.39 -> 1.23 GB, data gradient 4.63 -> 1.27 GB (blocks of 8 x 5 tiles; 3.38 one batch tile at a time), weight
 // gradient 5.04 -> 3.60 GB; the kernels' times move by 0-4 % (they are not bandwidth-bound), the neighbours' clocks gain.
-#ifndef DDRL_FC_SWZ
-#define DDRL_FC_SWZ 1
-#endif
 
 struct FcFwdB {
   static constexpr int PITCH = 80, PLANE = 128 * PITCH, B_OFF = NPL * PLANE, LDS_BYTES = 2 * NPL * PLANE;
@@ -39,11 +35,11 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wr = wave >> 1, wc = wave & 1;
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (!SPLIT && DDRL_FC_SWZ != 0 && (gridDim.y & 7) == 0) {  // XCD-aware tile order, see xcd_note above
+  if (!SPLIT && (gridDim.y & 7) == 0) {  // XCD-aware tile order, see xcd_note above
     const int lin = bx + 4 * by, xcd = lin & 7, q = lin >> 3;
     bx = q & 3, by = (q >> 2) * 8 + xcd;  // an XCD owns the batch tiles = xcd mod 8; the 4 feature tiles of one run together and share its a3 rows
   }
-  if (SPLIT && DDRL_FC_SWZ != 0) {
+  if (SPLIT) {
     // Split launches: the G = 4 x gridDim.y workgroups of one (encoder, split) share that K range of a3 (per batch tile) and of the
     // weights (per feature tile).  In dispatch order (x fastest, XCD = linear id mod 8) they would land on 8 different XCDs and every L2
     // would fetch its own copy from the memory side (51 MB instead of 19 MB at n = 256); here groups 8 i .. 8 i + 7 take XCDs 0..7, one
@@ -126,7 +122,6 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
 #pragma unroll
         for (int j = 0; j < 2; ++j) b[p][j] = *(const frag8*)(ldsf + bB[j] + p * K::PLANE + kg * 32);
       }
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
     }
   };
   if constexpr (SPLIT) {
-    constexpr int PER = (FLAT / 32) / DDRL_FC_ACT_SPLITS;  // the launcher passes nsplit = DDRL_FC_ACT_SPLITS
+    constexpr int PER = (FLAT / 32) / FC_ACT_SPLITS;  // the launcher passes nsplit = FC_ACT_SPLITS
     const int kb0 = split * PER;
 #pragma unroll
     for (int d = 0; d < DEPTH && d < PER; ++d) fetch(kb0 + d, d);
@@ -215,7 +210,7 @@ void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool
     if (nsplit > 1)
       hipLaunchKernelGGL(fc_fwd_planes_kernel<true>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, MB * FLAT, w.wlb, w.amax, c.params,
                          c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, MB * FEAT, c.n, c.L->NE, nsplit, w.wpart,
-                         per_sample_max ? w.actmax : (const float*)nullptr, DDRL_ACT_FUSED_MAX);
+                         per_sample_max ? w.actmax : (const float*)nullptr, ACT_FUSED_MAX);
     else
       hipLaunchKernelGGL(fc_fwd_planes_kernel<false>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, MB * FLAT, w.wlb, w.amax, c.params,
                          c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, MB * FEAT, c.n, c.L->NE, 1, w.wpart,
@@ -229,14 +224,8 @@ void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool
 // dh is split into NPL planes while it is staged, the weights come pre-split and transposed from optim.hip
 // (wdlb[e][plane][k 3136][n 512]); 128 x 128 tile, k-block 32 = 2 MFMA k-groups, one LDS stage.
 // ------------------------------------------------------------------------------------------------
-#ifndef DDRL_FCD_KBK
-#define DDRL_FCD_KBK 32
-#endif
-#ifndef DDRL_FCD_WPE
-#define DDRL_FCD_WPE 2
-#endif
-struct FcDgradB {  // k-block KBK = 32 or 16 features; row pitch = data + 16 B so that 16 lanes' fragments hit distinct banks
-  static constexpr int KBK = DDRL_FCD_KBK, WPE = DDRL_FCD_WPE, PITCH = 2 * KBK + 16, PLANE = 128 * PITCH, B_OFF = NPL * PLANE, LDS_BYTES = 2 * NPL * PLANE;
+struct FcDgradB {  // k-block KBK = 32 features; row pitch = data + 16 B so that 16 lanes' fragments hit distinct banks
+  static constexpr int KBK = 32, WPE = 2, PITCH = 2 * KBK + 16, PLANE = 128 * PITCH, B_OFF = NPL * PLANE, LDS_BYTES = 2 * NPL * PLANE;
   static constexpr int NAQ = KBK / 4, ARJ = 128 * NAQ / 256, AROWS = 256 / NAQ;  // dh: quads of 4 features per row, per thread, rows per round
   static constexpr int NWF = KBK / 8, WJ = 128 * NWF / 256, WCOLS = 256 / NWF;   // weights: fragments of 8 features per column
 };
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wr = wave >> 1, wc = wave & 1;
   int bx = blockIdx.x, by = blockIdx.y;
-  if (DDRL_FC_SWZ != 0 && (gridDim.y & 7) == 0) {  // XCD-aware tile order, see xcd_note above; gridDim.x = 25
+  if ((gridDim.y & 7) == 0) {  // XCD-aware tile order, see xcd_note above; gridDim.x = 25
     const int lin = bx + 25 * by, xcd = lin & 7, q = lin >> 3;
     if ((gridDim.y & 63) != 0) {
       bx = q % 25, by = (q / 25) * 8 + xcd;  // an XCD owns batch tiles = xcd mod 8 and walks their 25 column tiles one batch tile at a time
@@ -320,7 +309,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
 #pragma unroll
         for (int j = 0; j < 2; ++j) b[p][j] = *(const frag8*)(ldsg + bB[j] + p * K::PLANE + kg * 32);
       }
-      DDRL_PLANE_PRODUCTS;
 #pragma unroll
       for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -400,15 +388,11 @@ __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __res
   extern __shared__ __attribute__((aligned(16))) char ldsw[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wr = wave >> 1, wc = wave & 1;
-#if DDRL_FC_SWZ != 0
   // 1-D grid (launch site): linear id = xcd + 8 (t + 4 m): the four feature tiles t of one (column tile, split, encoder) unit run
   // together on ONE XCD and share the unit's a3 columns through its L2 (6.7 MB per unit, read once instead of four times)
   const int unit = (int)(blockIdx.x >> 5) * 8 + (int)(blockIdx.x & 7);
   if (unit >= 25 * ne * nsplit) return;
   const int bx = unit % 25, by = (int)(blockIdx.x >> 3) & 3, bz = unit / 25;
-#else
-  const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-#endif
   const int e = bz % ne, split = bz / ne;
   // dh is NORMALISED per sample (common.h Workspace::gsc): sample s is staged with the factor sd g_s / g_max (<= sd) and the sums are
   // multiplied by g_max / (sd sa); the bias gradient sums g_s dh[s] in fp32
@@ -491,7 +475,6 @@ __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __res
 #pragma unroll
           for (int j = 0; j < 2; ++j) b[p][j] = tr_fragment(ldsw, bB[j] + p * K::PLANE + kg * 16 * K::PITCH);
         }
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int t = 0; t < NPROD; ++t)
 #pragma unroll
@@ -543,11 +526,7 @@ void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int par
         (void)hipFuncSetAttribute((const void*)fc_wgrad_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FcWgradB::LDS_BYTES);
         configured_w = true;
       }
-#if DDRL_FC_SWZ != 0
       const dim3 wgrid((unsigned)((25 * L.NE * S + 7) / 8 * 32));
-#else
-      const dim3 wgrid((FLAT + 127) / 128, FEAT / 128, L.NE * S);
-#endif
       hipLaunchKernelGGL(fc_wgrad_planes_kernel, wgrid, dim3(256), FcWgradB::LDS_BYTES, st, w.dh, MB * FEAT, w.a3, MB * FLAT, w.amax, w.gsc, MB,
                          w.wpart, c.n, S, L.NE);
     }

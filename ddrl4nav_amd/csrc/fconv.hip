@@ -30,19 +30,6 @@
 #include "engine2.h"
 #include "ops.h"
 
-#ifdef DDRL_PLANES_BF16
-// The three-plane build (bf16x6) keeps the f32-input kernels for this layer (LDS budgets).  Every query answers "no", nothing launches.
-namespace ddrl {
-bool conv_has_first(const ConvGeom&) { return false; }
-int64_t conv_first_pack_floats(const ConvGeom&) { return 0; }
-int conv_first_wgrad_splits(const ConvGeom&) { return 0; }
-void launch_conv_first_pack(const ConvGeom&, const float*, float*, hipStream_t) {}
-void launch_conv_first_fwd(const ConvGeom&, const float*, const float*, const float*, int, float*, hipStream_t) {}
-void launch_conv_first_fwd_pool(const ConvGeom&, const float*, const float*, const float*, float*, uint8_t*, float*, hipStream_t) {}
-void launch_conv_first_wgrad(const ConvGeom&, const float*, const float*, float*, float*, float*, hipStream_t) {}
-void launch_conv_first_wgrad_pooled(const ConvGeom&, const float*, const float*, const uint8_t*, float*, float*, float*, hipStream_t) {}
-}  // namespace ddrl
-#else
 namespace ddrl {
 
 namespace fconv {
@@ -250,7 +237,6 @@ __global__ __launch_bounds__(512) void first_fwd_kernel(const float* __restrict_
               bf[p][j] = __builtin_bit_cast(frag8, (u4v){lo.x, lo.y, hh.x, hh.y});
             }
           }
-          DDRL_PLANE_PRODUCTS;
 #pragma unroll
           for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -500,7 +486,6 @@ __global__ __launch_bounds__(256, 2) void first_wgrad_kernel(const float* __rest
             bf[p][0] = tr_frag(lds, o, o + 32);
             if (two) bf[p][1] = tr_frag(lds, o + K::LPX_W * 8, o + K::LPX_W * 8 + 32);
           }
-          DDRL_PLANE_PRODUCTS;
 #pragma unroll
           for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -549,15 +534,11 @@ using FPedC1 = fconv::FGeo<4, 3, 48, 1>;   // NavPedPreNet.conv1 (image + 3 pede
 enum FirstId { kFNone = 0, kFN1d, kFNav, kFPed };
 
 static FirstId first_id(const ConvGeom& g) {
-#ifdef DDRL_PLANES_BF16
-  return kFNone;  // diagnostic three-plane build: first layers on the generic gather kernels (gconv.hip) as well
-#else
   if (g.stride != 1 || g.h != 48 || g.w != 48 || g.kh != g.kw || g.pad_h != 1 || g.pad_w != 1 || g.cout != 64) return kFNone;
   if (g.kh == 7 && g.cin == 3) return kFN1d;
   if (g.kh == 3 && g.cin == 1) return kFNav;
   if (g.kh == 3 && g.cin == 4) return kFPed;
   return kFNone;
-#endif
 }
 
 bool conv_has_first(const ConvGeom& g) { return first_id(g) != kFNone; }
@@ -643,4 +624,3 @@ void launch_conv_first_wgrad_pooled(const ConvGeom& g, const float* in, const fl
 }
 
 }  // namespace ddrl
-#endif  // DDRL_PLANES_BF16

@@ -386,22 +386,20 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_idx_kernel(const float* __re
 // element WRITE, and 1 KiB contiguous per wave is what the write path wants (one thread per window stores two half-used 128-byte lines per
 // instruction and measured 2.7 TB/s).  W even makes elements (0,1) and (2,3) of a quad two whole window halves; the byte and the pooled
 // gradient of a window are read by the two threads that own its rows, the second time from cache.
-#ifndef DDRL_POOL_QUADS
-#define DDRL_POOL_QUADS 4
-#endif
+constexpr int POOL_QUADS = 4;  // quads per thread
 template <typename IT>
 __global__ __launch_bounds__(256) void maxpool2_bwd_idx_kernel(const float* __restrict__ dpool, const uint8_t* __restrict__ code, IT total4,
                                                                int W, float* __restrict__ dz) {
   const IT ow = (IT)(W / 2);
-  IT e[DDRL_POOL_QUADS];
-  int ca[DDRL_POOL_QUADS], cb[DDRL_POOL_QUADS], sa[DDRL_POOL_QUADS], sb[DDRL_POOL_QUADS];
-  float ga[DDRL_POOL_QUADS], gb[DDRL_POOL_QUADS];
-  bool live[DDRL_POOL_QUADS];
+  IT e[POOL_QUADS];
+  int ca[POOL_QUADS], cb[POOL_QUADS], sa[POOL_QUADS], sb[POOL_QUADS];
+  float ga[POOL_QUADS], gb[POOL_QUADS];
+  bool live[POOL_QUADS];
   // every load of the thread's quads is issued before the first store: a wave's stores wait on its loads, and one quad per wave
   // lifetime leaves too few bytes in flight to fill the write path
 #pragma unroll
-  for (int k = 0; k < DDRL_POOL_QUADS; ++k) {
-    IT q = ((IT)blockIdx.x * DDRL_POOL_QUADS + k) * 256 + threadIdx.x;
+  for (int k = 0; k < POOL_QUADS; ++k) {
+    IT q = ((IT)blockIdx.x * POOL_QUADS + k) * 256 + threadIdx.x;
     live[k] = q < total4;
     q = live[k] ? q : total4 - 1;
     e[k] = q * 4;
@@ -417,7 +415,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_idx_kernel(const float* __re
     sb[k] = (int)(row2 & 1) * 2;
   }
 #pragma unroll
-  for (int k = 0; k < DDRL_POOL_QUADS; ++k) {
+  for (int k = 0; k < POOL_QUADS; ++k) {
     const float xa = (ca[k] & 4) ? ga[k] : 0.0f, xb = (cb[k] & 4) ? gb[k] : 0.0f;
     if (live[k])
       *(float4*)(dz + e[k]) = make_float4((ca[k] & 3) == sa[k] ? xa : 0.0f, (ca[k] & 3) == sa[k] + 1 ? xa : 0.0f,
@@ -432,13 +430,13 @@ template <typename IT>
 __global__ __launch_bounds__(256) void maxpool2_bwd_idx_pairs_kernel(const float* __restrict__ dpool, const uint8_t* __restrict__ code,
                                                                      IT pairs, int W, float* __restrict__ dz) {
   const IT pw = (IT)(W / 4);
-  IT off[DDRL_POOL_QUADS];
-  unsigned c[DDRL_POOL_QUADS];
-  float2 g[DDRL_POOL_QUADS];
-  bool live[DDRL_POOL_QUADS];
+  IT off[POOL_QUADS];
+  unsigned c[POOL_QUADS];
+  float2 g[POOL_QUADS];
+  bool live[POOL_QUADS];
 #pragma unroll
-  for (int k = 0; k < DDRL_POOL_QUADS; ++k) {
-    IT p = ((IT)blockIdx.x * DDRL_POOL_QUADS + k) * 256 + threadIdx.x;
+  for (int k = 0; k < POOL_QUADS; ++k) {
+    IT p = ((IT)blockIdx.x * POOL_QUADS + k) * 256 + threadIdx.x;
     live[k] = p < pairs;
     p = live[k] ? p : pairs - 1;
     const IT rp = p / pw, xp = p - rp * pw;
@@ -447,7 +445,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_idx_pairs_kernel(const float
     g[k] = *(const float2*)(dpool + 2 * p);
   }
 #pragma unroll
-  for (int k = 0; k < DDRL_POOL_QUADS; ++k) {
+  for (int k = 0; k < POOL_QUADS; ++k) {
     const unsigned c0 = c[k] & 255u, c1 = c[k] >> 8;
     const float x0 = (c0 & 4) ? g[k].x : 0.0f, x1 = (c1 & 4) ? g[k].y : 0.0f;
     if (live[k]) {
@@ -646,14 +644,14 @@ void launch_maxpool2_bwd_idx(const float* dpool, const uint8_t* code, int64_t pl
   const int64_t total4 = planes * H * W / 4;  // H, W even
   if (W % 4 == 0 && !(((uintptr_t)dpool & 7) | ((uintptr_t)code & 1))) {
     const int64_t pairs = total4 / 2;
-    const dim3 pgrid((unsigned)((pairs + 256 * DDRL_POOL_QUADS - 1) / (256 * DDRL_POOL_QUADS)));
+    const dim3 pgrid((unsigned)((pairs + 256 * POOL_QUADS - 1) / (256 * POOL_QUADS)));
     if (total4 * 4 < ((int64_t)1 << 32) - 1024)
       hipLaunchKernelGGL(maxpool2_bwd_idx_pairs_kernel<uint32_t>, pgrid, dim3(256), 0, st, dpool, code, (uint32_t)pairs, W, dz);
     else
       hipLaunchKernelGGL(maxpool2_bwd_idx_pairs_kernel<int64_t>, pgrid, dim3(256), 0, st, dpool, code, pairs, W, dz);
     return;
   }
-  const dim3 grid((unsigned)((total4 + 256 * DDRL_POOL_QUADS - 1) / (256 * DDRL_POOL_QUADS)));
+  const dim3 grid((unsigned)((total4 + 256 * POOL_QUADS - 1) / (256 * POOL_QUADS)));
   if (total4 * 4 < ((int64_t)1 << 32) - 1024)
     hipLaunchKernelGGL(maxpool2_bwd_idx_kernel<uint32_t>, grid, dim3(256), 0, st, dpool, code, (uint32_t)total4, W, dz);
   else

@@ -157,11 +157,11 @@ __global__ __launch_bounds__(256) void heads_act_kernel(float* __restrict__ h, i
         ha[i] = 0.0f;
         hc[i] = 0.0f;
       }
-      if (fc_nsplit == DDRL_FC_ACT_SPLITS) {
+      if (fc_nsplit == FC_ACT_SPLITS) {
         // the usual case: ALL partials of both encoders requested at once (a loop with a run-time trip count waits for every pair
         // before it asks for the next: 14 dependent round trips); same order of additions.  224 staging registers: this kernel
         // runs one wave per SIMD
-        constexpr int U = DDRL_FC_ACT_SPLITS;
+        constexpr int U = FC_ACT_SPLITS;
         float ta[U][8], tc[U][8];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -250,14 +250,8 @@ __global__ __launch_bounds__(256) void heads_act_kernel(float* __restrict__ h, i
 // WLDS (A > 8): the actor-head weight / bias gradient slots of hpart are written by
 // head_wgrad_kernel from dlogits instead (288 accumulator + weight registers do not fit a lane).
 constexpr int LOSS_WAVES = 4;      // waves per workgroup of heads_loss: one per SIMD (register-resident head weights, A = 7 .. 8 and A > 8)
-#ifndef DDRL_LOSS_WAVES6
-#define DDRL_LOSS_WAVES6 8         // A <= 6 (Pong): the weight rows live in LDS, 245 registers -> two waves per SIMD (round 6)
-#endif
-constexpr int LOSS_WAVES6 = DDRL_LOSS_WAVES6;
-#ifndef DDRL_LOSS_NS
-#define DDRL_LOSS_NS 4      // samples per wave and turn (a power of two): the scalar chain of the loss block runs once per NS samples
-#endif
-constexpr int LOSS_NS = DDRL_LOSS_NS;
+constexpr int LOSS_WAVES6 = 8;     // A <= 6 (Pong): the weight rows live in LDS, 245 registers -> two waves per SIMD (round 6)
+constexpr int LOSS_NS = 4;         // samples per wave and turn (a power of two): the scalar chain of the loss block runs once per NS samples
 // GREG: the actor head's weight / bias gradient is accumulated in registers (else: head_wgrad_kernel, A > 8)
 template <int MAXA, bool WLDS, bool GREG = !WLDS, int WAVES = LOSS_WAVES>
 __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
@@ -714,14 +708,11 @@ void launch_categorical_sample(const float* probs, int n, int A, uint64_t seed, 
 
 void launch_heads_act(const HeadsCall& c, const float* act_in, uint64_t seed, uint64_t stream_id, float* probs,
                       float* value, float* action_out, float* logp_out, hipStream_t st) {
-#ifndef DDRL_HEADS_ACT_WAVES
-#define DDRL_HEADS_ACT_WAVES 1
-#endif
   // register-resident head weights (A <= 8): ONE wave per workgroup, so that the samples of a small acting batch spread over the CUs (each
   // wave pulls 57 KB of split-K partials through its CU's path to L2; four per CU were 64 busy CUs of 256); A > 8 shares the LDS copy of
   // the head weights between four waves
   const bool small = c.L->A <= MAXA_SMALL;
-  const int wpw = small ? DDRL_HEADS_ACT_WAVES : 4;
+  const int wpw = small ? 1 : 4;
   int wgs = (c.n + wpw - 1) / wpw;
   if (wgs > 1024) wgs = 1024;
   const int nsplit = c.plain_features ? 1 : fc_forward_splits(c.n);

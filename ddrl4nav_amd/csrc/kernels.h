@@ -51,7 +51,7 @@ void launch_backward_amax_reset(const EncCall& c, hipStream_t st);  // zeroes th
 // fc2.hip (v2 engine)
 // Split-K factor of the FC forward for a batch of n samples (1 = plain; >1 only on the acting
 // path, where heads_act sums the partials).  7 k-blocks of 32 per split.
-inline int fc_forward_splits(int n) { return n <= 1024 ? DDRL_FC_ACT_SPLITS : 1; }
+inline int fc_forward_splits(int n) { return n <= 1024 ? FC_ACT_SPLITS : 1; }
 void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool per_sample_max = false);
 void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int part = 0);
 
@@ -60,7 +60,7 @@ void launch_conv_forward2(const EncCall& c, bool acting, hipStream_t st);
 
 // act.hip: conv1 + conv2 + conv3 of an acting forward in one launch, one workgroup per (sample, encoder); leaves a3 and every sample's
 // largest |a3| (Workspace::actmax), which the dense layer's split launch takes its plane scale from
-// (DDRL_ACT_FUSED_MAX: common.h, next to the carve of Workspace::actmax)
+// (ACT_FUSED_MAX: common.h, next to the carve of Workspace::actmax)
 void launch_act_convs(const EncCall& c, hipStream_t st);
 void launch_conv_dgrad3_2(const EncCall& c, hipStream_t st);
 void launch_conv_dgrad2_2(const EncCall& c, hipStream_t st);

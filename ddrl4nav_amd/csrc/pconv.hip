@@ -29,25 +29,6 @@
 #include "engine2.h"
 #include "ops.h"
 
-#ifdef DDRL_PLANES_BF16
-// The three-plane build (bf16x6) keeps the f32-input kernels of dconv.hip for these layers: three planes per operand do not fit the LDS
-// budgets of the tiles below.  Every query answers "no", nothing launches.
-namespace ddrl {
-bool conv_has_planes(const ConvGeom&) { return false; }
-bool conv_planes_has_pool(const ConvGeom&) { return false; }
-int64_t conv_planes_pack_floats(const ConvGeom&) { return 0; }
-int conv_planes_wgrad_splits(const ConvGeom&) { return 0; }
-void launch_sample_amax(const float*, int64_t, int, int, float*, hipStream_t, int) {}
-void launch_conv_planes_pack(const ConvGeom&, const float*, float*, float*, hipStream_t) {}
-void launch_conv_planes_fwd(const ConvGeom&, const float*, const float*, float*, const float*, int, float*, hipStream_t) {}
-void launch_conv_planes_dgrad(const ConvGeom&, const float*, const float*, float*, float*, hipStream_t) {}
-void launch_conv_planes_wgrad(const ConvGeom&, const float*, const float*, float*, float*, float*, hipStream_t) {}
-void launch_conv_planes_fwd_pool(const ConvGeom&, const float*, const float*, float*, const float*, const float*, float*, uint8_t*, float*, hipStream_t) {}
-void launch_conv_planes_dgrad_pooled(const ConvGeom&, const float*, const uint8_t*, const float*, float*, const float*, float*, float*, hipStream_t) {}
-void launch_conv_planes_wgrad_pooled(const ConvGeom&, const float*, const float*, const uint8_t*, const float*, const float*, float*, float*, float*,
-                                     hipStream_t) {}
-}  // namespace ddrl
-#else
 namespace ddrl {
 
 namespace pconv {
@@ -133,11 +114,9 @@ __global__ __launch_bounds__(256) void pack_planes_kernel(const float* __restric
 // UNPOOL (data gradient of such a layer): `in` is d(pooled) [CIN][HIN / 2][HIN / 2] and `ucode` the layer's decision bytes; the
 // staging forms d(pre-activation) on the fly -- the pooled gradient at the window's first maximum under the ReLU's sign, zero
 // elsewhere (gconv.hip maxpool2_bwd_idx_kernel) -- so the full-resolution gradient is never written or read either.
-#ifndef DDRL_PC_OCC2
-#define DDRL_PC_OCC2 1  // four-wave geometries: ask for two waves per SIMD (<= 256 registers), i.e. two RESIDENT workgroups per CU
-#endif
+// four-wave geometries: ask for two waves per SIMD (<= 256 registers), i.e. two RESIDENT workgroups per CU
 template <class K, bool POOL = false, bool UNPOOL = false>
-__global__ __launch_bounds__(K::THREADS, (DDRL_PC_OCC2 && K::THREADS <= 256) ? 2 : 1) void direct_planes_kernel(const float* __restrict__ in, int64_t in_sn, const unsigned short* __restrict__ wp,
+__global__ __launch_bounds__(K::THREADS, K::THREADS <= 256 ? 2 : 1) void direct_planes_kernel(const float* __restrict__ in, int64_t in_sn, const unsigned short* __restrict__ wp,
                                                                    const float* __restrict__ whdr, const float* __restrict__ amax,
                                                                    const float* __restrict__ bias, int act, float* __restrict__ out,
                                                                    int64_t out_sn, uint8_t* __restrict__ code,
@@ -276,7 +255,6 @@ __global__ __launch_bounds__(K::THREADS, (DDRL_PC_OCC2 && K::THREADS <= 256) ? 2
 #pragma unroll
           for (int j = 0; j < K::TN; ++j) bfr[p][j] = *(const frag8*)(ldsp + bB[j] + rowoff + toff + p * K::IMG_PLANE);
         }
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -395,9 +373,6 @@ __global__ __launch_bounds__(K::THREADS, (DDRL_PC_OCC2 && K::THREADS <= 256) ? 2
 // largest of the per-sample maxima the pre-pass leaves): a sum over samples is accurate in the absolute sense, relative to its
 // largest contribution.  The bias gradient (sum of dz) rides along in fp32 from the staging registers (ic block 0 only).
 // ================================================================================================
-#ifndef DDRL_PW_KO
-#define DDRL_PW_KO 0  // wgrad_planes_kernel timing knock-outs (1: staging only, 2: matrix work only; tools/build_variant.sh)
-#endif
 // (Round 5 also measured the taps of a stage as a software-pipelined sequence -- fragments of tap t + 1 requested before the MFMAs of
 // tap t, pinned with sched_group_barrier --: no gain, and one pinned region over a whole stage took hipcc 11 minutes; profiles/README.md.)
 using s4w = __attribute__((ext_vector_type(4))) short;
@@ -603,13 +578,11 @@ __global__ __launch_bounds__(256) void wgrad_planes_kernel(const float* __restri
     if (st_begin + 1 < st_end) fetch(st_begin + 1);
     __syncthreads();
     for (int st = st_begin; st < st_end; ++st) {
-#if DDRL_PW_KO != 1   // timing-only knock-out 1: no fragment reads, no matrix instructions (results are WRONG)
 #pragma unroll
       for (int g = 0; g < K::NKG; ++g) {
         frag8 a[NPL];
 #pragma unroll
         for (int p = 0; p < NPL; ++p) a[p] = tr_frag(ldsw, a_lane + p * K::A_PLANE + g * 2048, a_lane + p * K::A_PLANE + g * 2048 + 512);
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int t = 0; t < K::NT; ++t) {
           const int tap = K::ICW == 64 ? t : wx * K::NT + t;   // ICW = 32: the wave's half of the taps (wx is wave-uniform)
@@ -622,14 +595,11 @@ __global__ __launch_bounds__(256) void wgrad_planes_kernel(const float* __restri
           for (int m = 0; m < NPROD; ++m) acc[t] = mfma_planes(a[PA[m]], b[PB[m]], acc[t]);
         }
       }
-#endif
       __syncthreads();  // every wave is done with the stage
-#if DDRL_PW_KO != 2   // timing-only knock-out 2: the first stage is multiplied again and again (no loads, no splits, no LDS stores)
       if (st + 1 < st_end) {
         commit(st + 1);
         if (st + 2 < st_end) fetch(st + 2);
       }
-#endif
       __syncthreads();
     }
   }
@@ -672,34 +642,16 @@ __global__ __launch_bounds__(256) void wgrad_planes_kernel(const float* __restri
 // four waves x 7 tiles: 25 of 28 used, 224 accumulators, 94-111 KB of LDS -> ONE workgroup per CU) against one / four samples on
 // four waves x 4 tiles (400 of 512 columns, 128 accumulators, 57-62 KB -> TWO workgroups per CU): the second is faster although it
 // issues 14 % more matrix instructions (5x5 forward 4.29 -> 4.12 ms, 3x3 data gradient 1.81 -> 1.59 ms per 4,096 samples): at one
-// workgroup per CU nothing covers the barriers and commits of a k-block.  -DDDRL_PC_WIDE=1 selects the wide tiles.
+// workgroup per CU nothing covers the barriers and commits of a k-block: the wide tiles were not kept.
 // Later in the round: the 3x3 @10 layer with FIVE samples per workgroup (500 of 512 columns, 59 KB; nav iteration 23.39 -> 23.05 ms).
 // Then the register count: the four-wave kernels compiled to 320-370 registers, so that in spite of their LDS footprint only ONE
 // workgroup per CU was ever resident.  With the allocator asked for two waves per SIMD (launch bounds; 234-256 registers, no spills but
 // 38 in the 5x5 data gradient) two really are: nav iteration 22.71 -> 21.89 ms.  Under it the 5x5 forward on four waves x two tile pairs
 // (3.41 ms) beats the seven-wave form that had won before (3.54; 4.04 -> 3.70 against the one-resident-workgroup four-wave form).
-#ifndef DDRL_PC_WIDE
-#define DDRL_PC_WIDE 0
-#endif
-#if DDRL_PC_WIDE
-using PN1dC2F = pconv::Geo<64, 128, 5, 22, 1, 2, 4, 7, 5>;    // 2 x 400 columns = 25 of 28 column tiles
-using PN1dC3F = pconv::Geo<128, 256, 3, 10, 1, 8, 4, 7, 3>;   // 8 x 100 columns
-using PN1dC3D = pconv::Geo<256, 128, 3, 10, 1, 8, 4, 7, 3>;
-#else
-#ifndef DDRL_PC2_W7
-#define DDRL_PC2_W7 0  // 1: seven waves x one tile pair (400 of 448 columns); see the A/B notes below
-#endif
-#if DDRL_PC2_W7
-using PN1dC2F = pconv::Geo<64, 128, 5, 22, 1, 1, 7, 2, 5>;    // 400 of 448 columns, seven waves x one tile pair
-#else
-using PN1dC2F = pconv::Geo<64, 128, 5, 22, 1, 1, 4, 4, 5>;    // 400 of 512 columns
-#endif
-#ifndef DDRL_PC3_NS
-#define DDRL_PC3_NS 5  // samples per workgroup of the 3x3 @10 layer: 5 x 100 = 500 of 512 columns (4: 400 of 512)
-#endif
-using PN1dC3F = pconv::Geo<128, 256, 3, 10, 1, DDRL_PC3_NS, 4, 4, 3>;
-using PN1dC3D = pconv::Geo<256, 128, 3, 10, 1, DDRL_PC3_NS, 4, 4, 3>;
-#endif
+using PN1dC2F = pconv::Geo<64, 128, 5, 22, 1, 1, 4, 4, 5>;    // 400 of 512 columns (seven waves x one tile pair, 400 of 448: not kept, above)
+constexpr int PC3_NS = 5;  // samples per workgroup of the 3x3 @10 layer: 5 x 100 = 500 of 512 columns (4: 400 of 512)
+using PN1dC3F = pconv::Geo<128, 256, 3, 10, 1, PC3_NS, 4, 4, 3>;
+using PN1dC3D = pconv::Geo<256, 128, 3, 10, 1, PC3_NS, 4, 4, 3>;
 using PN1dC2D = pconv::Geo<128, 64, 5, 20, 3, 1, 4, 4, 5>;    // 484 of 512 columns
 using PNavC2F = pconv::Geo<64, 128, 3, 24, 1, 1, 6, 3, 3>;    // 576 columns = 18 column tiles
 using PNavC2D = pconv::Geo<128, 64, 3, 24, 1, 1, 6, 3, 3>;
@@ -717,11 +669,6 @@ using PAtC3D = pconv::Geo<64, 64, 3, 7, 2, 3, 4, 2, 9>;
 enum PlanesId { kPNone = -1, kPN1dC2, kPN1dC3, kPNavC2, kPNavC3, kPAtC3 };
 
 static PlanesId planes_id(const ConvGeom& g) {
-#ifdef DDRL_PLANES_BF16
-  // the three-plane diagnostic build (accuracy attribution only, never the shipped library) has no specialised plane kernels: every
-  // nav layer then runs on the generic gather kernels of gconv.hip (f32 inputs, three bf16 planes: several times slower)
-  return kPNone;
-#else
   if (g.stride != 1 || g.h != g.w || g.kh != g.kw || g.pad_h != g.pad_w) return kPNone;
   const auto is = [&](int cin, int cout, int ks, int h) { return g.cin == cin && g.cout == cout && g.kh == ks && g.h == h; };
   if (g.pad_h == 0) return is(64, 64, 3, 9) ? kPAtC3 : kPNone;
@@ -731,7 +678,6 @@ static PlanesId planes_id(const ConvGeom& g) {
   if (is(64, 128, 3, 24)) return kPNavC2;
   if (is(128, 256, 3, 12)) return kPNavC3;
   return kPNone;
-#endif
 }
 
 bool conv_has_planes(const ConvGeom& g) { return planes_id(g) != kPNone; }
@@ -804,17 +750,12 @@ static void run_planes_unpool(const float* dpool, const uint8_t* ucode, const fl
 
 // conv + ReLU + max_pool2d(2) in one launch for the layers whose tiles allow it (four column tiles per wave)
 bool conv_planes_has_pool(const ConvGeom& g) {
-#if DDRL_PC_WIDE
-  return false;
-#else
   const PlanesId id = planes_id(g);
   return id == kPN1dC2 || id == kPN1dC3 || id == kPNavC2 || id == kPNavC3;
-#endif
 }
 
 void launch_conv_planes_fwd_pool(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* given, const float* bias,
                                  float* pooled, uint8_t* code, float* out_amax, hipStream_t st) {
-#if !DDRL_PC_WIDE
   const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
   switch (planes_id(g)) {
     case kPN1dC2: run_planes_pool<PN1dC2F>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
@@ -823,7 +764,6 @@ void launch_conv_planes_fwd_pool(const ConvGeom& g, const float* in, const float
     case kPNavC3: run_planes_pool<PNavC3FP>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
     default: break;
   }
-#endif
 }
 
 void launch_conv_planes_fwd(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* bias, int act, float* out,
@@ -918,7 +858,6 @@ static void run_planes_wgrad_pooled(const ConvGeom& g, const float* in, const fl
 // weight / data gradient of a pooled layer straight from d(pooled) + decision bytes (the layers of conv_planes_has_pool)
 void launch_conv_planes_wgrad_pooled(const ConvGeom& g, const float* in, const float* dpool, const uint8_t* ucode, const float* given_in,
                                      const float* given_dp, float* part, float* dw, float* db, hipStream_t st) {
-#if !DDRL_PC_WIDE
   const int S = conv_planes_wgrad_splits(g);
   const int KT = g.cin * g.kh * g.kw;
   const int64_t slab = (int64_t)g.cout * KT + g.cout;
@@ -931,12 +870,10 @@ void launch_conv_planes_wgrad_pooled(const ConvGeom& g, const float* in, const f
     default: return;
   }
   launch_reduce_slabs2(part, S, slab, (int64_t)g.cout * KT, dw, g.cout, db, st);
-#endif
 }
 
 void launch_conv_planes_dgrad_pooled(const ConvGeom& g, const float* dpool, const uint8_t* ucode, const float* wpd, float* scales, const float* given,
                                      float* din, float* out_amax, hipStream_t st) {
-#if !DDRL_PC_WIDE
   const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
   switch (planes_id(g)) {
     case kPN1dC2: run_planes_unpool<PN1dC2D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
@@ -945,7 +882,6 @@ void launch_conv_planes_dgrad_pooled(const ConvGeom& g, const float* dpool, cons
     case kPNavC3: run_planes_unpool<PNavC3D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
     default: break;
   }
-#endif
 }
 
 // part: S slabs of COUT * KT + COUT floats, then 2 n floats of scratch for the per-sample scales
@@ -966,4 +902,3 @@ void launch_conv_planes_wgrad(const ConvGeom& g, const float* in, const float* d
 }
 
 }  // namespace ddrl
-#endif  // DDRL_PLANES_BF16

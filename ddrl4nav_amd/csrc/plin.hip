@@ -187,7 +187,6 @@ __global__ __launch_bounds__(256, 2) void nt_planes_kernel(NtParams P) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) bf[p][j] = *(const frag8*)(cur + bB[j] + (g * NPL + p) * 4096);
         }
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -378,7 +377,6 @@ __global__ __launch_bounds__(256, 2) void tn_planes_kernel(TnParams P) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) bf[p][j] = tr_frag(cur, bB[j] + p * 8192 + g * 4096, bB[j] + p * 8192 + g * 4096 + 1024);
         }
-        DDRL_PLANE_PRODUCTS;
 #pragma unroll
         for (int m = 0; m < NPROD; ++m)
 #pragma unroll
@@ -422,17 +420,9 @@ __global__ __launch_bounds__(256, 2) void tn_planes_kernel(TnParams P) {
 }  // namespace plin
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static bool planes_off() {
-#ifdef DDRL_PLANES_BF16
-  return true;
-#else
-  return false;
-#endif
-}
-
 // Layers deep and wide enough for 128 x 128 x 32 tiles; launches of fewer than 128 rows (acting with a few environments) stay on the
 // f32-input kernels, whose split-K fills the chip from one row tile.
-bool linear_has_planes(int K, int N) { return !planes_off() && K >= 128 && N >= 64; }
+bool linear_has_planes(int K, int N) { return K >= 128 && N >= 64; }
 bool linear_uses_planes(int n, int K, int N) { return linear_has_planes(K, N) && n >= 128; }
 
 static int kgs_of(int red) { return 2 * ((red + 31) / 32); }

@@ -567,9 +567,9 @@ def test_dense_weight_gradient_is_at_least_fp32_accurate(hp, kind):
 @pytest.mark.parametrize("n", [101, 6])
 @pytest.mark.parametrize("kind", ["uniform", "pong_wide"])
 def test_conv3_weight_gradient_is_at_least_fp32_accurate(hp, n, kind):
-    """conv_wgrad3_planes_kernel (dz3 and a2 staged channel-innermost as two scaled fp16 planes each, fragments through the
-    transposing LDS read, 2 samples per stage, 128 sample splits summed in fixed order): given the kernel's own dz3 and
-    a2, dW3 and db3 against float64, beside torch's fp32 weight gradient.  n = 101 leaves a one-sample last stage and
+    """conv_wgrad3_pipe_kernel (dz3 and a2 staged channel-innermost as two scaled fp16 planes each, fragments through the
+    transposing LDS read, 2 samples per turn in two half-stages, 128 sample splits summed in fixed order): given the kernel's own
+    dz3 and a2, dW3 and db3 against float64, beside torch's fp32 weight gradient.  n = 101 leaves a one-sample last turn and
     most of the 128 splits empty; n = 6 leaves all but three empty."""
     _bwd_setup(hp, n, 45, kind)
     got = _grad_views(hp)
@@ -591,8 +591,8 @@ def test_conv3_weight_gradient_is_at_least_fp32_accurate(hp, n, kind):
 @pytest.mark.parametrize("n", [77, 3])
 @pytest.mark.parametrize("kind", ["uniform", "pong_wide"])
 def test_conv2_weight_gradient_is_at_least_fp32_accurate(hp, n, kind):
-    """conv_wgrad2_planes_kernel (dz2 and a1 staged channel-innermost as two scaled fp16 planes each, one sample per stage,
-    fragments through the transposing LDS read): given the kernel's own dz2 and a1, dW2 and db2 against float64."""
+    """conv_wgrad2_pipe_kernel (dz2 and a1 staged channel-innermost as two scaled fp16 planes each, one sample per turn in two
+    half-stages, fragments through the transposing LDS read): given the kernel's own dz2 and a1, dW2 and db2 against float64."""
     _bwd_setup(hp, n, 46, kind)
     got = _grad_views(hp)
     g = torch.nn.grad

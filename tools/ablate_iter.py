@@ -3,7 +3,7 @@ kernel experiments recorded in profiles/README.md.  Usage: python tools/ablate_i
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddrl4nav_amd import _lib
-if os.environ.get("DDRL_ABL_LIB"): _lib.LIB_PATH = os.environ["DDRL_ABL_LIB"]  # knock-out builds of tools/ablate_engine.sh
+if os.environ.get("DDRL_ABL_LIB"): _lib.LIB_PATH = os.environ["DDRL_ABL_LIB"]  # a library build under tools/_scratch_abl/ (tools/build_variant.sh)
 from ddrl4nav_amd.engine import HotPath
 from ddrl4nav_amd.utils.recipe import flatten, make_weights
 B=65536

@@ -1,7 +1,7 @@
 """Per-iteration deviation of the HIP learner from the reference on the F4 learn fixture (B = 64, ten PPO iterations):
 losses against the stored fp32 run and against the float64 run, beside the reference's own spread, and the parameter
 deviation ratios of tests/parity_util.py after every iteration.  A/B of library builds through DDRL_ABL_LIB
-(e.g. a -DDDRL_PLANES_BF16 build under tools/_scratch_abl/).  Test infrastructure: uses the oracle as the checker.
+(e.g. a build of another commit under tools/_scratch_abl/).  Test infrastructure: uses the oracle as the checker.
 Usage: python tools/diag_f4_traj.py [tag] [mode: default|shared|smooth]"""
 import os
 import sys
