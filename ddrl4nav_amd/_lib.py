@@ -72,6 +72,7 @@ SIGNATURES = {
     "ddrl_gae": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
                            c_void_p]),
     "ddrl_episode_returns": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_frame_stack_push": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ddrl_ppo_iter": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,
                                 c_void_p]),
     "ddrl_clip_adam_step": (c_int32, [c_void_p, c_void_p]),

@@ -6,7 +6,9 @@ Pool layout (all on the GPU, [time][env] major so that GAE loads are coalesced a
   frames  uint8 [T+1, N, C, 84, 84]    values f32 [T+1, N]     rewards f32 [T, N]
   actions f32 [T, N]   logps f32 [T, N]   dones u8 [T, N]      adv / ret f32 [T, N]
 Frames arrive either as device tensors or through a pinned-host ring (data/ring.py) with
-hipMemcpyAsync on a copy stream, overlapping the previous step's forward.
+hipMemcpyAsync on a copy stream, overlapping the previous step's forward.  A slot is filled either with the whole stack
+(put_frames*) or from ONE new frame per env (put_new_frames*): csrc/fstack.hip then builds slot t from slot t-1 on the device,
+as the reference's FrameStackWrapper does on the host, and a quarter of the bytes cross PCIe at C = 4.
 
 Carry-over between rollouts (reference agent.py:286-292: ``rewards_step[0] = rewards_step[T]; exps = [exps[-1]]``): the
 reference keeps the WHOLE (T+1)-th Experience -- state, the action already sent to the env, its old log-prob, its value
@@ -21,6 +23,7 @@ import torch
 from ddrl4nav_amd.agent.agent import gae_device
 from ddrl4nav_amd.agent.statistics import EpisodeReturns
 from ddrl4nav_amd.data import Experience
+from ddrl4nav_amd.ops import frame_stack_push
 from ddrl4nav_amd.utils.staging import copy_into
 
 
@@ -49,6 +52,11 @@ class DeviceRollout:
         self.t0 = 0  # first step the next rollout has to act on: 1 after carry_over(keep_step=True), else 0
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.returns = EpisodeReturns(N, dev) if track_returns else None
+        # single-frame ingest (put_new_frames*): allocated at first use, a host that ships whole stacks pays nothing
+        self._newest = None                # uint8 [3, N, 84, 84]: 0 / 1 the ring's DMA targets (step parity), 2 put_new_frames' copy
+        self._reset_buf = None             # uint8 [2, N]: 0 a caller's reset flags brought to the device, 1 all ones (reset=True)
+        self._pushed = [None, None]        # events: the push kernel that read _newest[parity] is through
+        self._ring_rollout = -1            # the rollout (self.rollouts) whose first single-frame ring put ordered the copy stream
 
     # ---- ingest ---------------------------------------------------------------------------------
     def put_frames(self, t, frames):
@@ -65,6 +73,71 @@ class DeviceRollout:
             self.copy_stream.wait_stream(torch.cuda.current_stream())
         ring.pop_to(self.frames[t], stream=self.copy_stream)
         torch.cuda.current_stream().wait_stream(self.copy_stream)
+
+    def _single_frame_buffers(self):
+        if self._newest is None:
+            self._newest = torch.empty((3, self.N, 84, 84), dtype=torch.uint8, device=self.device)
+            self._reset_buf = torch.ones((2, self.N), dtype=torch.uint8, device=self.device)
+        return self._newest
+
+    def _reset_flags(self, t, reset):
+        """Checks (t, reset) of a single-frame put and returns the device flags [N] (or None).  reset: None = the dones recorded for step
+        t-1, True = every env, False = none, else flags [N] (non-zero = reset)."""
+        if t < self.t0:
+            raise ValueError("step %d was carried over from the previous rollout with its frames" % t)
+        if t == 0 and reset is not True:
+            raise ValueError("slot 0 has no previous stack: the first observation of a run is put with reset=True "
+                             "(after carry_over() slot 0 already holds the carried stack and the next put is t == 1)")
+        if reset is None:
+            return self._dones[t - 1]
+        if reset is True:
+            return self._reset_buf[1]
+        if reset is False:
+            return None
+        r = torch.as_tensor(reset)
+        if r.is_cuda and r.dtype == torch.uint8 and r.is_contiguous() and r.device == self.device:
+            return r
+        return copy_into(self._reset_buf[0], r)
+
+    def _push(self, t, newest, flags):
+        """frames[t] <- frames[t-1] shifted by one plane + `newest` (csrc/fstack.hip), on the current stream."""
+        # t == 0: every env is reset, the previous stack is read but never used (row T: any slot other than the one being written)
+        prev = self.frames[t - 1 if t > 0 else self.T] if self.C > 1 else None
+        frame_stack_push(prev, newest, flags, self.frames[t])
+
+    def put_new_frames(self, t, newest, reset=None):
+        """ONE new frame per env, uint8 [N,84,84] (device or pinned host) -> pool slot t, whose other planes are slot t-1's shifted by
+        one: FrameStackWrapper (warputils.py:112-131) on the device.  reset=None: the envs whose done was recorded for step t-1 start a
+        new stack (the natural order is act(t-1) -> env step -> record(t-1, r, d) -> put_new_frames(t, obs)); a tensor [N] overrides the
+        recorded dones; reset=True: every env (the first observation of a run, the only legal call for t == 0)."""
+        buf = self._single_frame_buffers()
+        flags = self._reset_flags(t, reset)
+        n = torch.as_tensor(newest)
+        direct = (n.is_cuda and n.dtype == torch.uint8 and n.is_contiguous() and n.device == self.device and n.data_ptr() % 16 == 0
+                  and tuple(n.shape) == (self.N, 84, 84))
+        self._push(t, n if direct else copy_into(buf[2], n), flags)
+
+    def put_new_frames_from_ring(self, t, ring, reset=None):
+        """put_new_frames with the frame taken from a pinned ring whose slots hold N * 7056 bytes: hipMemcpyAsync on the copy stream into
+        one of two staging buffers (step parity), the compute stream waits for it and runs the push kernel.  Ordered with events only, so
+        copy t + 1 still runs under forward t: the DMA of step t waits for the last push kernel that read the same staging
+        buffer (step t - 2's); and the FIRST such put of a rollout, at whatever t (slot 1 after the default carry_over()), orders the copy stream
+        behind everything the compute stream holds at that moment."""
+        buf = self._single_frame_buffers()
+        flags = self._reset_flags(t, reset)           # before the ring is touched: a refused call consumes no slot
+        cur = torch.cuda.current_stream()
+        k = t & 1
+        if self._ring_rollout != self.rollouts:     # finish() counts the rollouts: one wait per rollout, none per slot
+            self.copy_stream.wait_stream(cur)
+            self._ring_rollout = self.rollouts
+        if self._pushed[k] is None:
+            self._pushed[k] = torch.cuda.Event()
+        else:
+            self.copy_stream.wait_event(self._pushed[k])
+        ring.pop_to(buf[k], stream=self.copy_stream)
+        cur.wait_stream(self.copy_stream)
+        self._push(t, buf[k], flags)
+        self._pushed[k].record(cur)
 
     # ---- acting ---------------------------------------------------------------------------------
     def act(self, t):

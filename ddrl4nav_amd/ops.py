@@ -1,5 +1,6 @@
 """Thin ctypes wrappers of the operator-level C ABI (include/ddrl.h, ddrl_op_*): generic
-convolution, 2x2 max-pool and dense layers on torch-owned device buffers.  torch supplies memory
+convolution, 2x2 max-pool and dense layers on torch-owned device buffers, and the context-free
+frame-stack push (ddrl_frame_stack_push).  torch supplies memory
 and streams only; the arithmetic runs in csrc/gconv.hip and csrc/glinear.hip.  Used by
 ddrl4nav_amd.nn.generic to compose the reference's non-Atari encoders
 (USTC_lab/nn/nav_encoder.py, mlp_encoder.py)."""
@@ -22,6 +23,22 @@ def _st():
 def _f32(t):
     assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), "expected a contiguous fp32 device tensor"
     return t
+
+
+def frame_stack_push(prev, newest, reset, out):
+    """FrameStackWrapper.step / .reset on the device (include/ddrl.h, ddrl_frame_stack_push; csrc/fstack.hip): `out` [n,C,84,84] <- `prev`
+    [n,C,84,84] shifted by one plane with `newest` [n,84,84] as the last plane; envs whose `reset` byte ([n] uint8, or None) is not zero
+    get `newest` in every plane.  All uint8, contiguous, on one device; `prev` may be None when C == 1.  Asynchronous on the current
+    stream; returns `out`."""
+    n, C = out.shape[0], out.shape[1]
+    assert tuple(out.shape) == (n, C, 84, 84) and tuple(newest.shape) == (n, 84, 84), "expected [n,C,84,84] <- [n,84,84]"
+    for t in (prev, newest, reset, out):
+        assert t is None or (t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.device == out.device), \
+            "expected contiguous uint8 tensors on one device"
+    assert (prev is None and C == 1) or (prev is not None and tuple(prev.shape) == tuple(out.shape)), "prev must have out's shape"
+    assert reset is None or tuple(reset.shape) == (n,), "reset must be [n]"
+    check(_lib.load().ddrl_frame_stack_push(_p(prev), _p(newest), _p(reset), n, C, _p(out), _st()))
+    return out
 
 
 class Conv:

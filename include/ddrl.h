@@ -149,6 +149,17 @@ int32_t ddrl_gae(const float* values, const float* rewards, const uint8_t* dones
 int32_t ddrl_episode_returns(const float* rewards, const uint8_t* dones, int32_t T, int32_t N, float* rewards_sum,
                              float* rewards_episode, float* trace, int32_t* episodes_finished, void* stream);
 
+/* FrameStackWrapper.step / .reset (USTC_lab/env/gym_env/wrapper/warputils.py:112-131) on the device: the stacked observation of
+ * the next step from the current stack, ONE new frame per env and an optional per-env reset flag, in one streaming launch:
+ *   next[i][c] = newest[i]     for every c, when reset && reset[i] != 0   (.reset, :127-131, reached through NeverStopWrapper.step, :392-397)
+ *              = prev[i][c+1]  for c <  channels-1                        (deque append, :118-121: the oldest plane drops out)
+ *              = newest[i]     for c == channels-1                        (the newest plane is the LAST channel, :123-125)
+ *   prev / next uint8 [n, channels, 84, 84], newest uint8 [n, 84, 84], reset uint8 [n] or NULL; channels 1..4 (1: next = newest,
+ *   prev is not read).  prev, newest and next 16-byte aligned; next overlaps neither prev nor newest.  Needs no context, allocates
+ *   nothing, asynchronous on `stream`; the argument checks run before anything touches HIP.  Added after round 6 (additive: ABI 3). */
+int32_t ddrl_frame_stack_push(const uint8_t* prev, const uint8_t* newest, const uint8_t* reset, int32_t n, int32_t channels,
+                              uint8_t* next, void* stream);
+
 /* One iteration of the loss + backward half of PPO.learn (ppo.py:82-126, non-shared branch):
  * forward both encoders on B samples, dual-clip surrogate / value / entropy terms, backward
  * into the grad arena.  Gradients and loss sums are scaled by 1/B_global so that a SUM over
