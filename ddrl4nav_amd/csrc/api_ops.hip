@@ -372,8 +372,9 @@ int32_t ddrl_op_heads_act(const ddrl_heads_desc* d, const float* params, const f
   if (!aligned16(h_actor) || !aligned16(h_critic)) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (d->continuous) {
-    launch_gauss_act(gauss_layout(d), params, h_actor, h_critic, n, act_in, seed, stream_id, dist_out, value, action_out,
-                     logp_out, st);
+    // shared prenet: both heads read h_actor (include/ddrl.h), as in ddrl_op_heads_loss and the categorical path below
+    launch_gauss_act(gauss_layout(d), params, h_actor, d->shared ? h_actor : h_critic, n, act_in, seed, stream_id, dist_out, value,
+                     action_out, logp_out, st);
     return op_check();
   }
   ParamLayout L = cat_layout(d);
