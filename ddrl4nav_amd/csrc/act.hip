@@ -284,8 +284,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
       }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) big = fmaxf(big, __shfl_xor(big, off, 64));
+    big = wave_fmax(big);
     if (lane == 0) wmax[w] = big;
   }
   __syncthreads();  // the maxima are there, every wave has read its hand-over: the a2 planes go over it
@@ -372,8 +371,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
       }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) big = fmaxf(big, __shfl_xor(big, off, 64));
+    big = wave_fmax(big);
     if (lane == 0) wmax[8 + w] = big;
   }
   __syncthreads();
@@ -390,12 +388,8 @@ void launch_act_convs(const EncCall& c, hipStream_t st) {
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
   const int64_t MB = c.max_batch;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)act_convs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)act_convs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<act_convs_kernel<false>>((int)K::LDS_BYTES);
+  lds_limit_once<act_convs_kernel<true>>((int)K::LDS_BYTES);
   ActArgs a{c.frames, w.wp1b, w.wp2b, w.wp3b, w.amax, c.params,
             {L.enc_base[0] + L.enc.c1b, L.enc_base[L.NE - 1] + L.enc.c1b},
             {L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b},

@@ -26,22 +26,49 @@ static bool direct_ok(const ConvGeom& g, const void* in_side, const void* out_si
   return (g.in_sn & 3) == 0 && (g.out_sn & 3) == 0 && aligned16(in_side) && aligned16(out_side);
 }
 
+// The one place that asks the specialised families about a geometry.  Precedence: c1d over first over planes; their geometry sets are
+// disjoint today (c1d: h = 1; first: 48 x 48 inputs; planes: 9 .. 24), so at most one predicate holds and the order only matters for a
+// future overlap.  A new specialised layer of an existing family changes nothing here; a new family adds an arm.
+ConvRoute ddrl::conv_route(const ConvGeom& g) {
+  ConvRoute r{kConvGather, false, true, 0, 0, conv_wgrad_splits(g), 0, 0};
+  int splits = 0;
+  if (conv_has_c1d(g)) {  // c1d.hip: transposed weights for the scalar cache; the epilogue of its forward handles out_amax
+    r.family = kConvC1d;
+    r.backward = conv_has_c1d_backward(g);
+    r.pack5 = r.pack6 = conv_c1d_pack_floats(g);
+    splits = conv_c1d_wgrad_splits(g);
+  } else if (conv_has_first(g)) {  // fconv.hip: forward weight planes only (a first layer has no data gradient); scales inside the kernels
+    r.family = kConvFirst;
+    r.pool = true;
+    r.pack5 = conv_first_pack_floats(g);
+    splits = conv_first_wgrad_splits(g);
+  } else if (conv_has_planes(g)) {  // pconv.hip: n floats of per-sample scales per launch, 2 n (+ alignment) behind the weight-gradient slabs
+    r.family = kConvPlanes;
+    r.pool = conv_planes_has_pool(g);
+    r.pack5 = r.pack6 = conv_planes_pack_floats(g);
+    splits = conv_planes_wgrad_splits(g);
+    r.scratch_floats = g.n;
+    r.ws_tail_floats = 2 * (int64_t)g.n + 64;
+  }
+  if (splits > r.wgrad_splits) r.wgrad_splits = splits;  // a call may still take the gather kernels: ws holds the larger
+  return r;
+}
+
+// the family that serves one call: the geometry's, or the gather kernels when the call's view rules out the 16-byte loads of the
+// plane / first-layer kernels (c1d.hip loads single floats)
+static ConvFamily family_for(const ConvRoute& r, bool direct) { return (direct || r.family == kConvC1d) ? r.family : kConvGather; }
+
 // regions of a layer's packed buffer: 0-4 gather layouts + tables (gconv.hip), 5 / 6 the specialised forward / data-gradient layouts
 // of the layers that have them (pconv.hip / fconv.hip fp16 planes + header, c1d.hip transposed weights).  Read-only after ddrl_op_conv_pack;
 // nothing in it depends on the batch size of a call (the per-sample scales of a launch live in the caller's scales_scratch).
 struct PackView {
   int64_t off[7], total;
 };
-static PackView pack_view(const ConvGeom& g) {
+static PackView pack_view(const ConvGeom& g, const ConvRoute& r) {
   int64_t sz[7];
   conv_pack_sizes(g, sz);
-  sz[5] = sz[6] = 0;
-  if (conv_has_planes(g)) sz[5] = sz[6] = conv_planes_pack_floats(g);
-  if (conv_has_c1d(g)) sz[5] = sz[6] = conv_c1d_pack_floats(g);  // c1d.hip: transposed weights for the scalar cache
-  if (conv_has_first(g)) {  // fconv.hip: forward weight planes only (a first layer has no data gradient)
-    sz[5] = conv_first_pack_floats(g);
-    sz[6] = 0;
-  }
+  sz[5] = r.pack5;
+  sz[6] = r.pack6;
   PackView v;
   int64_t o = 0;
   for (int i = 0; i < 7; ++i) {
@@ -65,41 +92,38 @@ int32_t ddrl_op_conv_out_shape(const ddrl_conv_desc* d, int32_t* oh, int32_t* ow
 int32_t ddrl_op_conv_pack_floats(const ddrl_conv_desc* d, int64_t* floats) {
   ConvGeom g;
   if (!fill_geom(d, g) || !floats) return DDRL_ERR_INVALID_ARG;
-  *floats = pack_view(g).total;
+  *floats = pack_view(g, conv_route(g)).total;
   return DDRL_OK;
 }
 
 int32_t ddrl_op_conv_pack(const ddrl_conv_desc* d, const float* w, float* packed, void* stream) {
   ConvGeom g;
   if (!fill_geom(d, g) || !w || !packed || !aligned16(packed)) return DDRL_ERR_INVALID_ARG;
-  const PackView v = pack_view(g);
+  const ConvRoute r = conv_route(g);
+  const PackView v = pack_view(g, r);
   launch_conv_pack(g, w, packed + v.off[0], (int2*)(packed + v.off[1]), packed + v.off[2], (int2*)(packed + v.off[3]),
                    (int*)(packed + v.off[4]), (hipStream_t)stream);
-  if (conv_has_c1d(g))
-    launch_conv_c1d_pack(g, w, packed + v.off[5], packed + v.off[6], (hipStream_t)stream);
-  else if (conv_has_first(g))
-    launch_conv_first_pack(g, w, packed + v.off[5], (hipStream_t)stream);
-  else if (conv_has_planes(g))
-    launch_conv_planes_pack(g, w, packed + v.off[5], packed + v.off[6], (hipStream_t)stream);
+  switch (r.family) {
+    case kConvC1d: launch_conv_c1d_pack(g, w, packed + v.off[5], packed + v.off[6], (hipStream_t)stream); break;
+    case kConvFirst: launch_conv_first_pack(g, w, packed + v.off[5], (hipStream_t)stream); break;
+    case kConvPlanes: launch_conv_planes_pack(g, w, packed + v.off[5], packed + v.off[6], (hipStream_t)stream); break;
+    case kConvGather: break;
+  }
   return op_check();
 }
 
 int32_t ddrl_op_conv_scratch_floats(const ddrl_conv_desc* d, int64_t* floats) {
   ConvGeom g;
   if (!fill_geom(d, g) || !floats) return DDRL_ERR_INVALID_ARG;
-  *floats = conv_has_planes(g) ? (int64_t)g.n : 0;
+  *floats = conv_route(g).scratch_floats;
   return DDRL_OK;
 }
 
 int32_t ddrl_op_conv_ws_floats(const ddrl_conv_desc* d, int64_t* floats) {
   ConvGeom g;
   if (!fill_geom(d, g) || !floats) return DDRL_ERR_INVALID_ARG;
-  int splits = conv_wgrad_splits(g);
-  if (conv_planes_wgrad_splits(g) > splits) splits = conv_planes_wgrad_splits(g);
-  if (conv_first_wgrad_splits(g) > splits) splits = conv_first_wgrad_splits(g);
-  if (conv_c1d_wgrad_splits(g) > splits) splits = conv_c1d_wgrad_splits(g);
-  // + the per-sample scales of the plane kernels (pconv.hip): 2 n floats behind the slabs
-  *floats = (int64_t)splits * ((int64_t)g.cout * g.cin * g.kh * g.kw + g.cout) + (conv_has_planes(g) ? 2 * (int64_t)g.n + 64 : 0);
+  const ConvRoute r = conv_route(g);
+  *floats = (int64_t)r.wgrad_splits * ((int64_t)g.cout * g.cin * g.kh * g.kw + g.cout) + r.ws_tail_floats;
   return DDRL_OK;
 }
 
@@ -107,31 +131,32 @@ int32_t ddrl_op_conv_forward(const ddrl_conv_desc* d, const float* in, const flo
                              float* out, float* scales_scratch, float* out_amax, void* stream) {
   ConvGeom g;
   if (!fill_geom(d, g) || !in || !packed || !bias || !out || act < 0 || act > 1) return DDRL_ERR_INVALID_ARG;
-  const PackView v = pack_view(g);
-  if (conv_has_planes(g) && direct_ok(g, in, out) && !scales_scratch) return DDRL_ERR_INVALID_ARG;  // g.n floats (ddrl_op_conv_scratch_floats)
-  if (out_amax && !conv_has_c1d(g)) {
+  const ConvRoute r = conv_route(g);
+  const PackView v = pack_view(g, r);
+  const ConvFamily f = family_for(r, direct_ok(g, in, out));
+  if (f == kConvPlanes && !scales_scratch) return DDRL_ERR_INVALID_ARG;  // g.n floats (ddrl_op_conv_scratch_floats)
+  const bool amax_pass = out_amax && r.family != kConvC1d;
+  if (amax_pass) {
     // every other kernel family: the magnitudes come from a pass over the output just written (needs 16-byte loads of whole samples)
     const int64_t elems = (int64_t)g.cout * g.oh * g.ow;
     if ((elems & 3) || (g.out_sn & 3) || !aligned16(out)) return DDRL_ERR_INVALID_ARG;
   }
-  if (conv_has_c1d(g))
-    launch_conv_c1d_fwd(g, in, packed + v.off[5], bias, act, out, out_amax, (hipStream_t)stream);
-  else if (conv_has_first(g) && direct_ok(g, in, out))
-    launch_conv_first_fwd(g, in, packed + v.off[5], bias, act, out, (hipStream_t)stream);
-  else if (conv_has_first(g))
-    launch_conv_fwd(g, in, packed + v.off[0], (const int2*)(packed + v.off[1]), bias, act, out, (hipStream_t)stream);
-  else if (conv_has_planes(g) && direct_ok(g, in, out))
-    launch_conv_planes_fwd(g, in, packed + v.off[5], scales_scratch, bias, act, out, (hipStream_t)stream);
-  else   // any geometry, any stride / alignment (also the plane layers' when a strided view rules out their 16-byte loads)
-    launch_conv_fwd(g, in, packed + v.off[0], (const int2*)(packed + v.off[1]), bias, act, out, (hipStream_t)stream);
-  if (out_amax && !conv_has_c1d(g)) launch_sample_amax(out, g.out_sn, g.cout * g.oh * g.ow, g.n, out_amax, (hipStream_t)stream, 1);
+  switch (f) {
+    case kConvC1d: launch_conv_c1d_fwd(g, in, packed + v.off[5], bias, act, out, out_amax, (hipStream_t)stream); break;
+    case kConvFirst: launch_conv_first_fwd(g, in, packed + v.off[5], bias, act, out, (hipStream_t)stream); break;
+    case kConvPlanes: launch_conv_planes_fwd(g, in, packed + v.off[5], scales_scratch, bias, act, out, (hipStream_t)stream); break;
+    case kConvGather:  // any geometry, any stride / alignment
+      launch_conv_fwd(g, in, packed + v.off[0], (const int2*)(packed + v.off[1]), bias, act, out, (hipStream_t)stream);
+      break;
+  }
+  if (amax_pass) launch_sample_amax(out, g.out_sn, g.cout * g.oh * g.ow, g.n, out_amax, (hipStream_t)stream, 1);
   return op_check();
 }
 
 int32_t ddrl_op_conv_has_forward_pool(const ddrl_conv_desc* d) {
   ConvGeom g;
   if (!fill_geom(d, g)) return 0;
-  return (conv_has_first(g) || (conv_has_planes(g) && conv_planes_has_pool(g))) ? 1 : 0;
+  return conv_route(g).pool ? 1 : 0;
 }
 
 int32_t ddrl_op_sample_amax(const float* x, int64_t sn, int32_t elems, int32_t n, float* amax, void* stream) {
@@ -143,7 +168,8 @@ int32_t ddrl_op_sample_amax(const float* x, int64_t sn, int32_t elems, int32_t n
 int32_t ddrl_op_conv_pooled_uses_scales(const ddrl_conv_desc* d) {
   ConvGeom g;
   if (!fill_geom(d, g)) return 0;
-  return (!conv_has_first(g) && conv_has_planes(g) && conv_planes_has_pool(g)) ? 1 : 0;
+  const ConvRoute r = conv_route(g);
+  return (r.family == kConvPlanes && r.pool) ? 1 : 0;
 }
 
 int32_t ddrl_op_conv_forward_pool(const ddrl_conv_desc* d, const float* in, const float* packed, const float* bias, float* pooled,
@@ -151,14 +177,14 @@ int32_t ddrl_op_conv_forward_pool(const ddrl_conv_desc* d, const float* in, cons
   ConvGeom g;
   if (!fill_geom(d, g) || !in || !packed || !bias || !pooled || !code) return DDRL_ERR_INVALID_ARG;
   if ((g.in_sn & 3) || !aligned16(in)) return DDRL_ERR_INVALID_ARG;
-  if (!conv_has_first(g) && conv_has_planes(g) && !in_amax && !scales_scratch) return DDRL_ERR_INVALID_ARG;
-  const PackView v = pack_view(g);
-  if (conv_has_first(g))
+  const ConvRoute r = conv_route(g);
+  if (r.family == kConvPlanes && !in_amax && !scales_scratch) return DDRL_ERR_INVALID_ARG;  // also for a plane layer without the epilogue
+  if (!r.pool) return DDRL_ERR_UNSUPPORTED;  // the caller runs ddrl_op_conv_forward + ddrl_op_maxpool2_forward_idx
+  const PackView v = pack_view(g, r);
+  if (r.family == kConvFirst)
     launch_conv_first_fwd_pool(g, in, packed + v.off[5], bias, pooled, code, out_amax, (hipStream_t)stream);
-  else if (conv_has_planes(g) && conv_planes_has_pool(g))
-    launch_conv_planes_fwd_pool(g, in, packed + v.off[5], scales_scratch, in_amax, bias, pooled, code, out_amax, (hipStream_t)stream);
   else
-    return DDRL_ERR_UNSUPPORTED;  // the caller runs ddrl_op_conv_forward + ddrl_op_maxpool2_forward_idx
+    launch_conv_planes_fwd_pool(g, in, packed + v.off[5], scales_scratch, in_amax, bias, pooled, code, out_amax, (hipStream_t)stream);
   return op_check();
 }
 
@@ -167,8 +193,9 @@ int32_t ddrl_op_conv_dgrad_pooled(const ddrl_conv_desc* d, const float* dpool, c
   ConvGeom g;
   if (!fill_geom(d, g) || !dpool || !code || !packed || !din || (!dpool_amax && !scales_scratch)) return DDRL_ERR_INVALID_ARG;
   if ((g.in_sn & 3) || !aligned16(din) || !aligned16(dpool)) return DDRL_ERR_INVALID_ARG;
-  if (!(conv_has_planes(g) && conv_planes_has_pool(g))) return DDRL_ERR_UNSUPPORTED;
-  const PackView v = pack_view(g);
+  const ConvRoute r = conv_route(g);
+  if (!(r.family == kConvPlanes && r.pool)) return DDRL_ERR_UNSUPPORTED;  // a first layer has no data gradient
+  const PackView v = pack_view(g, r);
   launch_conv_planes_dgrad_pooled(g, dpool, code, packed + v.off[6], scales_scratch, dpool_amax, din, din_amax, (hipStream_t)stream);
   return op_check();
 }
@@ -178,26 +205,28 @@ int32_t ddrl_op_conv_wgrad_pooled(const ddrl_conv_desc* d, const float* in, cons
   ConvGeom g;
   if (!fill_geom(d, g) || !in || !dpool || !code || !packed || !ws || !dw || !db) return DDRL_ERR_INVALID_ARG;
   if ((g.in_sn & 3) || !aligned16(in) || !aligned16(dpool) || ((uintptr_t)code & 1)) return DDRL_ERR_INVALID_ARG;
-  if (conv_has_first(g))
+  const ConvRoute r = conv_route(g);
+  if (!r.pool) return DDRL_ERR_UNSUPPORTED;
+  if (r.family == kConvFirst)
     launch_conv_first_wgrad_pooled(g, in, dpool, code, ws, dw, db, (hipStream_t)stream);
-  else if (conv_has_planes(g) && conv_planes_has_pool(g))
-    launch_conv_planes_wgrad_pooled(g, in, dpool, code, in_amax, dpool_amax, ws, dw, db, (hipStream_t)stream);
   else
-    return DDRL_ERR_UNSUPPORTED;
+    launch_conv_planes_wgrad_pooled(g, in, dpool, code, in_amax, dpool_amax, ws, dw, db, (hipStream_t)stream);
   return op_check();
 }
 
 int32_t ddrl_op_conv_dgrad(const ddrl_conv_desc* d, const float* dz, const float* packed, float* din, float* scales_scratch, void* stream) {
   ConvGeom g;
   if (!fill_geom(d, g) || !dz || !packed || !din) return DDRL_ERR_INVALID_ARG;
-  const PackView v = pack_view(g);
-  if (conv_has_planes(g) && direct_ok(g, din, dz) && !conv_has_c1d_backward(g) && !scales_scratch) return DDRL_ERR_INVALID_ARG;
-  if (conv_has_c1d_backward(g))
-    launch_conv_c1d_dgrad(g, dz, packed + v.off[6], din, (hipStream_t)stream);
-  else if (conv_has_planes(g) && direct_ok(g, din, dz))
-    launch_conv_planes_dgrad(g, dz, packed + v.off[6], scales_scratch, din, (hipStream_t)stream);
-  else
-    launch_conv_dgrad(g, dz, packed + v.off[2], (const int2*)(packed + v.off[3]), din, (hipStream_t)stream);
+  const ConvRoute r = conv_route(g);
+  const PackView v = pack_view(g, r);
+  ConvFamily f = family_for(r, direct_ok(g, din, dz));
+  if (f == kConvFirst || !r.backward) f = kConvGather;  // no data gradient kernel in fconv.hip, nor for c1d.hip's first layer
+  if (f == kConvPlanes && !scales_scratch) return DDRL_ERR_INVALID_ARG;
+  switch (f) {
+    case kConvC1d: launch_conv_c1d_dgrad(g, dz, packed + v.off[6], din, (hipStream_t)stream); break;
+    case kConvPlanes: launch_conv_planes_dgrad(g, dz, packed + v.off[6], scales_scratch, din, (hipStream_t)stream); break;
+    default: launch_conv_dgrad(g, dz, packed + v.off[2], (const int2*)(packed + v.off[3]), din, (hipStream_t)stream); break;
+  }
   return op_check();
 }
 
@@ -206,15 +235,14 @@ int32_t ddrl_op_conv_wgrad(const ddrl_conv_desc* d, const float* in, const float
   ConvGeom g;
   if (!fill_geom(d, g) || !in || !dz || !packed || !ws || !dw || !db) return DDRL_ERR_INVALID_ARG;
   if (g.oh * g.ow < 32) return DDRL_ERR_UNSUPPORTED;
-  const PackView v = pack_view(g);
-  if (conv_has_c1d_backward(g))
-    launch_conv_c1d_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream);
-  else if (conv_has_first(g) && direct_ok(g, in, dz))
-    launch_conv_first_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream);
-  else if (conv_has_planes(g) && direct_ok(g, in, dz))
-    launch_conv_planes_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream);
-  else
-    launch_conv_wgrad(g, in, dz, (const int*)(packed + v.off[4]), ws, dw, db, (hipStream_t)stream);
+  const ConvRoute r = conv_route(g);
+  const PackView v = pack_view(g, r);
+  switch (r.backward ? family_for(r, direct_ok(g, in, dz)) : kConvGather) {
+    case kConvC1d: launch_conv_c1d_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream); break;
+    case kConvFirst: launch_conv_first_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream); break;
+    case kConvPlanes: launch_conv_planes_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream); break;
+    case kConvGather: launch_conv_wgrad(g, in, dz, (const int*)(packed + v.off[4]), ws, dw, db, (hipStream_t)stream); break;
+  }
   return op_check();
 }
 

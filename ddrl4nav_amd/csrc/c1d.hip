@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ in, 
     lm = fmaxf(lm, fabsf(v));
   }
   if (out_amax != nullptr) {   // the sample's largest |output| for the dense layer that reads the flattened rows (engine2.h amax_raise)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lm = fmaxf(lm, __shfl_xor(lm, off, 64));
+    lm = wave_fmax(lm);
     if ((threadIdx.x & 63) == 0) amax_raise(lm, out_amax + b);
   }
 }

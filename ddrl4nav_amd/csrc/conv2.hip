@@ -352,25 +352,18 @@ static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
   const ParamLayout& L = *c.L;
   if (!acting && (int64_t)c.n * 400 >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
     using R = Fwd1R<NE>;
-    static bool configured_r = false;
-    static int cus = 256;
-    if (!configured_r) {
-      (void)hipFuncSetAttribute((const void*)conv_fwd1_resident_kernel<NE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R::LDS_BYTES);
+    lds_limit_once<conv_fwd1_resident_kernel<NE>>((int)R::LDS_BYTES);
+    static const int cus = [] {
       int dev = 0;
       hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-      configured_r = true;
-    }
+      return hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
+    }();
     hipLaunchKernelGGL(conv_fwd1_resident_kernel<NE>, dim3((unsigned)cus), dim3(512), R::LDS_BYTES, st, c.frames, w.wp1b, w.amax, c.params,
                        L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, c.max_batch * 12800, c.n, w.m1, m1_words(c.max_batch), L.C);
     return;
   }
   using K = Fwd1B<NE>;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_fwd1_planes_kernel<NE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_fwd1_planes_kernel<NE>>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_fwd1_planes_kernel<NE>, dim3((unsigned)(((int64_t)c.n * 400 + 255) / 256)), dim3(256), K::LDS_BYTES, st, c.frames,
                      w.wp1b, w.amax, c.params, L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, c.max_batch * 12800, c.n,
                      acting ? (unsigned*)nullptr : w.m1, m1_words(c.max_batch), L.C);
@@ -541,11 +534,7 @@ static void launch_fwd2_planes(const EncCall& c, bool acting, hipStream_t st) {
   using K = Fwd2B;
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_fwd2_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_fwd2_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_fwd2_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)L.NE), dim3(256), K::LDS_BYTES, st, w.a1,
                      c.max_batch * 12800, w.wp2b, w.amax, c.params, L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b, w.a2, c.max_batch * 5184,
                      c.n, acting ? (unsigned*)nullptr : w.m2);
@@ -700,11 +689,7 @@ static void launch_fwd3_planes(const EncCall& c, bool acting, hipStream_t st) {
   using K = Fwd3B;
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_fwd3_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_fwd3_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_fwd3_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)L.NE), dim3(256), K::LDS_BYTES, st, w.a2,
                      c.max_batch * 5184, w.wp3b, w.amax, c.params, L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b, w.a3, c.max_batch * FLAT,
                      c.n, acting ? (unsigned*)nullptr : w.m3);
@@ -885,11 +870,7 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
 static void launch_dgrad3_planes(const EncCall& c, hipStream_t st) {
   using K = Dgrad3B;
   const Workspace& w = *c.ws;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_dgrad3_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_dgrad3_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_dgrad3_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)c.L->NE), dim3(K::THREADS), K::LDS_BYTES, st,
                      w.dz3, c.max_batch * FLAT, w.wd3b, w.amax, w.m2, w.dz2, c.max_batch * 5184, c.n);
 }
@@ -1039,11 +1020,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 void launch_conv_dgrad2_2(const EncCall& c, hipStream_t st) {
   const Workspace& w = *c.ws;
   ProfRange pr(c.prof, "ConvDgrad2", st);
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_dgrad2_both_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Dgrad2Both::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_dgrad2_both_kernel>((int)Dgrad2Both::LDS_BYTES);
   hipLaunchKernelGGL(conv_dgrad2_both_kernel, dim3((unsigned)((c.n + Dgrad2Both::SPT - 1) / Dgrad2Both::SPT), (unsigned)c.L->NE, 1),
                      dim3(Dgrad2Both::THREADS), Dgrad2Both::LDS_BYTES, st, w.dz2, c.max_batch * 5184, w.wd2b, w.amax, w.dz1, c.max_batch * 12800, c.n);
 }

@@ -21,8 +21,7 @@ __global__ __launch_bounds__(256) void dh_normalise_kernel(float* __restrict__ d
   f4 v0 = row[0], v1 = row[1];
   float m = fmaxf(fmaxf(fmaxf(fabsf(v0.x), fabsf(v0.y)), fmaxf(fabsf(v0.z), fabsf(v0.w))),
                   fmaxf(fmaxf(fabsf(v1.x), fabsf(v1.y)), fmaxf(fabsf(v1.z), fabsf(v1.w))));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_fmax(m);
   int ex = GSC_EXP_MIN;  // floor(log2 m) from the bit pattern (subnormal m clamps to the lower bound)
   if (m > 0.0f && m < 3.0e38f) ex = min(max((int)((__float_as_uint(m) >> 23) & 0xFFu) - 127, GSC_EXP_MIN), GSC_EXP_MAX);
   const float g = __uint_as_float((unsigned)(ex + 127) << 23), gi = __uint_as_float((unsigned)(127 - ex) << 23);

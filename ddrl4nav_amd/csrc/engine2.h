@@ -342,15 +342,20 @@ struct ExtraOf<Op, decltype((void)Op::EXTRA)> {
   static constexpr int v = Op::EXTRA;
 };
 
+// Raises a kernel's dynamic shared-memory limit before its first launch: once per kernel (one flag per instantiation of a template)
+template <auto Kernel>
+inline void lds_limit_once(int bytes) {
+  static bool configured = false;
+  if (!configured) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    configured = true;
+  }
+}
+
 template <class Op>
 inline void launch_engine2(dim3 grid, const typename Op::Params& p, hipStream_t st) {
   constexpr size_t bytes = (size_t)(2 * Op::STAGE + ExtraOf<Op>::v) * sizeof(float);
-  static bool configured = false;
-  if (!configured) {
-    if (bytes > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)engine2_kernel<Op>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    configured = true;
-  }
+  if (bytes > 64 * 1024) lds_limit_once<engine2_kernel<Op>>((int)bytes);
   hipLaunchKernelGGL(engine2_kernel<Op>, grid, dim3(Op::THREADS), bytes, st, p);
 }
 
@@ -407,6 +412,15 @@ __device__ __forceinline__ void split_planes(float x, float y, float scale, unsi
 }
 __device__ __forceinline__ f32x16 mfma_planes(frag8 a, frag8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 __host__ __device__ inline float plane_scale(float amax) { return f16_scale(amax); }
+// MFMA fragment through the transposing LDS read (ds_read_b64_tr_b16): the lane's 8 k-values from two 8-byte reads
+using s4w = __attribute__((ext_vector_type(4))) short;
+__device__ __forceinline__ frag8 tr_frag(const char* lds, int off_lo, int off_hi) {
+  typedef s4w __attribute__((address_space(3))) * lds_s4;
+  const s4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_lo));
+  const s4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_hi));
+  typedef __attribute__((ext_vector_type(8))) short s8w;
+  return __builtin_bit_cast(frag8, (s8w)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
 // frame bytes 0..255 are exact in fp16: the pixel operand of conv1 is ONE plane, "f16x2" = NPL products.
 // Feeding them as fp16 SUBNORMALS (0x00bb = b x 2^-24: one v_perm_b32 per pair of pixels, 2^24 folded into the epilogue's scale) was
 // measured and not kept: 110 M fewer vector-ALU instructions per iteration (4 %), ConvWgrad1 2.83 -> 2.78 ms, the PPO iteration
@@ -430,14 +444,19 @@ __host__ __device__ inline void planes_of(float w, float scale, unsigned short (
   p[0] = __builtin_bit_cast(unsigned short, h0);
   p[1] = __builtin_bit_cast(unsigned short, h1);
 }
+// the largest value of the wave, in every lane (ppo_math.h's wave_max is the DPP form on unsigned bit patterns: another function)
+__device__ __forceinline__ float wave_fmax(float m) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  return m;
+}
 // largest magnitude of the values a thread wrote -> the tensor's running maximum (float bits of non-negative values order like
 // unsigned integers; the maximum does not depend on the order of the atomics, so the result is deterministic).
 // One atomic per wave on ONE address serialises in the memory system (25,600 of them cost conv1's forward 6 ms): a wave
 // first LOOKS at the slot and only sends the atomic when it would raise it -- after the first few waves almost none does.
 // A stale look can only be too small (the slot never decreases), i.e. it costs an atomic, never a missed maximum.
 __device__ __forceinline__ void amax_update(float m, float* slot) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_fmax(m);
   if ((threadIdx.x & 63) == 0) {
     const unsigned bits = __float_as_uint(m);
     if (bits > __hip_atomic_load((unsigned*)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax((unsigned*)slot, bits);

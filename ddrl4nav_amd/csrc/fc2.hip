@@ -140,8 +140,7 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
       // the largest of them is taken here (order-free, hence deterministic; n <= 512 values), behind the loads just requested
       float m = 0.0f;
       for (int i = tid; i < n; i += 256) m = fmaxf(m, smax[e * smax_es + i]);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+      m = wave_fmax(m);
       float* red = (float*)ldsf;
       if (lane == 0) red[wave] = m;
       __syncthreads();
@@ -200,12 +199,8 @@ void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool
   const int nsplit = allow_split ? fc_forward_splits(c.n) : 1;  // 98 k-blocks = 14 x 7
   ProfRange pr(c.prof, nsplit > 1 ? "FcFwdSplit" : "FcFwd", st);
   {
-    static bool configured = false;
-    if (!configured) {
-      (void)hipFuncSetAttribute((const void*)fc_fwd_planes_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FcFwdB::LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)fc_fwd_planes_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FcFwdB::LDS_BYTES);
-      configured = true;
-    }
+    lds_limit_once<fc_fwd_planes_kernel<false>>((int)FcFwdB::LDS_BYTES);
+    lds_limit_once<fc_fwd_planes_kernel<true>>((int)FcFwdB::LDS_BYTES);
     const dim3 grid(FEAT / 128, (c.n + 127) / 128, c.L->NE * nsplit);
     if (nsplit > 1)
       hipLaunchKernelGGL(fc_fwd_planes_kernel<true>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, MB * FLAT, w.wlb, w.amax, c.params,
@@ -366,20 +361,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
 // 128 x 128 tile, 4 waves as 2 x 2 of 64 x 64, k-block = 32 samples = 2 MFMA k-groups, ONE LDS stage; the next k-block
 // waits in registers and is split + committed between two barriers while the CU's other workgroup computes.
 // ------------------------------------------------------------------------------------------------
-using s4v = __attribute__((ext_vector_type(4))) short;
 struct FcWgradB {
   static constexpr int KB = 32, PITCH = 320, PLANE = KB * PITCH, B_OFF = NPL * PLANE, LDS_BYTES = 2 * NPL * PLANE;
   static constexpr int64_t SLAB = (int64_t)FEAT * FLAT + FEAT;  // weights then bias, like the arena (= FcWgradB::SLAB)
 };
-
-__device__ __forceinline__ frag8 tr_fragment(const char* lds, int byte_off) {
-  typedef s4v __attribute__((address_space(3))) * lds_s4;
-  const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + byte_off));
-  const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + byte_off + 4 * FcWgradB::PITCH));
-  typedef __attribute__((ext_vector_type(8))) short s8v;
-  const s8v v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(frag8, v);
-}
 
 __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __restrict__ dh, int64_t dh_es, const float* __restrict__ a3,
                                                               int64_t a3_es, const float* __restrict__ amax, const float* __restrict__ gsc,
@@ -470,10 +455,11 @@ __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __res
         frag8 a[NPL][2], b[NPL][2];
 #pragma unroll
         for (int p = 0; p < NPL; ++p) {
+          const int off = p * K::PLANE + kg * 16 * K::PITCH;  // the second read: four rows on
 #pragma unroll
-          for (int i = 0; i < 2; ++i) a[p][i] = tr_fragment(ldsw, aA[i] + p * K::PLANE + kg * 16 * K::PITCH);
+          for (int i = 0; i < 2; ++i) a[p][i] = tr_frag(ldsw, aA[i] + off, aA[i] + off + 4 * K::PITCH);
 #pragma unroll
-          for (int j = 0; j < 2; ++j) b[p][j] = tr_fragment(ldsw, bB[j] + p * K::PLANE + kg * 16 * K::PITCH);
+          for (int j = 0; j < 2; ++j) b[p][j] = tr_frag(ldsw, bB[j] + off, bB[j] + off + 4 * K::PITCH);
         }
 #pragma unroll
         for (int t = 0; t < NPROD; ++t)
@@ -521,11 +507,7 @@ void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int par
   if (part != 1) {
     {
       ProfRange pr(c.prof, "FcWgrad", st);
-      static bool configured_w = false;
-      if (!configured_w) {
-        (void)hipFuncSetAttribute((const void*)fc_wgrad_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FcWgradB::LDS_BYTES);
-        configured_w = true;
-      }
+      lds_limit_once<fc_wgrad_planes_kernel>((int)FcWgradB::LDS_BYTES);
       const dim3 wgrid((unsigned)((25 * L.NE * S + 7) / 8 * 32));
       hipLaunchKernelGGL(fc_wgrad_planes_kernel, wgrid, dim3(256), FcWgradB::LDS_BYTES, st, w.dh, MB * FEAT, w.a3, MB * FLAT, w.amax, w.gsc, MB,
                          w.wpart, c.n, S, L.NE);
@@ -535,11 +517,7 @@ void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int par
   }
   if (part != 2) {
     ProfRange pr(c.prof, "FcDgrad", st);
-    static bool configured = false;
-    if (!configured) {
-      (void)hipFuncSetAttribute((const void*)fc_dgrad_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FcDgradB::LDS_BYTES);
-      configured = true;
-    }
+    lds_limit_once<fc_dgrad_planes_kernel>((int)FcDgradB::LDS_BYTES);
     hipLaunchKernelGGL(fc_dgrad_planes_kernel, dim3((FLAT + 127) / 128, (c.n + 127) / 128, L.NE), dim3(256), FcDgradB::LDS_BYTES, st, w.dh, MB * FEAT,
                        w.wdlb, w.amax, w.m3, w.dz3, MB * FLAT, c.n);
   }

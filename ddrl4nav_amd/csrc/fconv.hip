@@ -36,7 +36,6 @@ namespace fconv {
 
 using u2v = __attribute__((ext_vector_type(2))) unsigned;
 using u4v = __attribute__((ext_vector_type(4))) unsigned;
-using s4w = __attribute__((ext_vector_type(4))) short;
 
 template <int CIN_, int KS_, int HIN_, int PAD_>
 struct FGeo {
@@ -68,12 +67,6 @@ struct FGeo {
   static_assert(F_LDS <= 160 * 1024 && 2 * (W_LDS + 1024) <= 160 * 1024, "LDS budget (two weight-gradient workgroups per CU)");
 };
 
-__global__ __launch_bounds__(256) void weight_amax_kernel(const float* __restrict__ w, int64_t count, float* __restrict__ slot) {
-  float m = 0.0f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-  amax_update(m, slot);
-}
-
 // dst[k-group = KXH ky + kx / 4][plane][oc 64][lane half][8 k]: k = 8 half + 4 t + c  <->  kx = 4 (k-group % KXH) + 2 half + t; hdr[0] =
 // largest |w| (in), hdr[1] = scale (out)
 __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, int cin, int ks, unsigned short* __restrict__ dst,
@@ -97,11 +90,6 @@ __device__ __forceinline__ float scale_from(const float* red, int nw) {
   float m = 0.0f;
   for (int i = 0; i < nw; ++i) m = fmaxf(m, red[i]);
   return m > 0.0f ? fminf(plane_scale(m), 0x1p60f) : 0x1p60f;
-}
-__device__ __forceinline__ float wave_max(float m) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  return m;
 }
 __device__ __forceinline__ float amax4(f4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
@@ -166,7 +154,7 @@ __global__ __launch_bounds__(512) void first_fwd_kernel(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < K::CIN; ++c) m = fmaxf(m, amax4(sr[j][c]));
       }
-    m = wave_max(m);
+    m = wave_fmax(m);
     if (lane == 0) slot[wave] = m;
   };
   auto commit = [&](char* img, float scale) {
@@ -311,7 +299,7 @@ __global__ __launch_bounds__(512) void first_fwd_kernel(const float* __restrict_
     const bool more = bn < n;
     if (more) leave_amax(red + 8 * ((it + 1) & 1));
     if (POOL && out_amax != nullptr) {   // this workgroup owns the whole sample: its eight waves' maxima meet behind the barrier below
-      omx = wave_max(omx);
+      omx = wave_fmax(omx);
       if (lane == 0) omax[wave] = omx;
     }
     __syncthreads();
@@ -326,14 +314,6 @@ __global__ __launch_bounds__(512) void first_fwd_kernel(const float* __restrict_
     if (bn < n) fetch(bn);
     __syncthreads();
   }
-}
-
-__device__ __forceinline__ frag8 tr_frag(const char* lds, int off_lo, int off_hi) {
-  typedef s4w __attribute__((address_space(3))) * lds_s4;
-  const s4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_lo));
-  const s4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_hi));
-  typedef __attribute__((ext_vector_type(8))) short s8w;
-  return __builtin_bit_cast(frag8, (s8w)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 // UNPOOL: `dz` is d(pooled) [64][OH / 2][OH / 2] of the layer's ReLU + max_pool2d(2) and `ucode` its decision bytes; the staging
@@ -411,8 +391,8 @@ __global__ __launch_bounds__(256, 2) void first_wgrad_kernel(const float* __rest
 #pragma unroll
       for (int c = 0; c < K::CIN; ++c) mi = fmaxf(mi, amax4(ir[c]));
     }
-    md = wave_max(md);
-    mi = wave_max(mi);
+    md = wave_fmax(md);
+    mi = wave_fmax(mi);
     if (lane == 0) {
       red[wave] = md;
       red[4 + wave] = mi;
@@ -562,18 +542,14 @@ int64_t conv_first_pack_floats(const ConvGeom& g) {
 void launch_conv_first_pack(const ConvGeom& g, const float* w, float* region, hipStream_t st) {
   float* hdr = region + conv_first_pack_floats(g) - 64;
   (void)hipMemsetAsync(hdr, 0, 64 * sizeof(float), st);
-  hipLaunchKernelGGL(fconv::weight_amax_kernel, dim3(8), dim3(256), 0, st, w, (int64_t)g.cout * g.cin * g.kh * g.kw, hdr);
+  launch_weight_amax(w, (int64_t)g.cout * g.cin * g.kh * g.kw, hdr, nullptr, 8, st);
   hipLaunchKernelGGL(fconv::pack_kernel, dim3((((g.kh + 3) / 4) * g.kh * 1024 + 255) / 256), dim3(256), 0, st, w, g.cin, g.kh, (unsigned short*)region, hdr);
 }
 
 template <class K, bool POOL>
 static void run_first_fwd(const ConvGeom& g, const float* in, const float* region, const float* bias, int act, float* out, int64_t out_sn, uint8_t* code,
                           float* out_amax, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)fconv::first_fwd_kernel<K, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, K::F_LDS);
-    configured = true;
-  }
+  lds_limit_once<fconv::first_fwd_kernel<K, POOL>>(K::F_LDS);
   const int grid = g.n < 256 ? g.n : 256;  // one persistent workgroup per CU walks the samples
   hipLaunchKernelGGL((fconv::first_fwd_kernel<K, POOL>), dim3(grid), dim3(512), K::F_LDS, st, in, g.in_sn, (const unsigned short*)region,
                      region + K::W_BYTES / 4, bias, act, out, out_sn, code, out_amax, g.n);
@@ -603,11 +579,7 @@ int conv_first_wgrad_splits(const ConvGeom& g) {
 template <class K, bool UNPOOL>
 static void run_first_wgrad(const ConvGeom& g, const float* in, const float* dz, int64_t dz_sn, const uint8_t* ucode, float* part, float* dw, float* db,
                             hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)fconv::first_wgrad_kernel<K, UNPOOL>, hipFuncAttributeMaxDynamicSharedMemorySize, K::W_LDS);
-    configured = true;
-  }
+  lds_limit_once<fconv::first_wgrad_kernel<K, UNPOOL>>(K::W_LDS);
   const int S = conv_first_wgrad_splits(g);
   hipLaunchKernelGGL((fconv::first_wgrad_kernel<K, UNPOOL>), dim3(S), dim3(256), K::W_LDS, st, in, g.in_sn, dz, dz_sn, ucode, part, g.n, S);
   launch_reduce_slabs2(part, S, K::SLAB, (int64_t)64 * K::CIN * K::KK, dw, 64, db, st);

@@ -1,4 +1,6 @@
-// Internal launcher interface of the generic operators (gconv.hip, glinear.hip, gheads.hip).
+// Internal launcher interface of the generic operators: the gather kernels that serve any layer (gconv.hip, glinear.hip, gheads.hip) and
+// the specialised conv / dense families (pconv.hip, fconv.hip, c1d.hip, plin.hip).  Which conv family serves a layer is decided in ONE
+// place, conv_route (api_ops.hip); the ddrl_op_conv_* entry points switch on its answer and nothing else calls the conv_has_* predicates.
 #pragma once
 #include "common.h"
 
@@ -8,6 +10,20 @@ struct ConvGeom {
   int n, cin, h, w, cout, kh, kw, stride, lgs, pad_h, pad_w, oh, ow;
   int64_t in_sn, out_sn;  // sample strides (floats) of the input / output tensors ([c][h][w] dense inside)
 };
+
+// What the specialised conv families offer for a GEOMETRY, and every size that follows from it (api_ops.hip).  Whether one CALL can use
+// the family also depends on its pointers and strides (16-byte loads): that stays with the entry points, which fall back to the gather
+// kernels.
+enum ConvFamily { kConvGather, kConvPlanes, kConvFirst, kConvC1d };
+struct ConvRoute {
+  ConvFamily family;      // the specialised family of the geometry (kConvGather = none)
+  bool pool;              // the family has the ReLU + max-pool epilogue (and the gradients from d(pooled)) for this geometry
+  bool backward;          // the family has gradient kernels for it (c1d: the 32 -> 32 layer only; first: weight gradient only)
+  int64_t pack5, pack6;   // floats of packed regions 5 / 6
+  int wgrad_splits;       // largest split count any eligible launcher may use (sizes ws)
+  int64_t scratch_floats, ws_tail_floats;  // scales_scratch; floats of ws behind the slabs
+};
+ConvRoute conv_route(const ConvGeom& g);
 
 // gconv.hip
 bool conv_geom_fill(ConvGeom& g);  // derives lgs, oh, ow from the rest; false when unsupported
@@ -35,6 +51,11 @@ void launch_conv_planes_fwd(const ConvGeom& g, const float* in, const float* wpf
                             hipStream_t st);
 void launch_conv_planes_dgrad(const ConvGeom& g, const float* dz, const float* wpd, float* scales, float* din, hipStream_t st);
 bool conv_planes_has_pool(const ConvGeom& g);     // forward with ReLU + max_pool2d(2) in the epilogue
+// *slot (and *slot2 unless null) = max with the largest |w[0..count)|: the headers of packed plane regions (zeroed by the caller)
+void launch_weight_amax(const float* w, int64_t count, float* slot, float* slot2, unsigned blocks, hipStream_t st);
+inline unsigned weight_amax_blocks(int64_t count) {  // ~16 elements per thread, up to two workgroups per CU
+  return (unsigned)((count + 4095) / 4096 < 512 ? (count + 4095) / 4096 : 512);
+}
 void launch_sample_amax(const float* x, int64_t sn, int elems, int n, float* amax, hipStream_t st, int accumulate = 0);   // amax[b] = (max with) max |x[b][:]|
 void launch_conv_planes_fwd_pool(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* given, const float* bias,
                                  float* pooled, uint8_t* code, float* out_amax, hipStream_t st);

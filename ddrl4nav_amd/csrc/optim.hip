@@ -158,8 +158,7 @@ __global__ __launch_bounds__(256) void weights_amax_kernel(const float* __restri
   // one atomic per WORKGROUP: every wave of the grid looks at the (freshly zeroed) slot at the same moment, so the "look first" of
   // amax_update saves nothing here and 2,048 atomics on eight addresses took 35 of an earlier form's 42 us
   __shared__ float wm[4];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = wave_fmax(m);
   if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) atomicMax((unsigned*)(amax + amax_idx(t, e)), __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));

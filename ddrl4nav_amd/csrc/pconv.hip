@@ -25,6 +25,7 @@
 // flipping).  Geometry-dependent tile shapes (waves x column tiles per wave) are chosen so that NS samples' pixels fill the 32-wide
 // column tiles as well as the register budget allows (table at the bottom): 2 x 400 = 8 x 100 = 25 of 28 tiles, 576 = 4 x 144 = 18 of 18.
 #include <cstdlib>
+#include <type_traits>
 
 #include "engine2.h"
 #include "ops.h"
@@ -62,8 +63,7 @@ __global__ __launch_bounds__(256) void sample_amax_kernel(const float* __restric
     const f4 v = ld4(src + i);  // elems is a multiple of 4, the base 16-byte aligned (api_ops.hip direct_ok)
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_fmax(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -75,11 +75,12 @@ __global__ __launch_bounds__(256) void sample_amax_kernel(const float* __restric
 
 // ---- weights: largest magnitude, then the planes in the order the k index walks ----------------------------------------------
 // (the forward and the data-gradient region take the same scale: one pass over the weights leaves it in both headers)
+// (shared by the pack launchers of pconv.hip, plin.hip and fconv.hip; slot2 may be null)
 __global__ __launch_bounds__(256) void weight_amax_kernel(const float* __restrict__ w, int64_t count, float* __restrict__ slot, float* __restrict__ slot2) {
   float m = 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
   amax_update(m, slot);
-  amax_update(m, slot2);
+  if (slot2 != nullptr) amax_update(m, slot2);
 }
 // dst[row tile][cb][tap][plane][row 64][lane half 2][8 channels] (16-bit); hdr[0] = largest |w| (in), hdr[1] = scale (out).
 // dgrad = 0: rows = cout, channels = cin, taps as they are.  dgrad = 1: rows = cin, channels = cout, taps flipped.
@@ -375,15 +376,6 @@ __global__ __launch_bounds__(K::THREADS, K::THREADS <= 256 ? 2 : 1) void direct_
 // ================================================================================================
 // (Round 5 also measured the taps of a stage as a software-pipelined sequence -- fragments of tap t + 1 requested before the MFMAs of
 // tap t, pinned with sched_group_barrier --: no gain, and one pinned region over a whole stage took hipcc 11 minutes; profiles/README.md.)
-using s4w = __attribute__((ext_vector_type(4))) short;
-__device__ __forceinline__ frag8 tr_frag(const char* lds, int off_lo, int off_hi) {
-  typedef s4w __attribute__((address_space(3))) * lds_s4;
-  const s4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_lo));
-  const s4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_hi));
-  typedef __attribute__((ext_vector_type(8))) short s8w;
-  return __builtin_bit_cast(frag8, (s8w)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 template <int CIN_, int COUT_, int KS_, int HIN_, int PAD_, int NB_, int BR_, int ICW_>
 struct WGeo {
   static constexpr int CIN = CIN_, COUT = COUT_, KS = KS_, HIN = HIN_, PAD = PAD_, NB = NB_, BR = BR_, ICW = ICW_;
@@ -666,6 +658,33 @@ using PNavC3FP = pconv::Geo<128, 256, 3, 12, 1, 4, 5, 4, 3>;
 using PAtC3F = pconv::Geo<64, 64, 3, 9, 0, 5, 4, 2, 9>;
 using PAtC3D = pconv::Geo<64, 64, 3, 7, 2, 3, 4, 2, 9>;
 
+// ---- weight gradients ----------------------------------------------------------------------------------------------------------------
+//                          CIN  COUT KS HIN PAD NB BR ICW
+// (5x5 A/B, round 4: three tap groups of 9 / 9 / 7 taps across workgroups with (oc half, ic half) waves -- 144 accumulators, two
+// workgroups per CU, the dz band staged three times -- measured 6.3 against 4.45 ms: not kept)
+using PN1dC2W = pconv::WGeo<64, 128, 5, 22, 1, 1, 4, 32>;    // bands of 4 output rows: 80 kappa = 5 k-groups; wave = (oc half, 13 / 12 taps)
+using PN1dC3W = pconv::WGeo<128, 256, 3, 10, 1, 2, 10, 64>;  // 2 whole samples: 200 kappa of 208
+using PNavC2W = pconv::WGeo<64, 128, 3, 24, 1, 1, 4, 64>;    // bands of 4 rows: 96 kappa = 6 k-groups
+using PNavC3W = pconv::WGeo<128, 256, 3, 12, 1, 1, 12, 64>;  // one whole sample: 144 kappa = 9 k-groups
+using PAtC3W = pconv::WGeo<64, 64, 3, 9, 0, 2, 7, 64>;       // AtariPreNet conv3 as an operator: 2 whole samples, 98 kappa of 112
+
+// ---- the layers: one row each.  F forward, FP forward with ReLU + max_pool2d(2) in the epilogue (void: the layer has no pooled
+// kernels, neither forward nor gradients), D data gradient, W weight gradient.  A new layer = its aliases above, a row here, a case in
+// planes_id and in planes_dispatch.
+template <class F_, class FP_, class D_, class W_>
+struct PlanesLayer {
+  using F = F_;
+  using FP = FP_;
+  using D = D_;
+  using W = W_;
+  static constexpr bool HAS_POOL = !std::is_void<FP_>::value;
+};
+using LN1dC2 = PlanesLayer<PN1dC2F, PN1dC2F, PN1dC2D, PN1dC2W>;   // four column tiles per wave: the plain geometries pair up
+using LN1dC3 = PlanesLayer<PN1dC3F, PN1dC3F, PN1dC3D, PN1dC3W>;
+using LNavC2 = PlanesLayer<PNavC2F, PNavC2FP, PNavC2D, PNavC2W>;
+using LNavC3 = PlanesLayer<PNavC3F, PNavC3FP, PNavC3D, PNavC3W>;
+using LAtC3 = PlanesLayer<PAtC3F, void, PAtC3D, PAtC3W>;
+
 enum PlanesId { kPNone = -1, kPN1dC2, kPN1dC3, kPNavC2, kPNavC3, kPAtC3 };
 
 static PlanesId planes_id(const ConvGeom& g) {
@@ -680,11 +699,35 @@ static PlanesId planes_id(const ConvGeom& g) {
   return kPNone;
 }
 
+// fn(layer row) for the layer of g; nothing for a geometry without plane kernels
+template <class Fn>
+static void planes_dispatch(const ConvGeom& g, Fn&& fn) {
+  switch (planes_id(g)) {
+    case kPN1dC2: fn(LN1dC2{}); break;
+    case kPN1dC3: fn(LN1dC3{}); break;
+    case kPNavC2: fn(LNavC2{}); break;
+    case kPNavC3: fn(LNavC3{}); break;
+    case kPAtC3: fn(LAtC3{}); break;
+    default: break;
+  }
+}
+
 bool conv_has_planes(const ConvGeom& g) { return planes_id(g) != kPNone; }
+
+// conv + ReLU + max_pool2d(2) in one launch for the layers whose tiles allow it (four column tiles per wave)
+bool conv_planes_has_pool(const ConvGeom& g) {
+  bool has = false;
+  planes_dispatch(g, [&](auto l) { has = decltype(l)::HAS_POOL; });
+  return has;
+}
 
 // per-sample power-of-two plane scales of x[n][elems] (sample stride sn): what the plane kernels compute in their pre-pass
 void launch_sample_amax(const float* x, int64_t sn, int elems, int n, float* amax, hipStream_t st, int accumulate) {
   hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)n), dim3(256), 0, st, x, sn, elems, amax, accumulate);
+}
+
+void launch_weight_amax(const float* w, int64_t count, float* slot, float* slot2, unsigned blocks, hipStream_t st) {
+  hipLaunchKernelGGL(pconv::weight_amax_kernel, dim3(blocks), dim3(256), 0, st, w, count, slot, slot2);
 }
 
 // floats of ONE packed region (forward or data gradient): the planes (2 bytes x 2 planes per weight = 4 bytes) + a 64-float header
@@ -697,8 +740,7 @@ void launch_conv_planes_pack(const ConvGeom& g, const float* w, float* wpf, floa
   const unsigned blocks = (unsigned)((total + 255) / 256);
   (void)hipMemsetAsync(wpf + planes, 0, 64 * sizeof(float), st);
   (void)hipMemsetAsync(wpd + planes, 0, 64 * sizeof(float), st);
-  const unsigned ablocks = (unsigned)((total + 4095) / 4096 < 512 ? (total + 4095) / 4096 : 512);  // ~16 elements per thread
-  hipLaunchKernelGGL(pconv::weight_amax_kernel, dim3(ablocks), dim3(256), 0, st, w, total, wpf + planes, wpd + planes);
+  launch_weight_amax(w, total, wpf + planes, wpd + planes, weight_amax_blocks(total), st);
   for (int dg = 0; dg < 2; ++dg) {
     float* region = dg ? wpd : wpf;
     float* hdr = region + planes;
@@ -706,101 +748,53 @@ void launch_conv_planes_pack(const ConvGeom& g, const float* w, float* wpf, floa
   }
 }
 
-template <class K>
-static void run_planes(const float* in, int64_t in_sn, const float* region, int64_t planes, float* scales, const float* bias, int act,
-                       float* out, int64_t out_sn, int n, hipStream_t st, float* out_amax = nullptr) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)pconv::direct_planes_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
-  hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)n), dim3(256), 0, st, in, in_sn, K::CIN * K::RAW, scales, 0);
-  hipLaunchKernelGGL((pconv::direct_planes_kernel<K, false>), dim3((unsigned)((n + K::NS - 1) / K::NS), K::COUT / 64, 1), dim3(K::THREADS), K::LDS_BYTES, st, in,
-                     in_sn, (const unsigned short*)region, region + planes, scales, bias, act, out, out_sn, (uint8_t*)nullptr, (const uint8_t*)nullptr, out_amax, n);
-}
-
-template <class K>
-static void run_planes_pool(const float* in, int64_t in_sn, const float* region, int64_t planes, float* scales, const float* given, const float* bias,
-                            float* pooled, uint8_t* code, float* out_amax, int n, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)pconv::direct_planes_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
-  if (!given) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)n), dim3(256), 0, st, in, in_sn, K::CIN * K::RAW, scales, 0);
-  hipLaunchKernelGGL((pconv::direct_planes_kernel<K, true>), dim3((unsigned)((n + K::NS - 1) / K::NS), K::COUT / 64, 1), dim3(K::THREADS), K::LDS_BYTES, st, in,
-                     in_sn, (const unsigned short*)region, region + planes, given ? given : scales, bias, 1, pooled, (int64_t)K::COUT * (K::P / 4), code, (const uint8_t*)nullptr, out_amax, n);
-}
-
-// data gradient straight from d(pooled) + decision bytes (K = the layer's data-gradient geometry: CIN = dz channels, HIN = dz size).
-// The per-sample scales come from d(pooled) itself: max |d(pooled)| bounds max |dz| (the routing only drops elements).
-template <class K>
-static void run_planes_unpool(const float* dpool, const uint8_t* ucode, const float* region, int64_t planes, float* scales, const float* given,
-                              float* din, int64_t din_sn, float* out_amax, int n, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)pconv::direct_planes_kernel<K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
-  constexpr int64_t PSN = (int64_t)K::CIN * K::RAW / 4;
-  if (!given) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)n), dim3(256), 0, st, dpool, PSN, (int)PSN, scales, 0);
-  hipLaunchKernelGGL((pconv::direct_planes_kernel<K, false, true>), dim3((unsigned)((n + K::NS - 1) / K::NS), K::COUT / 64, 1), dim3(K::THREADS), K::LDS_BYTES,
-                     st, dpool, PSN, (const unsigned short*)region, region + planes, given ? given : scales, (const float*)nullptr, 0, din, din_sn, (uint8_t*)nullptr, ucode, out_amax, n);
-}
-
-// conv + ReLU + max_pool2d(2) in one launch for the layers whose tiles allow it (four column tiles per wave)
-bool conv_planes_has_pool(const ConvGeom& g) {
-  const PlanesId id = planes_id(g);
-  return id == kPN1dC2 || id == kPN1dC3 || id == kPNavC2 || id == kPNavC3;
-}
-
-void launch_conv_planes_fwd_pool(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* given, const float* bias,
-                                 float* pooled, uint8_t* code, float* out_amax, hipStream_t st) {
+// One launch of direct_planes_kernel<K, POOL, UNPOOL> behind the pre-pass over its input (given == nullptr: the magnitudes go to `scales`).
+// POOL: `out` is the pooled map (dense) + `code`.  UNPOOL: K = the layer's data-gradient geometry (CIN = dz channels, HIN = dz size), `in`
+// is d(pooled) (dense) + `ucode`; the per-sample scales come from d(pooled) itself: max |d(pooled)| bounds max |dz| (the routing only
+// drops elements).
+template <class K, bool POOL, bool UNPOOL>
+static void run_planes(const ConvGeom& g, const float* in, int64_t in_sn, const float* region, float* scales, const float* given, const float* bias,
+                       int act, float* out, int64_t out_sn, uint8_t* code, const uint8_t* ucode, float* out_amax, hipStream_t st) {
+  lds_limit_once<pconv::direct_planes_kernel<K, POOL, UNPOOL>>((int)K::LDS_BYTES);
   const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes_pool<PN1dC2F>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
-    case kPN1dC3: run_planes_pool<PN1dC3F>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
-    case kPNavC2: run_planes_pool<PNavC2FP>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
-    case kPNavC3: run_planes_pool<PNavC3FP>(in, g.in_sn, wpf, planes, scales, given, bias, pooled, code, out_amax, g.n, st); break;
-    default: break;
-  }
+  constexpr int elems = UNPOOL ? K::CIN * K::RAW / 4 : K::CIN * K::RAW;
+  if (UNPOOL) in_sn = elems;
+  if (POOL) out_sn = (int64_t)K::COUT * (K::P / 4);
+  if (!given) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, in, in_sn, elems, scales, 0);
+  hipLaunchKernelGGL((pconv::direct_planes_kernel<K, POOL, UNPOOL>), dim3((unsigned)((g.n + K::NS - 1) / K::NS), K::COUT / 64, 1), dim3(K::THREADS),
+                     K::LDS_BYTES, st, in, in_sn, (const unsigned short*)region, region + planes, given ? given : scales, bias, act, out, out_sn, code,
+                     ucode, out_amax, g.n);
 }
 
 void launch_conv_planes_fwd(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* bias, int act, float* out,
                             hipStream_t st) {
-  const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes<PN1dC2F>(in, g.in_sn, wpf, planes, scales, bias, act, out, g.out_sn, g.n, st); break;
-    case kPN1dC3: run_planes<PN1dC3F>(in, g.in_sn, wpf, planes, scales, bias, act, out, g.out_sn, g.n, st); break;
-    case kPNavC2: run_planes<PNavC2F>(in, g.in_sn, wpf, planes, scales, bias, act, out, g.out_sn, g.n, st); break;
-    case kPNavC3: run_planes<PNavC3F>(in, g.in_sn, wpf, planes, scales, bias, act, out, g.out_sn, g.n, st); break;
-    case kPAtC3: run_planes<PAtC3F>(in, g.in_sn, wpf, planes, scales, bias, act, out, g.out_sn, g.n, st); break;
-    default: break;
-  }
+  planes_dispatch(g, [&](auto l) {
+    run_planes<typename decltype(l)::F, false, false>(g, in, g.in_sn, wpf, scales, nullptr, bias, act, out, g.out_sn, nullptr, nullptr, nullptr, st);
+  });
 }
 
 void launch_conv_planes_dgrad(const ConvGeom& g, const float* dz, const float* wpd, float* scales, float* din, hipStream_t st) {
-  const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes<PN1dC2D>(dz, g.out_sn, wpd, planes, scales, nullptr, 0, din, g.in_sn, g.n, st); break;
-    case kPN1dC3: run_planes<PN1dC3D>(dz, g.out_sn, wpd, planes, scales, nullptr, 0, din, g.in_sn, g.n, st); break;
-    case kPNavC2: run_planes<PNavC2D>(dz, g.out_sn, wpd, planes, scales, nullptr, 0, din, g.in_sn, g.n, st); break;
-    case kPNavC3: run_planes<PNavC3D>(dz, g.out_sn, wpd, planes, scales, nullptr, 0, din, g.in_sn, g.n, st); break;
-    case kPAtC3: run_planes<PAtC3D>(dz, g.out_sn, wpd, planes, scales, nullptr, 0, din, g.in_sn, g.n, st); break;
-    default: break;
-  }
+  planes_dispatch(g, [&](auto l) {
+    run_planes<typename decltype(l)::D, false, false>(g, dz, g.out_sn, wpd, scales, nullptr, nullptr, 0, din, g.in_sn, nullptr, nullptr, nullptr, st);
+  });
 }
 
+void launch_conv_planes_fwd_pool(const ConvGeom& g, const float* in, const float* wpf, float* scales, const float* given, const float* bias,
+                                 float* pooled, uint8_t* code, float* out_amax, hipStream_t st) {
+  planes_dispatch(g, [&](auto l) {
+    using L = decltype(l);
+    if constexpr (L::HAS_POOL) run_planes<typename L::FP, true, false>(g, in, g.in_sn, wpf, scales, given, bias, 1, pooled, 0, code, nullptr, out_amax, st);
+  });
+}
 
-// ---- weight gradients ----------------------------------------------------------------------------------------------------------------
-//                          CIN  COUT KS HIN PAD NB BR ICW
-// (5x5 A/B, round 4: three tap groups of 9 / 9 / 7 taps across workgroups with (oc half, ic half) waves -- 144 accumulators, two
-// workgroups per CU, the dz band staged three times -- measured 6.3 against 4.45 ms: not kept)
-using PN1dC2W = pconv::WGeo<64, 128, 5, 22, 1, 1, 4, 32>;    // bands of 4 output rows: 80 kappa = 5 k-groups; wave = (oc half, 13 / 12 taps)
-using PN1dC3W = pconv::WGeo<128, 256, 3, 10, 1, 2, 10, 64>;  // 2 whole samples: 200 kappa of 208
-using PNavC2W = pconv::WGeo<64, 128, 3, 24, 1, 1, 4, 64>;    // bands of 4 rows: 96 kappa = 6 k-groups
-using PNavC3W = pconv::WGeo<128, 256, 3, 12, 1, 1, 12, 64>;  // one whole sample: 144 kappa = 9 k-groups
-using PAtC3W = pconv::WGeo<64, 64, 3, 9, 0, 2, 7, 64>;       // AtariPreNet conv3 as an operator: 2 whole samples, 98 kappa of 112
+// data / weight gradient of a pooled layer straight from d(pooled) + decision bytes (the layers of conv_planes_has_pool)
+void launch_conv_planes_dgrad_pooled(const ConvGeom& g, const float* dpool, const uint8_t* ucode, const float* wpd, float* scales, const float* given,
+                                     float* din, float* out_amax, hipStream_t st) {
+  planes_dispatch(g, [&](auto l) {
+    using L = decltype(l);
+    if constexpr (L::HAS_POOL) run_planes<typename L::D, false, true>(g, dpool, 0, wpd, scales, given, nullptr, 0, din, g.in_sn, nullptr, ucode, out_amax, st);
+  });
+}
 
 template <class K>
 static int wgrad_splits_of(int n) {
@@ -813,92 +807,40 @@ static int wgrad_splits_of(int n) {
 }
 
 int conv_planes_wgrad_splits(const ConvGeom& g) {
-  switch (planes_id(g)) {
-    case kPN1dC2: return wgrad_splits_of<PN1dC2W>(g.n);
-    case kPN1dC3: return wgrad_splits_of<PN1dC3W>(g.n);
-    case kPNavC2: return wgrad_splits_of<PNavC2W>(g.n);
-    case kPNavC3: return wgrad_splits_of<PNavC3W>(g.n);
-    case kPAtC3: return wgrad_splits_of<PAtC3W>(g.n);
-    default: return 0;
-  }
+  int s = 0;
+  planes_dispatch(g, [&](auto l) { s = wgrad_splits_of<typename decltype(l)::W>(g.n); });
+  return s;
 }
 
-template <class K>
-static void run_planes_wgrad(const ConvGeom& g, const float* in, const float* dz, float* part, float* scales, int S, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)pconv::wgrad_planes_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
-  float* sc_in = scales;
-  float* sc_dz = scales + g.n;
-  hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, in, g.in_sn, K::CIN * K::RAW, sc_in, 0);
-  hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, dz, g.out_sn, K::COUT * K::P, sc_dz, 0);
-  hipLaunchKernelGGL(pconv::wgrad_planes_kernel<K>, dim3((unsigned)((K::CIN / K::ICW) * S), K::COUT / 64, 1), dim3(256), K::LDS_BYTES, st, in, g.in_sn,
-                     dz, g.out_sn, (const uint8_t*)nullptr, sc_in, sc_dz, part, g.n, S);
-}
-
-template <class K>
-static void run_planes_wgrad_pooled(const ConvGeom& g, const float* in, const float* dpool, const uint8_t* ucode, float* part, float* scales,
-                                    const float* given_in, const float* given_dp, int S, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)pconv::wgrad_planes_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
-  float* sc_in = scales;
-  float* sc_dz = scales + g.n;
-  constexpr int64_t PSN = (int64_t)K::COUT * K::P / 4;
+// One launch of wgrad_planes_kernel<K, UNPOOL> behind the pre-passes over its operands (given_* == nullptr: the magnitudes go to the scratch
+// behind the slabs), then the reduction of the slabs.  part: S slabs of COUT * KT + COUT floats, then 2 n floats of scratch for the
+// per-sample magnitudes.  UNPOOL: `dz` is d(pooled) (dense) + `ucode`; max |d(pooled)| bounds max |dz|.
+template <class K, bool UNPOOL>
+static void run_planes_wgrad(const ConvGeom& g, const float* in, const float* dz, const uint8_t* ucode, const float* given_in, const float* given_dz,
+                             float* part, float* dw, float* db, hipStream_t st) {
+  lds_limit_once<pconv::wgrad_planes_kernel<K, UNPOOL>>((int)K::LDS_BYTES);
+  const int S = wgrad_splits_of<K>(g.n);
+  float* sc_in = part + (int64_t)S * K::SLAB;
+  float* sc_dz = sc_in + g.n;
+  constexpr int dz_elems = UNPOOL ? K::COUT * K::P / 4 : K::COUT * K::P;
+  const int64_t dz_sn = UNPOOL ? dz_elems : g.out_sn;
   if (!given_in) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, in, g.in_sn, K::CIN * K::RAW, sc_in, 0);
-  if (!given_dp) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, dpool, PSN, (int)PSN, sc_dz, 0);  // max |d(pooled)| bounds max |dz|
-  hipLaunchKernelGGL((pconv::wgrad_planes_kernel<K, true>), dim3((unsigned)((K::CIN / K::ICW) * S), K::COUT / 64, 1), dim3(256), K::LDS_BYTES, st, in,
-                     g.in_sn, dpool, PSN, ucode, given_in ? given_in : sc_in, given_dp ? given_dp : sc_dz, part, g.n, S);
+  if (!given_dz) hipLaunchKernelGGL(pconv::sample_amax_kernel, dim3((unsigned)g.n), dim3(256), 0, st, dz, dz_sn, dz_elems, sc_dz, 0);
+  hipLaunchKernelGGL((pconv::wgrad_planes_kernel<K, UNPOOL>), dim3((unsigned)((K::CIN / K::ICW) * S), K::COUT / 64, 1), dim3(256), K::LDS_BYTES, st, in,
+                     g.in_sn, dz, dz_sn, ucode, given_in ? given_in : sc_in, given_dz ? given_dz : sc_dz, part, g.n, S);
+  launch_reduce_slabs2(part, S, K::SLAB, (int64_t)K::COUT * K::KT, dw, K::COUT, db, st);
 }
 
-// weight / data gradient of a pooled layer straight from d(pooled) + decision bytes (the layers of conv_planes_has_pool)
+void launch_conv_planes_wgrad(const ConvGeom& g, const float* in, const float* dz, float* part, float* dw, float* db, hipStream_t st) {
+  planes_dispatch(g, [&](auto l) { run_planes_wgrad<typename decltype(l)::W, false>(g, in, dz, nullptr, nullptr, nullptr, part, dw, db, st); });
+}
+
 void launch_conv_planes_wgrad_pooled(const ConvGeom& g, const float* in, const float* dpool, const uint8_t* ucode, const float* given_in,
                                      const float* given_dp, float* part, float* dw, float* db, hipStream_t st) {
-  const int S = conv_planes_wgrad_splits(g);
-  const int KT = g.cin * g.kh * g.kw;
-  const int64_t slab = (int64_t)g.cout * KT + g.cout;
-  float* scales = part + (int64_t)S * slab;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes_wgrad_pooled<PN1dC2W>(g, in, dpool, ucode, part, scales, given_in, given_dp, S, st); break;
-    case kPN1dC3: run_planes_wgrad_pooled<PN1dC3W>(g, in, dpool, ucode, part, scales, given_in, given_dp, S, st); break;
-    case kPNavC2: run_planes_wgrad_pooled<PNavC2W>(g, in, dpool, ucode, part, scales, given_in, given_dp, S, st); break;
-    case kPNavC3: run_planes_wgrad_pooled<PNavC3W>(g, in, dpool, ucode, part, scales, given_in, given_dp, S, st); break;
-    default: return;
-  }
-  launch_reduce_slabs2(part, S, slab, (int64_t)g.cout * KT, dw, g.cout, db, st);
-}
-
-void launch_conv_planes_dgrad_pooled(const ConvGeom& g, const float* dpool, const uint8_t* ucode, const float* wpd, float* scales, const float* given,
-                                     float* din, float* out_amax, hipStream_t st) {
-  const int64_t planes = (int64_t)g.cout * g.cin * g.kh * g.kw * NPL / 2;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes_unpool<PN1dC2D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
-    case kPN1dC3: run_planes_unpool<PN1dC3D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
-    case kPNavC2: run_planes_unpool<PNavC2D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
-    case kPNavC3: run_planes_unpool<PNavC3D>(dpool, ucode, wpd, planes, scales, given, din, g.in_sn, out_amax, g.n, st); break;
-    default: break;
-  }
-}
-
-// part: S slabs of COUT * KT + COUT floats, then 2 n floats of scratch for the per-sample scales
-void launch_conv_planes_wgrad(const ConvGeom& g, const float* in, const float* dz, float* part, float* dw, float* db, hipStream_t st) {
-  const int S = conv_planes_wgrad_splits(g);
-  const int KT = g.cin * g.kh * g.kw;
-  const int64_t slab = (int64_t)g.cout * KT + g.cout;
-  float* scales = part + (int64_t)S * slab;
-  switch (planes_id(g)) {
-    case kPN1dC2: run_planes_wgrad<PN1dC2W>(g, in, dz, part, scales, S, st); break;
-    case kPN1dC3: run_planes_wgrad<PN1dC3W>(g, in, dz, part, scales, S, st); break;
-    case kPNavC2: run_planes_wgrad<PNavC2W>(g, in, dz, part, scales, S, st); break;
-    case kPNavC3: run_planes_wgrad<PNavC3W>(g, in, dz, part, scales, S, st); break;
-    case kPAtC3: run_planes_wgrad<PAtC3W>(g, in, dz, part, scales, S, st); break;
-    default: return;
-  }
-  launch_reduce_slabs2(part, S, slab, (int64_t)g.cout * KT, dw, g.cout, db, st);
+  planes_dispatch(g, [&](auto l) {
+    using L = decltype(l);
+    if constexpr (L::HAS_POOL) run_planes_wgrad<typename L::W, true>(g, in, dpool, ucode, given_in, given_dp, part, dw, db, st);
+  });
 }
 
 }  // namespace ddrl

@@ -31,7 +31,6 @@ namespace ddrl {
 namespace plin {
 
 using u2v = __attribute__((ext_vector_type(2))) unsigned;
-using s4w = __attribute__((ext_vector_type(4))) short;
 
 constexpr int STAGE = 32768, A_BYTES = 16384;          // bytes per stage: activation planes, then weight planes
 constexpr int LDS_NT = 2 * STAGE + 2 * 128 * 4;        // + the tile's row scales, + the largest |output| of every row of the tile
@@ -50,20 +49,11 @@ __global__ __launch_bounds__(256) void row_amax_kernel(const float* __restrict__
     const float y = i + 1 < width ? fabsf(v.y) : 0.0f, z = i + 2 < width ? fabsf(v.z) : 0.0f, w = i + 3 < width ? fabsf(v.w) : 0.0f;
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), y)), fmaxf(z, w));
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_fmax(m);
   if (lane == 0) {
     if (accumulate) amax_raise(m, amax + row);
     else amax[row] = m;
   }
-}
-
-// (both packed regions of a layer take the same scale: one pass over the weights leaves it in both headers)
-__global__ __launch_bounds__(256) void weight_amax_kernel(const float* __restrict__ w, int64_t count, float* __restrict__ slot, float* __restrict__ slot2) {
-  float m = 0.0f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-  amax_update(m, slot);
-  amax_update(m, slot2);
 }
 
 // dst[column tile][k-group][plane][column 128][lane half 2][8 k] (16-bit), zero beyond the matrix; hdr[0] = largest |w| (in), hdr[1] = scale.
@@ -262,14 +252,6 @@ __global__ __launch_bounds__(256, 2) void nt_planes_kernel(NtParams P) {
 }
 
 // ---- weight gradient ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ frag8 tr_frag(const char* lds, int off_lo, int off_hi) {
-  typedef s4w __attribute__((address_space(3))) * lds_s4;
-  const s4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_lo));
-  const s4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_hi));
-  typedef __attribute__((ext_vector_type(8))) short s8w;
-  return __builtin_bit_cast(frag8, (s8w)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 struct TnParams {
   const float* dout;
   int64_t ldd;
@@ -438,8 +420,7 @@ void launch_linear_planes_pack(const float* w, int K, int N, float* pf, float* p
     (void)hipMemsetAsync(hdrs[t], 0, 64 * sizeof(float), st);
   }
   const int64_t count = (int64_t)K * N;
-  const unsigned ablocks = (unsigned)((count + 4095) / 4096 < 512 ? (count + 4095) / 4096 : 512);  // ~16 elements per thread, up to two workgroups per CU
-  hipLaunchKernelGGL(plin::weight_amax_kernel, dim3(ablocks), dim3(256), 0, st, w, count, hdrs[0], hdrs[1]);
+  launch_weight_amax(w, count, hdrs[0], hdrs[1], weight_amax_blocks(count), st);  // both regions take the same scale: one pass over the weights
   for (int t = 0; t < 2; ++t) {
     float* region = t ? pd : pf;
     const int cols = t ? K : N, kgs = kgs_of(t ? N : K);
@@ -451,11 +432,7 @@ void launch_linear_planes_pack(const float* w, int K, int N, float* pf, float* p
 
 template <int DGRAD>
 static void run_nt(const plin::NtParams& p, dim3 grid, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)plin::nt_planes_kernel<DGRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, plin::LDS_NT);
-    configured = true;
-  }
+  lds_limit_once<plin::nt_planes_kernel<DGRAD>>(plin::LDS_NT);
   hipLaunchKernelGGL(plin::nt_planes_kernel<DGRAD>, grid, dim3(256), plin::LDS_NT, st, p);
 }
 
@@ -509,11 +486,7 @@ int linear_planes_wgrad_splits(int n, int K, int N) {
 // part: S slabs of N * K + N floats, then 2 n floats for the row scales
 void launch_linear_planes_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int n, int K, int N,
                                 float* dw, float* db, const float* given_in, const float* given_dout, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)plin::tn_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, plin::LDS_TN);
-    configured = true;
-  }
+  lds_limit_once<plin::tn_planes_kernel>(plin::LDS_TN);
   const int S = linear_planes_wgrad_splits(n, K, N);
   const int64_t slab = (int64_t)N * K + N;
   float* sc_i = part + (int64_t)S * slab;

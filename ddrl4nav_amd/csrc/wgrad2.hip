@@ -66,16 +66,7 @@ struct WgradSplit {
 // Round 6 replaced the one-stage form of this kernel (one turn in 103 KB of LDS, the next in 80 staging registers, split + committed
 // between two barriers; one sample per stage in 56 KB measured 3.22 against 3.07 ms) by the two-buffer pipeline below.
 // ================================================================================================
-using s4w = __attribute__((ext_vector_type(4))) short;
 using u4w = __attribute__((ext_vector_type(4))) unsigned;
-
-__device__ __forceinline__ frag8 tr_frag3(const char* lds, int off_lo, int off_hi) {
-  typedef s4w __attribute__((address_space(3))) * lds_s4;
-  const s4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_lo));
-  const s4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(lds + off_hi));
-  typedef __attribute__((ext_vector_type(8))) short s8w;
-  return __builtin_bit_cast(frag8, (s8w)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // ------------------------------------------------------------------------------------------------
 // The two-buffer software pipeline (the form of conv_wgrad2_pipe_kernel below).  A turn = two samples = 98 reduction indices, cut
@@ -235,13 +226,13 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
     const char* bb = ldsq + (H ? K::B1 : K::B0) + wj * (H ? K::B_HALF1 : K::B_HALF0) + b_lane;
     auto read_a = [&](int g, frag8 (&a)[NPL]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int p = 0; p < NPL; ++p) a[p] = tr_frag3(ab, p * APL + g * 2048, p * APL + g * 2048 + 512);
+      for (int p = 0; p < NPL; ++p) a[p] = tr_frag(ab, p * APL + g * 2048, p * APL + g * 2048 + 512);
     };
     auto read_b = [&](int blk, frag8 (&b)[NPL]) __attribute__((always_inline)) {
       const int g = blk / 9, t = blk % 9, toff = ((t / 3) * 9 + t % 3) * K::BP;
 #pragma unroll
       for (int p = 0; p < NPL; ++p)
-        b[p] = tr_frag3(bb, p * BPL + (H ? brow1[g][0] : brow0[g < K::NKG0 ? g : 0][0]) + toff, p * BPL + (H ? brow1[g][1] : brow0[g < K::NKG0 ? g : 0][1]) + toff);
+        b[p] = tr_frag(bb, p * BPL + (H ? brow1[g][0] : brow0[g < K::NKG0 ? g : 0][0]) + toff, p * BPL + (H ? brow1[g][1] : brow0[g < K::NKG0 ? g : 0][1]) + toff);
     };
     frag8 a[2][NPL], b[2][NPL];
     read_a(0, a[0]);
@@ -335,11 +326,7 @@ void launch_conv_wgrad3_2(const EncCall& c, float* grads, hipStream_t st) {
   const int want = 256 * Wgrad3P::WG_PER_CU / L.NE;  // as many workgroups as fit the chip at once
   const int S = c.splits->c3 < want ? c.splits->c3 : want;
   {
-    static bool configured = false;
-    if (!configured) {
-      (void)hipFuncSetAttribute((const void*)conv_wgrad3_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wgrad3P::LDS_BYTES);
-      configured = true;
-    }
+    lds_limit_once<conv_wgrad3_pipe_kernel>((int)Wgrad3P::LDS_BYTES);
     ProfRange pr(c.prof, "ConvWgrad3", st);
     hipLaunchKernelGGL(conv_wgrad3_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad3P::LDS_BYTES, st, w.a2, MB * 5184, w.dz3, MB * FLAT,
                        w.amax, w.gsc, MB, w.wpart, c.n, S, L.NE);
@@ -506,12 +493,12 @@ __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __re
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int p = 0; p < NPL; ++p) a[i][p] = tr_frag3(ab, a_lane[i] + p * K::A_PLANE + g * 2048, a_lane[i] + p * K::A_PLANE + g * 2048 + 512);
+        for (int p = 0; p < NPL; ++p) a[i][p] = tr_frag(ab, a_lane[i] + p * K::A_PLANE + g * 2048, a_lane[i] + p * K::A_PLANE + g * 2048 + 512);
     };
     auto read_b = [&](int blk, frag8 (&b)[NPL]) __attribute__((always_inline)) {
       const int g = blk >> 2, t = blk & 3;
 #pragma unroll
-      for (int p = 0; p < NPL; ++p) b[p] = tr_frag3(bb, p * BPL + brow[H][g][0] + t * K::BP, p * BPL + brow[H][g][1] + t * K::BP);
+      for (int p = 0; p < NPL; ++p) b[p] = tr_frag(bb, p * BPL + brow[H][g][0] + t * K::BP, p * BPL + brow[H][g][1] + t * K::BP);
     };
     // fragments one tap block ahead (the scheduling fence at the end of a block keeps the reads of the next one from being hoisted by
     // the compiler, so they are requested here, in front of the block's MFMAs)
@@ -598,11 +585,7 @@ void launch_conv_wgrad2_2(const EncCall& c, float* grads, hipStream_t st) {
   const int S = c.splits->c2 < want ? c.splits->c2 : want;
   {
     ProfRange pr(c.prof, "ConvWgrad2", st);
-    static bool configured = false;
-    if (!configured) {
-      (void)hipFuncSetAttribute((const void*)conv_wgrad2_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wgrad2P::LDS_BYTES);
-      configured = true;
-    }
+    lds_limit_once<conv_wgrad2_pipe_kernel>((int)Wgrad2P::LDS_BYTES);
     hipLaunchKernelGGL(conv_wgrad2_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad2P::LDS_BYTES, st, w.a1, MB * 12800, w.dz2, MB * 5184,
                        w.amax, w.gsc, MB, w.wpart, c.n, S, L.NE);
   }
@@ -871,11 +854,7 @@ template <int NE>
 static void launch_wgrad1_planes(const EncCall& c, int S, hipStream_t st) {
   using K = Wgrad1B<NE>;
   const Workspace& w = *c.ws;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad1_planes_kernel<NE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-    configured = true;
-  }
+  lds_limit_once<conv_wgrad1_planes_kernel<NE>>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_wgrad1_planes_kernel<NE>, dim3(1, S, 1), dim3(256), K::LDS_BYTES, st, c.frames, w.dz1, w.m1, m1_words(c.max_batch),
                      c.max_batch * 12800, w.amax, w.gsc, c.max_batch, w.wpart, c.n, S, c.L->C);
 }

@@ -118,6 +118,52 @@ def test_operator_abi_host_side_queries():
     assert f.value == 1024 * 8
 
 
+# (cin, h, w, cout, kh, kw, stride, pad) -> (pack_floats, ws_floats, scratch_floats, has_forward_pool, pooled_uses_scales) at n = 1, 5, 300, 4096.
+# Recorded from the library before the conv routing moved into conv_route (csrc/api_ops.hip): what callers size their buffers by.
+CONV_HOST_ANSWERS = {
+    (3, 48, 48, 64, 7, 7, 1, (1, 1)): [(233920, 151552, 0, 1, 0), (233920, 719872, 0, 1, 0), (233920, 7274496, 0, 1, 0), (233920, 7274496, 0, 1, 0)],
+    (64, 22, 22, 128, 5, 5, 1, (1, 1)): [(829376, 819778, 1, 1, 1), (829376, 3278922, 5, 1, 1), (829376, 38527128, 300, 1, 1), (829376, 39354432, 4096, 1, 1)],
+    (128, 10, 10, 256, 3, 3, 1, (1, 1)): [(1186816, 295234, 1, 1, 1), (1186816, 1180746, 5, 1, 1), (1186816, 11512216, 300, 1, 1), (1186816, 28344384, 4096, 1, 1)],
+    (1, 48, 48, 64, 3, 3, 1, (1, 1)): [(44544, 11520, 0, 1, 0), (44544, 57600, 0, 1, 0), (44544, 491520, 0, 1, 0), (44544, 491520, 0, 1, 0)],
+    (4, 48, 48, 64, 3, 3, 1, (1, 1)): [(46656, 42624, 0, 1, 0), (46656, 213120, 0, 1, 0), (46656, 1818624, 0, 1, 0), (46656, 1818624, 0, 1, 0)],
+    (64, 24, 24, 128, 3, 3, 1, (1, 1)): [(299072, 369346, 1, 1, 1), (299072, 1698762, 5, 1, 1), (299072, 16618264, 300, 1, 1), (299072, 28368960, 4096, 1, 1)],
+    (128, 12, 12, 256, 3, 3, 1, (1, 1)): [(1186880, 590402, 1, 1, 1), (1186880, 1771082, 5, 1, 1), (1186880, 11512216, 300, 1, 1), (1186880, 28344384, 4096, 1, 1)],
+    (64, 9, 9, 64, 3, 3, 1, (0, 0)): [(149952, 36994, 1, 0, 0), (149952, 73930, 5, 0, 0), (149952, 4247384, 300, 0, 0), (149952, 9461824, 4096, 0, 0)],
+    (1, 1, 960, 32, 1, 5, 2, (0, 0)): [(12544, 192, 0, 0, 0), (12544, 960, 0, 0, 0), (12544, 57600, 0, 0, 0), (12544, 98304, 0, 0, 0)],
+    (32, 1, 478, 32, 1, 3, 2, (0, 0)): [(19072, 6208, 0, 0, 0), (19072, 31040, 0, 0, 0), (19072, 1732032, 0, 0, 0), (19072, 2383872, 0, 0, 0)],
+    (32, 1, 101, 32, 1, 3, 2, (0, 0)): [(18880, 3104, 0, 0, 0), (18880, 6208, 0, 0, 0), (18880, 366272, 0, 0, 0), (18880, 2383872, 0, 0, 0)],
+    (5, 9, 11, 70, 3, 2, 1, (2, 0)): [(32832, 2170, 0, 0, 0), (32832, 10850, 0, 0, 0), (32832, 559860, 0, 0, 0), (32832, 833280, 0, 0, 0)],
+    (4, 20, 20, 32, 4, 4, 2, (0, 0)): [(38144, 2080, 0, 0, 0), (38144, 8320, 0, 0, 0), (38144, 395200, 0, 0, 0), (38144, 1597440, 0, 0, 0)],
+    (3, 16, 16, 8, 8, 8, 4, (0, 0)): [(46528, 1544, 0, 0, 0), (46528, 1544, 0, 0, 0), (46528, 33968, 0, 0, 0), (46528, 444672, 0, 0, 0)],
+}
+CONV_HOST_ANSWERS_NS = (1, 5, 300, 4096)
+
+
+def test_conv_host_side_answers_are_pinned():
+    """Sizes and capability flags of every conv geometry of tests/test_ops_gpu.py (all kernel families + layers that have none), and of
+    NavPreNet1D.conv2 read from a strided view (the answers depend on the geometry, not on the view).  A size query that disagrees
+    with a launcher is a device buffer overrun, so the exact values are pinned."""
+    from ctypes import byref, c_int64
+    from test_ops_gpu import CONVS
+    lib = _lib.load()
+
+    def answers(d):
+        a, b, c = c_int64(), c_int64(), c_int64()
+        _lib.check(lib.ddrl_op_conv_pack_floats(byref(d), byref(a)))
+        _lib.check(lib.ddrl_op_conv_ws_floats(byref(d), byref(b)))
+        _lib.check(lib.ddrl_op_conv_scratch_floats(byref(d), byref(c)))
+        return (a.value, b.value, c.value, lib.ddrl_op_conv_has_forward_pool(byref(d)), lib.ddrl_op_conv_pooled_uses_scales(byref(d)))
+
+    assert len(CONVS) == 16
+    for (_, cin, h, w, cout, kh, kw, s, pad) in CONVS:
+        want = CONV_HOST_ANSWERS[(cin, h, w, cout, kh, kw, s, pad)]
+        for n, row in zip(CONV_HOST_ANSWERS_NS, want):
+            assert answers(_lib.ConvDesc(n, cin, h, w, cout, kh, kw, s, pad[0], pad[1], 0, 0)) == row, (cin, h, w, cout, kh, kw, s, pad, n)
+    dense = 64 * 22 * 22
+    for extra in (1, 4):   # dense + 1 rules out the plane kernels' 16-byte loads for a call; dense + 4 does not
+        assert answers(_lib.ConvDesc(3, 64, 22, 22, 128, 5, 5, 1, 1, 1, dense + extra, 0)) == (829376, 2049350, 3, 1, 1)
+
+
 def test_clean_build_stays_within_its_time_budget(tmp_path):
     """Every HIP source compiles from scratch in well under five minutes (hipcc cross-compiles gfx950 without a GPU): the driver's
     build() check and a fresh checkout depend on it.  (Round 5: a scheduling experiment -- one sched_group_barrier-pinned region over

@@ -174,6 +174,49 @@ def test_conv_strided_sample_layout():
     assert float(out[:, cout * h * w:].abs().max()) == 0.0
 
 
+# (cin, h, cout, ks, extra floats per input sample, extra floats per output sample, runs the data gradient)
+@pytest.mark.parametrize("case", [(64, 22, 128, 5, 1, 0, True),     # NavPreNet1D.conv2, in_sn = dense + 1: no 16-byte loads -> gather kernels
+                                  (64, 22, 128, 5, 4, 8, True),     # the same in views the plane kernels can load: stays on csrc/pconv.hip
+                                  (3, 48, 64, 7, 0, 2, False)])     # NavPreNet1D.conv1, out_sn = dense + 2: csrc/fconv.hip ruled out -> gather
+def test_specialised_layers_in_strided_views(case):
+    """A layer that has a specialised kernel family, called on slices of wider per-sample records: the family serves the call where the
+    view allows its 16-byte loads (strides that are multiples of four floats), the gather kernels where it does not; either way the
+    results are the layer's, and the floats between the output samples stay untouched."""
+    from ddrl4nav_amd import _lib
+    from ddrl4nav_amd.ops import Conv, _p, _st
+    from ctypes import byref
+    cin, h, cout, ks, xin, xout, has_dgrad = case
+    n, pad = 3, 1
+    g = torch.Generator().manual_seed(sum(case))
+    conv = Conv(cin, h, h, cout, ks, ks, pad=(pad, pad), max_n=n)
+    oh, ein, eout = conv.oh, cin * h * h, cout * conv.oh * conv.oh
+    x = torch.randn(n, ein + xin, generator=g)
+    wt = torch.randn(cout, cin, ks, ks, generator=g) / (cin * ks * ks) ** 0.5
+    b = torch.randn(cout, generator=g)
+    dz = torch.randn(n, eout + xout, generator=g)
+    x64 = x[:, :ein].reshape(n, cin, h, h).double().requires_grad_(True)
+    wt64, b64 = wt.double().requires_grad_(True), b.double().requires_grad_(True)
+    z = F.conv2d(x64, wt64, b64, padding=pad)
+    z.backward(dz[:, :eout].reshape(z.shape).double())
+    conv.pack(wt.cuda())
+    lib = _lib.load()
+    d = conv.desc(n, in_sn=ein + xin, out_sn=eout + xout)
+    xd, bd, dzd = x.cuda(), b.cuda(), dz.cuda()   # keep the device copies alive across the asynchronous launches
+    out = torch.zeros(n, eout + xout).cuda()
+    _lib.check(lib.ddrl_op_conv_forward(byref(d), _p(xd), _p(conv.packed), _p(bd), 0, _p(out), _p(conv.scratch), _p(None), _st()))
+    close(out[:, :eout].reshape(z.shape), z)
+    if xout:
+        assert float(out[:, eout:].abs().max()) == 0.0
+    if has_dgrad:
+        din = torch.zeros(n, ein + xin).cuda()
+        _lib.check(lib.ddrl_op_conv_dgrad(byref(d), _p(dzd), _p(conv.packed), _p(din), _p(conv.scratch), _st()))
+        close(din[:, :ein].reshape(x64.shape), x64.grad)
+    dw, db = torch.full_like(wt, 7.0).cuda(), torch.full((cout,), 7.0).cuda()
+    _lib.check(lib.ddrl_op_conv_wgrad(byref(d), _p(xd), _p(dzd), _p(conv.packed), _p(conv.ws), _p(dw), _p(db), _st()))
+    close(dw, wt64.grad)
+    close(db, b64.grad)
+
+
 @pytest.mark.parametrize("planes_hw", [((3, 5), 44, 44), ((2, 7), 20, 20), ((1, 1), 2, 2), ((4, 3), 10, 6)])
 def test_maxpool_relu_pair_vs_torch(planes_hw):
     from ddrl4nav_amd.ops import maxpool2, maxpool2_relu_backward, maxpool2_idx, maxpool2_backward_idx
