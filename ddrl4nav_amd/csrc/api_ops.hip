@@ -79,6 +79,54 @@ static PackView pack_view(const ConvGeom& g, const ConvRoute& r) {
   return v;
 }
 
+// The one place that asks plin.hip about a dense layer.
+LinearRoute ddrl::linear_route(int n, int K, int N) {
+  LinearRoute r{};
+  r.has_planes = linear_has_planes(K, N);
+  r.planes = linear_uses_planes(n, K, N);
+  r.wt_f32 = (int64_t)((K + 31) / 32 * 32) * N;
+  r.wn_f32 = (int64_t)N * ((K + 3) / 4 * 4);
+  if (r.has_planes) {  // the fp16 plane layouts follow the f32 layouts (both regions start 16-byte aligned)
+    r.wt_planes = linear_planes_floats(N, K);
+    r.wn_planes = linear_planes_floats(K, N);
+  }
+  r.fwd_splits = linear_fwd_splits(n, K, N);
+  const int gather = linear_wgrad_splits(n, K, N), planes = r.has_planes ? linear_planes_wgrad_splits(n, K, N) : 0;
+  r.wgrad_splits = r.planes ? planes : gather;
+  // both are non-decreasing in n, and launches of a plane layer below 128 rows take the gather kernels: ws holds the larger
+  r.ws_splits = gather > planes ? gather : planes;
+  return r;
+}
+
+// the family of one call: without a workspace (no room for the row scales) the forward and the data gradient fall back to the gather
+// kernels, the forward in a single pass; the weight gradient requires ws, so it never falls back
+static bool planes_for(const LinearRoute& r, const float* ws) { return r.planes && ws != nullptr; }
+
+// regions of the caller's workspace for ONE launch of n rows (null without ws); a layer's operators run in turn and share it:
+//   forward: [scales: n, rounded up to 64 | part] on the plane kernels, [part] on the gather kernels; data gradient: [scales]
+//   weight gradient: [slabs: wgrad_splits x (N * K + N) | sc_in: n | sc_dout: n], the two scale rows on the plane kernels only
+struct LinearWs { float *scales, *part, *slabs, *sc_in, *sc_dout; };
+static LinearWs linear_ws(const LinearRoute& r, int n, int K, int N, float* ws) {
+  if (!ws) return LinearWs{};
+  float* tail = ws + (int64_t)r.wgrad_splits * ((int64_t)N * K + N);
+  return LinearWs{ws, ws + (r.planes ? align_up((int64_t)n, 64) : 0), ws, tail, tail + n};
+}
+// floats that hold the layout above for EVERY launch of n' <= n rows
+static int64_t linear_ws_capacity(int n, int K, int N) {
+  const int64_t wg = (int64_t)linear_route(n, K, N).ws_splits * ((int64_t)N * K + N);
+  // split-K partials of the forward: splits(n') * n' * N floats for a launch of n' <= n samples.  FEWER samples take MORE splits
+  // (the split count fills the chip), so the product is NOT largest at n' = n: with tn = ceil(N / 128) column tiles,
+  // splits(n') <= min(cap_K, ceil(512 / (tn ceil(n' / 128)))) gives splits(n') n' <= min(cap_K n, 65536 / tn + n).  (Sizing by n alone
+  // once let a 40,000-sample launch of a 65,536-sample layer write 2 x 40,000 x N partials into 1 x 65,536 x N floats.)
+  const int64_t tn = (N + 127) / 128;
+  int64_t cap_k = ((K + 31) / 32) / 8;
+  if (cap_k < 1) cap_k = 1;
+  const int64_t by_k = cap_k * (int64_t)n, by_fill = 65536 / tn + (int64_t)n + 128;
+  const int64_t fw = (by_k < by_fill ? by_k : by_fill) * N;
+  // + the row scales: up to n + 63 floats in front of `part`, 2 n behind the slabs
+  return (wg > fw ? wg : fw) + 2 * (int64_t)n + 128;
+}
+
 extern "C" {
 
 int32_t ddrl_op_conv_out_shape(const ddrl_conv_desc* d, int32_t* oh, int32_t* ow) {
@@ -278,22 +326,21 @@ static bool lin_ok(int32_t n, int32_t K, int32_t N) { return n >= 1 && K >= 1 &&
 
 int32_t ddrl_op_linear_pack_floats(int32_t K, int32_t N, int64_t* wt_floats, int64_t* wn_floats) {
   if (!lin_ok(1, K, N) || !wt_floats || !wn_floats) return DDRL_ERR_INVALID_ARG;
-  *wt_floats = (int64_t)((K + 31) / 32 * 32) * N;
-  *wn_floats = (int64_t)N * ((K + 3) / 4 * 4);
-  if (linear_has_planes(K, N)) {  // the fp16 plane layouts of plin.hip follow the f32 layouts (both regions start 16-byte aligned)
-    *wt_floats += linear_planes_fwd_floats(K, N);
-    *wn_floats += linear_planes_dgrad_floats(K, N);
-  }
+  const LinearRoute r = linear_route(1, K, N);
+  *wt_floats = r.wt_f32 + r.wt_planes;
+  *wn_floats = r.wn_f32 + r.wn_planes;
   return DDRL_OK;
 }
 
 int32_t ddrl_op_linear_pack(const float* w, int32_t K, int32_t N, float* wt, float* wn, void* stream) {
   if (!lin_ok(1, K, N) || !w || !wt || !wn || !aligned16(wt) || !aligned16(wn)) return DDRL_ERR_INVALID_ARG;
+  const LinearRoute r = linear_route(1, K, N);
+  if (r.has_planes) launch_linear_planes_pack(w, K, N, wt + r.wt_f32, wn + r.wn_f32, (hipStream_t)stream);
   launch_linear_pack(w, K, N, wt, wn, (hipStream_t)stream);
   return op_check();
 }
 
-int32_t ddrl_op_linear_uses_planes(int32_t n, int32_t K, int32_t N) { return lin_ok(n, K, N) && linear_uses_planes(n, K, N) ? 1 : 0; }
+int32_t ddrl_op_linear_uses_planes(int32_t n, int32_t K, int32_t N) { return lin_ok(n, K, N) && linear_route(n, K, N).planes ? 1 : 0; }
 
 int32_t ddrl_op_row_amax(const float* x, int64_t ld, int32_t width, int32_t n, float* amax, int32_t accumulate, void* stream) {
   if (!x || !amax || n < 1 || width < 1 || (ld & 3) || ld < (width + 3) / 4 * 4 || !aligned16(x)) return DDRL_ERR_INVALID_ARG;
@@ -305,7 +352,13 @@ int32_t ddrl_op_linear_forward(const float* in, int64_t ld_in, const float* wt, 
                                int64_t ld_out, int32_t n, int32_t K, int32_t N, float* ws, const float* in_amax, void* stream) {
   if (!lin_ok(n, K, N) || !in || !wt || !bias || !out || act < 0 || act > 1) return DDRL_ERR_INVALID_ARG;
   if ((ld_in & 3) || ld_in < (K + 3) / 4 * 4 || ld_out < N || !aligned16(in) || !aligned16(wt)) return DDRL_ERR_INVALID_ARG;
-  launch_linear_fwd(in, ld_in, wt, bias, out, ld_out, n, K, N, act, ws, in_amax, (hipStream_t)stream);
+  const LinearRoute r = linear_route(n, K, N);
+  const LinearWs v = linear_ws(r, n, K, N, ws);
+  if (planes_for(r, ws))
+    launch_linear_planes_fwd(in, ld_in, wt + r.wt_f32, bias, out, ld_out, n, K, N, act, r.fwd_splits, v.scales, v.part, in_amax,
+                             (hipStream_t)stream);
+  else
+    launch_linear_fwd(in, ld_in, wt, bias, out, ld_out, n, K, N, act, ws ? r.fwd_splits : 1, v.part, (hipStream_t)stream);
   return op_check();
 }
 
@@ -318,28 +371,21 @@ int32_t ddrl_op_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn
     if (amax_hi <= 0) amax_hi = K;   // default: every column
     if (amax_lo < 0 || amax_lo >= amax_hi || amax_hi > K || (amax_lo & 3) || (ld_din & 3) || !aligned16(din)) return DDRL_ERR_INVALID_ARG;
   }
-  launch_linear_dgrad(dout, ld_dout, wn, mask_src, ld_mask, din, ld_din, n, K, N, ws, dout_amax, din_amax, amax_lo, amax_hi, (hipStream_t)stream);
+  const LinearRoute r = linear_route(n, K, N);
+  if (planes_for(r, ws)) {
+    launch_linear_planes_dgrad(dout, ld_dout, wn + r.wn_f32, mask_src, ld_mask, din, ld_din, n, K, N, linear_ws(r, n, K, N, ws).scales,
+                               dout_amax, din_amax, amax_lo, amax_hi, (hipStream_t)stream);
+  } else {
+    launch_linear_dgrad(dout, ld_dout, wn, mask_src, ld_mask, din, ld_din, n, K, N, (hipStream_t)stream);
+    // no epilogue for it: a pass over the rows just written (the column range allows 16-byte loads: above)
+    if (din_amax) launch_row_amax(din + amax_lo, ld_din, amax_hi - amax_lo, n, din_amax, 1, (hipStream_t)stream);
+  }
   return op_check();
 }
 
 int32_t ddrl_op_linear_ws_floats(int32_t n, int32_t K, int32_t N, int64_t* floats) {
   if (!lin_ok(n, K, N) || !floats) return DDRL_ERR_INVALID_ARG;
-  int64_t wg = (int64_t)linear_wgrad_splits(n, K, N) * ((int64_t)N * K + N);   // non-decreasing in n
-  if (linear_has_planes(K, N)) {  // plin.hip's split counts (non-decreasing in n as well)
-    const int64_t wp = (int64_t)linear_planes_wgrad_splits(n, K, N) * ((int64_t)N * K + N);
-    if (wp > wg) wg = wp;
-  }
-  // split-K partials of the forward: splits(n') * n' * N floats for a launch of n' <= n samples.  FEWER samples take MORE splits
-  // (the split count fills the chip), so the product is NOT largest at n' = n: with tn = ceil(N / 128) column tiles,
-  // splits(n') <= min(cap_K, ceil(512 / (tn ceil(n' / 128)))) gives splits(n') n' <= min(cap_K n, 65536 / tn + n).  (Sizing by n alone
-  // once let a 40,000-sample launch of a 65,536-sample layer write 2 x 40,000 x N partials into 1 x 65,536 x N floats.)
-  const int64_t tn = (N + 127) / 128;
-  int64_t cap_k = ((K + 31) / 32) / 8;
-  if (cap_k < 1) cap_k = 1;
-  const int64_t by_k = cap_k * (int64_t)n, by_fill = 65536 / tn + (int64_t)n + 128;
-  const int64_t fw = (by_k < by_fill ? by_k : by_fill) * N;
-  // + the per-row plane scales of plin.hip: n floats (rounded up to 64) in front of the forward's partials, 2 n behind the slabs
-  *floats = (wg > fw ? wg : fw) + 2 * (int64_t)n + 128;
+  *floats = linear_ws_capacity(n, K, N);
   return DDRL_OK;
 }
 
@@ -348,7 +394,13 @@ int32_t ddrl_op_linear_wgrad(const float* in, int64_t ld_in, const float* dout, 
   if (!lin_ok(n, K, N) || !in || !dout || !ws || !dw || !db) return DDRL_ERR_INVALID_ARG;
   if ((ld_in & 3) || (ld_dout & 3) || ld_in < (K + 3) / 4 * 4 || ld_dout < N || !aligned16(in) || !aligned16(dout))
     return DDRL_ERR_INVALID_ARG;
-  launch_linear_wgrad(in, ld_in, dout, ld_dout, ws, n, K, N, dw, db, in_amax, dout_amax, (hipStream_t)stream);
+  const LinearRoute r = linear_route(n, K, N);
+  const LinearWs v = linear_ws(r, n, K, N, ws);
+  if (planes_for(r, ws))
+    launch_linear_planes_wgrad(in, ld_in, dout, ld_dout, v.slabs, r.wgrad_splits, v.sc_in, v.sc_dout, n, K, N, dw, db, in_amax, dout_amax,
+                               (hipStream_t)stream);
+  else
+    launch_linear_wgrad(in, ld_in, dout, ld_dout, v.slabs, r.wgrad_splits, n, K, N, dw, db, (hipStream_t)stream);
   return op_check();
 }
 

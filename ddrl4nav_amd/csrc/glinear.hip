@@ -3,9 +3,9 @@
 // sizes and leading dimensions.  These serve the encoders outside the Atari fast path
 // (reference USTC_lab/nn/nav_encoder.py:21-24,103-106, USTC_lab/nn/mlp_encoder.py:18 and the
 // `mlp` helper USTC_lab/nn/utils.py:10-20); the 3136->512 Atari layer keeps its own kernels (fc2.hip).
-// Since round 4 layers of K >= 128, N >= 64 in launches of >= 128 rows run as fp16 plane products instead (plin.hip; the launchers at
-// the bottom dispatch): these kernels remain for small layers, small launches (acting with a few environments: split-K fills the chip
-// from one row tile).
+// Since round 4 layers of K >= 128, N >= 64 in launches of >= 128 rows run as fp16 plane products instead (plin.hip; linear_route in
+// api_ops.hip decides): these kernels remain for small layers, small launches (acting with a few environments: split-K fills the chip
+// from one row tile), calls without ws.
 //
 // Layout contract (checked by the C ABI): every leading dimension is a multiple of 4 floats and
 // every base pointer 16-byte aligned, so that all staging loads are aligned f4 loads;
@@ -397,11 +397,7 @@ void launch_relu_mask(float* d, int64_t ld_d, const float* act, int64_t ld_act, 
                      width);
 }
 
-static int64_t wt_f32_floats(int K, int N) { return (int64_t)((K + 31) / 32 * 32) * N; }
-static int64_t wn_f32_floats(int K, int N) { return (int64_t)N * ((K + 3) / 4 * 4); }
-
 void launch_linear_pack(const float* w, int K, int N, float* wt, float* wn, hipStream_t st) {
-  if (linear_has_planes(K, N)) launch_linear_planes_pack(w, K, N, wt + wt_f32_floats(K, N), wn + wn_f32_floats(K, N), st);
   const int Kp32 = (K + 31) / 32 * 32, Kp4 = (K + 3) / 4 * 4;
   const int64_t total = (int64_t)N * (Kp32 > Kp4 ? Kp32 : Kp4);
   hipLaunchKernelGGL(linear_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, K, N, Kp32, Kp4, wt, wn);
@@ -436,32 +432,16 @@ void launch_linear_finish(const float* part, int nsplit, int n, int N, const flo
 }
 
 void launch_linear_fwd(const float* in, int64_t ld_in, const float* wt, const float* bias, float* out, int64_t ld_out, int n,
-                       int K, int N, int act, float* part, const float* in_scales, hipStream_t st) {
-  if (part && linear_uses_planes(n, K, N)) {
-    launch_linear_planes_fwd(in, ld_in, wt + wt_f32_floats(K, N), bias, out, ld_out, n, K, N, act, part, in_scales, st);
-    return;
-  }
-  const int S = part ? linear_fwd_splits(n, K, N) : 1;
+                       int K, int N, int act, int S, float* part, hipStream_t st) {
   glin::Fwd::Params p{in, ld_in, wt, bias, out, ld_out, n, K, N, act, S, part};
   launch_engine2<glin::Fwd>(dim3((N + 127) / 128, (n + 127) / 128, S), p, st);
-  if (S > 1)
-    hipLaunchKernelGGL(linear_finish_kernel, dim3((unsigned)(((int64_t)n * N + 255) / 256)), dim3(256), 0, st, part, S,
-                       (int64_t)n, N, bias, act, out, ld_out);
+  if (S > 1) launch_linear_finish(part, S, n, N, bias, act, out, ld_out, st);
 }
 
 void launch_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn, const float* mask_src, int64_t ld_mask,
-                         float* din, int64_t ld_din, int n, int K, int N, float* ws, const float* dout_scales, float* din_amax, int amax_lo,
-                         int amax_hi, hipStream_t st) {
-  if (ws && linear_uses_planes(n, K, N)) {
-    launch_linear_planes_dgrad(dout, ld_dout, wn + wn_f32_floats(K, N), mask_src, ld_mask, din, ld_din, n, K, N, ws, dout_scales, din_amax,
-                               amax_lo, amax_hi, st);
-    return;
-  }
+                         float* din, int64_t ld_din, int n, int K, int N, hipStream_t st) {
   glin::Dgrad::Params p{dout, ld_dout, wn, mask_src, ld_mask, din, ld_din, n, K, N, (K + 3) / 4 * 4};
   launch_engine2<glin::Dgrad>(dim3((K + 127) / 128, (n + 127) / 128, 1), p, st);
-  // small launches (fewer than 128 rows) and small layers: the magnitudes come from a pass over the rows just written (api_ops.hip
-  // checked that the column range allows 16-byte loads)
-  if (din_amax != nullptr) launch_row_amax(din + amax_lo, ld_din, amax_hi - amax_lo, n, din_amax, 1, st);
 }
 
 int linear_wgrad_splits(int n, int K, int N) {
@@ -473,17 +453,11 @@ int linear_wgrad_splits(int n, int K, int N) {
   return s < 1 ? 1 : s;
 }
 
-void launch_linear_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int n, int K, int N,
-                         float* dw, float* db, const float* in_scales, const float* dout_scales, hipStream_t st) {
-  if (linear_uses_planes(n, K, N)) {
-    launch_linear_planes_wgrad(in, ld_in, dout, ld_dout, part, n, K, N, dw, db, in_scales, dout_scales, st);
-    return;
-  }
-  const int S = linear_wgrad_splits(n, K, N);
+void launch_linear_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int S, int n, int K, int N,
+                         float* dw, float* db, hipStream_t st) {
   glin::Wgrad::Params p{dout, ld_dout, in, ld_in, part, n, K, N, S};
   launch_engine2<glin::Wgrad>(dim3((K + 127) / 128, (N + 127) / 128, S), p, st);
-  const int64_t slab = (int64_t)N * K + N;
-  launch_reduce_slabs2(part, S, slab, (int64_t)N * K, dw, N, db, st);
+  launch_reduce_slabs2(part, S, (int64_t)N * K + N, (int64_t)N * K, dw, N, db, st);
 }
 
 }  // namespace ddrl

@@ -1,6 +1,7 @@
 // Internal launcher interface of the generic operators: the gather kernels that serve any layer (gconv.hip, glinear.hip, gheads.hip) and
-// the specialised conv / dense families (pconv.hip, fconv.hip, c1d.hip, plin.hip).  Which conv family serves a layer is decided in ONE
-// place, conv_route (api_ops.hip); the ddrl_op_conv_* entry points switch on its answer and nothing else calls the conv_has_* predicates.
+// the specialised conv / dense families (pconv.hip, fconv.hip, c1d.hip, plin.hip).  Which family serves a layer is decided in ONE place per
+// operator kind, conv_route and linear_route (api_ops.hip): the entry points switch on the answer and hand each launcher its pointers into
+// the packed buffers and the workspace; nothing else calls the conv_has_* / linear_*_planes predicates.
 #pragma once
 #include "common.h"
 
@@ -98,39 +99,46 @@ void launch_relu_mask(float* d, int64_t ld_d, const float* act, int64_t ld_act, 
 void launch_accumulate(float* dst, const float* src, int64_t count, hipStream_t st);
 void launch_linear_pack(const float* w, int K, int N, float* wt, float* wn, hipStream_t st);
 int linear_fwd_splits(int n, int K, int N);
+// part: S * n * N partials of the forward (null when S = 1), S slabs of N * K + N floats of the weight gradient; plin.hip alike
 void launch_linear_fwd(const float* in, int64_t ld_in, const float* wt, const float* bias, float* out, int64_t ld_out, int n,
-                       int K, int N, int act, float* part, const float* in_scales, hipStream_t st);
+                       int K, int N, int act, int S, float* part, hipStream_t st);
 void launch_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn, const float* mask_src, int64_t ld_mask,
-                         float* din, int64_t ld_din, int n, int K, int N, float* ws, const float* dout_scales, float* din_amax, int amax_lo,
-                         int amax_hi, hipStream_t st);
+                         float* din, int64_t ld_din, int n, int K, int N, hipStream_t st);
 int linear_wgrad_splits(int n, int K, int N);
-void launch_linear_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int n, int K, int N,
-                         float* dw, float* db, const float* in_scales, const float* dout_scales, hipStream_t st);
-
+void launch_linear_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int S, int n, int K, int N,
+                         float* dw, float* db, hipStream_t st);
 void launch_linear_finish(const float* part, int nsplit, int n, int N, const float* bias, int act, float* out, int64_t ld_out, hipStream_t st);
 
 // plin.hip: the same three operators on the 16-bit matrix pipe (two scaled fp16 planes per operand, per-row activation scales) for layers
 // of K >= 128, N >= 64 and launches of n >= 128 rows; packed plane regions follow the f32 layouts inside wt / wn
 bool linear_has_planes(int K, int N);
 bool linear_uses_planes(int n, int K, int N);
-int64_t linear_planes_fwd_floats(int K, int N);
-int64_t linear_planes_dgrad_floats(int K, int N);
+int64_t linear_planes_floats(int cols, int red);  // one packed region: forward (N, K), data gradient (K, N)
 void launch_linear_planes_pack(const float* w, int K, int N, float* pf, float* pd, hipStream_t st);
-int linear_planes_fwd_splits(int n, int K, int N);
-// ws: n floats rounded up to 64 (row magnitudes of a pre-pass), then linear_planes_fwd_splits * n * N partials
-void launch_row_amax(const float* x, int64_t ld, int width, int n, float* amax, int accumulate, hipStream_t st);   // amax[b] = (max with) max |x[b][:width]|
-// given*: per-row magnitudes the caller already holds for that tensor (a producer's out_amax, launch_row_amax), or nullptr for a pre-pass into the scratch
+// amax[b] = (max with) max |x[b][:width]|; shared: the plane kernels' pre-pass, ddrl_op_row_amax, din_amax of the gather data gradient
+void launch_row_amax(const float* x, int64_t ld, int width, int n, float* amax, int accumulate, hipStream_t st);
+// given*: per-row magnitudes the caller already holds (a producer's out_amax, launch_row_amax); nullptr = a pre-pass into scales / sc_* (n floats)
 void launch_linear_planes_fwd(const float* in, int64_t ld_in, const float* pf, const float* bias, float* out, int64_t ld_out, int n, int K,
-                              int N, int act, float* ws, const float* given, hipStream_t st);
-// ws: n floats
+                              int N, int act, int S, float* scales, float* part, const float* given, hipStream_t st);
 // din_amax (may be null): n floats RAISED to the largest |din| of every row over the columns [amax_lo, amax_hi) (zeroed by the caller)
 void launch_linear_planes_dgrad(const float* dout, int64_t ld_dout, const float* pd, const float* mask_src, int64_t ld_mask, float* din,
-                                int64_t ld_din, int n, int K, int N, float* ws, const float* given, float* din_amax, int amax_lo, int amax_hi,
-                                hipStream_t st);
+                                int64_t ld_din, int n, int K, int N, float* scales, const float* given, float* din_amax, int amax_lo,
+                                int amax_hi, hipStream_t st);
 int linear_planes_wgrad_splits(int n, int K, int N);
-// part: linear_planes_wgrad_splits slabs of N * K + N floats, then 2 n floats
-void launch_linear_planes_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int n, int K, int N,
-                                float* dw, float* db, const float* given_in, const float* given_dout, hipStream_t st);
+void launch_linear_planes_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int S, float* sc_in,
+                                float* sc_dout, int n, int K, int N, float* dw, float* db, const float* given_in, const float* given_dout,
+                                hipStream_t st);
+
+// What serves a dense layer (K, N) in a launch of n rows, and every size that follows from it
+struct LinearRoute {
+  bool has_planes;               // the layer has packed plane regions
+  bool planes;                   // a launch of n rows runs on them
+  int64_t wt_f32, wn_f32;        // floats of the f32 layouts = offsets of the plane regions inside wt / wn
+  int64_t wt_planes, wn_planes;  // floats of the plane regions (0 without)
+  int fwd_splits, wgrad_splits;  // of the family that runs
+  int ws_splits;                 // largest weight-gradient split count of any launch of n' <= n rows (sizes ws)
+};
+LinearRoute linear_route(int n, int K, int N);
 
 // gheads.hip: Gaussian actor + critic heads; offsets into the caller's flat parameter arena
 struct GaussLayout {

@@ -405,28 +405,23 @@ __global__ __launch_bounds__(256, 2) void tn_planes_kernel(TnParams P) {
 // Layers deep and wide enough for 128 x 128 x 32 tiles; launches of fewer than 128 rows (acting with a few environments) stay on the
 // f32-input kernels, whose split-K fills the chip from one row tile.
 bool linear_has_planes(int K, int N) { return K >= 128 && N >= 64; }
-bool linear_uses_planes(int n, int K, int N) { return linear_has_planes(K, N) && n >= 128; }
+bool linear_uses_planes(int n, int K, int N) { return K >= 128 && N >= 64 && n >= 128; }
 
 static int kgs_of(int red) { return 2 * ((red + 31) / 32); }
-// floats of the packed plane regions behind the f32 layouts of wt / wn: planes (2 bytes x 2 planes) + a 64-float header
-int64_t linear_planes_fwd_floats(int K, int N) { return (int64_t)((N + 127) / 128) * kgs_of(K) * (NPL * 2048) / 2 + 64; }
-int64_t linear_planes_dgrad_floats(int K, int N) { return (int64_t)((K + 127) / 128) * kgs_of(N) * (NPL * 2048) / 2 + 64; }
+// floats of the planes of one packed region (2 bytes x 2 planes); its 64-float header follows them behind the f32 layouts of wt / wn
+static int64_t planes_floats(int cols, int red) { return (int64_t)((cols + 127) / 128) * kgs_of(red) * (NPL * 2048) / 2; }
+int64_t linear_planes_floats(int cols, int red) { return planes_floats(cols, red) + 64; }
 
 void launch_linear_planes_pack(const float* w, int K, int N, float* pf, float* pd, hipStream_t st) {
-  float* hdrs[2];
-  for (int t = 0; t < 2; ++t) {
-    const int cols = t ? K : N, kgs = kgs_of(t ? N : K);
-    hdrs[t] = (t ? pd : pf) + (int64_t)((cols + 127) / 128) * kgs * (NPL * 2048) / 2;
-    (void)hipMemsetAsync(hdrs[t], 0, 64 * sizeof(float), st);
-  }
+  float* hdrs[2] = {pf + planes_floats(N, K), pd + planes_floats(K, N)};
+  for (int t = 0; t < 2; ++t) (void)hipMemsetAsync(hdrs[t], 0, 64 * sizeof(float), st);
   const int64_t count = (int64_t)K * N;
   launch_weight_amax(w, count, hdrs[0], hdrs[1], weight_amax_blocks(count), st);  // both regions take the same scale: one pass over the weights
   for (int t = 0; t < 2; ++t) {
-    float* region = t ? pd : pf;
     const int cols = t ? K : N, kgs = kgs_of(t ? N : K);
-    float* hdr = hdrs[t];
     const int64_t total = (int64_t)((cols + 127) / 128) * kgs * 2048;
-    hipLaunchKernelGGL(plin::pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, K, N, t, kgs, (unsigned short*)region, hdr);
+    hipLaunchKernelGGL(plin::pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, K, N, t, kgs,
+                       (unsigned short*)(t ? pd : pf), hdrs[t]);
   }
 }
 
@@ -436,42 +431,25 @@ static void run_nt(const plin::NtParams& p, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(plin::nt_planes_kernel<DGRAD>, grid, dim3(256), plin::LDS_NT, st, p);
 }
 
-static void row_scales(const float* x, int64_t ld, int width, int n, float* amax, hipStream_t st, int accumulate = 0) {
+void launch_row_amax(const float* x, int64_t ld, int width, int n, float* amax, int accumulate, hipStream_t st) {
   hipLaunchKernelGGL(plin::row_amax_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, x, ld, width, n, amax, accumulate);
 }
 
-int linear_planes_fwd_splits(int n, int K, int N) {
-  const int tiles = ((N + 127) / 128) * ((n + 127) / 128);
-  int s = (512 + tiles - 1) / tiles;
-  const int cap = ((K + 31) / 32) / 8;  // at least 8 k-blocks per split (the bound ddrl_op_linear_ws_floats sizes the partials by)
-  if (s > cap) s = cap;
-  return s < 1 ? 1 : s;
-}
-
-// ws: n floats (row scales, rounded up to 64), then the split-K partials
-void launch_row_amax(const float* x, int64_t ld, int width, int n, float* amax, int accumulate, hipStream_t st) { row_scales(x, ld, width, n, amax, st, accumulate); }
-
-// given*: per-row scales the caller already holds (launch_row_scales on the same tensor), or nullptr for a pre-pass into the scratch
 void launch_linear_planes_fwd(const float* in, int64_t ld_in, const float* pf, const float* bias, float* out, int64_t ld_out, int n, int K,
-                              int N, int act, float* ws, const float* given, hipStream_t st) {
-  const int kgs = kgs_of(K);
-  const int64_t planes = (int64_t)((N + 127) / 128) * kgs * (NPL * 2048) / 2;
-  const int S = linear_planes_fwd_splits(n, K, N);
-  float* part = ws + (n + 63) / 64 * 64;
-  if (!given) row_scales(in, ld_in, K, n, ws, st);
-  plin::NtParams p{in, ld_in, given ? given : ws, (const unsigned short*)pf, pf + planes, n, N, kgs, bias, act, S, part, nullptr, 0, out, ld_out, nullptr, 0, 0};
+                              int N, int act, int S, float* scales, float* part, const float* given, hipStream_t st) {
+  if (!given) launch_row_amax(in, ld_in, K, n, scales, 0, st);
+  plin::NtParams p{in, ld_in, given ? given : scales, (const unsigned short*)pf, pf + planes_floats(N, K), n, N, kgs_of(K), bias, act, S, part, nullptr, 0,
+                   out, ld_out, nullptr, 0, 0};
   run_nt<0>(p, dim3((N + 127) / 128, (n + 127) / 128, S), st);
   if (S > 1) launch_linear_finish(part, S, n, N, bias, act, out, ld_out, st);
 }
 
 void launch_linear_planes_dgrad(const float* dout, int64_t ld_dout, const float* pd, const float* mask_src, int64_t ld_mask, float* din,
-                                int64_t ld_din, int n, int K, int N, float* ws, const float* given, float* din_amax, int amax_lo, int amax_hi,
-                                hipStream_t st) {
-  const int kgs = kgs_of(N);
-  const int64_t planes = (int64_t)((K + 127) / 128) * kgs * (NPL * 2048) / 2;
-  if (!given) row_scales(dout, ld_dout, N, n, ws, st);
-  plin::NtParams p{dout, ld_dout, given ? given : ws, (const unsigned short*)pd, pd + planes, n, K, kgs, nullptr, 0, 1, nullptr, mask_src, ld_mask, din, ld_din,
-                   din_amax, amax_lo, amax_hi};
+                                int64_t ld_din, int n, int K, int N, float* scales, const float* given, float* din_amax, int amax_lo,
+                                int amax_hi, hipStream_t st) {
+  if (!given) launch_row_amax(dout, ld_dout, N, n, scales, 0, st);
+  plin::NtParams p{dout, ld_dout, given ? given : scales, (const unsigned short*)pd, pd + planes_floats(K, N), n, K, kgs_of(N), nullptr, 0, 1, nullptr,
+                   mask_src, ld_mask, din, ld_din, din_amax, amax_lo, amax_hi};
   run_nt<1>(p, dim3((K + 127) / 128, (n + 127) / 128, 1), st);
 }
 
@@ -483,19 +461,15 @@ int linear_planes_wgrad_splits(int n, int K, int N) {
   return s < 1 ? 1 : s;
 }
 
-// part: S slabs of N * K + N floats, then 2 n floats for the row scales
-void launch_linear_planes_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int n, int K, int N,
-                                float* dw, float* db, const float* given_in, const float* given_dout, hipStream_t st) {
+void launch_linear_planes_wgrad(const float* in, int64_t ld_in, const float* dout, int64_t ld_dout, float* part, int S, float* sc_in,
+                                float* sc_dout, int n, int K, int N, float* dw, float* db, const float* given_in, const float* given_dout,
+                                hipStream_t st) {
   lds_limit_once<plin::tn_planes_kernel>(plin::LDS_TN);
-  const int S = linear_planes_wgrad_splits(n, K, N);
-  const int64_t slab = (int64_t)N * K + N;
-  float* sc_i = part + (int64_t)S * slab;
-  float* sc_d = sc_i + n;
-  if (!given_in) row_scales(in, ld_in, K, n, sc_i, st);
-  if (!given_dout) row_scales(dout, ld_dout, N, n, sc_d, st);
-  plin::TnParams p{dout, ld_dout, in, ld_in, given_dout ? given_dout : sc_d, given_in ? given_in : sc_i, part, n, K, N, S};
+  if (!given_in) launch_row_amax(in, ld_in, K, n, sc_in, 0, st);
+  if (!given_dout) launch_row_amax(dout, ld_dout, N, n, sc_dout, 0, st);
+  plin::TnParams p{dout, ld_dout, in, ld_in, given_dout ? given_dout : sc_dout, given_in ? given_in : sc_in, part, n, K, N, S};
   hipLaunchKernelGGL(plin::tn_planes_kernel, dim3((K + 127) / 128, (N + 127) / 128, S), dim3(256), plin::LDS_TN, st, p);
-  launch_reduce_slabs2(part, S, slab, (int64_t)N * K, dw, N, db, st);
+  launch_reduce_slabs2(part, S, (int64_t)N * K + N, (int64_t)N * K, dw, N, db, st);
 }
 
 }  // namespace ddrl

@@ -51,42 +51,40 @@ class _Dense:
 
     def __init__(self, module, relu, cap, device):
         self.m, self.relu = module, relu
-        self.K, self.N = module.in_features, module.out_features
+        self.K, self.N = module.in_features, _pad4(module.out_features)
         self.op = Linear(self.K, self.N, max_n=cap, device=device)
-        self._scale_buffers(cap, device)
-
-    def _scale_buffers(self, cap, device):
         # per-row magnitudes of the layer's input and of d(output) (include/ddrl.h "per-sample magnitudes"): found once per pass and
         # shared by the operators that read the same tensor (forward + weight gradient; data + weight gradient).  A caller that knows
         # the tensor's producer hands the producer's `out_amax` in instead (in_amax / dout_amax below) and the pre-pass is skipped.
         share = self.op.uses_planes(cap)
         self.in_sc = torch.empty((cap,), dtype=torch.float32, device=device) if share else None
         self.dout_sc = torch.empty((cap,), dtype=torch.float32, device=device) if share else None
+        self._fwd_sc = None
 
-    def _in_amax(self, x, ld_in, n, given=None):
-        if self.in_sc is None or not self.op.uses_planes(n):
+    def _amax(self, x, ld, width, n, buf, given):
+        if buf is None or not self.op.uses_planes(n):
             return None
-        return given if given is not None else self.op.row_amax(x, ld_in, self.K, n, self.in_sc)
+        return given if given is not None else self.op.row_amax(x, ld, width, n, buf)
 
-    def _dout_amax(self, dout, ld_dout, n, given=None):
-        if self.dout_sc is None or not self.op.uses_planes(n):
-            return None
-        return given if given is not None else self.op.row_amax(dout, ld_dout, self.N, n, self.dout_sc)
+    def _bias(self):
+        return self.m.bias.data
+
+    def _wgrad(self, x, ld_in, dout, ld_dout, n, **amax):
+        self.op.wgrad(x, ld_in, dout, ld_dout, self.m.weight.grad_view, self.m.bias.grad_view, n, **amax)
 
     def pack(self):
         self.op.pack(self.m.weight.data)
 
     def forward(self, x, ld_in, out, ld_out, n, in_amax=None):
-        self._fwd_sc = self._in_amax(x, ld_in, n, in_amax)     # kept for the weight gradient of the same pass
-        return self.op.forward(x, ld_in, self.m.bias.data, self.relu, out, ld_out, n, in_amax=self._fwd_sc)
+        self._fwd_sc = self._amax(x, ld_in, self.K, n, self.in_sc, in_amax)     # kept for the weight gradient of the same pass
+        return self.op.forward(x, ld_in, self._bias(), self.relu, out, ld_out, n, in_amax=self._fwd_sc)
 
     def backward(self, x, ld_in, dout, ld_dout, n, din=None, ld_din=0, mask_src=None, ld_mask=0, dout_amax=None, din_amax=None,
                  amax_cols=None):
         """dout = gradient w.r.t. this layer's PRE-activation output (the consumer applied the ReLU mask).  din_amax (zeroed by the
         caller): raised to every row's largest |din| over the columns amax_cols -- what the layer below will ask for."""
-        ds = self._dout_amax(dout, ld_dout, n, dout_amax)
-        self.op.wgrad(x, ld_in, dout, ld_dout, self.m.weight.grad_view, self.m.bias.grad_view, n, in_amax=getattr(self, "_fwd_sc", None),
-                      dout_amax=ds)
+        ds = self._amax(dout, ld_dout, self.N, n, self.dout_sc, dout_amax)
+        self._wgrad(x, ld_in, dout, ld_dout, n, in_amax=self._fwd_sc, dout_amax=ds)
         if din is not None:
             self.op.dgrad(dout, ld_dout, mask_src, ld_mask, din, ld_din, n, dout_amax=ds, din_amax=din_amax, amax_cols=amax_cols)
 
@@ -98,11 +96,8 @@ class _PaddedDense(_Dense):
     to the parameter's gradient view."""
 
     def __init__(self, module, relu, cap, device):
-        self.m, self.relu = module, relu
-        self.K, self.N_real = module.in_features, module.out_features
-        self.N = _pad4(self.N_real)
-        self.op = Linear(self.K, self.N, max_n=cap, device=device)
-        self._scale_buffers(cap, device)
+        super().__init__(module, relu, cap, device)
+        self.N_real = module.out_features
         f = dict(dtype=torch.float32, device=device)
         self.wpad, self.bpad = torch.zeros((self.N, self.K), **f), torch.zeros(self.N, **f)
         self.dwpad, self.dbpad = torch.zeros((self.N, self.K), **f), torch.zeros(self.N, **f)
@@ -112,19 +107,14 @@ class _PaddedDense(_Dense):
         self.bpad[:self.N_real].copy_(self.m.bias.data)
         self.op.pack(self.wpad)
 
-    def forward(self, x, ld_in, out, ld_out, n, in_amax=None):
-        self._fwd_sc = self._in_amax(x, ld_in, n, in_amax)
-        return self.op.forward(x, ld_in, self.bpad, self.relu, out, ld_out, n, in_amax=self._fwd_sc)
+    def _bias(self):
+        return self.bpad
 
-    def backward(self, x, ld_in, dout, ld_dout, n, din=None, ld_din=0, mask_src=None, ld_mask=0, dout_amax=None, din_amax=None,
-                 amax_cols=None):
-        ds = self._dout_amax(dout, ld_dout, n, dout_amax)
-        self.op.wgrad(x, ld_in, dout, ld_dout, self.dwpad, self.dbpad, n, in_amax=getattr(self, "_fwd_sc", None), dout_amax=ds)
+    def _wgrad(self, x, ld_in, dout, ld_dout, n, **amax):
+        self.op.wgrad(x, ld_in, dout, ld_dout, self.dwpad, self.dbpad, n, **amax)
         self.m.weight.grad_view.copy_(self.dwpad[:self.N_real])
         # bias gradient = column sums of dout, correctly rounded (see csrc/gail.hip:colsum_kernel)
         check(_lib.load().ddrl_op_colsum(_p(dout), ld_dout, n, self.N_real, _p(self.m.bias.grad_view), _st()))
-        if din is not None:
-            self.op.dgrad(dout, ld_dout, mask_src, ld_mask, din, ld_din, n, dout_amax=ds, din_amax=din_amax, amax_cols=amax_cols)
 
 
 def dense_layer(module, relu, cap, device):

@@ -387,8 +387,13 @@ int32_t ddrl_op_maxpool2_backward_idx(const float* dpool, const uint8_t* code, i
  * wt / wn = derived layouts written by ddrl_op_linear_pack (sizes from ddrl_op_linear_pack_floats). */
 int32_t ddrl_op_linear_pack_floats(int32_t K, int32_t N, int64_t* wt_floats, int64_t* wn_floats);
 int32_t ddrl_op_linear_pack(const float* w, int32_t K, int32_t N, float* wt, float* wn, void* stream);
-/* ws: scratch of ddrl_op_linear_ws_floats(n, K, N) floats (lets small n x N problems split K over
- * workgroups), or NULL for a single pass.
+/* ws: scratch of ddrl_op_linear_ws_floats(max n, K, N) floats, shared by the three operators of a layer (they run one after the other)
+ * and large enough for every launch of n <= max n rows.  Each launch lays it out from offset 0 (S = its split count):
+ *   forward        f32-input kernels: S * n * N split-K partials (lets small n x N problems split K over workgroups);
+ *                  plane kernels: n row scales (the pre-pass when in_amax == NULL) rounded up to 64 floats, then the partials.
+ *                  NULL: the f32-input kernels in a single pass.
+ *   data gradient  plane kernels: n row scales (the pre-pass when dout_amax == NULL).  NULL: the f32-input kernels.
+ *   weight grad.   S slabs of N * K + N floats; plane kernels: then n + n row scales (in, dout).  Required.
  * in_amax / dout_amax: layers of K >= 128, N >= 64 in launches of n >= 128 rows (ddrl_op_linear_uses_planes: 1) run as fp16 plane
  * products and scale every ROW of `in` / `dout` by a power of two from the row's largest magnitude ("per-sample magnitudes" above: from
  * the tensor's producer, from ddrl_op_row_amax, or NULL = the operator's own pre-pass).  The forward and the weight gradient read the
@@ -399,8 +404,7 @@ int32_t ddrl_op_linear_forward(const float* in, int64_t ld_in, const float* wt, 
                                float* out, int64_t ld_out, int32_t n, int32_t K, int32_t N, float* ws, const float* in_amax,
                                void* stream);
 /* din[b][k] = [mask_src[b][k] > 0 or mask_src == NULL] * sum_n dout[b][n] W[n][k]; mask_src is the
- * (ReLU) output of the layer that produced `in`.  ws: the same scratch as the forward's (the 16-bit plane kernels of layers with
- * K >= 128, N >= 64 keep their per-row scales there for launches of n >= 128 rows), or NULL for the f32-input kernels.
+ * (ReLU) output of the layer that produced `in`.  ws: the same scratch as the forward's (layout above).
  * din_amax (may be NULL): raised to the largest |din[b][k]| over the columns amax_lo <= k < amax_hi (amax_hi <= 0: all K columns;
  * amax_lo a multiple of 4) -- a slice when the consumer reads a slice of din (the layers behind a torch.cat). */
 int32_t ddrl_op_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn, const float* mask_src, int64_t ld_mask,

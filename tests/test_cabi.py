@@ -164,6 +164,50 @@ def test_conv_host_side_answers_are_pinned():
         assert answers(_lib.ConvDesc(3, 64, 22, 22, 128, 5, 5, 1, 1, 1, dense + extra, 0)) == (829376, 2049350, 3, 1, 1)
 
 
+# (K, N) -> (wt_floats, wn_floats, [(ws_floats, uses_planes) at n = 1, 127, 128, 300, 4096, 65536]).  Recorded from the library before the
+# dense routing moved into linear_route (csrc/api_ops.hip): what callers size their buffers by.
+LINEAR_HOST_ANSWERS = {
+    (7616, 256): (3899456, 3915840, [(1950082, 0), (3900286, 0), (3900288, 1), (9750488, 1), (17557888, 1), (25329792, 1)]),
+    (6400, 512): (6553664, 6553664, [(3277442, 0), (6555006, 0), (6555008, 1), (9832664, 1), (19672192, 1), (42139776, 1)]),
+    (9216, 512): (9437248, 9437248, [(4719234, 0), (9438590, 0), (9438592, 1), (14158040, 1), (18884736, 1), (42139776, 1)]),
+    (773, 512): (819264, 856128, [(396418, 0), (792958, 0), (792960, 1), (1982168, 1), (12689536, 1), (42139776, 1)]),
+    (512, 512): (524352, 524352, [(262786, 0), (525694, 0), (525696, 1), (1314008, 1), (8413312, 1), (42139776, 1)]),
+    (1536, 256): (786496, 786496, [(393602, 0), (787326, 0), (787328, 1), (1968088, 1), (12599424, 1), (25329792, 1)]),
+    (1024, 192): (458816, 393280, [(196930, 0), (393982, 0), (393984, 1), (984728, 1), (6305920, 1), (19030144, 1)]),
+    (516, 64): (104512, 74048, [(33218, 0), (66558, 0), (66560, 1), (166168, 1), (2125952, 1), (8519808, 1)]),
+    (128, 64): (24640, 16448, [(8386, 0), (16894, 0), (16896, 1), (42008, 1), (536704, 1), (4358272, 1)]),
+    (127, 64): (8192, 8192, [(8322, 0), (16766, 0), (16768, 0), (41688, 0), (532608, 0), (4325504, 0)]),
+    (128, 60): (7680, 7680, [(7870, 0), (15862, 0), (15864, 0), (39428, 0), (503680, 0), (4094080, 0)]),
+    (4, 128): (4096, 512, [(770, 0), (16638, 0), (16768, 0), (39128, 0), (532608, 0), (8519808, 0)]),
+    (37, 12): (768, 480, [(586, 0), (1906, 0), (1920, 0), (4328, 0), (57472, 0), (917632, 0)]),
+}
+LINEAR_HOST_ANSWERS_NS = (1, 127, 128, 300, 4096, 65536)
+
+
+def test_linear_host_side_answers_are_pinned():
+    """Sizes and the family flag of the dense layers of the nav / MLP / GAIL nets and of the layers at the edges of the plane kernels'
+    domain (K >= 128, N >= 64, n >= 128).  A size query that disagrees with a launcher is a device buffer overrun, so the exact values
+    are pinned; a workspace sized for n rows serves every launch of fewer rows, so ws_floats never decreases with n."""
+    from ctypes import byref, c_int64
+    lib = _lib.load()
+
+    def ws_floats(n, K, N):
+        f = c_int64()
+        _lib.check(lib.ddrl_op_linear_ws_floats(n, K, N, byref(f)))
+        return f.value
+
+    assert len(LINEAR_HOST_ANSWERS) == 13
+    for (K, N), (wt, wn, per_n) in LINEAR_HOST_ANSWERS.items():
+        a, b = c_int64(), c_int64()
+        _lib.check(lib.ddrl_op_linear_pack_floats(K, N, byref(a), byref(b)))
+        assert (a.value, b.value) == (wt, wn), (K, N)
+        for n, row in zip(LINEAR_HOST_ANSWERS_NS, per_n):
+            assert (ws_floats(n, K, N), lib.ddrl_op_linear_uses_planes(n, K, N)) == row, (K, N, n)
+        for ns in (range(1, 1025), range(1024, 65536 + 1, 1024)):
+            sizes = [ws_floats(n, K, N) for n in ns]
+            assert all(lo <= hi for lo, hi in zip(sizes, sizes[1:])), (K, N)
+
+
 def test_clean_build_stays_within_its_time_budget(tmp_path):
     """Every HIP source compiles from scratch in well under five minutes (hipcc cross-compiles gfx950 without a GPU): the driver's
     build() check and a fresh checkout depend on it.  (Round 5: a scheduling experiment -- one sched_group_barrier-pinned region over

@@ -468,6 +468,81 @@ def test_linear_launch_smaller_than_capacity_takes_more_splits():
     assert float(guard.min()) == 7.0 and float(guard.max()) == 7.0
 
 
+# (K, N, max_n), the rows n' launched on the same layer object: the smallest cases that cross the family boundary at 128 rows, and the
+# deep-K layer in which fewer rows take more splits
+REDZONES = [((516, 64, 1024), (1024, 640, 300, 128, 127, 1)), ((7616, 256, 1024), (1024, 129, 128))]
+
+
+@pytest.mark.parametrize("layer,rows", REDZONES)
+def test_linear_operators_stay_inside_the_workspace_they_asked_for(layer, rows):
+    """Every dense operator, at every launch size of a layer built for max_n rows, writes only inside the ddrl_op_linear_ws_floats(max_n)
+    floats it was given: the workspace is a view into the middle of a sentinel-filled buffer whose margins must stay untouched."""
+    from ddrl4nav_amd.ops import Linear
+    K, N, cap = layer
+    g = torch.Generator().manual_seed(K + N)
+    x, dz = torch.randn(cap, K, generator=g), torch.randn(cap, N, generator=g)
+    W, b = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
+    x64, dz64, W64 = x.double(), dz.double(), W.double()
+    lin = Linear(K, N, max_n=cap)
+    lin.pack(W.cuda())
+    floats, margin, sentinel = lin.ws.numel(), 4096, -7.25        # lin.ws: exactly ddrl_op_linear_ws_floats(max_n, K, N) floats
+    buf = torch.full((margin + floats + margin,), sentinel, device="cuda")
+    lin.ws = buf[margin:margin + floats]
+
+    def margins_untouched():
+        return bool((buf[:margin] == sentinel).all()) and bool((buf[margin + floats:] == sentinel).all())
+
+    xd, dzd, bd = x.cuda(), dz.cuda(), b.cuda()
+    for n in rows:
+        out = torch.empty(n, N, device="cuda")
+        lin.forward(xd, K, bd, False, out, N, n)
+        close(out, x64[:n] @ W64.t() + b.double())
+        assert margins_untouched(), ("forward", n)
+        want = dz64[:n] @ W64
+        for amax in (None, torch.zeros(n, device="cuda")):
+            din = torch.empty(n, K, device="cuda")
+            lin.dgrad(dzd, N, None, 0, din, K, n, din_amax=amax)
+            close(din, want)
+            assert amax is None or torch.equal(amax, din.abs().amax(dim=1))
+            assert margins_untouched(), ("dgrad", n, amax is not None)
+        dw, db = torch.empty(N, K, device="cuda"), torch.empty(N, device="cuda")
+        lin.wgrad(xd, K, dzd, N, dw, db, n)
+        close(dw, dz64[:n].t() @ x64[:n])
+        close(db, dz64[:n].sum(0))
+        assert margins_untouched(), ("wgrad", n)
+
+
+@pytest.mark.parametrize("shape", [(128, 128, 64), (300, 773, 512)])
+def test_linear_without_a_workspace_runs_on_the_gather_kernels(shape):
+    """ddrl_op_linear_forward / _dgrad with ws = NULL fall back to the f32-input kernels (the forward in a single pass) on launches the
+    plane kernels would serve, and agree with them to 2e-6 (the bound of the conv tests between two kernel families); the weight
+    gradient has no such arm: ws = NULL is an invalid argument."""
+    from ddrl4nav_amd import _lib
+    from ddrl4nav_amd.ops import Linear, _p, _st
+    n, K, N = shape
+    ld = (K + 3) // 4 * 4
+    g = torch.Generator().manual_seed(n + K + N)
+    x = torch.zeros(n, ld)
+    x[:, :K] = torch.randn(n, K, generator=g)
+    W, b, dz = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g), torch.randn(n, N, generator=g)
+    lin = Linear(K, N, max_n=n)
+    assert lin.uses_planes(n)
+    lin.pack(W.cuda())
+    xd, bd, dzd = x.cuda(), b.cuda(), dz.cuda()
+    out, out_ws = torch.empty(n, N, device="cuda"), torch.empty(n, N, device="cuda")
+    _lib.check(lin.lib.ddrl_op_linear_forward(_p(xd), ld, _p(lin.wt), _p(bd), 0, _p(out), N, n, K, N, None, None, _st()))
+    lin.forward(xd, ld, bd, False, out_ws, N, n)
+    close(out, x[:, :K].double() @ W.double().t() + b.double())
+    close(out, out_ws, tol=2e-6)
+    din, din_ws = torch.zeros(n, ld, device="cuda"), torch.zeros(n, ld, device="cuda")
+    _lib.check(lin.lib.ddrl_op_linear_dgrad(_p(dzd), N, _p(lin.wn), None, 0, _p(din), ld, n, K, N, None, None, None, 0, 0, _st()))
+    lin.dgrad(dzd, N, None, 0, din_ws, ld, n)
+    close(din[:, :K], dz.double() @ W.double())
+    close(din[:, :K], din_ws[:, :K], tol=2e-6)
+    dw, db = torch.empty(N, K, device="cuda"), torch.empty(N, device="cuda")
+    assert lin.lib.ddrl_op_linear_wgrad(_p(xd), ld, _p(dzd), N, None, _p(dw), _p(db), n, K, N, None, None, _st()) == -1  # DDRL_ERR_INVALID_ARG
+
+
 # ---- per-sample magnitudes left by the producers (include/ddrl.h "per-sample magnitudes", round 5) ------------------------------------
 @pytest.mark.parametrize("shape", [(37, 3, 48, 64, 7), (9, 64, 22, 128, 5), (11, 128, 10, 256, 3), (7, 1, 48, 64, 3), (6, 64, 24, 128, 3), (5, 128, 12, 256, 3)])
 def test_pooled_forward_and_data_gradient_leave_exact_sample_magnitudes(shape):
