@@ -86,6 +86,7 @@ struct NtParams {
   const unsigned short* bp;     // packed weight planes
   const float* whdr;            // [1] = weight scale
   int n, cols, kgs;             // rows, output columns, k-groups of the packed planes (even)
+  int red;                      // reduction length: columns [red, lda) of `a` are the caller's (padding, or a neighbour's slice of a cat buffer)
   // forward
   const float* bias;
   int act, nsplit;
@@ -135,9 +136,21 @@ __global__ __launch_bounds__(256, 2) void nt_planes_kernel(NtParams P) {
   f4 ar[4], br[4];
   const int kmax = (int)P.lda - 4;
   auto fetch = [&](int kb) {
-    const int kc = min(kb * 32 + k4 * 4, kmax);  // columns past the reduction length meet zero weights
+    const int kq = kb * 32 + k4 * 4, kc = min(kq, kmax);
 #pragma unroll
     for (int j = 0; j < 4; ++j) ar[j] = ld4(asrc[j] + kc);
+    // Columns at or past the reduction length never reach the planes: their weights are zero, but the row's scale is taken from its
+    // first `red` columns only, so a finite neighbour could scale to infinity there (inf x 0).  Block-uniform, and true for the last
+    // k-block of a reduction length that is no multiple of 32 only: every other block skips it.
+    if (kb * 32 + 32 > P.red) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ar[j].x = kq < P.red ? ar[j].x : 0.0f;
+        ar[j].y = kq + 1 < P.red ? ar[j].y : 0.0f;
+        ar[j].z = kq + 2 < P.red ? ar[j].z : 0.0f;
+        ar[j].w = kq + 3 < P.red ? ar[j].w : 0.0f;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) br[j] = *(const f4*)(bsrc + (int64_t)kb * 8192 + j * 2048);
   };
@@ -438,7 +451,7 @@ void launch_row_amax(const float* x, int64_t ld, int width, int n, float* amax, 
 void launch_linear_planes_fwd(const float* in, int64_t ld_in, const float* pf, const float* bias, float* out, int64_t ld_out, int n, int K,
                               int N, int act, int S, float* scales, float* part, const float* given, hipStream_t st) {
   if (!given) launch_row_amax(in, ld_in, K, n, scales, 0, st);
-  plin::NtParams p{in, ld_in, given ? given : scales, (const unsigned short*)pf, pf + planes_floats(N, K), n, N, kgs_of(K), bias, act, S, part, nullptr, 0,
+  plin::NtParams p{in, ld_in, given ? given : scales, (const unsigned short*)pf, pf + planes_floats(N, K), n, N, kgs_of(K), K, bias, act, S, part, nullptr, 0,
                    out, ld_out, nullptr, 0, 0};
   run_nt<0>(p, dim3((N + 127) / 128, (n + 127) / 128, S), st);
   if (S > 1) launch_linear_finish(part, S, n, N, bias, act, out, ld_out, st);
@@ -448,7 +461,7 @@ void launch_linear_planes_dgrad(const float* dout, int64_t ld_dout, const float*
                                 int64_t ld_din, int n, int K, int N, float* scales, const float* given, float* din_amax, int amax_lo,
                                 int amax_hi, hipStream_t st) {
   if (!given) launch_row_amax(dout, ld_dout, N, n, scales, 0, st);
-  plin::NtParams p{dout, ld_dout, given ? given : scales, (const unsigned short*)pd, pd + planes_floats(K, N), n, K, kgs_of(N), nullptr, 0, 1, nullptr,
+  plin::NtParams p{dout, ld_dout, given ? given : scales, (const unsigned short*)pd, pd + planes_floats(K, N), n, K, kgs_of(N), N, nullptr, 0, 1, nullptr,
                    mask_src, ld_mask, din, ld_din, din_amax, amax_lo, amax_hi};
   run_nt<1>(p, dim3((K + 127) / 128, (n + 127) / 128, 1), st);
 }

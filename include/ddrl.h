@@ -382,8 +382,11 @@ int32_t ddrl_op_maxpool2_backward_idx(const float* dpool, const uint8_t* code, i
                                       void* stream);
 
 /* nn.Linear(K, N) (+ReLU): out[b][:] = act(in[b][:K] W^T + bias).  Leading dimensions are
- * multiples of 4 floats (>= K rounded up to 4), pointers 16-byte aligned, N a multiple of 4;
- * padding columns [K, ld_in) must hold finite values (they meet zero weights).
+ * multiples of 4 floats (>= K rounded up to 4), pointers 16-byte aligned, N a multiple of 4.
+ * Columns [K, ld_in) of `in` and [N, ld_dout) of `dout` belong to the caller: padding, or the neighbouring slices of a wider
+ * torch.cat buffer.  The kernels may load them; they must hold finite values of any size, and no result depends on them (the
+ * f32-input kernels multiply them by zero weights, the plane kernels keep them out of the planes, the weight gradient drops
+ * the output columns they feed).  mask_src is read in columns [0, K) only.
  * wt / wn = derived layouts written by ddrl_op_linear_pack (sizes from ddrl_op_linear_pack_floats). */
 int32_t ddrl_op_linear_pack_floats(int32_t K, int32_t N, int64_t* wt_floats, int64_t* wn_floats);
 int32_t ddrl_op_linear_pack(const float* w, int32_t K, int32_t N, float* wt, float* wn, void* stream);
