@@ -168,6 +168,10 @@ SIGNATURES = {
     "ddrl_grad_allreduce_overlapped": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_clip_rmsprop": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_double, c_float, c_float, c_void_p,
                                        c_void_p]),
+    "ddrl_op_heads_bc_ws_floats": (c_int32, [c_int32, c_int32, POINTER(c_int64)]),
+    "ddrl_op_heads_bc_loss": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_gather_rows_u8": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

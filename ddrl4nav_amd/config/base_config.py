@@ -64,4 +64,5 @@ class BaseConfig:
     TRAIN_LOCK_KEY = "LOCK_KEY"
     ENV_NUM_DICT_KEY = "ENV_DICT"
     UPDATE_TAG_KEY = "UPDATE_TAG"
+    IMITATION_MODEL_KEY = "MODEL_IMITATION"   # :137: where the imitation pre-training publishes (nn/imitation.py)
     RENDER = 0

@@ -45,6 +45,12 @@ class ConfigNN:
     MODULE_TENSOR_DTYPE = torch.float32
     MODULE_NUMPY_DTYPE = numpy.float32
     MODULE_BITS = 32
+    # imitation pre-training (config_nn.py:75-83; the first name is the reference's spelling)
+    IMITATION_LEARINING_RATE = 0.0001       # :75
+    IMITATION_TRAINING_EPOCH = 10000        # :77
+    IMITATION_TRAINING_BATCH = 1024         # :79
+    IMITATION_SAVING_FREQUENCY = 100        # :81
+    IMITATION_TRAINING_TYPE = "classification"   # :83 ("regression" is an empty body in the reference: refused here)
     # GAIL / RND switches the agent constructor reads (config_nn.py:92-126); both are off on this path
     GAN_VALUE_TRICK = True          # :90
     GAN_DISCOUNT = 0.99             # :91

@@ -100,3 +100,16 @@ class batches:
         for lo in range(0, n, self.batch_size):
             items = [self.dataset[i] for i in order[lo:lo + self.batch_size]]
             yield [torch.from_numpy(np.stack([x for x, _ in items])), torch.from_numpy(np.stack([y for _, y in items]))]
+
+    def iter_indices(self):
+        """The same epoch as ``__iter__`` as lists of sample indices (for consumers that hold the data set on the device and
+        gather there, nn/imitation.py): the same two draws from the global generator, so under one ``torch.manual_seed`` both
+        forms see the same permutation and leave the generator in the same state."""
+        n = len(self.dataset)
+        torch.empty((), dtype=torch.int64).random_()
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        g = torch.Generator()
+        g.manual_seed(seed)
+        order = torch.randperm(n, generator=g).tolist()
+        for lo in range(0, n, self.batch_size):
+            yield order[lo:lo + self.batch_size]

@@ -100,5 +100,8 @@ class Basenn(torch.nn.Module):
     def states_normalization(self, states):
         pass
 
-    def imitation_learning(self, *args, **kwargs):
-        raise NotImplementedError("imitation pre-training is outside the hot path (SURVEY.md section 2 row 5)")
+    def imitation_learning(self, dataset, pipe, update_key, **kwargs):
+        """base.py:109-150: supervised pre-training on demonstrated (state, action) pairs before PPO begins.  Built for
+        classification on the Atari PPO net (nn/imitation.py); everything else raises NotImplementedError with the reason."""
+        from ddrl4nav_amd.nn.imitation import imitation_learning
+        return imitation_learning(self, dataset, pipe, update_key, **kwargs)

@@ -41,6 +41,38 @@ def frame_stack_push(prev, newest, reset, out):
     return out
 
 
+def heads_bc_ws_floats(n_actions, max_n):
+    """Floats of scratch ddrl_op_heads_bc_loss needs for launches of up to max_n samples."""
+    f = c_int64()
+    check(_lib.load().ddrl_op_heads_bc_ws_floats(int(n_actions), int(max_n), byref(f)))
+    return f.value
+
+
+def heads_bc_loss(w, b, n_actions, h, ld_h, n, labels, n_total, dh, ld_dh, dw, db, stats, ws):
+    """Cross-entropy of the Categorical actor's logits against demonstrated actions and its backward through the head layer (include/ddrl.h,
+    ddrl_op_heads_bc_loss; csrc/imit.hip): reads h [n][ld_h], w [A][512], b [A], labels [n] (floats); writes dh [n][ld_dh], dw, db and
+    stats = (loss share, correct count).  The mean runs over n_total samples.  Asynchronous on the current stream."""
+    check(_lib.load().ddrl_op_heads_bc_loss(_p(w), _p(b), int(n_actions), _p(h), int(ld_h), int(n), _p(labels), int(n_total), _p(dh),
+                                            int(ld_dh), _p(dw), _p(db), _p(stats), _p(ws), _st()))
+
+
+def gather_rows_u8(src, idx, dst, labels_src=None, labels_dst=None, n=None):
+    """dst[i] = src[idx[i]] for the first n entries of idx (int32, on the device), rows being everything behind the leading axis of the
+    contiguous uint8 tensors `src` / `dst`; labels_dst[i] = labels_src[idx[i]] (fp32) in the same launch (include/ddrl.h,
+    ddrl_op_gather_rows_u8).  Asynchronous on the current stream; returns dst."""
+    n = int(idx.numel() if n is None else n)
+    assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous() and src.is_cuda \
+        and dst.is_cuda, "expected contiguous uint8 device tensors"
+    assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() >= n, "idx: contiguous int32 on the device"
+    row_bytes = src[0].numel()
+    assert dst[0].numel() == row_bytes and dst.shape[0] >= n, "dst rows must match src rows"
+    for t in (labels_src, labels_dst):
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()), "labels: contiguous fp32 on the device"
+    assert labels_src is None or (labels_src.numel() >= src.shape[0] and labels_dst.numel() >= n)
+    check(_lib.load().ddrl_op_gather_rows_u8(_p(src), src.shape[0], row_bytes, _p(idx), n, _p(dst), _p(labels_src), _p(labels_dst), _st()))
+    return dst
+
+
 class Conv:
     """One Conv2d / Conv1d layer (torch weight layout [cout][cin][kh][kw]; Conv1d: h = kh = 1)."""
 

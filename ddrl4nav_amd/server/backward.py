@@ -4,6 +4,8 @@ Mirror of ``BackwardTrainThread.run`` (USTC_lab/server/backward.py:168-217) with
 (out of scope): the caller hands over batches (``consume``); everything the reference does per
 batch and per yielded iteration is kept, with the same config constants:
 
+  * ``MIMIC_START`` / ``MIMIC_START_LOAD_PATH``: the demonstration directory is read when the trainer is built and
+    ``net.imitation_learning`` runs before anything else (backward.py:117-129,170-174; nn/imitation.py);
   * ``LOAD_CHECKPOINT`` / ``LOAD_CHECKPOINT_PATH`` / ``LOAD_EPISODE``: state_dict loaded before the first batch, and every
     ``update_time`` offset by ``LOAD_EPISODE`` (backward.py:131-135,175-176,190);
   * the weights are published once at start and then whenever ``last and update_time % MODEL_TO_REDIS_FREQUENCY == 0``
@@ -97,6 +99,19 @@ class BackwardTrainer:
             self.load_checkpoint_path = config.LOAD_CHECKPOINT_PATH
             self.load_checkpoint_start += config.LOAD_EPISODE
         self.test = getattr(config, "TEST", False)
+        # imitation pre-training before PPO begins (backward.py:117-129)
+        self.mimic_start = bool(getattr(config, "MIMIC_START", False))
+        if self.mimic_start:
+            from ddrl4nav_amd.data.mimic_exp import MimicExpFactory
+            self.dataset = MimicExpFactory().mimic_reader(config.TASK_TYPE, config.MIMIC_START_LOAD_PATH)
+            self.imitation_learning_dict = {
+                "imitation_learning_rate": config_nn.IMITATION_LEARINING_RATE,
+                "imitation_training_batch": config_nn.IMITATION_TRAINING_BATCH,
+                "imitation_training_epoch": config_nn.IMITATION_TRAINING_EPOCH,
+                "imitation_saving_frequency": config_nn.IMITATION_SAVING_FREQUENCY,
+                "imitation_model_key": config.TASK_NAME + config.IMITATION_MODEL_KEY,
+                "imitation_training_type": config_nn.IMITATION_TRAINING_TYPE,
+            }
         self.device = net.device
         self.tensortype = config_nn.MODULE_TENSOR_DTYPE
         self.min_batch_size = config_nn.TRAINING_MIN_BATCH
@@ -111,6 +126,8 @@ class BackwardTrainer:
         self.published += 1
 
     def start(self):
+        if self.mimic_start:     # backward.py:170-174: before the checkpoint load and the first publish
+            self.net.imitation_learning(self.dataset, self.pipe, self.update_tag, **self.imitation_learning_dict)
         if self.load_checkpoint_path:
             self.net.load_state_dict(torch.load(self.load_checkpoint_path, map_location=self.device))
         self._publish()

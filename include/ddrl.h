@@ -499,6 +499,34 @@ int32_t ddrl_op_colsum(const float* x, int64_t ld, int32_t n, int32_t width, flo
 int32_t ddrl_op_clip_rmsprop(float* params, float* grads, float* square_avg, int64_t n_params, float lr, double alpha, float eps,
                              float max_norm, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Imitation pre-training (USTC_lab/nn/base.py:109-150, called from server/backward.py:117-129,168-174).  Added after
+ * round 6 (additive: ABI 3).
+ * ------------------------------------------------------------------------------------------ */
+/* The supervised head of Basenn._imitation_learning_classifier (USTC_lab/nn/base.py:131,143,147: CrossEntropyLoss on the
+ * logits + loss.backward() through the actor's last layer), on 512-wide encoder features:
+ *   logits = h W^T + b;  loss = sum_i -log_softmax(logits_i)[label_i] / n_total;  dlogit = (softmax - onehot) / n_total
+ *   dh [n][ld_dh] = sum_j dlogit_j w_j;  dw [A][512] and db [A] (overwritten);
+ *   stats[0] = this call's share of the loss, stats[1] = number of samples whose argmax (first maximum) equals the label.
+ * h [n][ld_h] and dh are 16-byte aligned with leading dimensions that are multiples of 4 floats (>= 512); w [A][512], b [A],
+ * dw, db and stats may sit anywhere in an fp32 arena.  A = n_actions in 2..18 (DDRL_ERR_UNSUPPORTED otherwise).  labels are
+ * floats as the reference's reader yields them (data/mimic_exp.py:206-212); a label outside [0, A) contributes no loss and
+ * no gradient and is never counted as correct.  log_softmax is z - max - log(sum exp(z - max)).  Deterministic: per-workgroup
+ * partial sums in `ws` (ddrl_op_heads_bc_ws_floats(A, max n) floats), reduced in a fixed order by a second launch. */
+int32_t ddrl_op_heads_bc_ws_floats(int32_t n_actions, int32_t max_n, int64_t* floats);
+int32_t ddrl_op_heads_bc_loss(const float* w, const float* b, int32_t n_actions, const float* h, int64_t ld_h, int32_t n,
+                              const float* labels, int64_t n_total, float* dh, int64_t ld_dh, float* dw, float* db, float* stats,
+                              float* ws, void* stream);
+/* The collation of one shuffled minibatch (the DataLoader of USTC_lab/nn/base.py:128,140-141) on the device:
+ *   dst[i][0:row_bytes) = src[idx[i]][0:row_bytes) for i < n, and labels_dst[i] = labels_src[idx[i]] in the same launch
+ *   (labels_src / labels_dst: both given or both NULL).
+ * src [n_rows][row_bytes] holds the whole demonstration set (uint8 [N, C, 84, 84]: row_bytes = C * 7056); row_bytes is a
+ * multiple of 16, src and dst are 16-byte aligned and do not overlap (DDRL_ERR_INVALID_ARG otherwise); idx is int32 on the
+ * device.  An index outside [0, n_rows) yields a zero row and label -1; nothing is read out of bounds.  Needs no context,
+ * allocates nothing, asynchronous on `stream`; the argument checks run before anything touches HIP. */
+int32_t ddrl_op_gather_rows_u8(const uint8_t* src, int64_t n_rows, int64_t row_bytes, const int32_t* idx, int32_t n, uint8_t* dst,
+                               const float* labels_src, float* labels_dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
