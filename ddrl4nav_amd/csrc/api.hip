@@ -58,11 +58,6 @@ struct ddrl_ctx : public ddrl::Profiler {
     if (_e != hipSuccess) return DDRL_ERR_HIP; \
   } while (0)
 
-static int32_t check_launch() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DDRL_OK : DDRL_ERR_HIP;
-}
-
 
 extern "C" {
 
@@ -210,6 +205,20 @@ static void ensure_packed(ddrl_ctx* ctx, hipStream_t st) {
   ctx->dirty = false;
 }
 
+// The head launch of a context: features and their gradients are [e][max_batch][512] in its workspace, dh leaves heads_loss normalised
+// per sample (268 MB less to re-read and re-write per iteration), and an acting forward of a small batch leaves the dense layer's output
+// as split-K partial sums for heads_act to finish (fc_forward_splits).
+static HeadsCall ctx_heads_call(const ddrl_ctx* ctx, int n, bool acting) {
+  const Workspace& w = ctx->ws;
+  const int64_t es = (int64_t)ctx->cfg.max_batch * FEAT;
+  HeadsCall c{&ctx->L, &ctx->cfg, ctx->params, n, w.h, es, w.dh, es};
+  const int nsplit = acting ? fc_forward_splits(n) : 1;
+  if (nsplit > 1) c.fc_part = w.wpart, c.fc_nsplit = nsplit;
+  c.dlogits = w.dlogits, c.dvalue = w.dvalue, c.hpart = w.hpart;
+  c.gsc = w.gsc, c.gsc_es = ctx->cfg.max_batch, c.amax = w.amax;
+  return c;
+}
+
 int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const float* act_in, uint64_t seed,
                      uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out, void* stream) {
   if (!ctx || !frames || !value) return DDRL_ERR_INVALID_ARG;
@@ -224,27 +233,26 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
   ec.keep_acts = ctx->keep_acts;
   ctx->acts_stored = ctx->keep_acts || n > ACT_FUSED_MAX;
   launch_encoder_forward(ec, true, st);
-  HeadsCall hc{&ctx->ws, &ctx->L, &ctx->cfg, ctx->params, n, ctx->cfg.max_batch};
   {
     ProfRange ps(prof, "heads_act", st);
-    launch_heads_act(hc, act_in, seed, stream_id, probs, value, action_out, logp_out, st);
+    launch_heads_act(ctx_heads_call(ctx, n, true), act_in, seed, stream_id, probs, value, action_out, logp_out, st);
   }
   ctx->last_n = n;
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_categorical_stats(const float* probs, int32_t n, int32_t A, float* p_hat, float* logits, float* entropy,
                                void* stream) {
   if (!probs || n < 1 || A < 1) return DDRL_ERR_INVALID_ARG;
   launch_categorical_stats(probs, n, A, p_hat, logits, entropy, (hipStream_t)stream);
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_categorical_sample(const float* probs, int32_t n, int32_t A, uint64_t seed, uint64_t stream_id,
                                 float* action_out, float* logp_out, void* stream) {
   if (!probs || !action_out || n < 1 || A < 1) return DDRL_ERR_INVALID_ARG;
   launch_categorical_sample(probs, n, A, seed, stream_id, action_out, logp_out, (hipStream_t)stream);
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_last_features(ddrl_ctx* ctx, int32_t n, float* h_actor, float* h_critic, void* stream) {
@@ -263,7 +271,7 @@ int32_t ddrl_gae(const float* values, const float* rewards, const uint8_t* dones
   if (!values || !rewards || !dones || !adv || !ret || T < 0 || N < 1) return DDRL_ERR_INVALID_ARG;
   if (T == 0) return DDRL_OK;  // len(experiences) <= 1 -> nothing to do (agent.py:125-126)
   launch_gae(values, rewards, dones, T, N, gamma, landa, adv, ret, (hipStream_t)stream);
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_episode_returns(const float* rewards, const uint8_t* dones, int32_t T, int32_t N, float* rewards_sum,
@@ -271,7 +279,7 @@ int32_t ddrl_episode_returns(const float* rewards, const uint8_t* dones, int32_t
   if (!rewards || !dones || !rewards_sum || !rewards_episode || T < 0 || N < 1) return DDRL_ERR_INVALID_ARG;
   if (T == 0) return DDRL_OK;
   launch_episode_returns(rewards, dones, T, N, rewards_sum, rewards_episode, trace, episodes_finished, (hipStream_t)stream);
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions, const float* old_logps,
@@ -285,18 +293,16 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
   if (ctx->buckets) ec.bucket_ev = ctx->bucket_ev;
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);
-  HeadsCall hc{&ctx->ws, &ctx->L, &ctx->cfg, ctx->params, B, ctx->cfg.max_batch};
-  hc.normalise_dh = true;  // dh leaves heads_loss already normalised per sample (268 MB less to re-read and re-write per iteration)
   launch_backward_amax_reset(ec, st);
   {
     ProfRange ps(ctx->profile ? ctx : nullptr, "heads_loss", st);
-    launch_heads_loss(hc, actions, old_logps, advs, rets, (float)(1.0 / (double)B_global), ctx->grads, st);
+    launch_heads_loss(ctx_heads_call(ctx, B, false), actions, old_logps, advs, rets, (float)(1.0 / (double)B_global), ctx->grads, st);
   }
   bucket_done(ec, BUCKET_HEADS, st);  // head-layer gradients and the three loss shares of the tail are final
   launch_encoder_backward(ec, ctx->grads, st, true);
   ctx->last_n = B;
   ctx->bucket_events_fresh = ctx->buckets;
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_grad_allreduce(ddrl_ctx* ctx, ddrl_comm* comm, void* stream) {
@@ -422,7 +428,7 @@ int32_t ddrl_encoder_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, vo
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);  // complete features (no split-K partials left for a head kernel to sum)
   ctx->last_n = n;
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_encoder_backward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, void* stream) {
@@ -430,7 +436,7 @@ int32_t ddrl_encoder_backward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, v
   hipStream_t st = (hipStream_t)stream;
   EncCall ec{ctx->profile ? ctx : nullptr, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n, ctx->cfg.max_batch};
   launch_encoder_backward(ec, ctx->grads, st);
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_encoder_buffers(ddrl_ctx* ctx, float** h, float** dh) {
@@ -446,16 +452,16 @@ int32_t ddrl_clip_adam_step(ddrl_ctx* ctx, void* stream) {
   ctx->step += 1;
   {
     ProfRange ps(ctx->profile ? ctx : nullptr, "clip_adam", st);
-    launch_clip_adam(ctx->cfg, ctx->L, ctx->ws, ctx->params, ctx->grads, ctx->m, ctx->v, ctx->step, st);
+    launch_clip_adam(ctx->cfg, ctx->L, ctx->ws.npart, ctx->params, ctx->grads, ctx->m, ctx->v, ctx->step, st);
   }
   ctx->dirty = true;
-  return check_launch();
+  return launch_status();
 }
 
 int32_t ddrl_u8_table(float* out256, void* stream) {
   if (!out256) return DDRL_ERR_INVALID_ARG;
   launch_fill_lut(out256, (hipStream_t)stream);
-  return check_launch();
+  return launch_status();
 }
 
 // Diagnostic views into the workspace (tests): which = 0 a1,1 a2,2 a3,3 h,4 dz1,5 dz2,6 dz3,7 dh,

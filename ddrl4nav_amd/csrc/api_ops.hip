@@ -7,10 +7,6 @@
 
 using namespace ddrl;
 
-static int32_t op_check() { return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP; }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static bool fill_geom(const ddrl_conv_desc* d, ConvGeom& g) {
   if (!d) return false;
   g.n = d->n; g.cin = d->cin; g.h = d->h; g.w = d->w; g.cout = d->cout; g.kh = d->kh; g.kw = d->kw;
@@ -157,7 +153,7 @@ int32_t ddrl_op_conv_pack(const ddrl_conv_desc* d, const float* w, float* packed
     case kConvPlanes: launch_conv_planes_pack(g, w, packed + v.off[5], packed + v.off[6], (hipStream_t)stream); break;
     case kConvGather: break;
   }
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_scratch_floats(const ddrl_conv_desc* d, int64_t* floats) {
@@ -198,7 +194,7 @@ int32_t ddrl_op_conv_forward(const ddrl_conv_desc* d, const float* in, const flo
       break;
   }
   if (amax_pass) launch_sample_amax(out, g.out_sn, g.cout * g.oh * g.ow, g.n, out_amax, (hipStream_t)stream, 1);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_has_forward_pool(const ddrl_conv_desc* d) {
@@ -210,7 +206,7 @@ int32_t ddrl_op_conv_has_forward_pool(const ddrl_conv_desc* d) {
 int32_t ddrl_op_sample_amax(const float* x, int64_t sn, int32_t elems, int32_t n, float* amax, void* stream) {
   if (!x || !amax || n < 1 || elems < 4 || (elems & 3) || (sn & 3) || sn < elems || !aligned16(x)) return DDRL_ERR_INVALID_ARG;
   launch_sample_amax(x, sn, elems, n, amax, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_pooled_uses_scales(const ddrl_conv_desc* d) {
@@ -233,7 +229,7 @@ int32_t ddrl_op_conv_forward_pool(const ddrl_conv_desc* d, const float* in, cons
     launch_conv_first_fwd_pool(g, in, packed + v.off[5], bias, pooled, code, out_amax, (hipStream_t)stream);
   else
     launch_conv_planes_fwd_pool(g, in, packed + v.off[5], scales_scratch, in_amax, bias, pooled, code, out_amax, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_dgrad_pooled(const ddrl_conv_desc* d, const float* dpool, const uint8_t* code, const float* packed, float* din,
@@ -245,7 +241,7 @@ int32_t ddrl_op_conv_dgrad_pooled(const ddrl_conv_desc* d, const float* dpool, c
   if (!(r.family == kConvPlanes && r.pool)) return DDRL_ERR_UNSUPPORTED;  // a first layer has no data gradient
   const PackView v = pack_view(g, r);
   launch_conv_planes_dgrad_pooled(g, dpool, code, packed + v.off[6], scales_scratch, dpool_amax, din, din_amax, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_wgrad_pooled(const ddrl_conv_desc* d, const float* in, const float* dpool, const uint8_t* code, const float* packed,
@@ -259,7 +255,7 @@ int32_t ddrl_op_conv_wgrad_pooled(const ddrl_conv_desc* d, const float* in, cons
     launch_conv_first_wgrad_pooled(g, in, dpool, code, ws, dw, db, (hipStream_t)stream);
   else
     launch_conv_planes_wgrad_pooled(g, in, dpool, code, in_amax, dpool_amax, ws, dw, db, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_dgrad(const ddrl_conv_desc* d, const float* dz, const float* packed, float* din, float* scales_scratch, void* stream) {
@@ -275,7 +271,7 @@ int32_t ddrl_op_conv_dgrad(const ddrl_conv_desc* d, const float* dz, const float
     case kConvPlanes: launch_conv_planes_dgrad(g, dz, packed + v.off[6], scales_scratch, din, (hipStream_t)stream); break;
     default: launch_conv_dgrad(g, dz, packed + v.off[2], (const int2*)(packed + v.off[3]), din, (hipStream_t)stream); break;
   }
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_conv_wgrad(const ddrl_conv_desc* d, const float* in, const float* dz, const float* packed, float* ws,
@@ -291,13 +287,13 @@ int32_t ddrl_op_conv_wgrad(const ddrl_conv_desc* d, const float* in, const float
     case kConvPlanes: launch_conv_planes_wgrad(g, in, dz, ws, dw, db, (hipStream_t)stream); break;
     case kConvGather: launch_conv_wgrad(g, in, dz, (const int*)(packed + v.off[4]), ws, dw, db, (hipStream_t)stream); break;
   }
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_maxpool2_forward(const float* in, int64_t planes, int32_t h, int32_t w, float* out, void* stream) {
   if (!in || !out || planes < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || ((uintptr_t)in & 7)) return DDRL_ERR_INVALID_ARG;
   launch_maxpool2_fwd(in, planes, h, w, out, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_maxpool2_relu_backward(const float* a, const float* dpool, int64_t planes, int32_t h, int32_t w, float* dz,
@@ -305,20 +301,20 @@ int32_t ddrl_op_maxpool2_relu_backward(const float* a, const float* dpool, int64
   if (!a || !dpool || !dz || planes < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || (((uintptr_t)a | (uintptr_t)dz) & 7))
     return DDRL_ERR_INVALID_ARG;
   launch_maxpool2_relu_bwd(a, dpool, planes, h, w, dz, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_maxpool2_forward_idx(const float* in, int64_t planes, int32_t h, int32_t w, float* out, uint8_t* code, void* stream) {
   if (!in || !out || !code || planes < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || ((uintptr_t)in & 7)) return DDRL_ERR_INVALID_ARG;
   launch_maxpool2_fwd_idx(in, planes, h, w, out, code, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_maxpool2_backward_idx(const float* dpool, const uint8_t* code, int64_t planes, int32_t h, int32_t w, float* dz,
                                       void* stream) {
   if (!dpool || !code || !dz || planes < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || ((uintptr_t)dz & 15)) return DDRL_ERR_INVALID_ARG;
   launch_maxpool2_bwd_idx(dpool, code, planes, h, w, dz, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 // ---- dense layer --------------------------------------------------------------------------------
@@ -337,7 +333,7 @@ int32_t ddrl_op_linear_pack(const float* w, int32_t K, int32_t N, float* wt, flo
   const LinearRoute r = linear_route(1, K, N);
   if (r.has_planes) launch_linear_planes_pack(w, K, N, wt + r.wt_f32, wn + r.wn_f32, (hipStream_t)stream);
   launch_linear_pack(w, K, N, wt, wn, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_linear_uses_planes(int32_t n, int32_t K, int32_t N) { return lin_ok(n, K, N) && linear_route(n, K, N).planes ? 1 : 0; }
@@ -345,7 +341,7 @@ int32_t ddrl_op_linear_uses_planes(int32_t n, int32_t K, int32_t N) { return lin
 int32_t ddrl_op_row_amax(const float* x, int64_t ld, int32_t width, int32_t n, float* amax, int32_t accumulate, void* stream) {
   if (!x || !amax || n < 1 || width < 1 || (ld & 3) || ld < (width + 3) / 4 * 4 || !aligned16(x)) return DDRL_ERR_INVALID_ARG;
   launch_row_amax(x, ld, width, n, amax, accumulate ? 1 : 0, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_linear_forward(const float* in, int64_t ld_in, const float* wt, const float* bias, int32_t act, float* out,
@@ -359,7 +355,7 @@ int32_t ddrl_op_linear_forward(const float* in, int64_t ld_in, const float* wt, 
                              (hipStream_t)stream);
   else
     launch_linear_fwd(in, ld_in, wt, bias, out, ld_out, n, K, N, act, ws ? r.fwd_splits : 1, v.part, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn, const float* mask_src, int64_t ld_mask,
@@ -380,7 +376,7 @@ int32_t ddrl_op_linear_dgrad(const float* dout, int64_t ld_dout, const float* wn
     // no epilogue for it: a pass over the rows just written (the column range allows 16-byte loads: above)
     if (din_amax) launch_row_amax(din + amax_lo, ld_din, amax_hi - amax_lo, n, din_amax, 1, (hipStream_t)stream);
   }
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_linear_ws_floats(int32_t n, int32_t K, int32_t N, int64_t* floats) {
@@ -401,7 +397,7 @@ int32_t ddrl_op_linear_wgrad(const float* in, int64_t ld_in, const float* dout, 
                                (hipStream_t)stream);
   else
     launch_linear_wgrad(in, ld_in, dout, ld_dout, v.slabs, r.wgrad_splits, n, K, N, dw, db, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 // ---- heads + optimiser on caller-owned arenas --------------------------------------------------
@@ -410,18 +406,8 @@ static bool heads_ok(const ddrl_heads_desc* d) {
   if (d->continuous) return d->n_actions >= 1 && d->n_actions <= 8;
   return d->n_actions >= 2 && d->n_actions <= 18;
 }
-static ParamLayout cat_layout(const ddrl_heads_desc* d) {
-  ParamLayout L = make_layout(d->n_actions, 4, d->shared != 0);  // encoder offsets are unused by the head kernels
-  L.actor_w = d->actor_w; L.actor_b = d->actor_b; L.critic_w = d->critic_w; L.critic_b = d->critic_b;
-  L.n_params = d->n_params;
-  return L;
-}
-static GaussLayout gauss_layout(const ddrl_heads_desc* d) {
-  GaussLayout L;
-  L.D = d->n_actions; L.shared = d->shared != 0;
-  L.actor_w = d->actor_w; L.actor_b = d->actor_b; L.log_std = d->log_std; L.critic_w = d->critic_w;
-  L.critic_b = d->critic_b; L.n_params = d->n_params;
-  return L;
+static HeadLayout head_layout(const ddrl_heads_desc* d) {
+  return HeadLayout{d->n_actions, d->shared != 0, d->actor_w, d->actor_b, d->log_std, d->critic_w, d->critic_b, d->n_params};
 }
 struct HeadsWs {
   float *dlogits, *dvalue, *hpart;
@@ -451,22 +437,17 @@ int32_t ddrl_op_heads_act(const ddrl_heads_desc* d, const float* params, const f
   if (!heads_ok(d) || !params || !h_actor || !h_critic || !value || n < 1) return DDRL_ERR_INVALID_ARG;
   if (!aligned16(h_actor) || !aligned16(h_critic)) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
+  const HeadLayout L = head_layout(d);
   if (d->continuous) {
     // shared prenet: both heads read h_actor (include/ddrl.h), as in ddrl_op_heads_loss and the categorical path below
-    launch_gauss_act(gauss_layout(d), params, h_actor, d->shared ? h_actor : h_critic, n, act_in, seed, stream_id, dist_out, value,
+    launch_gauss_act(L, params, h_actor, d->shared ? h_actor : h_critic, n, act_in, seed, stream_id, dist_out, value,
                      action_out, logp_out, st);
-    return op_check();
+    return launch_status();
   }
-  ParamLayout L = cat_layout(d);
-  Workspace w{};
-  w.h = const_cast<float*>(h_actor);
-  ddrl_config cfg;
-  ddrl_config_default(&cfg);
-  HeadsCall hc{&w, &L, &cfg, params, n, n};
-  hc.h_es = d->shared ? 0 : (int64_t)(h_critic - h_actor);
-  hc.plain_features = true;
+  const ParamLayout PL = head_param_layout(L);
+  const HeadsCall hc{&PL, nullptr, params, n, h_actor, d->shared ? 0 : (int64_t)(h_critic - h_actor), nullptr, 0};
   launch_heads_act(hc, act_in, seed, stream_id, dist_out, value, action_out, logp_out, st);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
@@ -481,24 +462,18 @@ int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, con
   hipStream_t st = (hipStream_t)stream;
   HeadsWs hw = heads_ws(d, n, ws);
   const float inv_b = (float)(1.0 / (double)B_global);
+  const HeadLayout L = head_layout(d);
   if (d->continuous) {
-    launch_gauss_loss(gauss_layout(d), *cfg, params, h_actor, d->shared ? h_actor : h_critic, n, actions, old_logps, advs,
+    launch_gauss_loss(L, *cfg, params, h_actor, d->shared ? h_actor : h_critic, n, actions, old_logps, advs,
                       rets, inv_b, dh_actor, dh_critic, hw.dlogits, hw.dvalue, hw.hpart, grads, st);
-    return op_check();
+    return launch_status();
   }
-  ParamLayout L = cat_layout(d);
-  Workspace w{};
-  w.h = const_cast<float*>(h_actor);
-  w.dh = dh_actor;
-  w.dlogits = hw.dlogits;
-  w.dvalue = hw.dvalue;
-  w.hpart = hw.hpart;
-  HeadsCall hc{&w, &L, cfg, params, n, n};
-  hc.h_es = d->shared ? 0 : (int64_t)(h_critic - h_actor);
-  hc.dh_es = d->shared ? 0 : (int64_t)(dh_critic - dh_actor);
-  hc.plain_features = true;
+  const ParamLayout PL = head_param_layout(L);
+  HeadsCall hc{&PL, cfg, params, n, h_actor, d->shared ? 0 : (int64_t)(h_critic - h_actor), dh_actor,
+               d->shared ? 0 : (int64_t)(dh_critic - dh_actor)};
+  hc.dlogits = hw.dlogits, hc.dvalue = hw.dvalue, hc.hpart = hw.hpart;
   launch_heads_loss(hc, actions, old_logps, advs, rets, inv_b, grads, st);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_clip_adam(const ddrl_config* cfg, float* params, float* grads, float* m, float* v, int64_t n_params,
@@ -508,10 +483,8 @@ int32_t ddrl_op_clip_adam(const ddrl_config* cfg, float* params, float* grads, f
   ParamLayout L = make_layout(2, 4, shared != 0);
   L.n_params = n_params;
   L.n_actor = shared ? n_params : n_actor;
-  Workspace w{};
-  w.npart = (double*)ws;
-  launch_clip_adam(*cfg, L, w, params, grads, m, v, step, (hipStream_t)stream);
-  return op_check();
+  launch_clip_adam(*cfg, L, (double*)ws, params, grads, m, v, step, (hipStream_t)stream);
+  return launch_status();
 }
 
 int32_t ddrl_op_clip_adam_ws_bytes(int64_t* bytes) {
@@ -523,13 +496,13 @@ int32_t ddrl_op_clip_adam_ws_bytes(int64_t* bytes) {
 int32_t ddrl_op_relu_mask(float* d, int64_t ld_d, const float* act, int64_t ld_act, int32_t n, int32_t width, void* stream) {
   if (!d || !act || n < 1 || width < 1 || ld_d < width || ld_act < width) return DDRL_ERR_INVALID_ARG;
   launch_relu_mask(d, ld_d, act, ld_act, n, width, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_accumulate(float* dst, const float* src, int64_t count, void* stream) {
   if (!dst || !src || count < 1) return DDRL_ERR_INVALID_ARG;
   launch_accumulate(dst, src, count, (hipStream_t)stream);
-  return op_check();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -65,6 +65,22 @@ inline ParamLayout make_layout(int A, int C, bool shared = false) {
   return L;
 }
 
+// The actor + critic head layers inside ANY flat arena, as ddrl_heads_desc gives them (api_ops.hip head_layout): the Categorical
+// (n <= 18 actions) and the Gaussian (n <= 8 action dims, + log_std) heads alike.
+struct HeadLayout {
+  int n;
+  int shared;  // 1: total_loss is differentiated (shared prenet), both heads read the actor's features and feed its dh
+  int64_t actor_w, actor_b, log_std, critic_w, critic_b, n_params;
+};
+// the Categorical kernels take the Atari arena's ParamLayout; its encoder offsets are only read by an acting launch that finishes the
+// dense layer's split-K partial sums, which a caller with features of its own never asks for
+inline ParamLayout head_param_layout(const HeadLayout& h) {
+  ParamLayout L = make_layout(h.n, 4, h.shared != 0);
+  L.actor_w = h.actor_w; L.actor_b = h.actor_b; L.critic_w = h.critic_w; L.critic_b = h.critic_b;
+  L.n_params = h.n_params;
+  return L;
+}
+
 // ---- device workspace carved out of the caller's buffer ------------------------------------
 struct Workspace {
   // derived weight layouts, [e] major
@@ -145,6 +161,13 @@ constexpr int HEAD_WG = 256;   // workgroups of the heads/loss kernel (fixed -> 
 constexpr int NORM_WG = 1024;  // workgroups of the grad-norm kernel
 
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+// argument checks and the status of the entry points (host side)
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool overlap(const void* a, const void* b, uint64_t a_bytes, uint64_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+inline int32_t launch_status() { return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP; }
 // words of the a1 sign mask per encoder (one per column), and the bit of output channel oc inside a column's word: lane half
 // hi = (oc >> 2) & 1 of the 32x32 MFMA tile holds oc as accumulator register r = (oc & 3) + 4 (oc >> 3) and shifts its 16 signs in
 // first register first, i.e. register r ends at bit 15 - r of half-word hi

@@ -36,12 +36,6 @@ __global__ __launch_bounds__(64) void frame_stack_push_kernel(const uint4* __res
   }
 }
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
-bool overlap(const void* a, const void* b, uint64_t a_bytes, uint64_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + b_bytes && y < x + a_bytes;
-}
-
 }  // namespace
 
 extern "C" int32_t ddrl_frame_stack_push(const uint8_t* prev, const uint8_t* newest, const uint8_t* reset, int32_t n,
@@ -49,11 +43,11 @@ extern "C" int32_t ddrl_frame_stack_push(const uint8_t* prev, const uint8_t* new
   // every check comes before the first HIP call: a host without a GPU gets the same answers
   if (channels < 1 || channels > 4) return DDRL_ERR_UNSUPPORTED;  // the range cfg_check accepts for in_channels
   if (n < 1 || n > INT32_MAX / WAVES_PER_ENV) return DDRL_ERR_INVALID_ARG;
-  if (!newest || !next || misaligned(newest) || misaligned(next)) return DDRL_ERR_INVALID_ARG;
+  if (!newest || !next || !ddrl::aligned16(newest) || !ddrl::aligned16(next)) return DDRL_ERR_INVALID_ARG;
   const uint64_t stack_bytes = (uint64_t)n * channels * PLANE_BYTES;
-  if (overlap(newest, next, (uint64_t)n * PLANE_BYTES, stack_bytes)) return DDRL_ERR_INVALID_ARG;
+  if (ddrl::overlap(newest, next, (uint64_t)n * PLANE_BYTES, stack_bytes)) return DDRL_ERR_INVALID_ARG;
   if (channels > 1) {  // C = 1: next = newest, prev is not read
-    if (!prev || misaligned(prev) || overlap(prev, next, stack_bytes, stack_bytes)) return DDRL_ERR_INVALID_ARG;
+    if (!prev || !ddrl::aligned16(prev) || ddrl::overlap(prev, next, stack_bytes, stack_bytes)) return DDRL_ERR_INVALID_ARG;
   }
   const dim3 grid((unsigned)n * WAVES_PER_ENV), block(64);
   const hipStream_t st = (hipStream_t)stream;
@@ -65,5 +59,5 @@ extern "C" int32_t ddrl_frame_stack_push(const uint8_t* prev, const uint8_t* new
     case 3: hipLaunchKernelGGL(frame_stack_push_kernel<3>, grid, block, 0, st, p, f, reset, o); break;
     default: hipLaunchKernelGGL(frame_stack_push_kernel<4>, grid, block, 0, st, p, f, reset, o); break;
   }
-  return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP;
+  return ddrl::launch_status();
 }

@@ -7,9 +7,9 @@
 //   gailv_loss = vlossf(data.values[-1], values[-1].squeeze()); v_loss += it        USTC_lab/nn/ppo.py:101-107
 //   Discriminator.learn: mean D(generator batch) - mean D(expert batch)              USTC_lab/nn/GAIL.py:76-80
 //   clip_grad_norm_(D.parameters(), WGAN_CLIP_GRAD_NUM); RMSprop(alpha=0.9).step()   USTC_lab/nn/GAIL.py:28,83-84
+#include "heads_common.h"
 #include "kernels.h"
 #include "ops.h"
-#include "ppo_math.h"
 
 namespace ddrl {
 
@@ -91,27 +91,18 @@ __global__ __launch_bounds__(VH_WAVES * 64) void value_head_loss_kernel(const fl
   }
 }
 
-// partials -> dw[512], db, and vloss_accum[0] += sum * inv_b * (1/2 for the squared error, ppo.py:57)
-__global__ __launch_bounds__(256) void value_head_reduce_kernel(const float* __restrict__ part, int nwg, ddrl_config cfg,
-                                                                float inv_b, float* __restrict__ dw, float* __restrict__ db,
-                                                                float* __restrict__ vloss_accum) {
-  __shared__ double sh[8][RED_OUT];
-  if (blockIdx.x == gridDim.x - 1) {  // the loss sum, by one wave
-    if (threadIdx.x >= 64) return;
-    const double s = wave_sum_partials(part, VH_STRIDE, nwg, FEAT + 1);
-    if (threadIdx.x == 0 && vloss_accum) vloss_accum[0] += (float)(s * (double)inv_b * (cfg.smooth_l1_loss ? 1.0 : 0.5));
-    return;
+// partials -> dw[512], db (either may be null), and vloss_accum[0] += the head's share of v_loss (ppo.py:57)
+struct ValueHeadReduce {
+  float inv_b;
+  int smooth_l1;
+  float *dw, *db, *vloss_accum;
+  static constexpr int N_STATS = 1;
+  __host__ __device__ int n_grad() const { return FEAT + 1; }
+  __device__ float* dst(int i) const { return i < FEAT ? (dw ? dw + i : nullptr) : db; }
+  __device__ void stat(int, double s) const {
+    if (vloss_accum) vloss_accum[0] += ppo_loss_stat(STAT_VALUE, s, inv_b, smooth_l1);
   }
-  // summed in double, rounded once, in the fixed order of ppo_math.h sum_partials8
-  const int i = blockIdx.x * RED_OUT + (threadIdx.x & (RED_OUT - 1));
-  const float s = sum_partials8(part, VH_STRIDE, nwg, min(i, FEAT), sh);
-  if (threadIdx.x >= RED_OUT || i > FEAT) return;
-  if (i < FEAT) {
-    if (dw) dw[i] = s;
-  } else if (db) {
-    db[0] = s;
-  }
-}
+};
 
 void launch_value_head_fwd(const float* w, const float* b, const float* h, int64_t ld_h, int n, float* value, hipStream_t st) {
   int wgs = (n + 3) / 4;
@@ -126,8 +117,7 @@ void launch_value_head_loss(const ddrl_config& cfg, bool shared, const float* w,
   const float gscale = shared ? inv_b * cfg.v_loss_theta : inv_b;
   hipLaunchKernelGGL(value_head_loss_kernel, dim3(VH_WG), dim3(VH_WAVES * 64), 0, st, w, b, h, ld_h, n, rets, cfg, gscale, dh,
                      ld_dh, part);
-  hipLaunchKernelGGL(value_head_reduce_kernel, dim3((FEAT + 1 + RED_OUT - 1) / RED_OUT + 1), dim3(256), 0, st, part, VH_WG, cfg, inv_b, dw, db,
-                     vloss_accum);
+  launch_head_reduce(part, VH_STRIDE, VH_WG, ValueHeadReduce{inv_b, cfg.smooth_l1_loss, dw, db, vloss_accum}, st);
 }
 
 // loss[0] (+)= sign * mean(score[:, 0]);  dscore[i][0] = sign / n_total, dscore[i][1..width) = 0 (padded columns).
@@ -228,16 +218,13 @@ __global__ __launch_bounds__(256) void sqnorm2_kernel(const float* __restrict__ 
 
 using namespace ddrl;
 
-static int32_t g_check() { return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP; }
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" {
 
 int32_t ddrl_op_value_head_forward(const float* w, const float* b, const float* h, int64_t ld_h, int32_t n, float* value,
                                    void* stream) {
-  if (!w || !b || !h || !value || n < 1 || ld_h < FEAT || (ld_h & 3) || !al16(h)) return DDRL_ERR_INVALID_ARG;
+  if (!w || !b || !h || !value || n < 1 || ld_h < FEAT || (ld_h & 3) || !aligned16(h)) return DDRL_ERR_INVALID_ARG;
   launch_value_head_fwd(w, b, h, ld_h, n, value, (hipStream_t)stream);
-  return g_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_value_head_ws_floats(int64_t* floats) {
@@ -250,10 +237,10 @@ int32_t ddrl_op_value_head_loss(const ddrl_config* cfg, int32_t shared, const fl
                                 int64_t ld_h, int32_t n, const float* rets, int64_t B_global, float* dh, int64_t ld_dh, float* dw,
                                 float* db, float* vloss_accum, float* ws, void* stream) {
   if (!cfg || !w || !b || !h || !rets || !dh || !ws || n < 1 || B_global < n) return DDRL_ERR_INVALID_ARG;
-  if (ld_h < FEAT || ld_dh < FEAT || (ld_h & 3) || (ld_dh & 3) || !al16(h) || !al16(dh)) return DDRL_ERR_INVALID_ARG;
+  if (ld_h < FEAT || ld_dh < FEAT || (ld_h & 3) || (ld_dh & 3) || !aligned16(h) || !aligned16(dh)) return DDRL_ERR_INVALID_ARG;
   launch_value_head_loss(*cfg, shared != 0, w, b, h, ld_h, n, rets, (float)(1.0 / (double)B_global), dh, ld_dh, dw, db,
                          vloss_accum, ws, (hipStream_t)stream);
-  return g_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_wgan_terms(const float* score, int64_t ld, int32_t n, int64_t n_total, float sign, float* dscore, int64_t ld_d,
@@ -261,13 +248,13 @@ int32_t ddrl_op_wgan_terms(const float* score, int64_t ld, int32_t n, int64_t n_
   if (!score || !dscore || !loss || n < 1 || n_total < n || ld < 1 || width < 1 || ld_d < width) return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(wgan_terms_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, score, ld, n, n_total, sign, dscore, ld_d,
                      width, loss, accumulate);
-  return g_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_colsum(const float* x, int64_t ld, int32_t n, int32_t width, float* out, void* stream) {
   if (!x || !out || n < 1 || width < 1 || ld < width) return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(colsum_kernel, dim3(width), dim3(256), 0, (hipStream_t)stream, x, ld, n, out);
-  return g_check();
+  return launch_status();
 }
 
 int32_t ddrl_op_clip_rmsprop(float* params, float* grads, float* square_avg, int64_t n_params, float lr, double alpha, float eps,
@@ -281,7 +268,7 @@ int32_t ddrl_op_clip_rmsprop(float* params, float* grads, float* square_avg, int
   RmsArgs a{lr, (float)alpha, (float)(1.0 - alpha), eps, max_norm};
   hipLaunchKernelGGL(clip_rmsprop_kernel, dim3(2048), dim3(256), 0, st, params, grads, square_avg, n_params, (const double*)ws,
                      NORM_WG, a);
-  return g_check();
+  return launch_status();
 }
 
 }  // extern "C"

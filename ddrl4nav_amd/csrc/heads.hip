@@ -8,8 +8,8 @@
 //   Critic.forward                             USTC_lab/nn/critic.py:14-21
 //   ForwardThread.run sampling + log_prob      USTC_lab/server/forward.py:132-138
 //   PPO.learn loss block + autograd            USTC_lab/nn/ppo.py:82-108,122-123
+#include "heads_common.h"
 #include "kernels.h"
-#include "ppo_math.h"
 
 namespace ddrl {
 
@@ -102,20 +102,6 @@ __device__ __forceinline__ void softmax_categorical(const float* z, int A, Dist<
     d.q[j] = d.p[j] / d.ps;
     d.lc[j] = logf(fminf(fmaxf(d.q[j], CAT_EPS), 1.0f - CAT_EPS));
   }
-}
-
-template <int MAXA>
-__device__ __forceinline__ float pick(const float (&a)[MAXA], int idx) {
-  // a chain of selects on registers.  Left to itself the compiler turns it into an indexed load from a private (scratch) copy of
-  // the array: a dependent round trip through the vector memory path per call, four per sample in heads_loss; the empty asm keeps
-  // every step a v_cndmask
-  float r = a[0];
-#pragma unroll
-  for (int j = 1; j < MAXA; ++j) {
-    r = (idx == j) ? a[j] : r;
-    asm volatile("" : "+v"(r));
-  }
-  return r;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(256) void heads_act_kernel(float* __restrict__ h, i
 // hpart layout per workgroup: [A*512 dWa][512 dwc][A dba][1 dbc][actor_sum, v_sum, ent_sum]
 // --------------------------------------------------------------------------------------------
 // WLDS (A > 8): the actor-head weight / bias gradient slots of hpart are written by
-// head_wgrad_kernel from dlogits instead (288 accumulator + weight registers do not fit a lane).
+// head_wgrad_kernel (heads_common.h) from dlogits instead.  The rows are summed by head_reduce_kernel over PpoHeadsReduce.
 constexpr int LOSS_WAVES = 4;      // waves per workgroup of heads_loss: one per SIMD (register-resident head weights, A = 7 .. 8 and A > 8)
 constexpr int LOSS_WAVES6 = 8;     // A <= 6 (Pong): the weight rows live in LDS, 245 registers -> two waves per SIMD (round 6)
 constexpr int LOSS_NS = 4;         // samples per wave and turn (a power of two): the scalar chain of the loss block runs once per NS samples
@@ -561,27 +547,18 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
       const bool first = (w == 0);
       if constexpr (GREG) {
 #pragma unroll
-        for (int j = 0; j < MAXA; ++j)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int idx = j * FEAT + lane * 8 + i;
-            red[idx] = first ? gwa[j][i] : red[idx] + gwa[j][i];
-          }
+        for (int j = 0; j < MAXA; ++j) turn_add_row(first, red, j * FEAT + lane * 8, gwa[j]);
       }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int idx = MAXA * FEAT + lane * 8 + i;
-        red[idx] = first ? gwc[i] : red[idx] + gwc[i];
-      }
+      turn_add_row(first, red, MAXA * FEAT + lane * 8, gwc);
       if (lane == 0) {
         if constexpr (GREG) {
 #pragma unroll
-          for (int j = 0; j < MAXA; ++j) red[SCAL + j] = first ? gba[j] : red[SCAL + j] + gba[j];
+          for (int j = 0; j < MAXA; ++j) turn_add(first, red[SCAL + j], gba[j]);
         }
-        red[SCAL + MAXA] = first ? gbc : red[SCAL + MAXA] + gbc;
-        red[SCAL + MAXA + 1] = first ? (float)s_actor : red[SCAL + MAXA + 1] + (float)s_actor;
-        red[SCAL + MAXA + 2] = first ? (float)s_v : red[SCAL + MAXA + 2] + (float)s_v;
-        red[SCAL + MAXA + 3] = first ? (float)s_ent : red[SCAL + MAXA + 3] + (float)s_ent;
+        turn_add(first, red[SCAL + MAXA], gbc);
+        turn_add(first, red[SCAL + MAXA + 1], (float)s_actor);
+        turn_add(first, red[SCAL + MAXA + 2], (float)s_v);
+        turn_add(first, red[SCAL + MAXA + 3], (float)s_ent);
       }
     }
     __syncthreads();
@@ -594,67 +571,6 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
   for (int i = threadIdx.x; i < FEAT; i += WAVES * 64) out[A * FEAT + i] = red[MAXA * FEAT + i];
   if (threadIdx.x == 0) out[(A + 1) * FEAT + A] = red[SCAL + MAXA];
   if (threadIdx.x < 3) out[(A + 1) * FEAT + A + 1 + threadIdx.x] = red[SCAL + MAXA + 1 + threadIdx.x];
-}
-
-// Actor-head weight / bias gradient for A > 8, from the dlogits heads_loss_kernel left behind:
-//   hpart[wg][j*512 + k] = sum_{b in the workgroup's samples} dlogits[b][j] * h_actor[b][k],  [A*512+512 + j] = sum dlogits[b][j]
-// (samples are dealt to workgroups round-robin; fixed order -> deterministic).
-template <int MAXA>
-__global__ __launch_bounds__(256) void head_wgrad_kernel(const float* __restrict__ h, const float* __restrict__ dlogits,
-                                                         int n, int A, float* __restrict__ hpart, int64_t hstride) {
-  float acc[MAXA][2], bsum[MAXA];
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) acc[j][0] = acc[j][1] = bsum[j] = 0.0f;
-  const int k = threadIdx.x;
-  for (int b = blockIdx.x; b < n; b += gridDim.x) {
-    const float h0 = h[(int64_t)b * FEAT + k], h1 = h[(int64_t)b * FEAT + 256 + k];
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j) {
-      const float g = (j < A) ? dlogits[(int64_t)b * A + min(j, A - 1)] : 0.0f;
-      acc[j][0] = __builtin_fmaf(g, h0, acc[j][0]);
-      acc[j][1] = __builtin_fmaf(g, h1, acc[j][1]);
-      bsum[j] += g;
-    }
-  }
-  float* out = hpart + (int64_t)blockIdx.x * hstride;
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) {
-    if (j < A) {
-      out[j * FEAT + k] = acc[j][0];
-      out[j * FEAT + 256 + k] = acc[j][1];
-      if (threadIdx.x == 0) out[(A + 1) * FEAT + j] = bsum[j];
-    }
-  }
-}
-
-// grads[head params] = sum over workgroups (fixed order, ppo_math.h sum_partials8: the arithmetic of the earlier one-thread-per-element
-// form, so the gradients are bit-identical to it); grads[n_params+0..2] = loss shares, by the last workgroup (one wave per loss).
-__global__ __launch_bounds__(256) void heads_reduce_kernel(const float* __restrict__ hpart, int64_t hstride, int nwg,
-                                                           ParamLayout L, ddrl_config cfg, float inv_b,
-                                                           float* __restrict__ grads) {
-  __shared__ double sh[8][RED_OUT];
-  const int A = L.A;
-  const int nloss0 = (A + 1) * FEAT + A + 1;
-  if (blockIdx.x == gridDim.x - 1) {
-    const int k = threadIdx.x >> 6;
-    if (k >= 3) return;
-    const double s = wave_sum_partials(hpart, hstride, nwg, nloss0 + k);
-    double r;
-    if (k == 0) r = -s * (double)inv_b;            // actor_loss = -mean(term)
-    else if (k == 1) r = s * (double)inv_b * (cfg.smooth_l1_loss ? 1.0 : 0.5);  // v_loss = mean(err^2)/2
-    else r = s * (double)inv_b;                    // entropy = mean(H)
-    if ((threadIdx.x & 63) == 0) grads[L.n_params + k] = (float)r;
-    return;
-  }
-  const int i = blockIdx.x * RED_OUT + (threadIdx.x & (RED_OUT - 1));
-  const float sum = sum_partials8(hpart, hstride, nwg, min(i, nloss0 - 1), sh);
-  if (threadIdx.x >= RED_OUT || i >= nloss0) return;
-  int64_t dst;
-  if (i < A * FEAT) dst = L.actor_w + i;
-  else if (i < (A + 1) * FEAT) dst = L.critic_w + (i - A * FEAT);
-  else if (i < (A + 1) * FEAT + A) dst = L.actor_b + (i - (A + 1) * FEAT);
-  else dst = L.critic_b;
-  grads[dst] = sum;
 }
 
 __global__ __launch_bounds__(256) void categorical_stats_kernel(const float* __restrict__ probs, int n, int A,
@@ -715,30 +631,27 @@ void launch_heads_act(const HeadsCall& c, const float* act_in, uint64_t seed, ui
   const int wpw = small ? 1 : 4;
   int wgs = (c.n + wpw - 1) / wpw;
   if (wgs > 1024) wgs = 1024;
-  const int nsplit = c.plain_features ? 1 : fc_forward_splits(c.n);
   auto kern = small ? heads_act_kernel<MAXA_SMALL, false> : heads_act_kernel<MAXA_LARGE, true>;
-  hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * wpw), 0, st, c.ws->h, c.h_es != HeadsCall::ES_UNSET ? c.h_es : c.max_batch * FEAT,
-                     nsplit > 1 ? c.ws->wpart : nullptr, nsplit > 1 ? nsplit : 0, c.params, *c.L, c.n,
-                     act_in, seed, stream_id, probs, value, action_out, logp_out);
+  // the kernel stores to h only where it finishes split-K partials (fc_nsplit > 0); finished features are read
+  hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * wpw), 0, st, const_cast<float*>(c.h), c.h_es, c.fc_part, c.fc_nsplit, c.params, *c.L,
+                     c.n, act_in, seed, stream_id, probs, value, action_out, logp_out);
 }
 
 void launch_heads_loss(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs,
                        const float* rets, float inv_b, float* grads, hipStream_t st) {
-  const int64_t hs = hpart_stride(c.L->A);
-  const bool large = c.L->A > MAXA_SMALL;
+  const ParamLayout& L = *c.L;
+  const int64_t hs = hpart_stride(L.A);
+  const bool large = L.A > MAXA_SMALL;
   // A <= 6 (Pong's six actions): the four samples' 7 x 4 dot products are reduced together (TR in the kernel), weight rows in LDS, eight waves
-  const bool six = c.L->A <= 6;
+  const bool six = L.A <= 6;
   auto kern = large ? heads_loss_kernel<MAXA_LARGE, true> : (six ? heads_loss_kernel<6, LOSS_WAVES6 == 8, true, LOSS_WAVES6> : heads_loss_kernel<MAXA_SMALL, false>);
-  hipLaunchKernelGGL(kern, dim3(HEAD_WG), dim3((six ? LOSS_WAVES6 : LOSS_WAVES) * 64), 0, st, c.ws->h, c.h_es != HeadsCall::ES_UNSET ? c.h_es : c.max_batch * FEAT, c.params,
-                     *c.L, *c.cfg, c.n, actions, old_logps, advs, rets, inv_b, c.ws->dh,
-                     c.dh_es != HeadsCall::ES_UNSET ? c.dh_es : c.max_batch * FEAT, c.ws->dlogits, c.ws->dvalue, c.ws->hpart, hs,
-                     c.normalise_dh ? c.ws->gsc : nullptr, c.max_batch, c.ws->amax);
+  hipLaunchKernelGGL(kern, dim3(HEAD_WG), dim3((six ? LOSS_WAVES6 : LOSS_WAVES) * 64), 0, st, c.h, c.h_es, c.params, L, *c.cfg, c.n,
+                     actions, old_logps, advs, rets, inv_b, c.dh, c.dh_es, c.dlogits, c.dvalue, c.hpart, hs, c.gsc, c.gsc_es, c.amax);
   if (large)
-    hipLaunchKernelGGL(head_wgrad_kernel<MAXA_LARGE>, dim3(HEAD_WG), dim3(256), 0, st, c.ws->h, c.ws->dlogits, c.n,
-                       c.L->A, c.ws->hpart, hs);
-  const int nsum = (c.L->A + 1) * FEAT + c.L->A + 1;  // gradient elements; + one workgroup for the three loss sums
-  hipLaunchKernelGGL(heads_reduce_kernel, dim3((nsum + RED_OUT - 1) / RED_OUT + 1), dim3(256), 0, st, c.ws->hpart, hs, HEAD_WG, *c.L,
-                     *c.cfg, inv_b, grads);
+    hipLaunchKernelGGL(head_wgrad_kernel<MAXA_LARGE>, dim3(HEAD_WG), dim3(256), 0, st, c.h, (int64_t)FEAT, (const float*)c.dlogits, c.n,
+                       L.A, c.hpart, hs, (L.A + 1) * FEAT);
+  const HeadLayout hl{L.A, L.NE == 1, L.actor_w, L.actor_b, 0, L.critic_w, L.critic_b, L.n_params};
+  launch_head_reduce(c.hpart, hs, HEAD_WG, PpoHeadsReduce{hl, 0, inv_b, c.cfg->smooth_l1_loss, grads}, st);
 }
 
 void launch_categorical_stats(const float* probs, int n, int A, float* p_hat, float* logits, float* entropy,

@@ -5,8 +5,7 @@
 //   Basenn._imitation_learning_classifier   USTC_lab/nn/base.py:120-150 (CrossEntropyLoss on the actor's logits + its autograd backward
 //                                           through actor_linear; the reference's own expression cannot run on a PPO net)
 //   DataLoader(dataset, batch, shuffle)     USTC_lab/nn/base.py:128,140-141 (the per-batch collation of the shuffled samples)
-#include "common.h"
-#include "ppo_math.h"
+#include "heads_common.h"
 
 namespace ddrl {
 
@@ -15,8 +14,8 @@ namespace ddrl {
 // samples per turn; lane i < NS then runs the softmax / log-sum-exp chain of sample i once (not 64 times on wave-uniform numbers) and
 // the others read its d(logits) back with v_readlane.  The head weights sit in LDS (up to 36 KB for the 18 Atari actions).
 //   GREG (A <= 8): the weight / bias gradient is accumulated in registers (64 + 8 per lane) and reduced over the workgroup's waves;
-//   else (A <= 18): d(logits) is stored and bc_wgrad_kernel forms the weight gradient (144 accumulators do not sit beside the rest).
-// Partials per workgroup: [A*512 dw][A db][loss sum][correct count]; bc_reduce_kernel sums them in a fixed order.
+//   else (A <= 18): d(logits) is stored and head_wgrad_kernel forms the weight gradient (144 accumulators do not sit beside the rest).
+// Partials per workgroup: [A*512 dw][A db][loss sum][correct count]; head_reduce_kernel sums them over BcReduce.
 constexpr int BC_WAVES = 4, BC_NS = 4, BC_MAX_WG = 64;
 constexpr int BC_A_SMALL = 8, BC_A_LARGE = 18;
 
@@ -26,17 +25,6 @@ inline int bc_workgroups(int n) {
   return w < BC_MAX_WG ? w : BC_MAX_WG;
 }
 inline int64_t bc_stride(int A) { return ((int64_t)A * FEAT + A + 2 + 3) & ~(int64_t)3; }
-
-template <int MAXA>
-__device__ __forceinline__ float bc_pick(const float (&a)[MAXA], int idx) {  // a chain of selects on registers (heads.hip pick)
-  float r = a[0];
-#pragma unroll
-  for (int j = 1; j < MAXA; ++j) {
-    r = (idx == j) ? a[j] : r;
-    asm volatile("" : "+v"(r));
-  }
-  return r;
-}
 
 template <int MAXA, bool GREG>
 __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __restrict__ h, int64_t ld_h, const float* __restrict__ w,
@@ -104,7 +92,7 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
       e[j] = (j < A) ? expf(zl[j] - m) : 0.0f;
       se += e[j];
     }
-    const float nll = valid ? -((bc_pick(zl, a) - m) - logf(se)) : 0.0f;
+    const float nll = valid ? -((pick(zl, a) - m) - logf(se)) : 0.0f;
     float gzl[MAXA];
 #pragma unroll
     for (int j = 0; j < MAXA; ++j) gzl[j] = (valid && j < A) ? (e[j] / se - ((j == a) ? 1.0f : 0.0f)) * inv_n : 0.0f;
@@ -163,20 +151,15 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
       const bool first = (wv == 0);
       if constexpr (GREG) {
 #pragma unroll
-        for (int j = 0; j < MAXA; ++j)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int idx = j * FEAT + lane * 8 + k;
-            wl[idx] = first ? gwa[j][k] : wl[idx] + gwa[j][k];
-          }
+        for (int j = 0; j < MAXA; ++j) turn_add_row(first, wl, j * FEAT + lane * 8, gwa[j]);
       }
       if (lane == 0) {
         if constexpr (GREG) {
 #pragma unroll
-          for (int j = 0; j < MAXA; ++j) red[j] = first ? gba[j] : red[j] + gba[j];
+          for (int j = 0; j < MAXA; ++j) turn_add(first, red[j], gba[j]);
         }
-        red[MAXA] = first ? (float)s_loss : red[MAXA] + (float)s_loss;
-        red[MAXA + 1] = first ? s_cnt : red[MAXA + 1] + s_cnt;
+        turn_add(first, red[MAXA], (float)s_loss);
+        turn_add(first, red[MAXA + 1], s_cnt);
       }
     }
     __syncthreads();
@@ -189,55 +172,16 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
   if (threadIdx.x < 2) out[A * FEAT + A + threadIdx.x] = red[MAXA + threadIdx.x];
 }
 
-// Weight / bias gradient for A > 8 from the d(logits) bc_loss_kernel left behind (heads.hip head_wgrad_kernel with a leading dimension):
-// samples are dealt to workgroups round-robin, each thread owns columns k and k + 256 of every row.
-template <int MAXA>
-__global__ __launch_bounds__(256) void bc_wgrad_kernel(const float* __restrict__ h, int64_t ld_h, const float* __restrict__ dlogits, int n,
-                                                       int A, float* __restrict__ part, int64_t pstride) {
-  float acc[MAXA][2], bsum[MAXA];
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) acc[j][0] = acc[j][1] = bsum[j] = 0.0f;
-  const int k = threadIdx.x;
-  for (int b = blockIdx.x; b < n; b += gridDim.x) {
-    const float h0 = h[(int64_t)b * ld_h + k], h1 = h[(int64_t)b * ld_h + 256 + k];
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j) {
-      const float g = (j < A) ? dlogits[(int64_t)b * A + min(j, A - 1)] : 0.0f;
-      acc[j][0] = __builtin_fmaf(g, h0, acc[j][0]);
-      acc[j][1] = __builtin_fmaf(g, h1, acc[j][1]);
-      bsum[j] += g;
-    }
-  }
-  float* out = part + (int64_t)blockIdx.x * pstride;
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) {
-    if (j < A) {
-      out[j * FEAT + k] = acc[j][0];
-      out[j * FEAT + 256 + k] = acc[j][1];
-      if (threadIdx.x == 0) out[A * FEAT + j] = bsum[j];
-    }
-  }
-}
-
-// dw / db = sum over the workgroups (ppo_math.h sum_partials8: fixed order, in double, rounded once); the last workgroup takes the two
-// statistics, one wave each.
-__global__ __launch_bounds__(256) void bc_reduce_kernel(const float* __restrict__ part, int64_t pstride, int nwg, int A, double inv_n,
-                                                        float* __restrict__ dw, float* __restrict__ db, float* __restrict__ stats) {
-  __shared__ double sh[8][RED_OUT];
-  const int nsum = A * FEAT + A;
-  if (blockIdx.x == gridDim.x - 1) {
-    const int k = threadIdx.x >> 6;
-    if (k >= 2) return;
-    const double s = wave_sum_partials(part, pstride, nwg, nsum + k);
-    if ((threadIdx.x & 63) == 0) stats[k] = (float)(k == 0 ? s * inv_n : s);
-    return;
-  }
-  const int i = blockIdx.x * RED_OUT + (threadIdx.x & (RED_OUT - 1));
-  const float sum = sum_partials8(part, pstride, nwg, min(i, nsum - 1), sh);
-  if (threadIdx.x >= RED_OUT || i >= nsum) return;
-  if (i < A * FEAT) dw[i] = sum;
-  else db[i - A * FEAT] = sum;
-}
+// dw / db and the two statistics (loss share of the n_total samples, correct count) from the partial rows
+struct BcReduce {
+  int A;
+  double inv_n;
+  float *dw, *db, *stats;
+  static constexpr int N_STATS = 2;
+  __host__ __device__ int n_grad() const { return A * FEAT + A; }
+  __device__ float* dst(int i) const { return i < A * FEAT ? dw + i : db + (i - A * FEAT); }
+  __device__ void stat(int k, double s) const { stats[k] = (float)(k == 0 ? s * inv_n : s); }
+};
 
 // ---- minibatch gather --------------------------------------------------------------------------------------------------------------
 // dst[i][:] = src[idx[i]][:] in 16-byte units.  A 256-thread workgroup moves GATHER_UNROLL x 256 consecutive units of one row (both loads
@@ -271,14 +215,6 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_rows_kernel(const uint4
 
 using namespace ddrl;
 
-namespace {
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool overlap(const void* a, const void* b, uint64_t a_bytes, uint64_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + b_bytes && y < x + a_bytes;
-}
-}  // namespace
-
 extern "C" {
 
 int32_t ddrl_op_heads_bc_ws_floats(int32_t n_actions, int32_t max_n, int64_t* floats) {
@@ -294,7 +230,7 @@ int32_t ddrl_op_heads_bc_loss(const float* w, const float* b, int32_t n_actions,
   // every check comes before the first HIP call: a host without a GPU gets the same answers
   if (!w || !b || !h || !labels || !dh || !dw || !db || !stats || !ws || n < 1 || n_total < n) return DDRL_ERR_INVALID_ARG;
   if (n_actions < 2 || n_actions > BC_A_LARGE) return DDRL_ERR_UNSUPPORTED;
-  if (ld_h < FEAT || ld_dh < FEAT || (ld_h & 3) || (ld_dh & 3) || !al16(h) || !al16(dh)) return DDRL_ERR_INVALID_ARG;
+  if (ld_h < FEAT || ld_dh < FEAT || (ld_h & 3) || (ld_dh & 3) || !aligned16(h) || !aligned16(dh)) return DDRL_ERR_INVALID_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const int A = n_actions, nwg = bc_workgroups(n);
   const int64_t ps = bc_stride(A);
@@ -306,18 +242,16 @@ int32_t ddrl_op_heads_bc_loss(const float* w, const float* b, int32_t n_actions,
     float* dlogits = ws + (int64_t)BC_MAX_WG * ps;
     hipLaunchKernelGGL((bc_loss_kernel<BC_A_LARGE, false>), dim3(nwg), dim3(BC_WAVES * 64), 0, st, h, ld_h, w, b, A, n, labels,
                        (float)inv_n, dh, ld_dh, dlogits, ws, ps);
-    hipLaunchKernelGGL(bc_wgrad_kernel<BC_A_LARGE>, dim3(nwg), dim3(256), 0, st, h, ld_h, (const float*)dlogits, n, A, ws, ps);
+    hipLaunchKernelGGL(head_wgrad_kernel<BC_A_LARGE>, dim3(nwg), dim3(256), 0, st, h, ld_h, (const float*)dlogits, n, A, ws, ps, A * FEAT);
   }
-  const int nsum = A * FEAT + A;  // gradient elements; + one workgroup for the two statistics
-  hipLaunchKernelGGL(bc_reduce_kernel, dim3((nsum + RED_OUT - 1) / RED_OUT + 1), dim3(256), 0, st, (const float*)ws, ps, nwg, A, inv_n,
-                     dw, db, stats);
-  return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP;
+  launch_head_reduce(ws, ps, nwg, BcReduce{A, inv_n, dw, db, stats}, st);
+  return launch_status();
 }
 
 int32_t ddrl_op_gather_rows_u8(const uint8_t* src, int64_t n_rows, int64_t row_bytes, const int32_t* idx, int32_t n, uint8_t* dst,
                                const float* labels_src, float* labels_dst, void* stream) {
   if (!src || !idx || !dst || n < 1 || n_rows < 1 || row_bytes < 16 || (row_bytes & 15)) return DDRL_ERR_INVALID_ARG;
-  if (!al16(src) || !al16(dst) || ((uintptr_t)idx & 3)) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(src) || !aligned16(dst) || ((uintptr_t)idx & 3)) return DDRL_ERR_INVALID_ARG;
   if ((labels_src == nullptr) != (labels_dst == nullptr)) return DDRL_ERR_INVALID_ARG;
   if (n_rows > INT64_MAX / row_bytes) return DDRL_ERR_INVALID_ARG;
   if (overlap(src, dst, (uint64_t)n_rows * row_bytes, (uint64_t)n * row_bytes)) return DDRL_ERR_INVALID_ARG;
@@ -326,7 +260,7 @@ int32_t ddrl_op_gather_rows_u8(const uint8_t* src, int64_t n_rows, int64_t row_b
   if (chunks > INT32_MAX / n) return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(n * chunks)), dim3(GATHER_THREADS), 0, (hipStream_t)stream, (const uint4*)src,
                      n_rows, row_vecs, (int)chunks, idx, (uint4*)dst, labels_src, labels_dst);
-  return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -74,7 +74,7 @@ void launch_conv_wgrad1_2(const EncCall& c, float* grads, hipStream_t st);
 void launch_pack_weights(const Workspace& w, const ParamLayout& L, const float* params, hipStream_t st);
 void launch_reduce_partials(const float* part, int nsplit, int64_t count, int ne, float* grads, int64_t off0,
                             int64_t off1, hipStream_t st);
-void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, const Workspace& w, float* params,
+void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, double* npart, float* params,
                       float* grads, float* m, float* v, int64_t step, hipStream_t st);
 void launch_episode_returns(const float* rewards, const uint8_t* dones, int T, int N, float* rsum, float* rep, float* trace,
                             int* finished, hipStream_t st);
@@ -82,25 +82,28 @@ void launch_gae(const float* values, const float* rewards, const uint8_t* dones,
                 float gamma, float landa, float* adv, float* ret, hipStream_t st);
 void launch_fill_lut(float* lut, hipStream_t st);
 
-// heads.hip
+// heads.hip: what one launch of the Categorical head kernels reads and writes.  The Atari context fills it from its workspace
+// (api.hip ctx_heads_call), the operator entry points from their arguments (api_ops.hip).
 struct HeadsCall {
-  const Workspace* ws;
   const ParamLayout* L;
-  const ddrl_config* cfg;
+  const ddrl_config* cfg;  // launch_heads_loss only
   const float* params;
   int n;
-  int64_t max_batch;
-  // generic callers (ddrl_op_heads_*): explicit actor->critic feature / gradient strides and no
-  // split-K FC partials to fold in; the Atari context leaves these at their defaults
-  // (a difference of two independent allocations: ANY value, negative included, is a valid stride -- the "unset" mark is a
-  // separate sentinel; a plain "< 0" test once sent every net whose critic buffer happened to lie below its actor buffer to
-  // h + max_batch * 512: wrong values, out-of-bounds reads)
-  static constexpr int64_t ES_UNSET = INT64_MIN;
-  int64_t h_es = ES_UNSET, dh_es = ES_UNSET;
-  bool plain_features = false;
-  // heads_loss also normalises dh per sample (Workspace::gsc, amax slots DH / GMAX, which the caller has zeroed): the Atari context's
-  // ddrl_ppo_iter; launch_encoder_backward is then told to skip its stand-alone dh_normalise_kernel
-  bool normalise_dh = false;
+  // features [n][512] of the actor's encoder and their gradient; the critic's encoder's lie h_es / dh_es floats further (a difference
+  // of two allocations: any value, negative included; not read with a shared prenet)
+  const float* h;
+  int64_t h_es;
+  float* dh;
+  int64_t dh_es;
+  // acting on the dense layer's split-K partial sums (fc2.hip): heads_act adds them up and WRITES the finished features to h
+  const float* fc_part = nullptr;
+  int fc_nsplit = 0;
+  float *dlogits = nullptr, *dvalue = nullptr, *hpart = nullptr;  // launch_heads_loss: [n][A], [n], [HEAD_WG][hpart_stride(A)]
+  // heads_loss also normalises dh per sample (scales to gsc[e * gsc_es + b], amax slots DH / GMAX, which the caller has zeroed;
+  // launch_encoder_backward is then told to skip its stand-alone dh_normalise_kernel); null = plain dh
+  float* gsc = nullptr;
+  int64_t gsc_es = 0;
+  float* amax = nullptr;
 };
 void launch_heads_act(const HeadsCall& c, const float* act_in, uint64_t seed, uint64_t stream_id,
                       float* probs, float* value, float* action_out, float* logp_out, hipStream_t st);

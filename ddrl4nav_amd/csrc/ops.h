@@ -141,16 +141,11 @@ struct LinearRoute {
 LinearRoute linear_route(int n, int K, int N);
 
 // gheads.hip: Gaussian actor + critic heads; offsets into the caller's flat parameter arena
-struct GaussLayout {
-  int D;       // action dims (<= 8)
-  int shared;  // 1: total_loss is differentiated (shared prenet), both heads feed dh_actor
-  int64_t actor_w, actor_b, log_std, critic_w, critic_b, n_params;
-};
 int64_t gauss_hpart_stride(int D);
-void launch_gauss_act(const GaussLayout& L, const float* params, const float* h_actor, const float* h_critic, int n,
+void launch_gauss_act(const HeadLayout& L, const float* params, const float* h_actor, const float* h_critic, int n,
                       const float* act_in, uint64_t seed, uint64_t stream_id, float* mu_out, float* value, float* action_out,
                       float* logp_out, hipStream_t st);
-void launch_gauss_loss(const GaussLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
+void launch_gauss_loss(const HeadLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
                        const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
                        const float* rets, float inv_b, float* dh_actor, float* dh_critic, float* dmu, float* dvalue,
                        float* hpart, float* grads, hipStream_t st);

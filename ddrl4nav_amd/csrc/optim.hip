@@ -321,9 +321,9 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, f
   }
 }
 
-void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, const Workspace& w, float* params, float* grads,
+void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, double* npart, float* params, float* grads,
                       float* m, float* v, int64_t step, hipStream_t st) {
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(NORM_WG), dim3(256), 0, st, grads, L.n_params, w.npart);
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(NORM_WG), dim3(256), 0, st, grads, L.n_params, npart);
   AdamArgs a;
   const double bc1 = 1.0 - pow((double)cfg.adam_beta1, (double)step);
   const double bc2 = 1.0 - pow((double)cfg.adam_beta2, (double)step);
@@ -341,7 +341,7 @@ void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, const Worksp
   a.clip = cfg.clip_grad;
   a.v_theta = cfg.v_loss_theta;
   a.ent_theta = cfg.ent_loss_theta;
-  hipLaunchKernelGGL(clip_adam_kernel, dim3(2048), dim3(256), 0, st, params, grads, m, v, L.n_params, L.n_actor, w.npart,
+  hipLaunchKernelGGL(clip_adam_kernel, dim3(2048), dim3(256), 0, st, params, grads, m, v, L.n_params, L.n_actor, npart,
                      NORM_WG, a);
 }
 

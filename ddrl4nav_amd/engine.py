@@ -8,16 +8,11 @@ from ctypes import byref, c_float, c_int32, c_int64, c_void_p, create_string_buf
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import STATS_FLOATS, Config, check
+from .ops import _p, _st
 
-
-def _ptr(t):
-    return c_void_p(0) if t is None else c_void_p(t.data_ptr())
-
-
-def _stream():
-    return c_void_p(torch.cuda.current_stream().cuda_stream)
+_ptr, _stream = _p, _st  # the names this module had for them: callers import `_stream` from here
 
 
 class HotPath:
@@ -43,8 +38,8 @@ class HotPath:
             self.adam_v = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
             self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
         ctx = c_void_p()
-        check(self.lib.ddrl_ctx_create(byref(self.cfg), _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m),
-                                       _ptr(self.adam_v), _ptr(self.workspace), self.workspace_bytes, byref(ctx)))
+        check(self.lib.ddrl_ctx_create(byref(self.cfg), _p(self.params), _p(self.grads), _p(self.adam_m),
+                                       _p(self.adam_v), _p(self.workspace), self.workspace_bytes, byref(ctx)))
         self.ctx = ctx
         self.process_group = process_group
         self.n_actions = int(n_actions)
@@ -130,31 +125,21 @@ class HotPath:
         else:
             assert act.dtype == torch.float32 and act.is_contiguous() and act.numel() == n
             action = act
-        check(self.lib.ddrl_forward(self.ctx, _ptr(frames), n, _ptr(act), int(seed) & (2 ** 64 - 1),
-                                    int(stream_id) & (2 ** 64 - 1), _ptr(probs), _ptr(value),
-                                    _ptr(action) if act is None else c_void_p(0), _ptr(logp), _stream()))
+        check(self.lib.ddrl_forward(self.ctx, _p(frames), n, _p(act), int(seed) & (2 ** 64 - 1),
+                                    int(stream_id) & (2 ** 64 - 1), _p(probs), _p(value),
+                                    _p(action) if act is None else c_void_p(0), _p(logp), _st()))
         return probs, value, action, logp
 
     def categorical_stats(self, probs):
-        n, A = probs.shape
-        p_hat = torch.empty_like(probs)
-        logits = torch.empty_like(probs)
-        ent = torch.empty(n, dtype=torch.float32, device=probs.device)
-        check(self.lib.ddrl_categorical_stats(_ptr(probs), n, A, _ptr(p_hat), _ptr(logits), _ptr(ent), _stream()))
-        return p_hat, logits, ent
+        return ops.categorical_stats(probs)
 
     def categorical_sample(self, probs, seed, stream_id):
-        n, A = probs.shape
-        action = torch.empty(n, dtype=torch.float32, device=probs.device)
-        logp = torch.empty(n, dtype=torch.float32, device=probs.device)
-        check(self.lib.ddrl_categorical_sample(_ptr(probs), n, A, int(seed) & (2 ** 64 - 1),
-                                               int(stream_id) & (2 ** 64 - 1), _ptr(action), _ptr(logp), _stream()))
-        return action, logp
+        return ops.categorical_sample(probs, seed, stream_id)
 
     def last_features(self, n):
         ha = torch.empty((n, 512), dtype=torch.float32, device=self.device)
         hc = torch.empty((n, 512), dtype=torch.float32, device=self.device)
-        check(self.lib.ddrl_last_features(self.ctx, n, _ptr(ha), _ptr(hc), _stream()))
+        check(self.lib.ddrl_last_features(self.ctx, n, _p(ha), _p(hc), _st()))
         return ha, hc
 
     # ---- GAE --------------------------------------------------------------------------------
@@ -166,8 +151,8 @@ class HotPath:
         assert values.is_contiguous() and rewards.is_contiguous() and dones.is_contiguous()
         adv = torch.empty((T, N), dtype=torch.float32, device=values.device) if adv is None else adv
         ret = torch.empty((T, N), dtype=torch.float32, device=values.device) if ret is None else ret
-        check(self.lib.ddrl_gae(_ptr(values), _ptr(rewards), _ptr(dones), T, N, float(np.float32(gamma)),
-                                float(np.float32(landa)), _ptr(adv), _ptr(ret), _stream()))
+        check(self.lib.ddrl_gae(_p(values), _p(rewards), _p(dones), T, N, float(np.float32(gamma)),
+                                float(np.float32(landa)), _p(adv), _p(ret), _st()))
         return adv, ret
 
     # ---- learner ----------------------------------------------------------------------------
@@ -176,8 +161,8 @@ class HotPath:
         for t in (actions, old_logps, advs, rets):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
         assert frames.dtype == torch.uint8 and frames.is_contiguous()
-        check(self.lib.ddrl_ppo_iter(self.ctx, _ptr(frames), _ptr(actions), _ptr(old_logps), _ptr(advs), _ptr(rets),
-                                     B, int(b_global if b_global is not None else B), _stream()))
+        check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames), _p(actions), _p(old_logps), _p(advs), _p(rets),
+                                     B, int(b_global if b_global is not None else B), _st()))
 
     def enable_overlap(self):
         """Record the per-layer bucket events in every ppo_iter and reduce bucket by bucket on a second stream."""
@@ -203,13 +188,13 @@ class HotPath:
         backward recorded for it; the compute stream then waits for the last one (only the small conv2 bucket is exposed)."""
         cs = self._comm_stream
         if self.comm is not None:
-            check(self.lib.ddrl_grad_allreduce_overlapped(self.ctx, self.comm.h, c_void_p(cs.cuda_stream), _stream()))
+            check(self.lib.ddrl_grad_allreduce_overlapped(self.ctx, self.comm.h, c_void_p(cs.cuda_stream), _st()))
             return
         from .dist import allreduce_flat
         # ordering against whatever the compute stream holds at this call; stale bucket events (no ppo_iter since the last
         # reduction) make the communication stream wait for the compute stream up front (ADVICE r3: no race, no overlap)
         fresh = c_int32()
-        check(self.lib.ddrl_grad_buckets_begin(self.ctx, c_void_p(cs.cuda_stream), _stream(), byref(fresh)))
+        check(self.lib.ddrl_grad_buckets_begin(self.ctx, c_void_p(cs.cuda_stream), _st(), byref(fresh)))
         last = len(self._buckets) - 1
         for b, ranges in enumerate(self._buckets):
             if fresh.value:
@@ -233,7 +218,7 @@ class HotPath:
             if self._overlap:
                 self._allreduce_overlapped()
             elif self.comm is not None:
-                check(self.lib.ddrl_grad_allreduce(self.ctx, self.comm.h, _stream()))
+                check(self.lib.ddrl_grad_allreduce(self.ctx, self.comm.h, _st()))
             else:
                 allreduce_flat(self.grads, self.process_group)
 
@@ -259,24 +244,18 @@ class HotPath:
         return out
 
     def clip_adam_step(self):
-        check(self.lib.ddrl_clip_adam_step(self.ctx, _stream()))
+        check(self.lib.ddrl_clip_adam_step(self.ctx, _st()))
 
     def stats_async(self, out_row):
         """Enqueue the copy of the 8-float statistics tail into `out_row` (a pinned host tensor row); no sync.  The values are
         those of stats() once the stream has passed this point."""
         out_row.copy_(self.grads[self.n_params:self.n_params + STATS_FLOATS], non_blocking=True)
 
-    @staticmethod
-    def stats_dict(row):
-        s = row.numpy() if hasattr(row, "numpy") else row
-        return {"ActorLoss": float(s[0]), "VLoss": float(s[1]), "EntLoss": float(s[2]), "PpoTotalLoss": float(s[3]),
-                "GradNorm": float(s[4]), "ClipCoef": float(s[5])}
+    stats_dict = staticmethod(ops.stats_dict)
 
     def stats(self):
         """Host copy of (actor_loss, v_loss, entropy, total, grad_norm, clip_coef) -- one sync."""
-        s = self.grads[self.n_params:self.n_params + 6].cpu().numpy()
-        return {"ActorLoss": float(s[0]), "VLoss": float(s[1]), "EntLoss": float(s[2]), "PpoTotalLoss": float(s[3]),
-                "GradNorm": float(s[4]), "ClipCoef": float(s[5])}
+        return ops.stats_dict(self.grads[self.n_params:self.n_params + 6].cpu())
 
     # ---- diagnostics ------------------------------------------------------------------------
     def keep_activations(self, on=True):
@@ -317,7 +296,7 @@ class HotPath:
 
     def u8_table(self):
         out = torch.empty(256, dtype=torch.float32, device=self.device)
-        check(self.lib.ddrl_u8_table(_ptr(out), _stream()))
+        check(self.lib.ddrl_u8_table(_p(out), _st()))
         return out
 
     def profile(self, on=True, acting=True):
@@ -348,10 +327,10 @@ class Timer:
         check(self.lib.ddrl_timer_create(byref(self.h)))
 
     def start(self):
-        check(self.lib.ddrl_timer_start(self.h, _stream()))
+        check(self.lib.ddrl_timer_start(self.h, _st()))
 
     def stop(self):
-        check(self.lib.ddrl_timer_stop(self.h, _stream()))
+        check(self.lib.ddrl_timer_stop(self.h, _st()))
 
     def elapsed_ms(self):
         ms = c_float()

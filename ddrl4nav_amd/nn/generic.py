@@ -15,7 +15,7 @@ from ctypes import byref, c_int64, c_void_p
 import torch
 from torch import nn
 
-from ddrl4nav_amd import _lib
+from ddrl4nav_amd import _lib, ops
 from ddrl4nav_amd._lib import STATS_FLOATS, HeadsDesc, check
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.nn.base import Basenn, PreNet
@@ -672,7 +672,7 @@ class GenericPPO(Basenn):
             dist = HipNormal(self, dist_out, self.actor.log_std.data, action, logp, self._calls)
         else:
             from ddrl4nav_amd.nn.distribution import HipCategorical
-            dist = HipCategorical(_CatOps(self), dist_out, self._seed, self._calls, action, logp)
+            dist = HipCategorical(ops, dist_out, self._seed, self._calls, action, logp)
         return (dist, logp if act is not None else None), values
 
     def _eval_logp(self, value, version):
@@ -786,33 +786,9 @@ class GenericPPO(Basenn):
                                              self._step, _p(self._adam_ws), _st()))
             self._dirty = True
             self.update_time += 1
-            s = self.grads[self.n_params:self.n_params + 6].cpu().numpy()
-            yield ({"PpoTotalLoss": float(s[3]), "ActorLoss": float(s[0]), "VLoss": float(s[1]), "EntLoss": float(s[2]),
+            s = self.stats()
+            yield ({"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
                     "PpoBackUpTime": time.time() - t0}, self.update_time, True)
 
     def stats(self):
-        s = self.grads[self.n_params:self.n_params + 6].cpu().numpy()
-        return {"ActorLoss": float(s[0]), "VLoss": float(s[1]), "EntLoss": float(s[2]), "PpoTotalLoss": float(s[3]),
-                "GradNorm": float(s[4]), "ClipCoef": float(s[5])}
-
-
-class _CatOps:
-    """categorical_stats / categorical_sample provider for HipCategorical (same C entry points as HotPath)."""
-
-    def __init__(self, net):
-        self.lib = net.lib
-
-    def categorical_stats(self, probs):
-        n, A = probs.shape
-        p_hat, logits = torch.empty_like(probs), torch.empty_like(probs)
-        ent = torch.empty(n, dtype=torch.float32, device=probs.device)
-        check(self.lib.ddrl_categorical_stats(_p(probs), n, A, _p(p_hat), _p(logits), _p(ent), _st()))
-        return p_hat, logits, ent
-
-    def categorical_sample(self, probs, seed, stream_id):
-        n, A = probs.shape
-        action = torch.empty(n, dtype=torch.float32, device=probs.device)
-        logp = torch.empty(n, dtype=torch.float32, device=probs.device)
-        check(self.lib.ddrl_categorical_sample(_p(probs), n, A, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1),
-                                               _p(action), _p(logp), _st()))
-        return action, logp
+        return ops.stats_dict(self.grads[self.n_params:self.n_params + 6].cpu())

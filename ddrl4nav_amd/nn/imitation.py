@@ -25,6 +25,7 @@ import torch
 
 from ddrl4nav_amd import _lib, ops
 from ddrl4nav_amd._lib import STATS_FLOATS, check
+from ddrl4nav_amd.ops import _p, _st
 from ddrl4nav_amd.nn.atari_encoder import frames_u8
 
 FEAT = 512
@@ -107,8 +108,8 @@ class ImitationTrainer:
         if hp.params.data_ptr() % 16 or self.grads.data_ptr() % 16:
             raise ValueError("the parameter / gradient arenas must be 16-byte aligned")
         ctx = c_void_p()
-        check(self.lib.ddrl_ctx_create(byref(self._cfg), c_void_p(hp.params.data_ptr()), c_void_p(self.grads.data_ptr()), c_void_p(0),
-                                       c_void_p(0), c_void_p(self._workspace.data_ptr()), wb.value, byref(ctx)))
+        check(self.lib.ddrl_ctx_create(byref(self._cfg), _p(hp.params), _p(self.grads), _p(None), _p(None), _p(self._workspace), wb.value,
+                                       byref(ctx)))
         self.ctx = ctx
         h, dh = c_void_p(), c_void_p()
         check(self.lib.ddrl_encoder_buffers(ctx, byref(h), byref(dh)))
@@ -136,17 +137,16 @@ class ImitationTrainer:
         """One optimiser step on the n samples frames_all[idx[:n]] (everything on the device, nothing waits for the host);
         stats_row: a pinned [2] host row that receives (loss, correct) asynchronously."""
         lib, p, g = self.lib, self.hp.params, self.grads
-        st = c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _st()
         wo, bo = self.enc_floats, self.enc_floats + self.A * FEAT
         ops.gather_rows_u8(frames_all, idx, self.frames, labels_all, self.labels, n)
-        check(lib.ddrl_encoder_forward(self.ctx, c_void_p(self.frames.data_ptr()), n, st))
+        check(lib.ddrl_encoder_forward(self.ctx, _p(self.frames), n, st))
         ops.heads_bc_loss(p[wo:], p[bo:], self.A, self.h, FEAT, n, self.labels, n, self.dh, FEAT, g[wo:], g[bo:], g[self.prefix:],
                           self._bc_ws)
-        check(lib.ddrl_encoder_backward(self.ctx, c_void_p(self.frames.data_ptr()), n, st))
+        check(lib.ddrl_encoder_backward(self.ctx, _p(self.frames), n, st))
         self.step_count += 1
-        check(lib.ddrl_op_clip_adam(byref(self._opt_cfg), c_void_p(p.data_ptr()), c_void_p(g.data_ptr()), c_void_p(self.m.data_ptr()),
-                                    c_void_p(self.v.data_ptr()), self.prefix, self.prefix, 1, self.step_count,
-                                    c_void_p(self._adam_ws.data_ptr()), st))
+        check(lib.ddrl_op_clip_adam(byref(self._opt_cfg), _p(p), _p(g), _p(self.m), _p(self.v), self.prefix, self.prefix, 1, self.step_count,
+                                    _p(self._adam_ws), st))
         check(lib.ddrl_params_changed(self.ctx))     # this context's packed encoder weights follow every step
         if stats_row is not None:
             stats_row.copy_(g[self.prefix:self.prefix + 2], non_blocking=True)

@@ -25,6 +25,34 @@ def _f32(t):
     return t
 
 
+_U64 = 2 ** 64 - 1
+STATS_KEYS = ("ActorLoss", "VLoss", "EntLoss", "PpoTotalLoss", "GradNorm", "ClipCoef")
+
+
+def stats_dict(row):
+    """The statistics tail of a gradient arena (include/ddrl.h DDRL_STATS_FLOATS; a host tensor or array) by name."""
+    s = row.numpy() if hasattr(row, "numpy") else row
+    return {k: float(s[i]) for i, k in enumerate(STATS_KEYS)}
+
+
+def categorical_stats(probs):
+    """(probs / sum, log(clamp(.)), entropy) of softmax outputs [n, A], as torch.distributions.Categorical derives them."""
+    n, A = probs.shape
+    p_hat, logits = torch.empty_like(probs), torch.empty_like(probs)
+    ent = torch.empty(n, dtype=torch.float32, device=probs.device)
+    check(_lib.load().ddrl_categorical_stats(_p(probs), n, A, _p(p_hat), _p(logits), _p(ent), _st()))
+    return p_hat, logits, ent
+
+
+def categorical_sample(probs, seed, stream_id):
+    """Fresh draws (and their log-probs) from Categorical(probs) with the inverse-CDF contract of the acting kernel."""
+    n, A = probs.shape
+    action = torch.empty(n, dtype=torch.float32, device=probs.device)
+    logp = torch.empty(n, dtype=torch.float32, device=probs.device)
+    check(_lib.load().ddrl_categorical_sample(_p(probs), n, A, int(seed) & _U64, int(stream_id) & _U64, _p(action), _p(logp), _st()))
+    return action, logp
+
+
 def frame_stack_push(prev, newest, reset, out):
     """FrameStackWrapper.step / .reset on the device (include/ddrl.h, ddrl_frame_stack_push; csrc/fstack.hip): `out` [n,C,84,84] <- `prev`
     [n,C,84,84] shifted by one plane with `newest` [n,84,84] as the last plane; envs whose `reset` byte ([n] uint8, or None) is not zero

@@ -197,8 +197,14 @@ def judge(key, err_k, err_32, draws, where):
         assert err_k <= OP_TOL, (key, where, err_k, err_32)
 
 
+def _carve(low, high):
+    """Device copies of two host tensors inside ONE allocation, `low` at the lower address (separate allocations land in any order)."""
+    buf = torch.cat([low.reshape(-1), high.reshape(-1)]).cuda()
+    return buf[:low.numel()].view(low.shape), buf[low.numel():].view(high.shape)
+
+
 # ---- 1. the loss block ------------------------------------------------------------------------------------------------------------
-def run_heads_loss(c, null_dh_critic=False):
+def run_heads_loss(c, null_dh_critic=False, critic_below=False):
     _lib, lib = _load()
     L = H.head_layout(c.continuous, c.A)
     d = _desc(c, L)
@@ -211,6 +217,10 @@ def run_heads_loss(c, null_dh_critic=False):
     ha, hc = c.ha.cuda(), c.hc.cuda()
     dh_a = torch.full((c.n + 2, H.FEAT), SENT, **f)
     dh_c = None if null_dh_critic else torch.full((c.n + 2, H.FEAT), SENT, **f)
+    if critic_below:     # the critic's features and their gradient at LOWER addresses than the actor's: negative strides in the kernels
+        hc, ha = _carve(c.hc, c.ha)
+        dh_c, dh_a = _carve(dh_c.cpu(), dh_a.cpu())
+        assert hc.data_ptr() < ha.data_ptr() and dh_c.data_ptr() < dh_a.data_ptr()
     cfg = _cfg(c)
     acts, old, adv, ret = (t.contiguous().cuda() for t in (c.actions, c.old_logps, c.advs, c.rets))
     _lib.check(lib.ddrl_op_heads_loss(byref(d), byref(cfg), _p(params), _p(ha), _p(hc), c.n, _p(acts), _p(old), _p(adv), _p(ret),
@@ -305,13 +315,16 @@ def test_heads_loss_every_branch_vs_float64(spec):
 
 
 # ---- 2. acting --------------------------------------------------------------------------------------------------------------------
-def run_heads_act(c, act_in, seed=0, stream_id=0, outs=("dist", "action", "logp")):
+def run_heads_act(c, act_in, seed=0, stream_id=0, outs=("dist", "action", "logp"), critic_below=False):
     _lib, lib = _load()
     L = H.head_layout(c.continuous, c.A)
     d = _desc(c, L)
     f = dict(dtype=torch.float32, device="cuda")
     params = H.fill_arena(L, c.params, fill=0.5).cuda()
     ha, hc = c.ha.cuda(), c.hc.cuda()
+    if critic_below:
+        hc, ha = _carve(c.hc, c.ha)
+        assert hc.data_ptr() < ha.data_ptr()
     w = c.A
     o = {"dist": torch.full((c.n + 1, w), SENT, **f) if "dist" in outs else None,
          "action": torch.full((c.n + 1, w) if c.continuous else (c.n + 1,), SENT, **f) if "action" in outs else None,
@@ -340,8 +353,11 @@ def test_heads_act_evaluates_given_actions_vs_float64(spec):
     h_critic that points at a DIFFERENT finite buffer: the value is critic(h_actor) all the same (include/ddrl.h)."""
     cont, A, n, shared = spec
     c = H.make_case(cont, A, n, shared, 0, seed=2)
-    got = run_heads_act(c, c.actions)
-    fam, where = "gauss" if cont else "cat", str(spec)
+    check_heads_act(c, run_heads_act(c, c.actions), str(spec))
+
+
+def check_heads_act(c, got, where):
+    fam, shared, n = "gauss" if c.continuous else "cat", c.shared, c.n
     ref = {}
     for dt in (torch.float64, torch.float32):
         Pd = {k: v.to(dt) for k, v in c.params.items()}
@@ -379,6 +395,19 @@ def test_gauss_act_sampling_is_consistent_and_reproducible(D, n, shared):
     assert torch.equal(only_v["value"], a["value"])
     ev = run_heads_act(c, a["action"], outs=("logp",))
     assert torch.equal(ev["logp"], a["logp"]) and torch.equal(ev["value"], a["value"])   # evaluating the drawn action: the same number
+
+
+@gpu
+def test_split_heads_with_the_critic_buffers_below_the_actors():
+    """Split encoders, h_critic / dh_critic at LOWER addresses than h_actor / dh_actor (both carved from one tensor, so the order is
+    certain): the distance between the two is a stride like any other, negative included.  A = 6, n = 5: two waves' turns, the second
+    ragged.  Same float64 restatement and tolerances as the grids above."""
+    spec = (0, 6, 5, 0, 0, "default", 5)
+    c = _case(spec)
+    H.check_recipe(c)
+    check_heads_loss(c, run_heads_loss(c, critic_below=True), "critic-below " + _id(spec))
+    c = H.make_case(0, 6, 5, 0, 0, seed=2)
+    check_heads_act(c, run_heads_act(c, c.actions, critic_below=True), "critic-below act cat6-n5-split")
 
 
 @gpu
