@@ -136,6 +136,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_heads_loss": (c_int32, [POINTER(HeadsDesc), POINTER(Config), c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_heads_diag_ws_floats": (c_int32, [POINTER(HeadsDesc), c_int32, POINTER(c_int64)]),
+    "ddrl_op_heads_diag": (c_int32, [POINTER(HeadsDesc), POINTER(Config), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_ppo_diag": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "ddrl_op_clip_adam_ws_bytes": (c_int32, [POINTER(c_int64)]),
     "ddrl_op_clip_adam": (c_int32, [POINTER(Config), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
                                     c_int64, c_void_p, c_void_p]),

@@ -26,6 +26,7 @@ struct ddrl_ctx : public ddrl::Profiler {
   int64_t step;
   bool dirty;
   int last_n;
+  int iter_n = 0;  // batch of the ddrl_ppo_iter whose features the context still holds (0: another forward came since); ddrl_ppo_diag
   bool profile;
   bool profile_acting;  // ddrl_profile_enable(on = 1): also time the (small, latency-bound) ddrl_forward launches
   bool keep_acts = false;   // ddrl_debug_keep_activations: ddrl_forward also stores a1 / a2 (its fused kernel keeps them on chip)
@@ -238,6 +239,7 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
     launch_heads_act(ctx_heads_call(ctx, n, true), act_in, seed, stream_id, probs, value, action_out, logp_out, st);
   }
   ctx->last_n = n;
+  ctx->iter_n = 0;
   return launch_status();
 }
 
@@ -301,7 +303,25 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
   bucket_done(ec, BUCKET_HEADS, st);  // head-layer gradients and the three loss shares of the tail are final
   launch_encoder_backward(ec, ctx->grads, st, true);
   ctx->last_n = B;
+  ctx->iter_n = B;
   ctx->bucket_events_fresh = ctx->buckets;
+  return launch_status();
+}
+
+// the diagnostics head on what ddrl_ppo_iter left behind: its features, and -- its head partials being reduced -- the front of their
+// buffer for the workgroups' rows of doubles
+int32_t ddrl_ppo_diag(ddrl_ctx* ctx, const float* actions, const float* old_logps, const float* rets, int32_t B, double* sums8,
+                      void* stream) {
+  if (!ctx || !actions || !old_logps || !rets || !sums8 || ((uintptr_t)sums8 & 7) != 0) return DDRL_ERR_INVALID_ARG;
+  if (B < 1 || B != ctx->iter_n) return DDRL_ERR_INVALID_ARG;
+  static_assert((int64_t)DIAG_MAX_WG * DIAG_SLOTS * 2 <= (int64_t)HEAD_WG * ((2 + 1) * FEAT), "the diagnostics rows fit the smallest hpart");
+  hipStream_t st = (hipStream_t)stream;
+  const HeadsCall hc = ctx_heads_call(ctx, B, false);
+  const ParamLayout& L = *hc.L;
+  const DiagCall c{HeadLayout{L.A, L.NE == 1, L.actor_w, L.actor_b, 0, L.critic_w, L.critic_b, L.n_params}, false, hc.cfg->ppo_clip,
+                   hc.params, B, hc.h, L.NE == 1 ? 0 : hc.h_es, (double*)hc.hpart};
+  ProfRange ps(ctx->profile ? ctx : nullptr, "heads_diag", st);
+  launch_heads_diag(c, actions, old_logps, rets, sums8, 0, nullptr, nullptr, st);
   return launch_status();
 }
 
@@ -428,6 +448,7 @@ int32_t ddrl_encoder_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, vo
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);  // complete features (no split-K partials left for a head kernel to sum)
   ctx->last_n = n;
+  ctx->iter_n = 0;
   return launch_status();
 }
 

@@ -476,6 +476,26 @@ int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, con
   return launch_status();
 }
 
+int32_t ddrl_op_heads_diag_ws_floats(const ddrl_heads_desc* d, int32_t max_n, int64_t* floats) {
+  if (!heads_ok(d) || max_n < 1 || !floats) return DDRL_ERR_INVALID_ARG;
+  *floats = (int64_t)DIAG_MAX_WG * DIAG_SLOTS * 2;  // one row of doubles per workgroup, whatever the batch
+  return DDRL_OK;
+}
+
+int32_t ddrl_op_heads_diag(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                           const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* rets,
+                           double* sums8, int32_t accumulate, float* logp_out, float* value_out, float* ws, void* stream) {
+  if (!heads_ok(d) || !cfg || !params || !h_actor || !actions || !old_logps || !rets || !sums8 || !ws || n < 1)
+    return DDRL_ERR_INVALID_ARG;
+  if (!d->shared && !h_critic) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(h_actor) || (!d->shared && !aligned16(h_critic)) || !aligned16(ws) || ((uintptr_t)sums8 & 7) != 0)
+    return DDRL_ERR_INVALID_ARG;
+  const DiagCall c{head_layout(d), d->continuous != 0, cfg->ppo_clip, params, n, h_actor,
+                   d->shared ? 0 : (int64_t)(h_critic - h_actor), (double*)ws};
+  launch_heads_diag(c, actions, old_logps, rets, sums8, accumulate, logp_out, value_out, (hipStream_t)stream);
+  return launch_status();
+}
+
 int32_t ddrl_op_clip_adam(const ddrl_config* cfg, float* params, float* grads, float* m, float* v, int64_t n_params,
                           int64_t n_actor, int32_t shared, int64_t step, void* ws, void* stream) {
   if (!cfg || !params || !grads || !m || !v || !ws || n_params < 1 || n_actor < 0 || n_actor > n_params || step < 1)

@@ -15,7 +15,6 @@
 namespace ddrl {
 
 constexpr int MAXD = 8;
-constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;  // math.log(math.sqrt(2 * math.pi))
 
 
 struct GHeadRegs {

@@ -17,7 +17,6 @@ namespace ddrl {
 // gradient accumulators in registers; 8 < A <= 18 (the full Atari action set) reads the weights
 // from LDS and leaves the actor-head weight gradient to head_wgrad_kernel.
 constexpr int MAXA_SMALL = 8, MAXA_LARGE = 18;
-constexpr float CAT_EPS = 1.1920928955078125e-07f;  // torch.finfo(float32).eps
 
 
 template <int MAXA, bool WLDS>
@@ -70,39 +69,6 @@ __device__ __forceinline__ void load_head_weights(HeadRegs<MAXA, WLDS>& R, const
   R.bc = params[L.critic_b];
 }
 
-
-template <int MAXA>
-struct Dist {
-  float p[MAXA];    // softmax output
-  float q[MAXA];    // p / sum(p)                      (Categorical.probs)
-  float lc[MAXA];   // log(clamp(q, eps, 1-eps))       (Categorical.logits)
-  float ps;
-};
-
-template <int MAXA>
-__device__ __forceinline__ void softmax_categorical(const float* z, int A, Dist<MAXA>& d) {
-  float m = z[0];
-#pragma unroll
-  for (int j = 1; j < MAXA; ++j)
-    if (j < A) m = fmaxf(m, z[j]);
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) {
-    d.p[j] = (j < A) ? expf(z[j] - m) : 0.0f;
-    s += d.p[j];
-  }
-  d.ps = 0.0f;
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) {
-    d.p[j] = d.p[j] / s;
-    d.ps += d.p[j];
-  }
-#pragma unroll
-  for (int j = 0; j < MAXA; ++j) {
-    d.q[j] = d.p[j] / d.ps;
-    d.lc[j] = logf(fminf(fmaxf(d.q[j], CAT_EPS), 1.0f - CAT_EPS));
-  }
-}
 
 // --------------------------------------------------------------------------------------------
 // acting: probs / value / sample-or-evaluate

@@ -21,12 +21,52 @@ __device__ __forceinline__ float pick(const float (&a)[N], int idx) {
   return r;
 }
 
+// ---- the distributions' arithmetic that more than one head kernel evaluates ------------------------------------------------------------
+// Categorical (heads.hip acting + loss, diag.hip): softmax, then torch.distributions.Categorical(probs)'s own bookkeeping; entries
+// j >= A are masked.  Gaussian (gheads.hip, diag.hip): per dimension  -(a - mu)^2 / (2 var) - log(std) - LOG_SQRT_2PI.
+constexpr float CAT_EPS = 1.1920928955078125e-07f;  // torch.finfo(float32).eps
+constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;  // math.log(math.sqrt(2 * math.pi))
+
+template <int MAXA>
+struct Dist {
+  float p[MAXA];    // softmax output
+  float q[MAXA];    // p / sum(p)                      (Categorical.probs)
+  float lc[MAXA];   // log(clamp(q, eps, 1-eps))       (Categorical.logits)
+  float ps;
+};
+
+template <int MAXA>
+__device__ __forceinline__ void softmax_categorical(const float* z, int A, Dist<MAXA>& d) {
+  float m = z[0];
+#pragma unroll
+  for (int j = 1; j < MAXA; ++j)
+    if (j < A) m = fmaxf(m, z[j]);
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXA; ++j) {
+    d.p[j] = (j < A) ? expf(z[j] - m) : 0.0f;
+    s += d.p[j];
+  }
+  d.ps = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXA; ++j) {
+    d.p[j] = d.p[j] / s;
+    d.ps += d.p[j];
+  }
+#pragma unroll
+  for (int j = 0; j < MAXA; ++j) {
+    d.q[j] = d.p[j] / d.ps;
+    d.lc[j] = logf(fminf(fmaxf(d.q[j], CAT_EPS), 1.0f - CAT_EPS));
+  }
+}
+
 // ---- workgroup epilogue of the loss kernels: the waves add their sums into LDS one after the other (fixed order) ---------------------
 //   for (w = 0; w < WAVES; ++w) { if (wave == w) { ...turn_add / turn_add_row with first = (w == 0)... } __syncthreads(); }
 // turn_add: a scalar (by one lane); turn_add_row: the lane's 8 columns of a 512-wide row, at = row * 512 + lane * 8.  Where the buffer
 // aliases LDS that the sample loop still reads (head weights), a __syncthreads() comes first.  (The loop stays in the kernels: passed to
 // a helper as a lambda, the body moved the register allocation of heads_loss_kernel's prologue.)
 __device__ __forceinline__ void turn_add(bool first, float& slot, float x) { slot = first ? x : slot + x; }
+__device__ __forceinline__ void turn_add(bool first, double& slot, double x) { slot = first ? x : slot + x; }  // double partial rows (diag.hip)
 __device__ __forceinline__ void turn_add_row(bool first, float* buf, int at, const float (&g)[8]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) turn_add(first, buf[at + i], g[i]);

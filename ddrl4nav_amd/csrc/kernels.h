@@ -115,4 +115,20 @@ void launch_categorical_sample(const float* probs, int n, int A, uint64_t seed, 
 void launch_categorical_stats(const float* probs, int n, int A, float* p_hat, float* logits,
                               float* entropy, hipStream_t st);
 
+// diag.hip: the read-only diagnostics head of both families (include/ddrl.h ddrl_op_heads_diag).  Features as in HeadsCall: the
+// critic's lie h_es floats behind the actor's (any sign; 0 with a shared prenet).  part = DIAG_MAX_WG rows of DIAG_SLOTS doubles.
+constexpr int DIAG_SLOTS = 8, DIAG_MAX_WG = 1024;
+struct DiagCall {
+  HeadLayout L;
+  bool continuous;
+  float ppo_clip;
+  const float* params;
+  int n;
+  const float* h;
+  int64_t h_es;
+  double* part;
+};
+void launch_heads_diag(const DiagCall& c, const float* actions, const float* old_logps, const float* rets, double* sums8,
+                       int accumulate, float* logp_out, float* value_out, hipStream_t st);
+
 }  // namespace ddrl

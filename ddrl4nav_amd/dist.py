@@ -64,6 +64,21 @@ def allreduce_flat(flat, group=None):
     return flat
 
 
+def allgather_diag_sums(sums, group=None):
+    """The diagnostics sums of a PPO update (ops.diag_dict) over the ranks of `group`: every rank contributes its 8 doubles (a host
+    sequence), receives all rows and folds them in rank order (ops.combine_diag_sums), so all ranks hold bit-identical numbers -- and
+    take the same early-stopping decision.  One process: the row itself."""
+    from .ops import combine_diag_sums
+    row = torch.as_tensor([float(x) for x in sums], dtype=torch.float64)
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return combine_diag_sums([row])
+    if dist.get_backend(group) == "nccl":
+        row = row.cuda()
+    rows = [torch.empty_like(row) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(rows, row, group=group)
+    return combine_diag_sums([r.cpu() for r in rows])
+
+
 def broadcast_params(flat, src=0, group=None):
     """Make the replicas bit-identical at start-up (weights come from rank 0)."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:

@@ -164,6 +164,25 @@ class HotPath:
         check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames), _p(actions), _p(old_logps), _p(advs), _p(rets),
                                      B, int(b_global if b_global is not None else B), _st()))
 
+    def ppo_diag(self, actions, old_logps, rets, out=None):
+        """The eight diagnostics sums (ops.diag_dict) of THIS rank's batch on the features the last ppo_iter left behind, i.e. for the
+        policy its loss was evaluated with; call between ppo_iter and clip_adam_step.  Reads only.  Returns 8 float64 on the device
+        (`out`, or a buffer this object reuses); asynchronous."""
+        if out is None:
+            if getattr(self, "_diag_sums", None) is None:
+                self._diag_sums = torch.zeros(ops.DIAG_SLOTS, dtype=torch.float64, device=self.device)
+            out = self._diag_sums
+        assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.numel() == ops.DIAG_SLOTS
+        for t in (actions, old_logps, rets):
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+        check(self.lib.ddrl_ppo_diag(self.ctx, _p(actions), _p(old_logps), _p(rets), int(actions.numel()), _p(out), _st()))
+        return out
+
+    def diag_global(self, sums):
+        """Host: this rank's sums combined over the ranks of the process group (bit-identical everywhere)."""
+        from .dist import allgather_diag_sums
+        return allgather_diag_sums(sums.cpu().tolist() if hasattr(sums, "cpu") else sums, self.process_group)
+
     def enable_overlap(self):
         """Record the per-layer bucket events in every ppo_iter and reduce bucket by bucket on a second stream."""
         from ctypes import c_int32

@@ -243,9 +243,20 @@ class Discriminator(Basenn):
         return {"GradNorm": float(s[0]), "ClipCoef": float(s[1]), "lr": self.lr}
 
 
+def refuse_diag_options(config_nn):
+    """PPO_DIAGNOSTICS / TARGET_KL (nn/ppo.py) are not built for a generator that carries the extra GAIL critic."""
+    if bool(getattr(config_nn, "PPO_DIAGNOSTICS", False)) or getattr(config_nn, "TARGET_KL", None) is not None:
+        raise NotImplementedError("PPO_DIAGNOSTICS / TARGET_KL are not built for NETWORK_TYPE='gail': the diagnostics head evaluates one "
+                                  "critic, the generator's value loss here is the sum over two (ppo.py:95-107), so ExplainedVariance would "
+                                  "describe half of what VLoss reports; unset both")
+
+
 class GAIL(Basenn):
     def __init__(self, generator, discriminator: Discriminator, gail_critic):
         super().__init__(discriminator.config, discriminator.config_nn)
+        refuse_diag_options(discriminator.config_nn)
+        if getattr(generator, "diagnostics", False):
+            raise NotImplementedError("the generator was built with PPO_DIAGNOSTICS / TARGET_KL, which GAIL does not support")
         self.device = discriminator.device
         self.generator = generator
         self.discriminator = discriminator

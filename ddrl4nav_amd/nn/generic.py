@@ -484,6 +484,8 @@ class GenericPPO(Basenn):
     def __init__(self, actor, critic, prenet=None, rnd=None, config=None, config_nn=None, max_batch=None,
                  process_group=None):
         super().__init__(config, config_nn)
+        # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional; nn/ppo.py): the four diagnostics in every loss dict, KL early stopping
+        self.diagnostics, self.target_kl = ops.diag_options(config_nn)
         if rnd is not None:
             raise NotImplementedError("RND is disabled in the reference defaults (USE_RND=False) and out of scope")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -567,6 +569,8 @@ class GenericPPO(Basenn):
         f = dict(dtype=torch.float32, device=self.device)
         self._heads_ws = torch.empty(wf.value, **f)
         self._adam_ws = torch.empty(cb.value, dtype=torch.uint8, device=self.device)
+        self._diag_ws = torch.empty(ops.heads_diag_ws_floats(d, self.cap), **f)    # 64 KB: there whether the diagnostics are on or not
+        self._diag_sums = torch.zeros(ops.DIAG_SLOTS, dtype=torch.float64, device=self.device)
         # an encoder that owns its d(loss)/d(h) buffer (AtariPreNet: inside its kernel workspace) gets the gradient written there
         self._dh = [e._dh if getattr(e, "_dh", None) is not None else torch.empty((self.cap, FEAT), **f) for e in self._encs]
         c = self._cfg_nn
@@ -728,9 +732,13 @@ class GenericPPO(Basenn):
         return states / 255
 
     # ---- learn (ppo.py:77-146) -----------------------------------------------------------------------
-    def _iter_chunk(self, st, n, actions, old_logps, advs, rets, b_global, extra_rets=()):
-        """forward + loss + backward of one micro-batch; gradients land in self.gtmp (overwritten)."""
+    def _iter_chunk(self, st, n, actions, old_logps, advs, rets, b_global, extra_rets=(), diag_first=None):
+        """forward + loss + backward of one micro-batch; gradients land in self.gtmp (overwritten).  diag_first (None: off): the
+        diagnostics sums of the micro-batch are written to (True) or added to (False) self._diag_sums."""
         ha, hc = self._features(st, n)
+        if diag_first is not None:
+            ops.heads_diag(self._hd, self._cfg, self.params, ha, hc, n, actions, old_logps, rets, sums=self._diag_sums,
+                           accumulate=not diag_first, ws=self._diag_ws)
         dha = self._dh[0]
         dhc = dha if self.share_cnn_net else self._dh[1]
         check(self.lib.ddrl_op_heads_loss(byref(self._hd), byref(self._cfg), _p(self.params), _p(ha), _p(hc), n, _p(actions),
@@ -772,11 +780,18 @@ class GenericPPO(Basenn):
             for ci, lo in enumerate(range(0, B, self.cap)):
                 hi = min(B, lo + self.cap)
                 self._iter_chunk([s[lo:hi] for s in dstates], hi - lo, actions[lo:hi], old_logps[lo:hi], advs[lo:hi],
-                                 rets[lo:hi], b_global, [x[lo:hi] for x in extra_rets])
+                                 rets[lo:hi], b_global, [x[lo:hi] for x in extra_rets], diag_first=(ci == 0) if self.diagnostics else None)
                 if ci == 0:
                     self.grads.copy_(self.gtmp)
                 else:
                     check(self.lib.ddrl_op_accumulate(_p(self.grads), _p(self.gtmp), total, _st()))
+            d = None
+            if self.diagnostics:
+                # before anything is applied, combined over the ranks so that all of them decide alike (nn/ppo.py)
+                from ddrl4nav_amd.dist import allgather_diag_sums
+                d = ops.diag_dict(allgather_diag_sums(self._diag_sums.cpu().tolist(), self._process_group))
+                if ops.kl_stop(d, self.target_kl):
+                    return   # this iteration's step is not applied: no all-reduce, no Adam, no yield, update_time as it was
             if world > 1:
                 from ddrl4nav_amd.dist import allreduce_flat
                 allreduce_flat(self.grads, self._process_group)
@@ -787,8 +802,11 @@ class GenericPPO(Basenn):
             self._dirty = True
             self.update_time += 1
             s = self.stats()
-            yield ({"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                    "PpoBackUpTime": time.time() - t0}, self.update_time, True)
+            loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
+                        "PpoBackUpTime": time.time() - t0}
+            if d is not None:
+                loss_log.update(d)
+            yield loss_log, self.update_time, True
 
     def stats(self):
         return ops.stats_dict(self.grads[self.n_params:self.n_params + 6].cpu())

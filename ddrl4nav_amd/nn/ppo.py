@@ -10,6 +10,7 @@ import time
 
 import torch
 
+from ddrl4nav_amd import ops
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.engine import HotPath
 from ddrl4nav_amd.nn.base import Basenn
@@ -33,6 +34,9 @@ class PPO(Basenn):
     def __init__(self, actor, critic, prenet=None, rnd=None, config=None, config_nn=None, max_batch=None,
                  process_group=None):
         super().__init__(config, config_nn)
+        # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional, like DEFERRED_LOSS_READBACK): ApproxKL, ClipFraction, ExplainedVariance and
+        # RatioMax in every loss dict, and KL early stopping (ValueError when TARGET_KL meets the deferred read-back)
+        self.diagnostics, self.target_kl = ops.diag_options(config_nn)
         if hasattr(actor, "log_std"):
             raise NotImplementedError("the Atari fast path has a Categorical actor only (reference atari.yaml)")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -59,6 +63,7 @@ class PPO(Basenn):
         # True = all iterations enqueued, one sync, then the yields (config_nn.DEFERRED_LOSS_READBACK; bench.py sets it)
         self.deferred_stats = bool(getattr(config_nn, "DEFERRED_LOSS_READBACK", False))
         self._stats_rows = None
+        self._diag_rows = self._diag_dev = None
         n_actions = actor.action_output_dim
         in_ch = (prenet if prenet is not None else actor.pre).conv1.in_channels
         cap = int(max_batch if max_batch is not None else max(2 * config_nn.TRAINING_MIN_BATCH, 2048))
@@ -159,6 +164,9 @@ class PPO(Basenn):
         # data-parallel: every rank scales by 1 / (sum of the ranks' batch sizes) -- shards may be uneven
         from ddrl4nav_amd.dist import global_batch
         b_global = global_batch(B, self._process_group)
+        diag = self.diagnostics
+        if self.target_kl is not None and self.deferred_stats:   # net.deferred_stats switched on after construction
+            raise ValueError("TARGET_KL needs the host after every iteration: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
         if self.deferred_stats:
             # All TRAINING_ITER_TIME iterations are enqueued back to back; every iteration's 8-float statistics tail goes to its own
             # pinned host row by an asynchronous copy and ONE synchronisation precedes the yields (the reference syncs four times per
@@ -169,9 +177,16 @@ class PPO(Basenn):
             k = self.training_iter_time
             if self._stats_rows is None or self._stats_rows.shape[0] < k:
                 self._stats_rows = torch.empty((k, 8), dtype=torch.float32).pin_memory()
+            if diag and (self._diag_rows is None or self._diag_rows.shape[0] < k):
+                # the eight diagnostics sums of every iteration: a device row each (the next iteration must not overwrite what a copy
+                # still reads) and a pinned host row next to the statistics row
+                self._diag_rows = torch.empty((k, ops.DIAG_SLOTS), dtype=torch.float64).pin_memory()
+                self._diag_dev = torch.zeros((k, ops.DIAG_SLOTS), dtype=torch.float64, device=self.device)
             t0 = time.time()
             for i in range(k):
                 self._hp.ppo_iter(frames, actions, old_logps, advs, rets, b_global=b_global)
+                if diag:
+                    self._diag_rows[i].copy_(self._hp.ppo_diag(actions, old_logps, rets, out=self._diag_dev[i]), non_blocking=True)
                 self._hp.allreduce_grads()
                 self._hp.clip_adam_step()
                 self._hp.stats_async(self._stats_rows[i])
@@ -180,16 +195,29 @@ class PPO(Basenn):
             for i in range(k):
                 self.update_time += 1
                 s = self._hp.stats_dict(self._stats_rows[i])
-                yield ({"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                        "PpoBackUpTime": dt}, self.update_time, True)
+                loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
+                            "PpoBackUpTime": dt}
+                if diag:   # the ranks' rows are combined after the one synchronisation (a collective per iteration, on the host)
+                    loss_log.update(ops.diag_dict(self._hp.diag_global(self._diag_rows[i])))
+                yield loss_log, self.update_time, True
             return
         for _ in range(self.training_iter_time):
             t0 = time.time()
             self._hp.ppo_iter(frames, actions, old_logps, advs, rets, b_global=b_global)
+            d = None
+            if diag:
+                # read before anything is applied: the sums describe the policy this iteration's loss was evaluated with, combined
+                # over the ranks so that every rank takes the same decision (a rank that stopped alone would leave the others
+                # waiting in the gradient all-reduce)
+                d = ops.diag_dict(self._hp.diag_global(self._hp.ppo_diag(actions, old_logps, rets)))
+                if ops.kl_stop(d, self.target_kl):
+                    return   # this iteration's step is not applied: no all-reduce, no Adam, no yield, update_time as it was
             self._hp.allreduce_grads()
             self._hp.clip_adam_step()
             self.update_time += 1
             s = self._hp.stats()  # one device->host copy (the reference does four .item() syncs)
             loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"],
                         "EntLoss": s["EntLoss"], "PpoBackUpTime": time.time() - t0}
+            if d is not None:
+                loss_log.update(d)
             yield loss_log, self.update_time, True

@@ -4,6 +4,7 @@ frame-stack push (ddrl_frame_stack_push).  torch supplies memory
 and streams only; the arithmetic runs in csrc/gconv.hip and csrc/glinear.hip.  Used by
 ddrl4nav_amd.nn.generic to compose the reference's non-Atari encoders
 (USTC_lab/nn/nav_encoder.py, mlp_encoder.py)."""
+import math
 from ctypes import byref, c_int32, c_int64, c_void_p
 
 import torch
@@ -33,6 +34,79 @@ def stats_dict(row):
     """The statistics tail of a gradient arena (include/ddrl.h DDRL_STATS_FLOATS; a host tensor or array) by name."""
     s = row.numpy() if hasattr(row, "numpy") else row
     return {k: float(s[i]) for i, k in enumerate(STATS_KEYS)}
+
+
+DIAG_KEYS = ("ApproxKL", "ClipFraction", "ExplainedVariance", "RatioMax")
+DIAG_SLOTS = 8   # include/ddrl.h ddrl_op_heads_diag: n, sum k3, clipped, sum ret, sum ret^2, sum e, sum e^2, max ratio
+
+
+def diag_dict(sums):
+    """The diagnostics of a PPO update from the eight sums of ddrl_op_heads_diag / ddrl_ppo_diag (any sequence of 8 numbers on the
+    host; plain Python, no GPU): ApproxKL = mean(expm1(x) - x), x = logp - old_logp; ClipFraction = share of samples whose ratio is
+    outside 1 +- ppo_clip; ExplainedVariance = 1 - Var(ret - v) / Var(ret), population variances, nan when the returns are constant;
+    RatioMax = the largest ratio."""
+    s = [float(x) for x in (sums.tolist() if hasattr(sums, "tolist") else sums)]
+    n = s[0]
+    if n <= 0:
+        return {k: math.nan for k in DIAG_KEYS}
+    var_ret = s[4] / n - (s[3] / n) ** 2
+    var_e = s[6] / n - (s[5] / n) ** 2
+    ev = 1.0 - var_e / var_ret if var_ret != 0.0 else math.nan
+    return {"ApproxKL": s[1] / n, "ClipFraction": s[2] / n, "ExplainedVariance": ev, "RatioMax": s[7]}
+
+
+def combine_diag_sums(rows):
+    """One global row from the ranks' (or micro-batches') rows, combined in the order given: slots 0-6 summed, slot 7 the largest.
+    Every rank that folds the same rows in the same order ends with the same bits."""
+    out = [0.0] * DIAG_SLOTS
+    for r in rows:
+        r = [float(x) for x in (r.tolist() if hasattr(r, "tolist") else r)]
+        for k in range(DIAG_SLOTS - 1):
+            out[k] += r[k]
+        out[7] = r[7] if (r[7] > out[7] or r[7] != r[7]) else out[7]
+    return out
+
+
+def diag_options(config_nn):
+    """(diagnostics on, target KL or None) from config_nn.PPO_DIAGNOSTICS / TARGET_KL (both optional, read like
+    DEFERRED_LOSS_READBACK).  TARGET_KL implies the diagnostics and needs the host in the loop after every iteration."""
+    target = getattr(config_nn, "TARGET_KL", None)
+    if target is not None:
+        target = float(target)
+        if not target > 0.0:
+            raise ValueError("TARGET_KL must be a positive number or None, got %r" % (target,))
+        if bool(getattr(config_nn, "DEFERRED_LOSS_READBACK", False)):
+            raise ValueError("TARGET_KL stops an update from the host after every iteration; DEFERRED_LOSS_READBACK enqueues all "
+                             "iterations before the first read-back: set one of the two")
+    return bool(getattr(config_nn, "PPO_DIAGNOSTICS", False)) or target is not None, target
+
+
+def kl_stop(diag, target_kl):
+    """The early-stopping rule: the iteration whose loss saw ApproxKL > 1.5 x TARGET_KL is not applied."""
+    return target_kl is not None and diag["ApproxKL"] > 1.5 * target_kl
+
+
+def heads_diag_ws_floats(desc, max_n):
+    f = c_int64()
+    check(_lib.load().ddrl_op_heads_diag_ws_floats(byref(desc), int(max_n), byref(f)))
+    return f.value
+
+
+def heads_diag(desc, cfg, params, h_actor, h_critic, n, actions, old_logps, rets, sums=None, accumulate=False, logp_out=None,
+               value_out=None, ws=None):
+    """The eight sums behind diag_dict for n samples of finished 512-wide features (include/ddrl.h ddrl_op_heads_diag; csrc/diag.hip),
+    Categorical or Gaussian by `desc`; reads only.  sums: 8 float64 on the device (accumulate: added to, slot 7 raised);
+    logp_out / value_out: optional [n] fp32.  Asynchronous on the current stream; returns sums."""
+    if sums is None:
+        assert not accumulate, "accumulate needs the sums of the earlier calls"
+        sums = torch.empty(DIAG_SLOTS, dtype=torch.float64, device=params.device)
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == DIAG_SLOTS
+    if ws is None:
+        ws = torch.empty(heads_diag_ws_floats(desc, n), dtype=torch.float32, device=params.device)
+    check(_lib.load().ddrl_op_heads_diag(byref(desc), byref(cfg), _p(_f32(params)), _p(h_actor), _p(h_critic), int(n), _p(_f32(actions)),
+                                         _p(_f32(old_logps)), _p(_f32(rets)), _p(sums), 1 if accumulate else 0, _p(logp_out),
+                                         _p(value_out), _p(ws), _st()))
+    return sums
 
 
 def categorical_stats(probs):

@@ -169,6 +169,13 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
                       const float* old_logps, const float* advs, const float* rets, int32_t B,
                       int64_t B_global, void* stream);
 
+/* The sums of ddrl_op_heads_diag (below; sums8 = 8 doubles of device memory, overwritten) on the features the last ddrl_ppo_iter left
+ * in the context, i.e. for the policy that iteration's loss was evaluated with.  Run between ddrl_ppo_iter and ddrl_clip_adam_step;
+ * reads only, so gradients and statistics are untouched.  DDRL_ERR_INVALID_ARG when B is not that call's B (or no ddrl_ppo_iter
+ * came last). */
+int32_t ddrl_ppo_diag(ddrl_ctx* ctx, const float* actions, const float* old_logps, const float* rets, int32_t B, double* sums8,
+                      void* stream);
+
 /* clip_grad_norm_(all params, clip_grad_norm) + actor Adam + critic Adam (ppo.py:125-129).
  * Run after the (optional) all-reduce of the grad arena.  grads[n_params + 4] <- global grad
  * norm, grads[n_params + 5] <- clip coefficient, grads[n_params + 3] <- total loss. */
@@ -446,6 +453,22 @@ int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, con
                            const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
                            const float* rets, int64_t B_global, float* dh_actor, float* dh_critic, float* grads, float* ws,
                            void* stream);
+/* Diagnostics of a PPO update (the reference has none; added after round 6, additive: ABI 3): how far the policy that the loss is
+ * evaluated with has moved from the one that collected the batch, how many samples sit on the flat part of the clipped surrogate, and
+ * what the critic explains of the returns.  Read-only on the features / parameters the loss entry points read; per sample
+ *   x = logp - old_logp (fp32; logp as ddrl_op_heads_loss differentiates it),  r = exp(x) (fp32),  e = ret - v (double)
+ * and sums8[0..8) (DEVICE memory, doubles) =
+ *   n,  sum(expm1(x) - x) (the "k3" KL estimator, every term in double and >= 0),  #{r outside [1 - ppo_clip, 1 + ppo_clip]} (the
+ *   bounds as fp32, the test ppo_surrogate applies),  sum(ret),  sum(ret^2),  sum(e),  sum(e^2)  (terms and partial sums in double,
+ *   fixed order),  max r.
+ * accumulate != 0: added to what sums8 holds (slot 7: the larger), so that micro-batches build one global result.  logp_out /
+ * value_out ([n], may be NULL) receive the per-sample log-prob and value.  h_critic is not read when d->shared.  ws =
+ * ddrl_op_heads_diag_ws_floats floats (any max_n), 16-byte aligned like h_actor / h_critic; sums8 8-byte aligned.  The argument checks
+ * run before anything touches HIP. */
+int32_t ddrl_op_heads_diag_ws_floats(const ddrl_heads_desc* d, int32_t max_n, int64_t* floats);
+int32_t ddrl_op_heads_diag(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                           const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* rets,
+                           double* sums8, int32_t accumulate, float* logp_out, float* value_out, float* ws, void* stream);
 /* clip_grad_norm_ + Adam (two lr groups split at n_actor, or one when shared) on flat arenas;
  * `step` is the 1-based Adam step count; ws = ddrl_op_clip_adam_ws_bytes bytes. */
 int32_t ddrl_op_clip_adam_ws_bytes(int64_t* bytes);
