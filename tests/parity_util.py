@@ -298,6 +298,18 @@ class Margins:
         except OSError:
             pass
 
+    def record_vs_fp32_oracle(self, test, ratios):
+        """Log (never assert) {tensor: kernel error / the fp32 oracle's error, both against the same float64 gradient} under
+        <tensor>__vs_fp32_oracle."""
+        slot = self.measured.setdefault(test, {})
+        for name, v in ratios.items():
+            k = name + "__vs_fp32_oracle"
+            slot[k] = max(slot.get(k, 0.0), float(v))
+        try:
+            self._flush()
+        except OSError:
+            pass
+
     def _flush(self):
         os.makedirs(os.path.dirname(_MEASURED_OUT), exist_ok=True)
         old = {}
@@ -313,6 +325,64 @@ class Margins:
         json.dump(old, open(_MEASURED_OUT, "w"), indent=1, sort_keys=True)
 
 MARGINS = Margins()
+
+
+# ---- one PPO gradient of the Atari oracle in float64, under another implementation's leaky-ReLU decisions -----------------------------
+def oracle_threads():
+    return min(8, max(1, os.cpu_count() or 1))
+
+
+def ppo_backward(net, x, actions, old_logps, advs, rets, smooth_l1=False):
+    """The loss block and the backward of one iteration as oracle.learn runs them (total.backward() for the shared net, actor_loss /
+    v_loss.backward() otherwise), gradients left in net's parameters.  Returns [actor_loss, v_loss, entropy] as floats."""
+    net.zero_grad()
+    total, al, vl, ent = O.ppo_losses(net, x, actions, old_logps, advs, rets, smooth_l1)
+    if isinstance(net, O.OracleSharedPPO):
+        total.backward()
+    else:
+        al.backward()
+        vl.backward()
+    return [al.item(), vl.item(), ent.item()]
+
+
+class Oracle64:
+    """What oracle64_with_kernel_decisions returns: .net (float64, gradients in place), .encs (its encoders, .tap filled), .losses
+    ([actor_loss, v_loss, entropy]), .net32 (the fp32 oracle's gradients under the same decisions, or None)."""
+
+    def __init__(self, net, encs, losses, net32):
+        self.net, self.encs, self.losses, self.net32 = net, encs, losses, net32
+
+
+def oracle64_with_kernel_decisions(hp, net_cls, weights, frames, actions, old_logps, advs, rets, smooth_l1=False, with_fp32=False,
+                                   **net_args):
+    """float64 oracle backward under the kernel's leaky-ReLU decisions.  `net_cls(**net_args)` is O.OraclePPO or O.OracleSharedPPO,
+    `weights` its recipe dict; call hp.ppo_iter(...) on the same batch first.  test_gpu_parity._adopt_kernel_decisions asserts that at
+    most 8 decisions per layer differ from the fp32 oracle's, all with |z| < 2e-5.  with_fp32: the fp32 oracle runs its backward under
+    the same decisions too (the yardstick's own error against float64)."""
+    from test_gpu_parity import _adopt_kernel_decisions, _release_decisions
+    n = frames.shape[0]
+    x = O.frames_to_f32(frames)
+    t = lambda a: torch.from_numpy(np.asarray(a))
+    threads = torch.get_num_threads()
+    torch.set_num_threads(oracle_threads())
+    try:
+        net32 = net_cls(**net_args)
+        net32.load_weights(weights)
+        _adopt_kernel_decisions(hp, net32, n, x)
+        net = net_cls(**net_args)
+        net.load_weights(weights)
+        net.double()
+        encs32 = [m for m in net32.modules() if isinstance(m, O.Encoder)]
+        encs = [m for m in net.modules() if isinstance(m, O.Encoder)]
+        for a, b in zip(encs, encs32):
+            a.forced, a.tap = b.forced, {}
+        losses = ppo_backward(net, x.double(), t(actions).double(), t(old_logps).double(), t(advs).double(), t(rets).double(), smooth_l1)
+        if with_fp32:
+            ppo_backward(net32, x, t(actions), t(old_logps), t(advs), t(rets), smooth_l1)
+        _release_decisions(net32)
+    finally:
+        torch.set_num_threads(threads)
+    return Oracle64(net, encs, losses, net32 if with_fp32 else None)
 
 
 def loss_envelope(ref, *others):

@@ -8,6 +8,8 @@ in tests/parity_util.py (PARAM_LIMIT 1.5, LOSS_LIMIT 2.0, VS_TORCH_LIMIT 1.25, A
 copies what was measured, with the limit of its kind beside it, so that the headroom of every bound is on record.
 
 usage: python tools/update_margins.py [--source gpurun_out/margins_measured.json] [--note "r04, MI355X"]
+
+--only PREFIX: the source holds a run of some test files only; replace the records whose test name starts with PREFIX and keep the rest.
 """
 import argparse
 import json
@@ -23,11 +25,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--source", default=os.path.join(ROOT, "gpurun_out", "margins_measured.json"))
     ap.add_argument("--note", default="")
+    ap.add_argument("--only", default=None, help="replace the records of tests whose name starts with this; keep every other record")
     args = ap.parse_args()
     import parity_util as P
     measured = json.load(open(args.source))
     out = {"_doc": "RECORD of measured ratios (deviation of the HIP path / the reference's own deviation, tests/parity_util.py); "
                    "the limits are fixed in tests/parity_util.py and are NOT read from this file"}
+    path = os.path.join(ROOT, "tests", "golden", "margins.json")
+    if args.only is not None:
+        out.update({t: d for t, d in json.load(open(path)).items() if t != "_doc" and not t.startswith(args.only)})
+        measured = {t: d for t, d in measured.items() if t.startswith(args.only)}
     over = []
     for test, d in sorted(measured.items()):
         slot = out.setdefault(test, {})
@@ -36,11 +43,14 @@ def main():
                 slot[key] = {"measured": round(float(v), 4), "limit": None,
                              "note": (args.note + "; " if args.note else "") + "record only: ratio against the reference's oneDNN runs alone"}
                 continue
+            if key.endswith("__vs_fp32_oracle"):   # recorded, never asserted: the kernel's gradient error over the fp32 oracle's own
+                slot[key] = {"measured": round(float(v), 4), "limit": None,
+                             "note": (args.note + "; " if args.note else "") + "record only: max error against float64 / the fp32 oracle's"}
+                continue
             limit = P.MARGINS.limit(test, key)
             slot[key] = {"measured": round(float(v), 4), "limit": limit, "note": args.note}
             if v > limit:
                 over.append((test, key, v, limit))
-    path = os.path.join(ROOT, "tests", "golden", "margins.json")
     json.dump(out, open(path, "w"), indent=1, sort_keys=True)
     print("wrote", path)
     for test, key, v, limit in over:
