@@ -87,7 +87,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, w = wave_u(), l31 = lane & 31, hi = lane >> 5, l15 = lane & 15, q4 = lane >> 4;
   const int b = blockIdx.x, e = blockIdx.y, C = A.C, ROWS = 32 * A.NE;
-  const float r255 = PIXEL_UNIT / (255.0f * plane_scale(A.amax[amax_idx(AMAX_W1, e)]));
+  const float r255 = 1.0f / (255.0f * plane_scale(A.amax[amax_idx(AMAX_W1, e)]));
   const float sa1 = plane_scale(A.amax[amax_idx(AMAX_A1, e)]);
   const float inv2 = 1.0f / (sa1 * plane_scale(A.amax[amax_idx(AMAX_W2, e)]));
   const float sw3 = plane_scale(A.amax[amax_idx(AMAX_W3, e)]);
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         char* d = lds + K::A1_OFF + l31 * K::A1_CH + (P / 20) * K::A1_ROW + (P % 20) * 2;
 #pragma unroll
         for (int p = 0; p < NPL; ++p) *(lds_pair*)(d + p * K::A1_PLANE) = lds_pair{pa[p], pb[p]};
-        if (KEEP) *(f4*)(A.a1 + e * A.a1_es + (int64_t)b * 12800 + l31 * 400 + P) = y;
+        if (KEEP) *(f4*)(A.a1 + e * A.a1_es + (int64_t)b * A1_N + l31 * C1_P + P) = y;
       }
     }
   }
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           y2[j][r] = leaky_f(__builtin_fmaf(sum, inv2, bias[32 + oc]));
           if (c < 81) {
             big = fmaxf(big, fabsf(y2[j][r]));
-            if (KEEP) A.a2[e * A.a2_es + (int64_t)b * 5184 + oc * 81 + c] = y2[j][r];
+            if (KEEP) A.a2[e * A.a2_es + (int64_t)b * A2_N + oc * C2_P + c] = y2[j][r];
           }
         }
       }
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           const int oc = 16 * mt + 4 * q4 + r;
           const float y = leaky_f(__builtin_fmaf(sum, inv3, bias[96 + oc]));
           if (c < 49) {
-            A.a3[e * A.a3_es + (int64_t)b * FLAT + oc * 49 + c] = y;
+            A.a3[e * A.a3_es + (int64_t)b * A3_N + oc * C3_P + c] = y;
             big = fmaxf(big, fabsf(y));
           }
         }
@@ -387,14 +387,13 @@ void launch_act_convs(const EncCall& c, hipStream_t st) {
   using K = ActG;
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
-  const int64_t MB = c.max_batch;
   lds_limit_once<act_convs_kernel<false>>((int)K::LDS_BYTES);
   lds_limit_once<act_convs_kernel<true>>((int)K::LDS_BYTES);
   ActArgs a{c.frames, w.wp1b, w.wp2b, w.wp3b, w.amax, c.params,
             {L.enc_base[0] + L.enc.c1b, L.enc_base[L.NE - 1] + L.enc.c1b},
             {L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b},
             {L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b},
-            w.a1, w.a2, w.a3, MB * 12800, MB * 5184, MB * FLAT, w.actmax, ACT_FUSED_MAX, c.n, L.C, L.NE};
+            w.a1, w.a2, w.a3, w.es(A1_N), w.es(A2_N), w.es(A3_N), w.actmax, ACT_FUSED_MAX, c.n, L.C, L.NE};
   ProfRange pr(c.prof, "ActConvs", st);
   if (c.keep_acts)
     hipLaunchKernelGGL(act_convs_kernel<true>, dim3((unsigned)c.n, (unsigned)L.NE), dim3(K::THREADS), K::LDS_BYTES, st, a);

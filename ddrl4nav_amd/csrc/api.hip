@@ -106,9 +106,7 @@ static int32_t validate(const ddrl_config* c) {
   if (c->n_actions < 2 || c->n_actions > 18) return DDRL_ERR_UNSUPPORTED;  // heads kernels: A <= 18 (full Atari set)
   if (c->in_channels < 1 || c->in_channels > 4) return DDRL_ERR_UNSUPPORTED;  // stacked frames: conv1's kernels give each of their four waves one channel
   if (c->share_cnn_net != 0 && c->share_cnn_net != 1) return DDRL_ERR_INVALID_ARG;
-  // 32-bit element indexing inside one encoder's activation tensor
-  // the kernels address a1 / da1 with 32-bit BYTE offsets from wave-uniform bases (max_batch <= 83,886)
-  if ((int64_t)c->max_batch * 32 * 400 * 4 >= (int64_t)1 << 32) return DDRL_ERR_UNSUPPORTED;
+  if (c->max_batch > MAX_BATCH_LIMIT) return DDRL_ERR_UNSUPPORTED;
   return DDRL_OK;
 }
 
@@ -195,10 +193,6 @@ int32_t ddrl_set_step(ddrl_ctx* ctx, int64_t step) {
   return DDRL_OK;
 }
 
-// the activation slots of Workspace::amax start every forward at zero: conv_fwd1_planes_kernel, the first launch of every forward,
-// zeroes them itself (the conv epilogues then raise them); the gradient slots are reset by launch_encoder_backward
-static void amax_begin(ddrl_ctx*, hipStream_t) {}
-
 static void ensure_packed(ddrl_ctx* ctx, hipStream_t st) {
   if (!ctx->dirty) return;
   ProfRange ps(ctx->profile ? ctx : nullptr, "pack_weights", st);
@@ -211,13 +205,16 @@ static void ensure_packed(ddrl_ctx* ctx, hipStream_t st) {
 // as split-K partial sums for heads_act to finish (fc_forward_splits).
 static HeadsCall ctx_heads_call(const ddrl_ctx* ctx, int n, bool acting) {
   const Workspace& w = ctx->ws;
-  const int64_t es = (int64_t)ctx->cfg.max_batch * FEAT;
-  HeadsCall c{&ctx->L, &ctx->cfg, ctx->params, n, w.h, es, w.dh, es};
+  HeadsCall c{&ctx->L, &ctx->cfg, ctx->params, n, w.h, w.es(H_N), w.dh, w.es(H_N)};
   const int nsplit = acting ? fc_forward_splits(n) : 1;
   if (nsplit > 1) c.fc_part = w.wpart, c.fc_nsplit = nsplit;
   c.dlogits = w.dlogits, c.dvalue = w.dvalue, c.hpart = w.hpart;
-  c.gsc = w.gsc, c.gsc_es = ctx->cfg.max_batch, c.amax = w.amax;
+  c.gsc = w.gsc, c.gsc_es = w.es(1), c.amax = w.amax;
   return c;
+}
+// The encoder launch of a context on n samples' frames
+static EncCall ctx_enc_call(ddrl_ctx* ctx, const uint8_t* frames, int n, Profiler* prof) {
+  return EncCall{prof, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n};
 }
 
 int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const float* act_in, uint64_t seed,
@@ -226,11 +223,10 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
   if (n < 1 || n > ctx->cfg.max_batch) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   ensure_packed(ctx, st);
-  amax_begin(ctx, st);
   // HIP events around launches of tens of microseconds cost about as much as the launches (an event
   // record drains the queue): the acting path is only timed when asked for explicitly (on = 1)
   Profiler* prof = ctx->profile && ctx->profile_acting ? ctx : nullptr;
-  EncCall ec{prof, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n, ctx->cfg.max_batch};
+  EncCall ec = ctx_enc_call(ctx, frames, n, prof);
   ec.keep_acts = ctx->keep_acts;
   ctx->acts_stored = ctx->keep_acts || n > ACT_FUSED_MAX;
   launch_encoder_forward(ec, true, st);
@@ -263,7 +259,7 @@ int32_t ddrl_last_features(ddrl_ctx* ctx, int32_t n, float* h_actor, float* h_cr
   const size_t bytes = (size_t)n * FEAT * sizeof(float);
   if (h_actor) HIP_TRY(hipMemcpyAsync(h_actor, ctx->ws.h, bytes, hipMemcpyDeviceToDevice, st));
   if (h_critic)
-    HIP_TRY(hipMemcpyAsync(h_critic, ctx->ws.h + (ctx->L.NE == 2 ? (int64_t)ctx->cfg.max_batch * FEAT : 0), bytes,
+    HIP_TRY(hipMemcpyAsync(h_critic, ctx->ws.h + (ctx->L.NE == 2 ? ctx->ws.es(H_N) : 0), bytes,
                            hipMemcpyDeviceToDevice, st));
   return DDRL_OK;
 }
@@ -290,8 +286,7 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
   if (B < 1 || B > ctx->cfg.max_batch || B_global < B) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   ensure_packed(ctx, st);
-  amax_begin(ctx, st);
-  EncCall ec{ctx->profile ? ctx : nullptr, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, B, ctx->cfg.max_batch};
+  EncCall ec = ctx_enc_call(ctx, frames, B, ctx->profile ? ctx : nullptr);
   if (ctx->buckets) ec.bucket_ev = ctx->bucket_ev;
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);
@@ -336,7 +331,6 @@ int32_t ddrl_grad_allreduce(ddrl_ctx* ctx, ddrl_comm* comm, void* stream) {
 static int bucket_ranges(const ddrl_ctx* ctx, int b, int64_t (&off)[2], int64_t (&cnt)[2]) {
   const ParamLayout& L = ctx->L;
   const EncLayout& E = L.enc;
-  const int64_t C = ctx->cfg.in_channels;
   if (b == BUCKET_HEADS) {
     off[0] = L.actor_w;
     cnt[0] = (L.critic_b + 1) - L.actor_w;
@@ -346,10 +340,10 @@ static int bucket_ranges(const ddrl_ctx* ctx, int b, int64_t (&off)[2], int64_t 
   }
   int64_t o, n;
   switch (b) {
-    case BUCKET_CONV1: o = E.c1w; n = (int64_t)C1_OC * C * 64 + C1_OC; break;
-    case BUCKET_CONV2: o = E.c2w; n = (int64_t)C2_OC * C2_K + C2_OC; break;
-    case BUCKET_CONV3: o = E.c3w; n = (int64_t)C3_OC * C3_K + C3_OC; break;
-    case BUCKET_FC: o = E.lw; n = (int64_t)FEAT * FLAT + FEAT; break;
+    case BUCKET_CONV1: o = E.c1w; n = slab1_floats(L.C); break;
+    case BUCKET_CONV2: o = E.c2w; n = SLAB2; break;
+    case BUCKET_CONV3: o = E.c3w; n = SLAB3; break;
+    case BUCKET_FC: o = E.lw; n = SLAB_FC; break;
     default: return 0;
   }
   for (int e = 0; e < L.NE; ++e) {
@@ -443,8 +437,7 @@ int32_t ddrl_encoder_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, vo
   if (!ctx || !frames || n < 1 || n > ctx->cfg.max_batch || ctx->L.NE != 1) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   ensure_packed(ctx, st);
-  amax_begin(ctx, st);
-  EncCall ec{ctx->profile ? ctx : nullptr, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n, ctx->cfg.max_batch};
+  const EncCall ec = ctx_enc_call(ctx, frames, n, ctx->profile ? ctx : nullptr);
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);  // complete features (no split-K partials left for a head kernel to sum)
   ctx->last_n = n;
@@ -455,7 +448,7 @@ int32_t ddrl_encoder_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, vo
 int32_t ddrl_encoder_backward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, void* stream) {
   if (!ctx || !frames || n < 1 || n > ctx->cfg.max_batch || ctx->L.NE != 1) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  EncCall ec{ctx->profile ? ctx : nullptr, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n, ctx->cfg.max_batch};
+  const EncCall ec = ctx_enc_call(ctx, frames, n, ctx->profile ? ctx : nullptr);
   launch_encoder_backward(ec, ctx->grads, st);
   return launch_status();
 }
@@ -489,33 +482,17 @@ int32_t ddrl_u8_table(float* out256, void* stream) {
 // 8 dlogits, 9 dvalue, 10 / 11 / 12 the sign masks m1 / m2 / m3, 13 the per-sample scales of 4..7.  Returns the device pointer and the encoder stride in floats (words).
 int32_t ddrl_debug_buffer(ddrl_ctx* ctx, int32_t which, float** ptr, int64_t* enc_stride) {
   if (!ctx || !ptr || !enc_stride) return DDRL_ERR_INVALID_ARG;
-  const int64_t MB = ctx->cfg.max_batch;
   const Workspace& w = ctx->ws;
-  switch (which) {
-    case 0:
-      if (!ctx->acts_stored) return DDRL_ERR_UNSUPPORTED;
-      *ptr = w.a1; *enc_stride = MB * 32 * 400; break;
-    case 1:
-      if (!ctx->acts_stored) return DDRL_ERR_UNSUPPORTED;
-      *ptr = w.a2; *enc_stride = MB * 64 * 81; break;
-    case 2: *ptr = w.a3; *enc_stride = MB * FLAT; break;
-    case 3: *ptr = w.h; *enc_stride = MB * FEAT; break;
-    case 4: *ptr = w.dz1; *enc_stride = MB * 32 * 400; break;
-    case 5: *ptr = w.dz2; *enc_stride = MB * 64 * 81; break;
-    case 6: *ptr = w.dz3; *enc_stride = MB * FLAT; break;
-    case 7: *ptr = w.dh; *enc_stride = MB * FEAT; break;
-    case 8: *ptr = w.dlogits; *enc_stride = 0; break;
-    case 9: *ptr = w.dvalue; *enc_stride = 0; break;
-    // sign masks (32-bit words, returned through the float pointer; layouts in common.h Workspace::m1 / m2 / m3)
-    case 10: *ptr = (float*)w.m1; *enc_stride = m1_words(MB); break;
-    case 11: *ptr = (float*)w.m2; *enc_stride = MB * 81 * 2; break;
-    case 12: *ptr = (float*)w.m3; *enc_stride = MB * 49 * 2; break;
-    // per-sample scale g_s of the normalised backward (common.h Workspace::gsc): buffers 4..7 hold g_s^-1 x the true gradients
-    case 13: *ptr = w.gsc; *enc_stride = MB; break;
-    // running maxima / bounds behind the plane scales, amax[slot][encoder] (common.h AMAX_*): enc_stride = 1, slot stride = 2
-    case 14: *ptr = w.amax; *enc_stride = 1; break;
-    default: return DDRL_ERR_INVALID_ARG;
-  }
+  // per-sample elements by `which`; the sign masks are 32-bit words returned through the float pointer (layouts in common.h
+  // Workspace::m1 / m2 / m3); dlogits / dvalue have no encoder part; 13: buffers 4..7 hold g_s^-1 x the true gradients
+  // (Workspace::gsc); 14: amax[slot][encoder] (common.h AMAX_*), enc_stride = 1, slot stride = 2
+  const struct { const void* p; int per_sample; } view[] = {
+      {w.a1, A1_N}, {w.a2, A2_N}, {w.a3, A3_N}, {w.h, H_N}, {w.dz1, A1_N}, {w.dz2, A2_N}, {w.dz3, A3_N}, {w.dh, H_N},
+      {w.dlogits, 0}, {w.dvalue, 0}, {w.m1, M1_N}, {w.m2, M2_N}, {w.m3, M3_N}, {w.gsc, 1}, {w.amax, 0}};
+  if (which < 0 || which >= (int32_t)(sizeof(view) / sizeof(view[0]))) return DDRL_ERR_INVALID_ARG;
+  if (which <= 1 && !ctx->acts_stored) return DDRL_ERR_UNSUPPORTED;  // the last forward kept a1 / a2 on chip
+  *ptr = (float*)view[which].p;
+  *enc_stride = which == 14 ? 1 : w.es(view[which].per_sample);
   return DDRL_OK;
 }
 

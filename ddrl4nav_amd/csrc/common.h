@@ -17,6 +17,22 @@ constexpr int C2_IC = 32, C2_OC = 64, C2_KS = 4, C2_S = 2, C2_IW = 20, C2_OW = 9
 constexpr int C3_IC = 64, C3_OC = 64, C3_KS = 3, C3_S = 1, C3_IW = 9, C3_OW = 7, C3_P = 49, C3_K = 576;
 constexpr float LEAKY = 0.01f;  // F.leaky_relu default negative_slope
 
+// ---- the Atari context's workspace, described once (carve() below lays it out; launchers, kernels and api.hip use these names) ----
+// elements of ONE SAMPLE of each per-sample tensor: floats of the activations and their gradients (a1 / dz1, a2 / dz2, a3 / dz3,
+// h / dh), 32-bit words of the sign masks (Workspace::m1 / m2 / m3: one per pixel, one per (pixel, lane half))
+constexpr int A1_N = C1_OC * C1_P, A2_N = C2_OC * C2_P, A3_N = FLAT, H_N = FEAT;
+constexpr int M1_N = C1_P, M2_N = C2_P * 2, M3_N = C3_P * 2;
+static_assert(A1_N == 12800 && A2_N == 5184 && A3_N == C3_OC * C3_P && M1_N == 400 && M2_N == 162 && M3_N == 98, "per-sample sizes");
+// every per-encoder region is carved for two encoders, also with one shared prenet (the layout does not depend on it), and every
+// packed weight region with room for three 16-bit planes per tensor (engine2.h: NPL = 2 of them are in use)
+constexpr int ENC_SLOTS = 2, PLANE_ROOM = 3;
+// the kernels address a1 / dz1 with 32-bit BYTE offsets from wave-uniform bases: one encoder's part stays below 4 GB (83,886 samples)
+constexpr int MAX_BATCH_LIMIT = (int)((((int64_t)1 << 32) - 1) / (A1_N * sizeof(float)));
+// floats of one weight-gradient slab: a layer's weights followed by its bias, like the arena (make_layout).  One slab per (split,
+// encoder slot) in Workspace::wpart; the kernels' K::SLAB, the reductions into the arena and the all-reduce buckets are these
+constexpr int slab1_floats(int C) { return C1_OC * C * C1_KS * C1_KS + C1_OC; }  // conv1's depends on the stacked frames
+constexpr int64_t SLAB2 = (int64_t)C2_OC * C2_K + C2_OC, SLAB3 = (int64_t)C3_OC * C3_K + C3_OC, SLAB_FC = (int64_t)FEAT * FLAT + FEAT;
+
 // ---- flat parameter arena (named_parameters() order, reference nn/base.py:60-66) ----------
 struct EncLayout {  // offsets relative to the encoder's base
   int64_t c1w, c1b, c2w, c2b, c3w, c3b, lw, lb, size;
@@ -83,6 +99,9 @@ inline ParamLayout head_param_layout(const HeadLayout& h) {
 
 // ---- device workspace carved out of the caller's buffer ------------------------------------
 struct Workspace {
+  int64_t max_batch;  // the batch every per-sample tensor is carved for
+  // floats (words) from encoder 0's part of a per-sample tensor to encoder 1's: es(A1_N) for a1 / dz1, es(M2_N) for m2, es(1) for gsc
+  int64_t es(int per_sample) const { return max_batch * per_sample; }
   // derived weight layouts, [e] major
   // 16-bit weight planes, NPL per tensor (engine2.h: two scaled fp16 planes by default).  conv1, conv2.hip conv_fwd1_planes_kernel:
   // [channel 4][ky pair 4][plane NPL][lane half 2][row 32 NE][kx 8] 16-bit
@@ -106,7 +125,7 @@ struct Workspace {
   // sign bits of a1 (1 = NOT positive: the leaky slope applies), written by conv1's forward for the leaky-ReLU mask of the conv1 weight gradient (which would
   // otherwise re-read all of a1 for its signs): [e][column] 32-bit words, column = sample * 400 + output pixel, bit m1_bit(oc) of
   // the word = output channel oc (the order in which an MFMA lane holds its 16 accumulator rows, so that the producer shifts
-  // the bits in as it walks its registers and stores its half-word).  m1_words(max_batch) words per encoder.
+  // the bits in as it walks its registers and stores its half-word).
   unsigned* m1;
   // sign bits of a2 for conv3's data gradient, whose epilogue has conv2's forward tile layout (column = (sample, pixel), lane half
   // hi, accumulator register r <-> channel i * 32 + acc_row(r, hi)): [e][sample][pixel 81][hi 2] words, bit 16 i + 15 - r set =
@@ -168,10 +187,9 @@ inline bool overlap(const void* a, const void* b, uint64_t a_bytes, uint64_t b_b
   return x < y + b_bytes && y < x + a_bytes;
 }
 inline int32_t launch_status() { return hipGetLastError() == hipSuccess ? DDRL_OK : DDRL_ERR_HIP; }
-// words of the a1 sign mask per encoder (one per column), and the bit of output channel oc inside a column's word: lane half
+// the bit of output channel oc inside a column's word of the a1 sign mask (Workspace::m1): lane half
 // hi = (oc >> 2) & 1 of the 32x32 MFMA tile holds oc as accumulator register r = (oc & 3) + 4 (oc >> 3) and shifts its 16 signs in
 // first register first, i.e. register r ends at bit 15 - r of half-word hi
-__host__ __device__ inline int64_t m1_words(int64_t max_batch) { return max_batch * 400; }
 __host__ __device__ inline int m1_bit(int oc) { return ((oc >> 2) & 1) * 16 + 15 - ((oc & 3) + 4 * (oc >> 3)); }
 
 constexpr int ACT_FUSED_MAX = 512;  // acting launches of at most this many samples take the fused kernel (Workspace::actmax is carved for it)
@@ -201,49 +219,48 @@ inline Splits choose_splits(int max_batch, int NE = 2) {
 inline int64_t hpart_stride(int A) { return align_up((int64_t)(A + 1) * FEAT + A + 1 + 4, 64); }
 
 inline int64_t carve(Workspace& w, const ddrl_config& c, void* base) {
-  const int64_t MB = c.max_batch, C = c.in_channels, A = c.n_actions;
+  const int64_t A = c.n_actions;
+  w.max_batch = c.max_batch;
   int64_t off = 0;
   auto take = [&](int64_t floats) -> float* {
     float* p = base ? (float*)((char*)base + off) : nullptr;
     off += align_up(floats * 4, 256);
     return p;
   };
-  w.wp1b = (unsigned short*)take(4 * 4 * 3 * 2 * 64 * 8 / 2);
-  w.wlb = (unsigned short*)take(2 * 3 * (int64_t)FLAT * FEAT / 2);
-  w.wdlb = (unsigned short*)take(2 * 3 * (int64_t)FLAT * FEAT / 2);
+  // the packed planes of one weight tensor: n16 16-bit elements per (encoder, plane), layouts at the Workspace fields
+  auto take_planes = [&](int64_t n16) { return (unsigned short*)take(ENC_SLOTS * PLANE_ROOM * n16 / 2); };
+  // a per-sample tensor, both encoders' parts
+  auto take_enc = [&](int per_sample) { return take(ENC_SLOTS * w.es(per_sample)); };
+  w.wp1b = take_planes(4 * 4 * 2 * C1_OC * C1_KS);
+  w.wlb = take_planes((int64_t)FLAT * FEAT);
+  w.wdlb = take_planes((int64_t)FLAT * FEAT);
   w.amax = take(64);
-  w.actmax = take(2 * ACT_FUSED_MAX);  // [2 encoders][ACT_FUSED_MAX]
-  w.wp2b = (unsigned short*)take(2 * 32 * 3 * 64 * 16 / 2);
-  w.wp3b = (unsigned short*)take(2 * 8 * 5 * 3 * 64 * 16 / 2);
-  w.wd2b = (unsigned short*)take(2 * 2 * 4 * 4 * 3 * 64 * 16 / 2);
-  w.wd3b = (unsigned short*)take(2 * 8 * 5 * 3 * 64 * 16 / 2);
-  w.a1 = take(2 * MB * 32 * 400);
-  w.m1 = (unsigned*)take(2 * m1_words(MB));
-  w.m2 = (unsigned*)take(2 * MB * 81 * 2);
-  w.m3 = (unsigned*)take(2 * MB * 49 * 2);
-  w.a2 = take(2 * MB * 64 * 81);
-  w.a3 = take(2 * MB * FLAT);
-  w.h = take(2 * MB * FEAT);
-  w.dz1 = take(2 * MB * 32 * 400);
-  w.dz2 = take(2 * MB * 64 * 81);
-  w.dz3 = take(2 * MB * FLAT);
-  w.dh = take(2 * MB * FEAT);
-  w.gsc = take(2 * MB);
-  w.dlogits = take(MB * A);
-  w.dvalue = take(MB);
-  Splits s = choose_splits(c.max_batch, c.share_cnn_net ? 1 : 2);
-  // slabs hold weights followed by bias, like the arena
-  int64_t p1 = (int64_t)s.c1 * 2 * (32 * C * 64 + 32);
-  int64_t p2 = (int64_t)s.c2 * 2 * (64 * 512 + 64);
-  int64_t p3 = (int64_t)s.c3 * 2 * (64 * 576 + 64);
-  int64_t pf = (int64_t)s.fc * 2 * ((int64_t)FEAT * FLAT + FEAT);
-  int64_t pm = p1;
-  if (p2 > pm) pm = p2;
-  if (p3 > pm) pm = p3;
-  if (pf > pm) pm = pf;
-  // the acting path parks the split-K partial sums of the FC forward here (fc_forward_splits)
-  const int64_t pact = (int64_t)FC_ACT_SPLITS * 2 * (MB < 1024 ? MB : 1024) * FEAT;
-  if (pact > pm) pm = pact;
+  w.actmax = take(ENC_SLOTS * ACT_FUSED_MAX);
+  w.wp2b = take_planes(C2_IC * C2_OC * 16);
+  w.wp3b = take_planes(8 * 5 * C3_OC * 16);
+  w.wd2b = take_planes(2 * 8 * 2 * 64 * 2 * 8);
+  w.wd3b = take_planes(8 * 5 * C3_OC * 16);  // carved like wp3b; its 4 x 9 (k-block, tap) cells take less
+  w.a1 = take_enc(A1_N);
+  w.m1 = (unsigned*)take_enc(M1_N);
+  w.m2 = (unsigned*)take_enc(M2_N);
+  w.m3 = (unsigned*)take_enc(M3_N);
+  w.a2 = take_enc(A2_N);
+  w.a3 = take_enc(A3_N);
+  w.h = take_enc(H_N);
+  w.dz1 = take_enc(A1_N);
+  w.dz2 = take_enc(A2_N);
+  w.dz3 = take_enc(A3_N);
+  w.dh = take_enc(H_N);
+  w.gsc = take_enc(1);
+  w.dlogits = take(w.max_batch * A);
+  w.dvalue = take(w.max_batch);
+  const Splits s = choose_splits(c.max_batch, c.share_cnn_net ? 1 : 2);
+  // the largest of the four layers' slabs, and of the split-K partial sums of the dense forward that the acting path parks here
+  // (fc_forward_splits)
+  int64_t pm = 0;
+  for (int64_t p : {(int64_t)s.c1 * ENC_SLOTS * slab1_floats(c.in_channels), s.c2 * ENC_SLOTS * SLAB2, s.c3 * ENC_SLOTS * SLAB3, s.fc * ENC_SLOTS * SLAB_FC,
+                    (int64_t)FC_ACT_SPLITS * ENC_SLOTS * (w.max_batch < 1024 ? w.max_batch : 1024) * FEAT})
+    if (p > pm) pm = p;
   w.wpart_floats = pm;
   w.wpart = take(pm);
   w.hpart = take((int64_t)HEAD_WG * hpart_stride(A));

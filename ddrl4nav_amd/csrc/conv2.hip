@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   // tile geometry: 256 output pixels of at most two samples and the input rows they need
-  const int c0 = blockIdx.x * 256, ctot = n * 400, clast = min(c0 + 255, ctot - 1);
+  const int c0 = blockIdx.x * 256, ctot = n * C1_P, clast = min(c0 + 255, ctot - 1);
   const int b0 = c0 / 400, b1 = clast / 400, oyf0 = (c0 % 400) / 20, iy0_start = 4 * oyf0;
   int nrows0, nrows1 = 0;
   if (b1 == b0) {
@@ -62,8 +62,9 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
   }
   const int nd0 = nrows0 * 21, nd_total = nd0 + nrows1 * 21;
   const int64_t src0 = (int64_t)b0 * (C * 7056) + iy0_start * 84, src1 = (int64_t)b1 * (C * 7056);  // C stacked frames per sample (1..4)
-  // this kernel opens every forward: it also resets the running maxima that the conv2 / conv3 epilogues raise afterwards (a
-  // separate 16-byte memset is a kernel of its own: 5 of the ~100 us of an acting step)
+  // this kernel opens every forward: it also resets the running maxima that the conv2 / conv3 epilogues raise afterwards, so the
+  // activation slots of Workspace::amax start every forward at zero without a call from the entry points (a separate 16-byte
+  // memset is a kernel of its own: 5 of the ~100 us of an acting step); the gradient slots are reset by launch_encoder_backward
   if (blockIdx.x == 0 && tid < (AMAX_DH - AMAX_FIRST_ACT) * 2) amax[amax_idx(AMAX_FIRST_ACT, 0) + tid] = 0.0f;
   int64_t imsrc[6];
   int imdst[6];
@@ -156,14 +157,14 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
   __syncthreads();
   float r255[NE];  // 1/255 of the frame normalisation and the scale of the encoder's weight planes
 #pragma unroll
-  for (int i = 0; i < NE; ++i) r255[i] = PIXEL_UNIT / (255.0f * plane_scale(amax[amax_idx(AMAX_W1, i)]));
+  for (int i = 0; i < NE; ++i) r255[i] = 1.0f / (255.0f * plane_scale(amax[amax_idx(AMAX_W1, i)]));
   // (the scale of a1's planes comes from a bound that pack_weights derives from the weights, common.h AMAX_A1: no maximum here)
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int c = c0 + wc * 64 + j * 32 + l31;
     if (c >= ctot) continue;
     const int b = c / 400, pix = c % 400;
-    const uint32_t lanep = (uint32_t)((b * 12800 + pix + hi * (4 * 400)) * 4);
+    const uint32_t lanep = (uint32_t)((b * A1_N + pix + hi * (4 * C1_P)) * 4);
 #pragma unroll
     for (int i = 0; i < NE; ++i) {  // i = encoder
       float* base = out + i * out_es;
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
       for (int r = 0; r < 16; ++r) {
         const int oc = acc_row(r, hi);
         const float y = leaky_f(__builtin_fmaf(acc[i][j][r], r255[i], bias[i * 32 + oc]));  // one rounding less than mul + add
-        st1_so(base + acc_row(r, 0) * 400, lanep, y);
+        st1_so(base + acc_row(r, 0) * C1_P, lanep, y);
         // y > 0 <=> its bit pattern, as a signed integer, is >= 1 <=> (pattern -sat 1) has a clear sign; alignbit shifts that sign
         // in: two VALU instructions per output (compare + select + or: three and two s_nop)
         bits = __builtin_amdgcn_alignbit(bits, (unsigned)__builtin_elementwise_sub_sat((int)__float_as_uint(y), 1), 31);
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
   const int tid = threadIdx.x, gq = tid >> 8, lt = tid & 255, lane = tid & 63, wc = (tid >> 6) & 3, l31 = lane & 31, hi = lane >> 5;
   char* img = ldsr + K::IMG_OFF + gq * K::GROUP_IMG;
   float* bias = (float*)(ldsr + K::BIAS_OFF);
-  const int ctot = n * 400, ntiles = (ctot + 255) / 256;
+  const int ctot = n * C1_P, ntiles = (ctot + 255) / 256;
   // this kernel opens every training forward: it resets the running maxima that the conv2 / conv3 epilogues raise afterwards
   if (blockIdx.x == 0 && tid < (AMAX_DH - AMAX_FIRST_ACT) * 2) amax[amax_idx(AMAX_FIRST_ACT, 0) + tid] = 0.0f;
   // weight planes of the C stacked frames: a plain copy of global memory, 1,024 quads per frame
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
   if (tid < K::ROWS) bias[tid] = params[(tid >> 5 ? bias_off1 : bias_off0) + (tid & 31)];
   float r255[NE];
 #pragma unroll
-  for (int i = 0; i < NE; ++i) r255[i] = PIXEL_UNIT / (255.0f * plane_scale(amax[amax_idx(AMAX_W1, i)]));
+  for (int i = 0; i < NE; ++i) r255[i] = 1.0f / (255.0f * plane_scale(amax[amax_idx(AMAX_W1, i)]));
   int abase[NE];
 #pragma unroll
   for (int i = 0; i < NE; ++i) abase[i] = (hi * K::ROWS + i * 32 + l31) * 16;
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
       const int c = cur.c0 + wc * 64 + j * 32 + l31;
       if (c >= ctot) continue;
       const int b = c / 400, pix = c % 400;
-      const uint32_t lanep = (uint32_t)((b * 12800 + pix + hi * (4 * 400)) * 4);
+      const uint32_t lanep = (uint32_t)((b * A1_N + pix + hi * (4 * C1_P)) * 4);
 #pragma unroll
       for (int i = 0; i < NE; ++i) {
         float* base = out + i * out_es;
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
         for (int r = 0; r < 16; ++r) {
           const int oc = acc_row(r, hi);
           const float y = leaky_f(__builtin_fmaf(acc[i][j][r], r255[i], bias[i * 32 + oc]));
-          st1_so(base + acc_row(r, 0) * 400, lanep, y);
+          st1_so(base + acc_row(r, 0) * C1_P, lanep, y);
           bits = __builtin_amdgcn_alignbit(bits, (unsigned)__builtin_elementwise_sub_sat((int)__float_as_uint(y), 1), 31);
         }
         if (m1 != nullptr) ((unsigned short*)(m1 + i * m1_es))[2 * (int64_t)c + hi] = (unsigned short)bits;
@@ -350,7 +351,7 @@ template <int NE>
 static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
-  if (!acting && (int64_t)c.n * 400 >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
+  if (!acting && (int64_t)c.n * C1_P >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
     using R = Fwd1R<NE>;
     lds_limit_once<conv_fwd1_resident_kernel<NE>>((int)R::LDS_BYTES);
     static const int cus = [] {
@@ -359,14 +360,14 @@ static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
       return hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
     }();
     hipLaunchKernelGGL(conv_fwd1_resident_kernel<NE>, dim3((unsigned)cus), dim3(512), R::LDS_BYTES, st, c.frames, w.wp1b, w.amax, c.params,
-                       L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, c.max_batch * 12800, c.n, w.m1, m1_words(c.max_batch), L.C);
+                       L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n, w.m1, w.es(M1_N), L.C);
     return;
   }
   using K = Fwd1B<NE>;
   lds_limit_once<conv_fwd1_planes_kernel<NE>>((int)K::LDS_BYTES);
-  hipLaunchKernelGGL(conv_fwd1_planes_kernel<NE>, dim3((unsigned)(((int64_t)c.n * 400 + 255) / 256)), dim3(256), K::LDS_BYTES, st, c.frames,
-                     w.wp1b, w.amax, c.params, L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, c.max_batch * 12800, c.n,
-                     acting ? (unsigned*)nullptr : w.m1, m1_words(c.max_batch), L.C);
+  hipLaunchKernelGGL(conv_fwd1_planes_kernel<NE>, dim3((unsigned)(((int64_t)c.n * C1_P + 255) / 256)), dim3(256), K::LDS_BYTES, st, c.frames,
+                     w.wp1b, w.amax, c.params, L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n,
+                     acting ? (unsigned*)nullptr : w.m1, w.es(M1_N), L.C);
 }
 
 // ================================================================================================
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2B::WPE,
   for (int j = 0; j < K::NIJ; ++j) {
     const int u = min(tid + 256 * j, K::NIU - 1);
     const int s = u / (100 * K::KC), rem = u % (100 * K::KC), q = rem % 100;
-    isrc[j] = a1 + e * a1_es + (int64_t)min(b0 + s, n - 1) * 12800 + rem * 4;  // + kb * 1600
+    isrc[j] = a1 + e * a1_es + (int64_t)min(b0 + s, n - 1) * A1_N + rem * 4;  // + kb * 1600
     idst[j] = (s * K::KC + rem / 100) * K::CH + (q / 5) * K::ROW + (q % 5) * 8;
   }
   const unsigned short* wsrc = wp2b + (int64_t)e * (32 * NPL * 64 * 16) + tid * 8;  // + kb * KC * NPL * 1024 + j * 2048
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2B::WPE,
   f4 ir[K::NIJ], wr[K::NWJ];
   auto fetch = [&](int kb) {
 #pragma unroll
-    for (int j = 0; j < K::NIJ; ++j) ir[j] = ld4(isrc[j] + kb * (400 * K::KC));
+    for (int j = 0; j < K::NIJ; ++j) ir[j] = ld4(isrc[j] + kb * (C1_P * K::KC));
 #pragma unroll
     for (int j = 0; j < K::NWJ; ++j) wr[j] = *(const f4*)(wsrc + kb * (K::KC * NPL * 1024) + j * 2048);
   };
@@ -512,8 +513,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2B::WPE,
     const int c = wc * 64 + j * 32 + l31;
     const int s = c / 81, pix = c % 81;
     if (c >= K::SPT * 81 || b0 + s >= n) continue;
-    float* base = out + e * out_es + (int64_t)b0 * 5184;
-    const uint32_t lb = (uint32_t)((s * 5184 + pix + hi * (4 * 81)) * 4);
+    float* base = out + e * out_es + (int64_t)b0 * A2_N;
+    const uint32_t lb = (uint32_t)((s * A2_N + pix + hi * (4 * C2_P)) * 4);
     unsigned bits = 0u;  // sign mask of a2 (common.h Workspace::m2): the signs of the lane's 32 channels, shifted in register by register
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -521,12 +522,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd2B::WPE,
       for (int r = 0; r < 16; ++r) {
         const int oc = i * 32 + acc_row(r, hi);
         const float y = leaky_f(__builtin_fmaf(acc[i][j][r], inv, bias[oc]));
-        st1_so(base + (i * 32 + acc_row(r, 0)) * 81, lb, y);
+        st1_so(base + (i * 32 + acc_row(r, 0)) * C2_P, lb, y);
         big = fmaxf(big, fabsf(y));
         bits = __builtin_amdgcn_alignbit(bits, (unsigned)__builtin_elementwise_sub_sat((int)__float_as_uint(y), 1), 31);  // conv1's epilogue
       }
     // i = 0 went in first and now sits in the upper half: swap so that bit 16 i + 15 - r belongs to register r of half i
-    if (m2 != nullptr) m2[(e * (out_es / 5184) + b0 + s) * 162 + pix * 2 + hi] = (bits >> 16) | (bits << 16);
+    if (m2 != nullptr) m2[(e * (out_es / A2_N) + b0 + s) * M2_N + pix * 2 + hi] = (bits >> 16) | (bits << 16);
   }
   amax_update(big, amax + amax_idx(AMAX_A2, e));
 }
@@ -536,7 +537,7 @@ static void launch_fwd2_planes(const EncCall& c, bool acting, hipStream_t st) {
   const ParamLayout& L = *c.L;
   lds_limit_once<conv_fwd2_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_fwd2_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)L.NE), dim3(256), K::LDS_BYTES, st, w.a1,
-                     c.max_batch * 12800, w.wp2b, w.amax, c.params, L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b, w.a2, c.max_batch * 5184,
+                     w.es(A1_N), w.wp2b, w.amax, c.params, L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b, w.a2, w.es(A2_N),
                      c.n, acting ? (unsigned*)nullptr : w.m2);
 }
 
@@ -577,7 +578,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd3B::WPE,
   for (int j = 0; j < K::NIJ; ++j) {
     const int u = min(tid + 256 * j, K::NPX - 1);
     const int s = u / 81, px = u % 81;
-    isrc[j] = a2 + e * a2_es + (int64_t)min(b0 + s, n - 1) * 5184 + px;  // + (8 kb + c) * 81
+    isrc[j] = a2 + e * a2_es + (int64_t)min(b0 + s, n - 1) * A2_N + px;  // + (8 kb + c) * 81
   }
   const unsigned short* wsrc = wp3b + (int64_t)e * (8 * 5 * NPL * 64 * 16) + tid * 8;  // + kb * 5 * NPL * 1024 + j * 2048
   // ---- operand bases
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd3B::WPE,
 #pragma unroll
     for (int j = 0; j < K::NIJ; ++j)
 #pragma unroll
-      for (int c = 0; c < 8; ++c) ir[j][c] = isrc[j][(kb * 8 + c) * 81];
+      for (int c = 0; c < 8; ++c) ir[j][c] = isrc[j][(kb * 8 + c) * C2_P];
 #pragma unroll
     for (int j = 0; j < K::NWJ; ++j)
       if (j + 1 < K::NWJ || tid + 256 * j < K::W_BYTES / 16) wr[j] = *(const f4*)(wsrc + kb * (5 * NPL * 1024) + j * 2048);
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd3B::WPE,
     const int s = c / 49, pix = c % 49;
     if (c >= K::SPT * 49 || b0 + s >= n) continue;
     float* base = out + e * out_es + (int64_t)b0 * FLAT;
-    const uint32_t lb = (uint32_t)((s * FLAT + pix + hi * (4 * 49)) * 4);
+    const uint32_t lb = (uint32_t)((s * A3_N + pix + hi * (4 * C3_P)) * 4);
     unsigned bits = 0u;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -676,12 +677,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fwd3B::WPE,
       for (int r = 0; r < 16; ++r) {
         const int oc = i * 32 + acc_row(r, hi);
         const float y = leaky_f(__builtin_fmaf(acc[i][j][r], inv, bias[oc]));
-        st1_so(base + (i * 32 + acc_row(r, 0)) * 49, lb, y);
+        st1_so(base + (i * 32 + acc_row(r, 0)) * C3_P, lb, y);
         big = fmaxf(big, fabsf(y));
         bits = __builtin_amdgcn_alignbit(bits, (unsigned)__builtin_elementwise_sub_sat((int)__float_as_uint(y), 1), 31);  // conv1's epilogue
       }
     // sign mask of a3 (common.h Workspace::m3): bit 16 i + 15 - r = register r of half i is not positive
-    if (m3 != nullptr) m3[(e * (out_es / FLAT) + b0 + s) * 98 + pix * 2 + hi] = (bits >> 16) | (bits << 16);
+    if (m3 != nullptr) m3[(e * (out_es / A3_N) + b0 + s) * M3_N + pix * 2 + hi] = (bits >> 16) | (bits << 16);
   }
   amax_update(big, amax + amax_idx(AMAX_A3, e));
 }
@@ -691,14 +692,14 @@ static void launch_fwd3_planes(const EncCall& c, bool acting, hipStream_t st) {
   const ParamLayout& L = *c.L;
   lds_limit_once<conv_fwd3_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_fwd3_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)L.NE), dim3(256), K::LDS_BYTES, st, w.a2,
-                     c.max_batch * 5184, w.wp3b, w.amax, c.params, L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b, w.a3, c.max_batch * FLAT,
+                     w.es(A2_N), w.wp3b, w.amax, c.params, L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b, w.a3, w.es(A3_N),
                      c.n, acting ? (unsigned*)nullptr : w.m3);
 }
 
 // ================================================================================================
 
 // Training launches, and acting launches of more than ACT_FUSED_MAX samples (they skip the sign masks only the backward reads)
-void launch_conv_forward2(const EncCall& c, bool acting, hipStream_t st) {
+void launch_conv_forward(const EncCall& c, bool acting, hipStream_t st) {
   {
     ProfRange pr(c.prof, acting ? "ConvFwd1.act" : "ConvFwd1", st);
     if (c.L->NE == 2) {
@@ -781,7 +782,7 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
     for (int j = 0; j < K::NIJ; ++j)
 #pragma unroll
-      for (int c = 0; c < K::KOC; ++c) ir[j][c] = isrc[j][(kb * K::KOC + c) * 49];
+      for (int c = 0; c < K::KOC; ++c) ir[j][c] = isrc[j][(kb * K::KOC + c) * C3_P];
 #pragma unroll
     for (int j = 0; j < K::NWJ; ++j)
       if (j + 1 < K::NWJ || tid + K::THREADS * j < K::NWQ) wr[j] = *(const f4*)(wsrc + kb * (9 * NPL * 1024) + j * (K::THREADS * 8));
@@ -851,17 +852,17 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
     const int c = wc * (32 * K::TN) + j * 32 + l31;
     const int s = c / 81, pix = c % 81;
     if (c >= K::SPT * 81 || b0 + s >= n) continue;
-    const int64_t off = (int64_t)(b0 + s) * 5184 + pix + hi * (4 * 81);
+    const int64_t off = (int64_t)(b0 + s) * A2_N + pix + hi * (4 * C2_P);
     float* op = out + e * out_es + off;
     // the signs of a2 at this lane's 32 (channel, pixel) positions: one word written by conv2's forward, whose tile layout
     // this epilogue shares (common.h Workspace::m2) -- not 32 reads of a2
-    const unsigned mw = m2[(e * (out_es / 5184) + b0 + s) * 162 + pix * 2 + hi];
+    const unsigned mw = m2[(e * (out_es / A2_N) + b0 + s) * M2_N + pix * 2 + hi];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float g = leaky_bit(mw, 16 * i + 15 - r, acc[i][j][r] * inv);
-        op[(i * 32 + acc_row(r, 0)) * 81] = g;
+        op[(i * 32 + acc_row(r, 0)) * C2_P] = g;
         big = fmaxf(big, fabsf(g));
       }
   }
@@ -872,10 +873,10 @@ static void launch_dgrad3_planes(const EncCall& c, hipStream_t st) {
   const Workspace& w = *c.ws;
   lds_limit_once<conv_dgrad3_planes_kernel>((int)K::LDS_BYTES);
   hipLaunchKernelGGL(conv_dgrad3_planes_kernel, dim3((unsigned)((c.n + K::SPT - 1) / K::SPT), 1, (unsigned)c.L->NE), dim3(K::THREADS), K::LDS_BYTES, st,
-                     w.dz3, c.max_batch * FLAT, w.wd3b, w.amax, w.m2, w.dz2, c.max_batch * 5184, c.n);
+                     w.dz3, w.es(A3_N), w.wd3b, w.amax, w.m2, w.dz2, w.es(A2_N), c.n);
 }
 
-void launch_conv_dgrad3_2(const EncCall& c, hipStream_t st) {
+void launch_conv_dgrad3(const EncCall& c, hipStream_t st) {
   ProfRange pr(c.prof, "ConvDgrad3", st);
   launch_dgrad3_planes(c, st);
 }
@@ -918,7 +919,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = tid; i < K::W_OFF / 16; i += K::THREADS) *(f4*)(ldsd2 + i * 16) = zero4();  // images incl. their zero borders
   // ---- staging maps.  unit u = tid: sample u / 81, pixel u % 81 -> 8 loads of stride 81 (the k-block's 8 oc)
   const int u = min(tid, K::NIU - 1);
-  const float* isrc = dz2 + e * dz_es + (int64_t)min(b0 + u / 81, n - 1) * 5184 + u % 81;  // + (8 kb + c) * 81
+  const float* isrc = dz2 + e * dz_es + (int64_t)min(b0 + u / C2_P, n - 1) * A2_N + u % C2_P;  // + (8 kb + c) * 81
   const int idst = ((u / 81) * 121 + ((u % 81) / 9 + 1) * 11 + (u % 81) % 9 + 1) * 16;
   // weight quad q = tid + 512 j of the two parities' k-blocks (W_HALF bytes each, one after the other in LDS)
   const unsigned short* wsrc[K::NWJ];
@@ -942,7 +943,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   f4 wr[K::NWJ];
   auto fetch = [&](int kb) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) ir[c] = isrc[(kb * 8 + c) * 81];
+    for (int c = 0; c < 8; ++c) ir[c] = isrc[(kb * 8 + c) * C2_P];
 #pragma unroll
     for (int j = 0; j < K::NWJ; ++j) wr[j] = *(const f4*)(wsrc[j] + kb * (2 * NPL * 1024));
   };
@@ -1005,11 +1006,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (c >= K::SPT * 100 || b0 + s >= n) continue;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-      float* base = out + e * out_es + (int64_t)(b0 + s) * 12800 + (2 * (pq / 10) + a) * 20 + 2 * (pq % 10);
+      float* base = out + e * out_es + (int64_t)(b0 + s) * A1_N + (2 * (pq / 10) + a) * 20 + 2 * (pq % 10);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float g0 = acc[2 * a][j][r] * inv, g1 = acc[2 * a + 1][j][r] * inv;
-        *(float2*)(base + acc_row(r, hi) * 400) = make_float2(g0, g1);
+        *(float2*)(base + acc_row(r, hi) * C1_P) = make_float2(g0, g1);
         big = fmaxf(big, fmaxf(fabsf(g0), fabsf(g1)));
       }
     }
@@ -1017,12 +1018,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   amax_update(big, amax + amax_idx(AMAX_DZ1, e));  // da1 before the leaky mask: an upper bound of what conv1's weight gradient stages
 }
 
-void launch_conv_dgrad2_2(const EncCall& c, hipStream_t st) {
+void launch_conv_dgrad2(const EncCall& c, hipStream_t st) {
   const Workspace& w = *c.ws;
   ProfRange pr(c.prof, "ConvDgrad2", st);
   lds_limit_once<conv_dgrad2_both_kernel>((int)Dgrad2Both::LDS_BYTES);
   hipLaunchKernelGGL(conv_dgrad2_both_kernel, dim3((unsigned)((c.n + Dgrad2Both::SPT - 1) / Dgrad2Both::SPT), (unsigned)c.L->NE, 1),
-                     dim3(Dgrad2Both::THREADS), Dgrad2Both::LDS_BYTES, st, w.dz2, c.max_batch * 5184, w.wd2b, w.amax, w.dz1, c.max_batch * 12800, c.n);
+                     dim3(Dgrad2Both::THREADS), Dgrad2Both::LDS_BYTES, st, w.dz2, w.es(A2_N), w.wd2b, w.amax, w.dz1, w.es(A1_N), c.n);
 }
 
 }  // namespace ddrl

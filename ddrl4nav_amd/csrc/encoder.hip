@@ -1,5 +1,5 @@
-// Launch sequencing of the encoder forward / backward on the v2 engine kernels
-// (conv2.hip, wgrad2.hip, fc2.hip).  Reference call sites being replaced: PPO.forward
+// Launch sequencing of the encoder forward / backward on the plane kernels
+// (conv2.hip, wgrad2.hip, fc2.hip, act.hip).  Reference call sites being replaced: PPO.forward
 // (USTC_lab/nn/ppo.py:72-75) and the autograd backward of PPO.learn (ppo.py:122-123).
 #include "engine2.h"
 #include "kernels.h"
@@ -47,39 +47,37 @@ static void launch_backward_amax(const EncCall& c, hipStream_t st) {
   const Workspace& w = *c.ws;
   launch_backward_amax_reset(c, st);
   ProfRange pr(c.prof, "dh_normalise", st);
-  hipLaunchKernelGGL(dh_normalise_kernel, dim3((c.n + 3) / 4, c.L->NE), dim3(256), 0, st, w.dh, c.max_batch * FEAT, c.n, w.gsc, c.max_batch,
+  hipLaunchKernelGGL(dh_normalise_kernel, dim3((c.n + 3) / 4, c.L->NE), dim3(256), 0, st, w.dh, w.es(H_N), c.n, w.gsc, w.es(1),
                      w.amax);
 }
 
 void launch_encoder_forward(const EncCall& c, bool acting, hipStream_t st) {
   if (acting && c.n <= ACT_FUSED_MAX) {  // latency-bound: one launch for the three convolutions (act.hip), then the batched dense layer
     launch_act_convs(c, st);
-    launch_fc_forward2(c, true, st, true);
+    launch_fc_forward(c, true, st, true);
     return;
   }
-  launch_conv_forward2(c, acting, st);
-  launch_fc_forward2(c, acting, st);
+  launch_conv_forward(c, acting, st);
+  launch_fc_forward(c, acting, st);
 }
 
 // Backward of both encoders given dh[e][n][512] (written by heads_loss).  Every weight-gradient
 // kernel leaves split-K partial slabs that reduce_partials sums into the grad arena.
-// Order: the data-gradient chain first (dense, conv3, conv2: kernels on the bf16 matrix pipe, then conv1's weight
-// gradient, also on it), the three fp32-MFMA weight gradients last.  Every buffer a weight gradient reads (dh, dz3, dz2
-// and the activations) is still intact then.  The layer-by-layer order measured 42.07 vs 41.84 ms per PPO iteration on one
-// box, not kept: it alternates bf16-pipe and fp32-pipe kernels, and each fp32 kernel that follows a bf16 one starts at the
-// lower clock the denser pipe leaves behind.
+// Order: the data-gradient chain first (dense, conv3, conv2), then conv1's weight gradient, which reads the dz1 the chain ends with,
+// then the other three weight gradients.  Every buffer a weight gradient reads (dh, dz3, dz2 and the activations) is still intact
+// then: no data-gradient kernel overwrites its input.
 void launch_encoder_backward(const EncCall& c, float* grads, hipStream_t st, bool dh_normalised) {
   if (!dh_normalised) launch_backward_amax(c, st);  // dh from heads_loss arrives normalised (heads.hip); anyone else's is normalised here
-  launch_fc_backward2(c, grads, st, 1);
-  launch_conv_dgrad3_2(c, st);
-  launch_conv_dgrad2_2(c, st);
-  launch_conv_wgrad1_2(c, grads, st);  // no data gradient for conv1: the frames are leaves
+  launch_fc_backward(c, grads, st, 1);
+  launch_conv_dgrad3(c, st);
+  launch_conv_dgrad2(c, st);
+  launch_conv_wgrad1(c, grads, st);  // no data gradient for conv1: the frames are leaves
   bucket_done(c, BUCKET_CONV1, st);
-  launch_fc_backward2(c, grads, st, 2);
+  launch_fc_backward(c, grads, st, 2);
   bucket_done(c, BUCKET_FC, st);       // 95 % of the arena's bytes: its all-reduce runs under the two conv weight gradients below
-  launch_conv_wgrad3_2(c, grads, st);
+  launch_conv_wgrad3(c, grads, st);
   bucket_done(c, BUCKET_CONV3, st);
-  launch_conv_wgrad2_2(c, grads, st);
+  launch_conv_wgrad2(c, grads, st);
   bucket_done(c, BUCKET_CONV2, st);
 }
 

@@ -1,4 +1,10 @@
-// Pipelined f32-MFMA tile engine shared by every GEMM-shaped kernel of the library.
+// Two things live here:
+//   (a) the pipelined f32-MFMA tile engine of the f32-input operator kernels (gconv.hip, glinear.hip): engine2_kernel and what it
+//       is built from, down to launch_engine2;
+//   (b) the helpers every kernel file uses: register vectors and LDS-direct loads at the top, and behind the engine the plane
+//       scheme ("f16x3"), the running maxima and the per-sample magnitudes of the operator kernels.
+//
+// The engine:
 //
 //   C[row][col] = sum_k A(row,k) * B(k,col),  rows -> MFMA A operand -> accumulator registers,
 //   cols -> MFMA B operand -> lanes (stores are coalesced along cols).
@@ -12,9 +18,8 @@
 //   * ops stage RAW tensors (input planes, weight slabs) with wide coalesced loads instead of
 //     gathering an im2col tile element by element (the generic gather ops of gconv.hip are the
 //     exception, for layers without a specialised kernel);
-//   * the order of LDS reads and MFMAs inside a k-block is pinned (compute_block), and ops choose
-//     by trait whether commit/fetch run before or after the MFMA block (COMMIT_FIRST, IGLP, OCC,
-//     EXTRA, PRE_EPILOGUE below).
+//   * the order of LDS reads and MFMAs inside a k-block is pinned (compute_block); an op may ask for
+//     LLVM's own interleave instead (IGLP below).
 //
 // An Op provides:
 //   constants  THREADS, TM, TN, KSTEPS, STAGE (floats per LDS buffer)
@@ -22,7 +27,6 @@
 //   bool  init(P, tid, lds)            tile coordinates, lane bases abase[TM], bbase[TN], kb range
 //   void  fetch(P, kb, regs)           issue global loads of k-block kb
 //   void  commit(regs, buf)            registers -> LDS buffer
-//   void  extra(cur)                   optional side work on the published buffer (bias sums)
 //   static constexpr int aoff(s), boff(s)   immediates of k-step s (in floats)
 //   void  epilogue(P, acc)
 #pragma once
@@ -39,18 +43,10 @@ using f2 = __attribute__((ext_vector_type(2))) float;
 __device__ __forceinline__ f4 ld4(const float* p) { return *(const f4*)p; }
 __device__ __forceinline__ void st4(float* p, f4 v) { *(f4*)p = v; }
 __device__ __forceinline__ f4 zero4() { return (f4){0.0f, 0.0f, 0.0f, 0.0f}; }
-// Load through the  scalar base + 32-bit lane offset  addressing form (global_load v, v_off, s[base]): the
-// k-block dependent part of the address is a wave-uniform pointer, the lane part a loop-invariant byte offset
-// kept in ONE register, so no address arithmetic runs on the vector ALU inside the k loop.  That matters
-// because VALU instructions do not overlap f32 MFMAs on a SIMD (tools/mfma_peak.hip: ~3.5 cycles of
-// matrix-pipe time lost per VALU instruction).  The empty asm keeps the zero-extension next to the load;
-// hoisted out of the loop it would turn back into a 64-bit vector add per load.  pin_offsets() "redefines" the
-// loop-carried offset registers in place (no copy) and must run once per fetch, BEFORE any branch that
-// selects between load paths (a redefinition inside one arm costs a register copy per offset at the join).
 // LDS-direct staging: one global_load_lds_dwordx4 moves 16 bytes per lane from global memory straight into
 // LDS (no staging registers, no ds_write): the 64 lanes of a wave fill the 1 KB that starts at `lds_wave_base`
-// (wave-uniform) in lane order.  Completion is tracked by vmcnt; the engine waits for it before the barrier
-// that publishes the stage (engine2_step).
+// (wave-uniform) in lane order.  Completion is tracked by vmcnt: the kernel waits for it (wait_vmcnt) before the
+// barrier that publishes the stage.
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 __device__ __forceinline__ void ld16_to_lds(const void* uniform_base, uint32_t lane_bytes, float* lds_wave_base) {
@@ -75,30 +71,15 @@ __device__ __forceinline__ void wait_vmcnt() {
 // compiler keeps the arm behind its wave-uniform branch instead of hoisting / sinking its instructions
 // into the common path (which costs per-lane selects or register copies there).
 __device__ __forceinline__ void rare_path() { asm volatile("; rare path"); }
-template <int N>
-__device__ __forceinline__ void pin_offsets(uint32_t (&off)[N]) {
-#pragma unroll
-  for (int j = 0; j < N; ++j) asm volatile("" : "+v"(off[j]));
-}
-__device__ __forceinline__ f4 ld4_so(const void* uniform_base, uint32_t lane_bytes) {
-  return *(const f4*)((const char*)uniform_base + lane_bytes);
-}
 // a store written out in the scalar-base form (global_store_dword v_off, v_data, s[base]) measured 61 fewer vector instructions per
 // ConvFwd1 workgroup but ConvFwd2 2.36 -> 2.51 ms, iteration 25.18 -> 25.40 ms: not kept
 __device__ __forceinline__ void st1_so(void* uniform_base, uint32_t lane_bytes, float v) {
   *(float*)((char*)uniform_base + lane_bytes) = v;
 }
-__device__ __forceinline__ float ld1f_so(const void* uniform_base, uint32_t lane_bytes) {
-  return *(const float*)((const char*)uniform_base + lane_bytes);
-}
-__device__ __forceinline__ unsigned ld1u_so(const void* uniform_base, uint32_t lane_bytes) {
-  return *(const unsigned*)((const char*)uniform_base + lane_bytes);
-}
 
 // leaky_relu(v) = max(v, LEAKY * v) for a slope below one: one multiply + one max (bit-identical to the
 // compare/select form, signed zeros included)
 __device__ __forceinline__ float leaky_f(float v) { return __builtin_fmaxf(v, v * LEAKY); }
-__device__ __forceinline__ float leaky_g(float act, float g) { return act > 0.0f ? g : g * LEAKY; }
 // the same with the decision taken from bit `bit` of a sign mask (bit SET = act is not positive): g * LEAKY or g * 1 without a
 // compare (bfe, bfi, mul)
 __device__ __forceinline__ float leaky_bit(unsigned mask, int bit, float g) {
@@ -196,106 +177,24 @@ __device__ __forceinline__ void compute_block(const Op& op, const float* __restr
   }
 }
 
-// Ops may declare `static constexpr int OCC` = waves per SIMD the register allocator must leave
-// room for (second __launch_bounds__ argument); default 1.
-template <class Op, class = void>
-struct OccOf {
-  static constexpr int v = 1;
-};
-template <class Op>
-struct OccOf<Op, decltype((void)Op::OCC)> {
-  static constexpr int v = Op::OCC;
-};
-
-// Ops may declare `static constexpr int COMMIT_FIRST = 1`: commit + fetch run before the MFMA block
-// of each iteration instead of after it (measured per op: helps the conv weight gradients, whose
-// commits carry the ReLU masks / u8 conversions; hurts the forward and data-gradient kernels).
-template <class Op, class = void>
-struct CommitFirstOf {
-  static constexpr bool v = false;
-};
-template <class Op>
-struct CommitFirstOf<Op, decltype((void)Op::COMMIT_FIRST)> {
-  static constexpr bool v = Op::COMMIT_FIRST != 0;
-};
-
-// Ops may stage (part of) a k-block with LDS-direct loads: `static constexpr int DIRECT_PENDING` = number of
-// register-prefetch global loads fetch() issues (they are issued AFTER the direct loads of an iteration
-// and may stay in flight across the barrier), and direct(P, kb, stage) issues the direct loads of k-block kb.
-template <class Op, class = void>
-struct HasDirect {
-  static constexpr bool v = false;
-};
-template <class Op>
-struct HasDirect<Op, decltype((void)Op::DIRECT_PENDING)> {
-  static constexpr bool v = true;
-};
-template <class Op>
-__device__ __forceinline__ void wait_direct(bool fetch_in_flight) {
-  if constexpr (HasDirect<Op>::v) {
-    if constexpr (Op::DIRECT_PENDING == 0) {
-      wait_vmcnt<0>();
-    } else {
-      if (fetch_in_flight) wait_vmcnt<Op::DIRECT_PENDING>();
-      else wait_vmcnt<0>();
-    }
-  }
-}
-
-// Ops may define pre_epilogue(P): issued before the last k-block (see engine2_kernel).
-template <class Op, class = void>
-struct HasPreEpilogue {
-  static constexpr bool v = false;
-};
-template <class Op>
-struct HasPreEpilogue<Op, decltype((void)Op::PRE_EPILOGUE)> {
-  static constexpr bool v = true;
-};
-
 // One k-block of the pipeline with the LDS buffer index as a compile-time constant: every LDS address of
 // the block is then  lane register + immediate  (no per-iteration buffer arithmetic on the vector ALU).
-// BUF = -1: the buffer index is the run-time argument `rbuf` (the tail of the k loop, which also hosts the
-// pre-epilogue hook, is compiled once this way).
+// BUF = -1: the buffer index is the run-time argument `rbuf` (the tail of the k loop is compiled once this way).
 template <class Op, int BUF>
 __device__ __forceinline__ void engine2_step(Op& op, const typename Op::Params& P, int kb, int kbe, typename Op::Regs& regs,
                                              f32x16 (&acc)[Op::TM][Op::TN], float* lds2, int rbuf = 0) {
   float* cur = lds2 + (BUF < 0 ? rbuf : BUF) * Op::STAGE;
   float* nxt = lds2 + (BUF < 0 ? rbuf ^ 1 : BUF ^ 1) * Op::STAGE;
-  if constexpr (HasDirect<Op>::v) {
-    // LDS-direct part of the next stage: in flight under this block's MFMAs (the other buffer was released by
-    // the barrier that ended the previous block)
-    if (kb + 1 < kbe) op.direct(P, kb + 1, nxt);
-  }
-  op.extra(cur);
-  if constexpr (HasPreEpilogue<Op>::v && BUF < 0) {
-    // global loads the epilogue needs (e.g. the activations for the leaky-ReLU mask) are issued
-    // before the last k-block, so their latency hides under its MFMAs instead of being exposed
-    if (kb == kbe - 1) op.pre_epilogue(P);
-  }
-  if constexpr (CommitFirstOf<Op>::v) {
-    // ops with a VALU-heavy commit (masks, u8 conversion): write the NEXT stage and issue the
-    // following fetch before this block's MFMAs, so the scheduler can run them under the MFMAs
-    if (kb + 1 < kbe) {
-      op.commit(regs, nxt);
-      if (kb + 2 < kbe) op.fetch(P, kb + 2, regs);
-    }
-    compute_block<Op>(op, cur, lds2, acc);
-  } else {
-    compute_block<Op>(op, cur, lds2, acc);
-    if (kb + 1 < kbe) {
-      op.commit(regs, nxt);
-      if (kb + 2 < kbe) op.fetch(P, kb + 2, regs);
-    }
-  }
-  wait_direct<Op>(kb + 2 < kbe);
-  if constexpr (HasDirect<Op>::v) {
-    if (kb + 1 < kbe) op.direct_done(P, kb + 1, nxt);  // e.g. zero-fill of a ragged last k-block
+  compute_block<Op>(op, cur, lds2, acc);
+  if (kb + 1 < kbe) {
+    op.commit(regs, nxt);
+    if (kb + 2 < kbe) op.fetch(P, kb + 2, regs);
   }
   __syncthreads();
 }
 
 template <class Op>
-__global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(typename Op::Params P) {
+__global__ __launch_bounds__(Op::THREADS, 1) void engine2_kernel(typename Op::Params P) {
   extern __shared__ __attribute__((aligned(16))) float lds2[];
   Op op;
   const int tid = threadIdx.x;
@@ -312,17 +211,14 @@ __global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(type
   int kb = op.kb_begin;
   const int kbe = op.kb_end;
   if (kb < kbe) {
-    if constexpr (HasDirect<Op>::v) op.direct(P, kb, lds2);
     op.fetch(P, kb, regs);
     op.commit(regs, lds2);
     if (kb + 1 < kbe) op.fetch(P, kb + 1, regs);
-    wait_direct<Op>(kb + 1 < kbe);
-    if constexpr (HasDirect<Op>::v) op.direct_done(P, kb, lds2);
   }
   __syncthreads();
   // The loop is unrolled by the two LDS buffers (engine2_step) and leaves the last one or two k-blocks to a
   // tail with a run-time buffer index (an exit in the middle of the unrolled loop would cost a copy of every
-  // accumulator register per iteration; the tail also keeps the pre-epilogue registers out of the loop).
+  // accumulator register per iteration).
   for (; kb + 2 < kbe; kb += 2) {
     engine2_step<Op, 0>(op, P, kb, kbe, regs, acc, lds2);
     engine2_step<Op, 1>(op, P, kb + 1, kbe, regs, acc, lds2);
@@ -330,17 +226,6 @@ __global__ __launch_bounds__(Op::THREADS, OccOf<Op>::v) void engine2_kernel(type
   for (int rbuf = 0; kb < kbe; ++kb, rbuf ^= 1) engine2_step<Op, -1>(op, P, kb, kbe, regs, acc, lds2, rbuf);
   op.epilogue(P, acc, lds2);
 }
-
-// Ops may declare `static constexpr int EXTRA` = floats of LDS behind the two stage buffers that
-// live for the whole kernel (e.g. the bias vector for the epilogue); default 0.
-template <class Op, class = void>
-struct ExtraOf {
-  static constexpr int v = 0;
-};
-template <class Op>
-struct ExtraOf<Op, decltype((void)Op::EXTRA)> {
-  static constexpr int v = Op::EXTRA;
-};
 
 // Raises a kernel's dynamic shared-memory limit before its first launch: once per kernel (one flag per instantiation of a template)
 template <auto Kernel>
@@ -354,7 +239,7 @@ inline void lds_limit_once(int bytes) {
 
 template <class Op>
 inline void launch_engine2(dim3 grid, const typename Op::Params& p, hipStream_t st) {
-  constexpr size_t bytes = (size_t)(2 * Op::STAGE + ExtraOf<Op>::v) * sizeof(float);
+  constexpr size_t bytes = (size_t)(2 * Op::STAGE) * sizeof(float);
   if (bytes > 64 * 1024) lds_limit_once<engine2_kernel<Op>>((int)bytes);
   hipLaunchKernelGGL(engine2_kernel<Op>, grid, dim3(Op::THREADS), bytes, st, p);
 }
@@ -427,7 +312,6 @@ __device__ __forceinline__ frag8 tr_frag(const char* lds, int off_lo, int off_hi
 // 25.43 -> 25.37 ms (0.2 %) -- and the results are NOT the same bits: the conv1 weight gradient's mean error against float64 grows from
 // 1.0 x to 1.6 x that of an fp32 evaluation (products of a subnormal pixel with the small plane of dz1 lose bits inside the pipe), which
 // breaks tests/test_gpu_parity.py::test_conv1_weight_gradient_is_at_least_fp32_accurate.  Vector-ALU count is not what bounds these kernels.
-constexpr float PIXEL_UNIT = 1.0f;
 __device__ __forceinline__ unsigned pixel_pair(unsigned a, unsigned b) {
   const f16x2_t v = {(_Float16)(float)a, (_Float16)(float)b};
   return __builtin_bit_cast(unsigned, v);

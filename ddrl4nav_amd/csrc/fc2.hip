@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
 #pragma unroll
   for (int j = 0; j < 4; ++j) asrc[j] = a3 + e * a3_es + (int64_t)min(b0 + rr + 32 * j, n - 1) * FLAT + k4 * 4;
   const int k8 = tid & 3, cc = tid >> 2;
-  const unsigned short* wsrc = wlb + (int64_t)e * 3 * FLAT * FEAT + (int64_t)(n0 + cc) * FLAT + k8 * 8;
+  const unsigned short* wsrc = wlb + (int64_t)e * PLANE_ROOM * FLAT * FEAT + (int64_t)(n0 + cc) * FLAT + k8 * 8;
   int aA[2], bB[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) aA[i] = (wr * 64 + i * 32 + l31) * K::PITCH + hi * 16;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
   for (int j = 0; j < 2; ++j) {
     const int nn = n0 + wc * 64 + j * 32 + l31;
     const float bias = SPLIT ? 0.0f : params[(e ? bias_off1 : bias_off0) + nn];
-    float* dst = SPLIT ? part + ((int64_t)split * 2 + e) * n * FEAT : h + e * h_es;
+    float* dst = SPLIT ? part + ((int64_t)split * ENC_SLOTS + e) * n * FEAT : h + e * h_es;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -193,9 +193,8 @@ __global__ __launch_bounds__(256) void fc_fwd_planes_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
-void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool per_sample_max) {
+void launch_fc_forward(const EncCall& c, bool allow_split, hipStream_t st, bool per_sample_max) {
   const Workspace& w = *c.ws;
-  const int64_t MB = c.max_batch;
   const int nsplit = allow_split ? fc_forward_splits(c.n) : 1;  // 98 k-blocks = 14 x 7
   ProfRange pr(c.prof, nsplit > 1 ? "FcFwdSplit" : "FcFwd", st);
   {
@@ -203,12 +202,12 @@ void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool
     lds_limit_once<fc_fwd_planes_kernel<true>>((int)FcFwdB::LDS_BYTES);
     const dim3 grid(FEAT / 128, (c.n + 127) / 128, c.L->NE * nsplit);
     if (nsplit > 1)
-      hipLaunchKernelGGL(fc_fwd_planes_kernel<true>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, MB * FLAT, w.wlb, w.amax, c.params,
-                         c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, MB * FEAT, c.n, c.L->NE, nsplit, w.wpart,
+      hipLaunchKernelGGL(fc_fwd_planes_kernel<true>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, w.es(A3_N), w.wlb, w.amax, c.params,
+                         c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, w.es(H_N), c.n, c.L->NE, nsplit, w.wpart,
                          per_sample_max ? w.actmax : (const float*)nullptr, ACT_FUSED_MAX);
     else
-      hipLaunchKernelGGL(fc_fwd_planes_kernel<false>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, MB * FLAT, w.wlb, w.amax, c.params,
-                         c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, MB * FEAT, c.n, c.L->NE, 1, w.wpart,
+      hipLaunchKernelGGL(fc_fwd_planes_kernel<false>, grid, dim3(256), FcFwdB::LDS_BYTES, st, w.a3, w.es(A3_N), w.wlb, w.amax, c.params,
+                         c.L->enc_base[0] + c.L->enc.lb, c.L->enc_base[c.L->NE - 1] + c.L->enc.lb, w.h, w.es(H_N), c.n, c.L->NE, 1, w.wpart,
                          (const float*)nullptr, 0);
   }
 }
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
   const int n8 = tid % K::NWF, cc = tid / K::NWF;
   const unsigned short* wsrc[K::WJ];
 #pragma unroll
-  for (int j = 0; j < K::WJ; ++j) wsrc[j] = wdlb + (int64_t)e * 3 * FLAT * FEAT + (int64_t)min(k0 + cc + K::WCOLS * j, FLAT - 1) * FEAT + n8 * 8;
+  for (int j = 0; j < K::WJ; ++j) wsrc[j] = wdlb + (int64_t)e * PLANE_ROOM * FLAT * FEAT + (int64_t)min(k0 + cc + K::WCOLS * j, FLAT - 1) * FEAT + n8 * 8;
   int aA[2], bB[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) aA[i] = (wr * 64 + i * 32 + l31) * K::PITCH + hi * 16;
@@ -327,14 +326,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
     // channel = 32 i' + acc_row(r', hi') there -> word (b, pixel, hi'), bit 16 i' + 15 - r'; 51 MB instead of the 1.6 GB of a3
     const int ch = k / 49, pix = k % 49;
     const int mbit = 16 * (ch >> 5) + 15 - ((ch & 3) + 4 * ((ch & 31) >> 3));
-    const unsigned* mp = m3 + (int64_t)e * (a3_es / FLAT) * 98 + pix * 2 + ((ch >> 2) & 1);
+    const unsigned* mp = m3 + (int64_t)e * (a3_es / A3_N) * M3_N + pix * 2 + ((ch >> 2) & 1);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       unsigned mw[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int b = min(b0 + wr * 64 + i * 32 + acc_row(r, hi), n - 1);
-        mw[r] = mp[(int64_t)b * 98];
+        mw[r] = mp[(int64_t)b * M3_N];
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -363,7 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FcDgradB::W
 // ------------------------------------------------------------------------------------------------
 struct FcWgradB {
   static constexpr int KB = 32, PITCH = 320, PLANE = KB * PITCH, B_OFF = NPL * PLANE, LDS_BYTES = 2 * NPL * PLANE;
-  static constexpr int64_t SLAB = (int64_t)FEAT * FLAT + FEAT;  // weights then bias, like the arena (= FcWgradB::SLAB)
+  static constexpr int64_t SLAB = SLAB_FC;
 };
 
 __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __restrict__ dh, int64_t dh_es, const float* __restrict__ a3,
@@ -476,7 +475,7 @@ __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __res
       __syncthreads();
     }
   }
-  float* slab = part + ((int64_t)split * 2 + e) * K::SLAB;
+  float* slab = part + ((int64_t)split * ENC_SLOTS + e) * K::SLAB;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int k = k0 + wc * 64 + j * 32 + l31;
@@ -499,9 +498,8 @@ __global__ __launch_bounds__(256) void fc_wgrad_planes_kernel(const float* __res
   }
 }
 
-void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int part) {  // part: 0 = both, 1 = data gradient only, 2 = weight gradient only
+void launch_fc_backward(const EncCall& c, float* grads, hipStream_t st, int part) {  // part: 0 = both, 1 = data gradient only, 2 = weight gradient only
   const Workspace& w = *c.ws;
-  const int64_t MB = c.max_batch;
   const ParamLayout& L = *c.L;
   const int S = c.splits->fc;
   if (part != 1) {
@@ -509,7 +507,7 @@ void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int par
       ProfRange pr(c.prof, "FcWgrad", st);
       lds_limit_once<fc_wgrad_planes_kernel>((int)FcWgradB::LDS_BYTES);
       const dim3 wgrid((unsigned)((25 * L.NE * S + 7) / 8 * 32));
-      hipLaunchKernelGGL(fc_wgrad_planes_kernel, wgrid, dim3(256), FcWgradB::LDS_BYTES, st, w.dh, MB * FEAT, w.a3, MB * FLAT, w.amax, w.gsc, MB,
+      hipLaunchKernelGGL(fc_wgrad_planes_kernel, wgrid, dim3(256), FcWgradB::LDS_BYTES, st, w.dh, w.es(H_N), w.a3, w.es(A3_N), w.amax, w.gsc, w.es(1),
                          w.wpart, c.n, S, L.NE);
     }
     ProfRange pr(c.prof, "reduce_partials", st);
@@ -518,8 +516,8 @@ void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int par
   if (part != 2) {
     ProfRange pr(c.prof, "FcDgrad", st);
     lds_limit_once<fc_dgrad_planes_kernel>((int)FcDgradB::LDS_BYTES);
-    hipLaunchKernelGGL(fc_dgrad_planes_kernel, dim3((FLAT + 127) / 128, (c.n + 127) / 128, L.NE), dim3(256), FcDgradB::LDS_BYTES, st, w.dh, MB * FEAT,
-                       w.wdlb, w.amax, w.m3, w.dz3, MB * FLAT, c.n);
+    hipLaunchKernelGGL(fc_dgrad_planes_kernel, dim3((FLAT + 127) / 128, (c.n + 127) / 128, L.NE), dim3(256), FcDgradB::LDS_BYTES, st, w.dh, w.es(H_N),
+                       w.wdlb, w.amax, w.m3, w.dz3, w.es(A3_N), c.n);
   }
 }
 

@@ -32,7 +32,6 @@ struct Common {
   int l31, hi, wc;
   static constexpr int aoff(int s) { return 2 * s * LDA; }
   static constexpr int boff(int s) { return 2 * s * LDB; }
-  __device__ __forceinline__ void extra(const float*) {}
   __device__ __forceinline__ void lanes(int tid) {
     const int lane = tid & 63;
     wc = tid >> 6;

@@ -73,7 +73,6 @@ struct Common {
   int abase[2], bbase[2];
   int kb_begin, kb_end;
   int wr, wc, l31, hi;
-  __device__ __forceinline__ void extra(const float*) {}
   __device__ __forceinline__ void lanes(int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     l31 = lane & 31;

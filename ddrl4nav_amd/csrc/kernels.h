@@ -35,7 +35,6 @@ struct EncCall {
   const float* params;
   const uint8_t* frames;  // [n][4][84][84]
   int n;
-  int64_t max_batch;
   hipEvent_t* bucket_ev = nullptr;  // [GRAD_BUCKETS] or null (single rank: nothing to overlap)
   bool keep_acts = false;           // acting launches: also store a1 / a2 (ddrl_debug_keep_activations; the fused kernel of act.hip keeps them on chip)
 };
@@ -48,27 +47,27 @@ void launch_encoder_forward(const EncCall& c, bool acting, hipStream_t st);
 void launch_encoder_backward(const EncCall& c, float* grads, hipStream_t st, bool dh_normalised = false);
 void launch_backward_amax_reset(const EncCall& c, hipStream_t st);  // zeroes the gradient slots of Workspace::amax
 
-// fc2.hip (v2 engine)
+// fc2.hip
 // Split-K factor of the FC forward for a batch of n samples (1 = plain; >1 only on the acting
 // path, where heads_act sums the partials).  7 k-blocks of 32 per split.
 inline int fc_forward_splits(int n) { return n <= 1024 ? FC_ACT_SPLITS : 1; }
-void launch_fc_forward2(const EncCall& c, bool allow_split, hipStream_t st, bool per_sample_max = false);
-void launch_fc_backward2(const EncCall& c, float* grads, hipStream_t st, int part = 0);
+void launch_fc_forward(const EncCall& c, bool allow_split, hipStream_t st, bool per_sample_max = false);
+void launch_fc_backward(const EncCall& c, float* grads, hipStream_t st, int part = 0);
 
-// conv2.hip (v2 engine)
-void launch_conv_forward2(const EncCall& c, bool acting, hipStream_t st);
+// conv2.hip
+void launch_conv_forward(const EncCall& c, bool acting, hipStream_t st);
+void launch_conv_dgrad3(const EncCall& c, hipStream_t st);
+void launch_conv_dgrad2(const EncCall& c, hipStream_t st);
 
 // act.hip: conv1 + conv2 + conv3 of an acting forward in one launch, one workgroup per (sample, encoder); leaves a3 and every sample's
 // largest |a3| (Workspace::actmax), which the dense layer's split launch takes its plane scale from
 // (ACT_FUSED_MAX: common.h, next to the carve of Workspace::actmax)
 void launch_act_convs(const EncCall& c, hipStream_t st);
-void launch_conv_dgrad3_2(const EncCall& c, hipStream_t st);
-void launch_conv_dgrad2_2(const EncCall& c, hipStream_t st);
 
-// wgrad2.hip (v2 engine)
-void launch_conv_wgrad3_2(const EncCall& c, float* grads, hipStream_t st);
-void launch_conv_wgrad2_2(const EncCall& c, float* grads, hipStream_t st);
-void launch_conv_wgrad1_2(const EncCall& c, float* grads, hipStream_t st);
+// wgrad2.hip
+void launch_conv_wgrad3(const EncCall& c, float* grads, hipStream_t st);
+void launch_conv_wgrad2(const EncCall& c, float* grads, hipStream_t st);
+void launch_conv_wgrad1(const EncCall& c, float* grads, hipStream_t st);
 
 // optim.hip
 void launch_pack_weights(const Workspace& w, const ParamLayout& L, const float* params, hipStream_t st);

@@ -38,8 +38,8 @@ __device__ __forceinline__ void pack_fc_planes_body(const float* __restrict__ pa
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const float sc = plane_scale(amax[amax_idx(AMAX_WL, e)]);
   const float* src = params + L.enc_base[e] + L.enc.lw;
-  unsigned short* d = dst + (int64_t)e * 3 * FLAT * FEAT;
-  unsigned short* t = dst_t + (int64_t)e * 3 * FLAT * FEAT;
+  unsigned short* d = dst + (int64_t)e * PLANE_ROOM * FLAT * FEAT;
+  unsigned short* t = dst_t + (int64_t)e * PLANE_ROOM * FLAT * FEAT;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = n0 + ty + 8 * j, k = k0 + tx;

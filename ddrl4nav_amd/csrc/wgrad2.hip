@@ -91,7 +91,7 @@ struct Wgrad3P {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
   static_assert(98 * 8 * 8 * 4 <= LDS_BYTES, "the bias reduction reuses the buffers");
   static constexpr int WG_PER_CU = (WPE >= 2 && LDS_BYTES <= 80 * 1024) ? 2 : 1;
-  static constexpr int64_t SLAB = 64 * 576 + 64;
+  static constexpr int64_t SLAB = SLAB3;
 };
 
 __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(const float* __restrict__ a2, int64_t a2_es, const float* __restrict__ dz3,
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
       const int second = h && kl > 0, px = h ? (kl > 0 ? kl - 1 : 48) : kl;   // half 1: local 0 = sample 0's last pixel, then sample 1
       alive[h][t] = u < au ? 1.0f : 0.0f;
       a_s1 |= (unsigned)second << (h * 4 + t);
-      aoff[h][t] = second * FLAT + (c8 * 8) * 49 + px;                                       // + sample0 * FLAT, + c * 49
+      aoff[h][t] = second * A3_N + (c8 * 8) * C3_P + px;                                       // + sample0 * FLAT, + c * 49
       awr[h][t] = (h ? K::A1 : K::A0) + kl * 128 + ((c8 * 16) ^ (((kl >> 1) & 1) * 64));
       ared[h][t] = u < au ? (c8 * 98 + second * 49 + px) * 8 : -1;                            // slot of the unit's bias sums in the final reduction
     }
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
       const int u = tid + 256 * t, uc = min(u, bu - 1), c8 = uc / pxh, lp = uc % pxh;
       const int second = h && lp >= 27, pos = h ? (lp >= 27 ? lp - 27 : 54 + lp) : lp;       // half 1: rows 6..8 of sample 0, then sample 1
       b_s1 |= (unsigned)second << (h * 4 + t);
-      boff[h][t] = second * 5184 + (c8 * 8) * 81 + pos;                                       // + sample0 * 5184, + c * 81
+      boff[h][t] = second * A2_N + (c8 * 8) * C2_P + pos;                                       // + sample0 * 5184, + c * 81
       bwr[h][t] = (h ? K::B1 : K::B0) + (c8 >> 2) * (h ? K::B_HALF1 : K::B_HALF0) + lp * K::BP + (c8 & 3) * 16;
     }
   }
@@ -176,17 +176,17 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
     const int nb = K::NB1;
     if (j < nb) {
       const int second = (int)((b_s1 >> (h * 4 + j)) & 1u);
-      const int64_t base = (int64_t)(second && 2 * s0 + 1 >= n ? 2 * s0 * 5184 + boff[h][j] - 5184 : 2 * s0 * 5184 + boff[h][j]);
+      const int64_t base = (int64_t)(second && 2 * s0 + 1 >= n ? 2 * s0 * A2_N + boff[h][j] - A2_N : 2 * s0 * A2_N + boff[h][j]);
       const float* src = a2b + base;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) br[j][c] = src[c * 81];
+      for (int c = 0; c < 8; ++c) br[j][c] = src[c * C2_P];
     } else {
       const int t = j - nb;
       const int second = (int)((a_s1 >> (h * 4 + t)) & 1u);
-      const int64_t base = (int64_t)(second && 2 * s0 + 1 >= n ? 2 * s0 * FLAT + aoff[h][t] - FLAT : 2 * s0 * FLAT + aoff[h][t]);
+      const int64_t base = (int64_t)(second && 2 * s0 + 1 >= n ? 2 * s0 * A3_N + aoff[h][t] - A3_N : 2 * s0 * A3_N + aoff[h][t]);
       const float* src = dzb + base;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) ar[t][c] = src[c * 49];
+      for (int c = 0; c < 8; ++c) ar[t][c] = src[c * C3_P];
     }
   };
   auto commit_unit = [&](int h, int j, float g0, float g1) __attribute__((always_inline)) {  // g = the samples' g_s (0: absent sample)
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
     }
   }
   // ---- epilogue: slab[oc][ic][tap] (torch layout of conv3.weight), then the bias partial
-  float* slab = part + ((int64_t)split * 2 + e) * K::SLAB;
+  float* slab = part + ((int64_t)split * ENC_SLOTS + e) * K::SLAB;
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -319,17 +319,16 @@ __global__ __launch_bounds__(256, Wgrad3P::WPE) void conv_wgrad3_pipe_kernel(con
   }
 }
 
-void launch_conv_wgrad3_2(const EncCall& c, float* grads, hipStream_t st) {
+void launch_conv_wgrad3(const EncCall& c, float* grads, hipStream_t st) {
   const Workspace& w = *c.ws;
-  const int64_t MB = c.max_batch;
   const ParamLayout& L = *c.L;
   const int want = 256 * Wgrad3P::WG_PER_CU / L.NE;  // as many workgroups as fit the chip at once
   const int S = c.splits->c3 < want ? c.splits->c3 : want;
   {
     lds_limit_once<conv_wgrad3_pipe_kernel>((int)Wgrad3P::LDS_BYTES);
     ProfRange pr(c.prof, "ConvWgrad3", st);
-    hipLaunchKernelGGL(conv_wgrad3_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad3P::LDS_BYTES, st, w.a2, MB * 5184, w.dz3, MB * FLAT,
-                       w.amax, w.gsc, MB, w.wpart, c.n, S, L.NE);
+    hipLaunchKernelGGL(conv_wgrad3_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad3P::LDS_BYTES, st, w.a2, w.es(A2_N), w.dz3, w.es(A3_N),
+                       w.amax, w.gsc, w.es(1), w.wpart, c.n, S, L.NE);
   }
   ProfRange pr(c.prof, "reduce_partials", st);
   launch_reduce_partials(w.wpart, S, Wgrad3P::SLAB, L.NE, grads, L.enc_base[0] + L.enc.c3w, L.enc_base[1] + L.enc.c3w, st);
@@ -368,7 +367,7 @@ struct Wgrad2P {
   static_assert(AU0 <= 256 * NA && AU1 <= 256 * NA && BU0 <= 256 * NBU && BU1 <= 256 * NBU, "units per thread");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
   static_assert(648 * 8 * 4 <= LDS_BYTES, "the bias reduction reuses the buffers");
-  static constexpr int64_t SLAB = 64 * 512 + 64;
+  static constexpr int64_t SLAB = SLAB2;
 };
 
 __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __restrict__ a1, int64_t a1_es, const float* __restrict__ dz2,
@@ -406,14 +405,14 @@ __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __re
     for (int t = 0; t < K::NA; ++t) {
       const int u = tid + 256 * t, uc = min(u, au - 1), c8 = uc / kaph, kl = uc % kaph;
       alive[h][t] = u < au ? 1.0f : 0.0f;
-      aoff[h][t] = (c8 * 8) * 81 + kap0 + kl;                                      // + sample * 5184, + c * 81
+      aoff[h][t] = (c8 * 8) * C2_P + kap0 + kl;                                      // + sample * 5184, + c * 81
       awr[h][t] = abase + kl * 128 + ((c8 * 16) ^ (((kl >> 1) & 1) * 64));
       ared[h][t] = u < au ? (c8 * 81 + kap0 + kl) * 8 : -1;                        // slot of the unit's bias sums in the final reduction
     }
 #pragma unroll
     for (int t = 0; t < K::NBU; ++t) {
       const int u = tid + 256 * t, uc = min(u, bu - 1), c8 = uc / pxh, pos = uc % pxh;
-      boff[h][t] = (c8 * 8) * 400 + (h ? K::ROW1 * 20 : 0) + pos;                  // + sample * 12800, + c * 400
+      boff[h][t] = (c8 * 8) * C1_P + (h ? K::ROW1 * 20 : 0) + pos;                  // + sample * 12800, + c * 400
       bwr[h][t] = bbase + pos * K::BP + c8 * 16;
     }
   }
@@ -446,13 +445,13 @@ __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __re
   constexpr int NU = K::NBU + K::NA;
   auto fetch_unit = [&](int h, int j, int s) __attribute__((always_inline)) {
     if (j < K::NBU) {
-      const float* src = a1b + (int64_t)s * 12800 + boff[h][j];
+      const float* src = a1b + (int64_t)s * A1_N + boff[h][j];
 #pragma unroll
-      for (int c = 0; c < 8; ++c) br[j][c] = src[c * 400];
+      for (int c = 0; c < 8; ++c) br[j][c] = src[c * C1_P];
     } else {
-      const float* src = dzb + (int64_t)s * 5184 + aoff[h][j - K::NBU];
+      const float* src = dzb + (int64_t)s * A2_N + aoff[h][j - K::NBU];
 #pragma unroll
-      for (int c = 0; c < 8; ++c) ar[j - K::NBU][c] = src[c * 81];
+      for (int c = 0; c < 8; ++c) ar[j - K::NBU][c] = src[c * C2_P];
     }
   };
   // the four-instruction split (engine2.h split_planes); the plain split_planes_c, which the compiler packs into v_pk_mul / v_pk_fma
@@ -554,7 +553,7 @@ __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __re
     }
   }
   // ---- epilogue: slab[oc][ic][ky][kx] (torch layout of conv2.weight), then the bias partial
-  float* slab = part + ((int64_t)split * 2 + e) * K::SLAB;
+  float* slab = part + ((int64_t)split * ENC_SLOTS + e) * K::SLAB;
 #pragma unroll
   for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -577,17 +576,16 @@ __global__ __launch_bounds__(256) void conv_wgrad2_pipe_kernel(const float* __re
   }
 }
 
-void launch_conv_wgrad2_2(const EncCall& c, float* grads, hipStream_t st) {
+void launch_conv_wgrad2(const EncCall& c, float* grads, hipStream_t st) {
   const Workspace& w = *c.ws;
-  const int64_t MB = c.max_batch;
   const ParamLayout& L = *c.L;
   const int want = 256 / L.NE;  // as many workgroups as fit the chip at once (106.5 KB of LDS: one per CU)
   const int S = c.splits->c2 < want ? c.splits->c2 : want;
   {
     ProfRange pr(c.prof, "ConvWgrad2", st);
     lds_limit_once<conv_wgrad2_pipe_kernel>((int)Wgrad2P::LDS_BYTES);
-    hipLaunchKernelGGL(conv_wgrad2_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad2P::LDS_BYTES, st, w.a1, MB * 12800, w.dz2, MB * 5184,
-                       w.amax, w.gsc, MB, w.wpart, c.n, S, L.NE);
+    hipLaunchKernelGGL(conv_wgrad2_pipe_kernel, dim3((unsigned)(L.NE * S)), dim3(256), Wgrad2P::LDS_BYTES, st, w.a1, w.es(A1_N), w.dz2, w.es(A2_N),
+                       w.amax, w.gsc, w.es(1), w.wpart, c.n, S, L.NE);
   }
   ProfRange pr(c.prof, "reduce_partials", st);
   launch_reduce_partials(w.wpart, S, Wgrad2P::SLAB, L.NE, grads, L.enc_base[0] + L.enc.c2w, L.enc_base[1] + L.enc.c2w, st);
@@ -613,7 +611,6 @@ struct Wgrad1B {
   // k-blocks (output rows) share 4 of their 8 input rows, so only the 4 new ones are loaded, converted and written per block
   static constexpr int IMG_OFF = 2 * A_BYTES, IMG_BYTES = 2 * 4 * 16 * 192 + 64, STAGE = A_BYTES;
   static constexpr int TPE = 256 / NE, QPE = 2 * 32 * 5, NDZ_J = (QPE + TPE - 1) / TPE;
-  static constexpr int64_t SLAB = 32 * 256 + 32;
   static constexpr size_t LDS_BYTES = 2 * A_BYTES + IMG_BYTES;
 };
 
@@ -643,8 +640,8 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
   for (int j = 0; j < K::NDZ_J; ++j) {
     const int idx = te + K::TPE * j, c = min(idx, K::QPE - 1);
     const int row5 = c / 5, q4 = c % 5, smp = row5 >> 5, oc = row5 & 31, f = q4 >> 1, half = q4 & 1;
-    dzoff[j] = (uint32_t)((smp * 12800 + oc * 400 + q4 * 4) * 4);
-    mcol[j] = (uint32_t)((smp * 400 + q4 * 4) * 4);  // byte offset of the quad's four mask words inside the pair's output row
+    dzoff[j] = (uint32_t)((smp * A1_N + oc * C1_P + q4 * 4) * 4);
+    mcol[j] = (uint32_t)((smp * M1_N + q4 * 4) * 4);  // byte offset of the quad's four mask words inside the pair's output row
     mbit[j] = m1_bit(oc);
     adst[j] = ((smp * 3 + f) * NPL * K::ROWS + ew * 32 + oc) * 16 + half * 8;
     dz_s1 |= (unsigned)smp << j;
@@ -708,17 +705,17 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
 #pragma unroll
       for (int j = 0; j < K::NDZ_J; ++j) gsj[j] = ld_gs(gs, min(2 * pair + (int)((dz_s1 >> j) & 1u), n - 1));
     }
-    const int64_t sb = ew * dz_es + (int64_t)pair * (2 * 12800) + oy * 20;
+    const int64_t sb = ew * dz_es + (int64_t)pair * (2 * A1_N) + oy * 20;
     const char* dzb = (const char*)(dz + sb);
-    const char* mb = (const char*)(m1 + ew * m1_es + (int64_t)pair * 800 + oy * 20);
+    const char* mb = (const char*)(m1 + ew * m1_es + (int64_t)pair * (2 * M1_N) + oy * 20);
     const char* fp = (const char*)frames + (int64_t)pair * (2 * fs) + (oy + gfirst) * 336;
     // odd batch tail: the second sample does not exist -> its slots read the first sample, commit() zeroes its dz
 #pragma unroll
     for (int j = 0; j < K::NDZ_J; ++j) {
-      const uint32_t o = full ? dzoff[j] : dzoff[j] - ((dz_s1 >> j) & 1u) * (12800u * 4u);
+      const uint32_t o = full ? dzoff[j] : dzoff[j] - ((dz_s1 >> j) & 1u) * ((uint32_t)A1_N * 4u);
       dzr[j] = *(const f4*)(dzb + o);
       // the lanes of one (sample, quad) -- all 32 output channels -- read the same 16 bytes: one cache line per wave instruction
-      mkr[j] = *(const u4w*)(mb + (full ? mcol[j] : mcol[j] - ((dz_s1 >> j) & 1u) * 1600u));
+      mkr[j] = *(const u4w*)(mb + (full ? mcol[j] : mcol[j] - ((dz_s1 >> j) & 1u) * ((uint32_t)M1_N * 4u)));
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -820,11 +817,11 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
   // slabs [32 oc][64 C taps] + [32] (the arena's conv1.weight, conv1.bias): weights (scaled by the 1/255 of the frame
   // normalisation), then the bias partial
   const int ktaps = 64 * C;
-  const int64_t slab_floats = 32 * ktaps + 32;
+  const int64_t slab_floats = slab1_floats(C);
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
-    const float r255 = amax[amax_idx(AMAX_GMAX, i)] * PIXEL_UNIT / (255.0f * WGRAD_HEADROOM * plane_scale(amax[amax_idx(AMAX_DZ1, i)]));
-    float* slab = part + ((int64_t)split * 2 + i) * slab_floats;
+    const float r255 = amax[amax_idx(AMAX_GMAX, i)] / (255.0f * WGRAD_HEADROOM * plane_scale(amax[amax_idx(AMAX_DZ1, i)]));
+    float* slab = part + ((int64_t)split * ENC_SLOTS + i) * slab_floats;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int col = wc * 64 + j * 32 + l31;
@@ -846,7 +843,7 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
     for (int smp = 0; smp < 2; ++smp)
 #pragma unroll
       for (int q = 0; q < 5; ++q) sum += red[e * K::QPE + (smp * 32 + oc) * 5 + q];
-    part[((int64_t)split * 2 + e) * slab_floats + 32 * ktaps + oc] = sum;
+    part[((int64_t)split * ENC_SLOTS + e) * slab_floats + 32 * ktaps + oc] = sum;
   }
 }
 
@@ -855,11 +852,11 @@ static void launch_wgrad1_planes(const EncCall& c, int S, hipStream_t st) {
   using K = Wgrad1B<NE>;
   const Workspace& w = *c.ws;
   lds_limit_once<conv_wgrad1_planes_kernel<NE>>((int)K::LDS_BYTES);
-  hipLaunchKernelGGL(conv_wgrad1_planes_kernel<NE>, dim3(1, S, 1), dim3(256), K::LDS_BYTES, st, c.frames, w.dz1, w.m1, m1_words(c.max_batch),
-                     c.max_batch * 12800, w.amax, w.gsc, c.max_batch, w.wpart, c.n, S, c.L->C);
+  hipLaunchKernelGGL(conv_wgrad1_planes_kernel<NE>, dim3(1, S, 1), dim3(256), K::LDS_BYTES, st, c.frames, w.dz1, w.m1, w.es(M1_N),
+                     w.es(A1_N), w.amax, w.gsc, w.es(1), w.wpart, c.n, S, c.L->C);
 }
 
-void launch_conv_wgrad1_2(const EncCall& c, float* grads, hipStream_t st) {
+void launch_conv_wgrad1(const EncCall& c, float* grads, hipStream_t st) {
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
   const int S = c.splits->c1;
@@ -872,7 +869,7 @@ void launch_conv_wgrad1_2(const EncCall& c, float* grads, hipStream_t st) {
     }
   }
   ProfRange pr(c.prof, "reduce_partials", st);
-  launch_reduce_partials(w.wpart, S, (int64_t)32 * 64 * L.C + 32, L.NE, grads, L.enc_base[0] + L.enc.c1w, L.enc_base[1] + L.enc.c1w, st);
+  launch_reduce_partials(w.wpart, S, slab1_floats(L.C), L.NE, grads, L.enc_base[0] + L.enc.c1w, L.enc_base[1] + L.enc.c1w, st);
 }
 
 }  // namespace ddrl

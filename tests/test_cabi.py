@@ -164,6 +164,50 @@ def test_conv_host_side_answers_are_pinned():
         assert answers(_lib.ConvDesc(3, 64, 22, 22, 128, 5, 5, 1, 1, 1, dense + extra, 0)) == (829376, 2049350, 3, 1, 1)
 
 
+# (share_cnn_net, in_channels, n_actions) -> (n_params, n_actor, [workspace bytes at each max_batch of ATARI_HOST_ANSWERS_MBS]).  Recorded from the
+# library of the commit before the workspace sizes got their names in csrc/common.h: what callers allocate by.  The batches lie on
+# both sides of every cap of choose_splits (pairs against 256 / 512 splits, 32-sample tiles against 5 / 10) and of the 1024 cap of the
+# acting path's partial sums, and end at the last supported size.
+ATARI_HOST_ANSWERS = {
+    (0, 1, 2): (3357507, 1679010, [55256832, 55608064, 80756480, 297606400, 477529344, 477882112, 1557067008, 23147820288, 29596230912]),
+    (0, 1, 6): (3359559, 1681062, [57353984, 57705216, 82854144, 299711744, 479642880, 479995648, 1559229696, 23150966016, 29599670272]),
+    (0, 1, 18): (3365715, 1687218, [63645440, 63996672, 89147392, 306027776, 485983488, 486336256, 1565717760, 23160403200, 29609988096]),
+    (0, 4, 2): (3369795, 1685154, [55256832, 55608064, 80756480, 297606400, 477529344, 477882112, 1557067008, 23147820288, 29596230912]),
+    (0, 4, 6): (3371847, 1687206, [57353984, 57705216, 82854144, 299711744, 479642880, 479995648, 1559229696, 23150966016, 29599670272]),
+    (0, 4, 18): (3378003, 1693362, [63645440, 63996672, 89147392, 306027776, 485983488, 486336256, 1565717760, 23160403200, 29609988096]),
+    (1, 1, 2): (1679523, 1679523, [55256832, 55608064, 80756480, 350469376, 553157888, 553510656, 1632695552, 23223448832, 29671859456]),
+    (1, 1, 6): (1681575, 1681575, [57353984, 57705216, 82854144, 352574720, 555271424, 555624192, 1634858240, 23226594560, 29675298816]),
+    (1, 1, 18): (1687731, 1687731, [63645440, 63996672, 89147392, 358890752, 561612032, 561964800, 1641346304, 23236031744, 29685616640]),
+    (1, 4, 2): (1685667, 1685667, [55256832, 55608064, 80756480, 350469376, 553157888, 553510656, 1632695552, 23223448832, 29671859456]),
+    (1, 4, 6): (1687719, 1687719, [57353984, 57705216, 82854144, 352574720, 555271424, 555624192, 1634858240, 23226594560, 29675298816]),
+    (1, 4, 18): (1693875, 1693875, [63645440, 63996672, 89147392, 358890752, 561612032, 561964800, 1641346304, 23236031744, 29685616640]),
+}
+ATARI_HOST_ANSWERS_MBS = (1, 2, 37, 512, 1024, 1025, 4096, 65536, 83886)
+
+
+def test_atari_host_side_answers_are_pinned():
+    """ddrl_workspace_bytes and ddrl_param_count of the Atari context over both prenet arrangements, 1 and 4 stacked frames and 2 / 6 / 18
+    actions.  A size query that disagrees with carve() or with a launcher's stride is a device buffer overrun, so the exact values
+    are pinned; a context serves every batch up to its max_batch, so the byte count never decreases with it."""
+    from ctypes import byref, c_int64
+    lib = _lib.load()
+
+    def answers(shared, C, A, mb):
+        cfg = _lib.default_config(max_batch=mb, share_cnn_net=shared, in_channels=C, n_actions=A)
+        n, na, wb = c_int64(), c_int64(), c_int64()
+        _lib.check(lib.ddrl_param_count(byref(cfg), byref(n), byref(na)))
+        _lib.check(lib.ddrl_workspace_bytes(byref(cfg), byref(wb)))
+        return wb.value, n.value, na.value
+
+    assert len(ATARI_HOST_ANSWERS) == 12
+    for (shared, C, A), (n_params, n_actor, per_mb) in ATARI_HOST_ANSWERS.items():
+        for mb, nbytes in zip(ATARI_HOST_ANSWERS_MBS, per_mb):
+            assert answers(shared, C, A, mb) == (nbytes, n_params, n_actor), (shared, C, A, mb)
+    for shared, C, A in ((0, 4, 6), (1, 1, 18)):
+        sizes = [answers(shared, C, A, mb)[0] for mb in range(1, 2049)]
+        assert all(lo <= hi for lo, hi in zip(sizes, sizes[1:])), (shared, C, A)
+
+
 # (K, N) -> (wt_floats, wn_floats, [(ws_floats, uses_planes) at n = 1, 127, 128, 300, 4096, 65536]).  Recorded from the library before the
 # dense routing moved into linear_route (csrc/api_ops.hip): what callers size their buffers by.
 LINEAR_HOST_ANSWERS = {

@@ -867,3 +867,47 @@ def test_gradient_buckets_cover_the_arena_and_the_overlapped_allreduce_is_the_fl
         res.append((h.params.cpu().numpy().copy(), h.stats()))
         h.close()
     assert np.array_equal(res[0][0], res[1][0]) and res[0][1] == res[1][1]
+
+
+# (max_batch, share_cnn_net, in_channels) -> ([(byte offset from the workspace base, enc_stride) of ddrl_debug_buffer(which = 0..14)],
+# [[(offset, count), ...] of each gradient bucket]).  Recorded from the library of the commit before the workspace sizes got their
+# names in csrc/common.h.  The contexts are the smallest that show both encoder slots, an odd batch and 1 stacked frame in the numbers.
+CTX_ANSWERS = {
+    (3, 0, 4): ([(40407296, 38400), (40730880, 15552), (40855296, 9408), (40930560, 1536), (40942848, 38400), (41250048, 15552),
+                 (41374464, 9408), (41449728, 1536), (41462272, 0), (41462528, 0), (40714496, 1200), (40724224, 486), (40728320, 294),
+                 (41462016, 3), (38633472, 1)],
+                [[(1684128, 3591), (3371847, 8)], [(0, 8224), (1687719, 8224)], [(77984, 1606144), (1765703, 1606144)],
+                 [(41056, 36928), (1728775, 36928)], [(8224, 32832), (1695943, 32832)]]),
+    (37, 1, 1): ([(40407296, 473600), (44391936, 191808), (45926400, 116032), (46854656, 18944), (47006208, 473600), (50795008, 191808),
+                  (52329472, 116032), (53257728, 18944), (53409792, 0), (53410816, 0), (44196096, 14800), (44314624, 5994),
+                  (44362752, 3626), (53409280, 37), (38633472, 1)],
+                 [[(1677984, 3591), (1681575, 8)], [(0, 2080)], [(71840, 1606144)], [(34912, 36928)], [(2080, 32832)]]),
+}
+
+
+@pytest.mark.parametrize("max_batch,shared,channels", sorted(CTX_ANSWERS))
+def test_context_views_and_buckets_are_pinned(max_batch, shared, channels):
+    """Where ddrl_debug_buffer finds every workspace tensor, the encoder stride it reports, and the ranges of the gradient buckets: the
+    tests and the all-reduce address device memory by them."""
+    from ctypes import byref, c_int64, c_void_p
+    from ddrl4nav_amd._lib import check
+    from ddrl4nav_amd.engine import HotPath
+    want_views, want_buckets = CTX_ANSWERS[(max_batch, shared, channels)]
+    hp = HotPath(max_batch, in_channels=channels, share_cnn_net=shared)
+    try:
+        hp.params.normal_(0, 0.02)
+        hp.params_changed()
+        frames = torch.randint(0, 256, (max_batch, channels, 84, 84), dtype=torch.uint8, device="cuda")
+        z = torch.zeros(max_batch, dtype=torch.float32, device="cuda")
+        hp.ppo_iter(frames, z, z.clone(), torch.ones_like(z), z.clone())  # a1 / a2 are stored: which = 0 / 1 are not refused
+        torch.cuda.synchronize()
+        views = []
+        for which in range(15):
+            p, es = c_void_p(), c_int64()
+            check(hp.lib.ddrl_debug_buffer(hp.ctx, which, byref(p), byref(es)))
+            views.append((p.value - hp.workspace.data_ptr(), es.value))
+        assert views == want_views
+        hp.enable_overlap()
+        assert hp.grad_buckets() == want_buckets
+    finally:
+        hp.close()
