@@ -176,6 +176,12 @@ SIGNATURES = {
     "ddrl_op_heads_bc_loss": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_gather_rows_u8": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_moments_ws_floats": (c_int32, [c_int64, POINTER(c_int64)]),
+    "ddrl_op_moments": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_moments_affine": (c_int32, [c_void_p, c_double, c_void_p, c_void_p]),
+    "ddrl_op_normalize": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_gather_minibatch": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -194,17 +200,36 @@ def load():
     # the two).  Loading in the other order leaves two HIP runtimes in one process.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.ddrl_abi_version()
-    if got != ABI_VERSION:
-        raise DdrlError("libddrl_hip.so ABI version %d, this binding needs %d: rebuild with `make -C ddrl4nav_amd/csrc`"
-                        % (got, ABI_VERSION))
+    _bind(lib)
     _lib = lib
     _warn_removed_switches()
     return lib
+
+
+def _bind(lib):
+    """Set restype / argtypes of every symbol of SIGNATURES on `lib`.  The ABI version is asked first, and a symbol the library does
+    not export -- an additive entry point newer than the build -- is the same DdrlError with the rebuild hint, not an AttributeError."""
+    hint = "rebuild with `make -C ddrl4nav_amd/csrc`"
+    try:
+        version = lib.ddrl_abi_version
+    except AttributeError:
+        raise DdrlError("libddrl_hip.so does not export ddrl_abi_version: %s" % hint) from None
+    version.restype, version.argtypes = SIGNATURES["ddrl_abi_version"]
+    got = version()
+    if got != ABI_VERSION:
+        raise DdrlError("libddrl_hip.so ABI version %d, this binding needs %d: %s" % (got, ABI_VERSION, hint))
+    missing = []
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.restype = res
+        fn.argtypes = args
+    if missing:
+        raise DdrlError("libddrl_hip.so (ABI version %d) was built before this binding and does not export %s: %s"
+                        % (got, ", ".join(missing), hint))
 
 
 # environment switches of earlier rounds that no longer do anything (INTEGRATION.md): a launch script that still sets one keeps running,

@@ -6,15 +6,13 @@
 // for bit), its partial row is DIAG_SLOTS doubles and its reduce map adds them up (slot 7: the larger).  It reads only.
 #include "heads_common.h"
 #include "kernels.h"
+#include "rows.h"
 
 namespace ddrl {
 
 constexpr int DIAG_WAVES = 4;   // waves per workgroup: they share the LDS copy of the head weights
 constexpr int DIAG_NS = 4;      // samples per wave and turn: the softmax / log / exp chain runs once per NS samples (as heads_loss)
 constexpr int DIAG_MAXD = 8, DIAG_MAXA = 18;
-
-// the larger of two non-negative doubles; a NaN stays visible
-__device__ __forceinline__ double diag_max(double a, double b) { return (a > b || a != a) ? a : b; }
 
 // LDS: [MAXN actor rows][critic row][MAXN actor bias][MAXN var][MAXN log(std)][critic bias].  Rows >= L.n are neither staged nor read.
 template <int MAXN, bool CONT>
@@ -151,28 +149,7 @@ __global__ __launch_bounds__(DIAG_WAVES * 64) void heads_diag_kernel(
   if (threadIdx.x < DIAG_SLOTS) part[(int64_t)blockIdx.x * DIAG_SLOTS + threadIdx.x] = red[threadIdx.x];
 }
 
-// Reduce map of the diagnostics: one wave per slot walks the workgroups' rows (ascending, 64 apart per lane) and folds its lanes with
-// the xor butterfly -- a fixed order; slot 7 takes the larger instead of the sum.  No atomics.
-__global__ __launch_bounds__(DIAG_SLOTS * 64) void heads_diag_reduce_kernel(const double* __restrict__ part, int nwg,
-                                                                            double* __restrict__ sums, int accumulate) {
-  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool is_max = (k == DIAG_SLOTS - 1);
-  double s = 0.0;
-  for (int w = lane; w < nwg; w += 64) {
-    const double x = part[(int64_t)w * DIAG_SLOTS + k];
-    s = is_max ? diag_max(s, x) : s + x;
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double y = __shfl_xor(s, off, 64);
-    s = is_max ? diag_max(s, y) : s + y;
-  }
-  if (lane == 0) {
-    if (accumulate) s = is_max ? diag_max(sums[k], s) : sums[k] + s;
-    sums[k] = s;
-  }
-}
-
+// Reduce map of the diagnostics: rows.h rows_fold_kernel adds the workgroups' rows up in a fixed order; slot 7 takes the larger.
 void launch_heads_diag(const DiagCall& c, const float* actions, const float* old_logps, const float* rets, double* sums8,
                        int accumulate, float* logp_out, float* value_out, hipStream_t st) {
   const int per_wg = DIAG_WAVES * DIAG_NS;
@@ -182,7 +159,8 @@ void launch_heads_diag(const DiagCall& c, const float* actions, const float* old
                            : (c.L.n <= 8 ? heads_diag_kernel<8, false> : heads_diag_kernel<DIAG_MAXA, false>);
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(DIAG_WAVES * 64), 0, st, c.h, c.h_es, c.params, c.L, c.ppo_clip, c.n, actions, old_logps,
                      rets, c.part, logp_out, value_out);
-  hipLaunchKernelGGL(heads_diag_reduce_kernel, dim3(1), dim3(DIAG_SLOTS * 64), 0, st, (const double*)c.part, wgs, sums8, accumulate);
+  hipLaunchKernelGGL((rows_fold_kernel<DIAG_SLOTS, DIAG_SLOTS - 1>), dim3(1), dim3(DIAG_SLOTS * 64), 0, st, (const double*)c.part, wgs, sums8,
+                     accumulate);
 }
 
 }  // namespace ddrl

@@ -6,6 +6,7 @@
 //                                           through actor_linear; the reference's own expression cannot run on a PPO net)
 //   DataLoader(dataset, batch, shuffle)     USTC_lab/nn/base.py:128,140-141 (the per-batch collation of the shuffled samples)
 #include "heads_common.h"
+#include "rows.h"
 
 namespace ddrl {
 
@@ -184,30 +185,14 @@ struct BcReduce {
 };
 
 // ---- minibatch gather --------------------------------------------------------------------------------------------------------------
-// dst[i][:] = src[idx[i]][:] in 16-byte units.  A 256-thread workgroup moves GATHER_UNROLL x 256 consecutive units of one row (both loads
-// requested before the first store): a 7,056-byte frame is one workgroup, a four-frame stack four.  The row index is uniform per
-// workgroup.  An index outside [0, n_rows) reads nothing: a zero row, label -1.
-constexpr int GATHER_THREADS = 256, GATHER_UNROLL = 2, GATHER_CHUNK = GATHER_THREADS * GATHER_UNROLL;
-
+// dst[i][:] = src[idx[i]][:] by the row mover of rows.h.  An index outside [0, n_rows) reads nothing: a zero row, label -1.
 __global__ __launch_bounds__(GATHER_THREADS) void gather_rows_kernel(const uint4* __restrict__ src, int64_t n_rows, int64_t row_vecs,
                                                                       int chunks, const int32_t* __restrict__ idx, uint4* __restrict__ dst,
                                                                       const float* __restrict__ labels_src, float* __restrict__ labels_dst) {
   const int i = blockIdx.x / chunks, c = blockIdx.x % chunks;
   const int64_t r = idx[i];
   const bool ok = r >= 0 && r < n_rows;
-  const int64_t u0 = (int64_t)c * GATHER_CHUNK + threadIdx.x;
-  uint4 v[GATHER_UNROLL];
-#pragma unroll
-  for (int t = 0; t < GATHER_UNROLL; ++t) {
-    const int64_t u = u0 + t * GATHER_THREADS;
-    v[t] = make_uint4(0u, 0u, 0u, 0u);
-    if (ok && u < row_vecs) v[t] = src[r * row_vecs + u];
-  }
-#pragma unroll
-  for (int t = 0; t < GATHER_UNROLL; ++t) {
-    const int64_t u = u0 + t * GATHER_THREADS;
-    if (u < row_vecs) dst[(int64_t)i * row_vecs + u] = v[t];
-  }
+  gather_row_chunk(src, r, ok, row_vecs, c, i, dst);
   if (labels_dst != nullptr && c == 0 && threadIdx.x == 0) labels_dst[i] = ok ? labels_src[r] : -1.0f;
 }
 
@@ -255,11 +240,11 @@ int32_t ddrl_op_gather_rows_u8(const uint8_t* src, int64_t n_rows, int64_t row_b
   if ((labels_src == nullptr) != (labels_dst == nullptr)) return DDRL_ERR_INVALID_ARG;
   if (n_rows > INT64_MAX / row_bytes) return DDRL_ERR_INVALID_ARG;
   if (overlap(src, dst, (uint64_t)n_rows * row_bytes, (uint64_t)n * row_bytes)) return DDRL_ERR_INVALID_ARG;
-  const int64_t row_vecs = row_bytes / 16;
-  const int64_t chunks = (row_vecs + GATHER_CHUNK - 1) / GATHER_CHUNK;
-  if (chunks > INT32_MAX / n) return DDRL_ERR_INVALID_ARG;
+  int64_t row_vecs;
+  int chunks;
+  if (!gather_grid(row_bytes, n, &row_vecs, &chunks)) return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(n * chunks)), dim3(GATHER_THREADS), 0, (hipStream_t)stream, (const uint4*)src,
-                     n_rows, row_vecs, (int)chunks, idx, (uint4*)dst, labels_src, labels_dst);
+                     n_rows, row_vecs, chunks, idx, (uint4*)dst, labels_src, labels_dst);
   return launch_status();
 }
 

@@ -486,6 +486,8 @@ class GenericPPO(Basenn):
         super().__init__(config, config_nn)
         # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional; nn/ppo.py): the four diagnostics in every loss dict, KL early stopping
         self.diagnostics, self.target_kl = ops.diag_options(config_nn)
+        from ddrl4nav_amd.nn.minibatch import refuse_minibatch_options
+        refuse_minibatch_options(config_nn, "the operator-composed GenericPPO")
         if rnd is not None:
             raise NotImplementedError("RND is disabled in the reference defaults (USE_RND=False) and out of scope")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):

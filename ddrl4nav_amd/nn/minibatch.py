@@ -1,0 +1,208 @@
+"""PPO minibatch epochs on the Atari fast path: TRAINING_ITER_TIME epochs of PPO_MINIBATCHES optimiser steps each, on shuffled or
+contiguous minibatches, with optional advantage normalisation -- what the reference does not have (USTC_lab/nn/ppo.py:77-146 runs
+TRAINING_ITER_TIME full-batch steps on raw advantages).
+
+The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the ConfigNN contract does not carry them):
+
+  PPO_MINIBATCHES      1       K optimiser steps per epoch; a count, so every rank of a group does the same number of collectives
+  PPO_SHUFFLE          False   True: a fresh permutation of this rank's samples every epoch
+  NORMALIZE_ADVANTAGE  False   "batch": (adv - mean) / (std + eps) over the whole (global) batch, once per learn call;
+                               "minibatch": over every (global) minibatch
+  ADV_NORM_EPS         1e-8    the eps above
+
+With all four at their defaults PPO.learn does not come here.  Per step, everything on the device and in stream order: one
+ddrl_op_gather_minibatch into ONE staging buffer (shuffle on; off: contiguous views, nothing is copied), the moments / affine /
+normalise operators of csrc/minibatch.hip where asked for, then ppo_iter -> ppo_diag -> allreduce_grads -> clip_adam_step as in
+nn/ppo.py.  split() and epoch_order() are plain CPU functions: a test recomputes every minibatch from them.
+"""
+import time
+
+import torch
+
+from ddrl4nav_amd import ops
+
+DEFAULTS = (1, False, None, 1e-8)
+MODES = ("batch", "minibatch")
+KNOBS = ("PPO_MINIBATCHES", "PPO_SHUFFLE", "NORMALIZE_ADVANTAGE", "ADV_NORM_EPS")
+
+
+def minibatch_options(config_nn):
+    """(K, shuffle, mode or None, eps) from config_nn; ValueError for K < 1, an unknown mode or a negative eps."""
+    k = getattr(config_nn, "PPO_MINIBATCHES", 1)
+    if isinstance(k, bool) or int(k) != k or int(k) < 1:
+        raise ValueError("PPO_MINIBATCHES must be an integer >= 1, got %r" % (k,))
+    mode = getattr(config_nn, "NORMALIZE_ADVANTAGE", False)
+    if mode is None or mode is False:
+        mode = None
+    elif mode not in MODES:
+        raise ValueError("NORMALIZE_ADVANTAGE must be False, 'batch' or 'minibatch', got %r" % (mode,))
+    eps = float(getattr(config_nn, "ADV_NORM_EPS", 1e-8))
+    if not eps >= 0.0:
+        raise ValueError("ADV_NORM_EPS must be >= 0, got %r" % (eps,))
+    return int(k), bool(getattr(config_nn, "PPO_SHUFFLE", False)), mode, eps
+
+
+def refuse_minibatch_options(config_nn, who):
+    """GenericPPO and GAIL keep their states as float lists per encoder input: the frame-row collation does not serve them."""
+    if minibatch_options(config_nn) != DEFAULTS:
+        raise ValueError("%s are built for the Atari fast path alone (nn/ppo.py PPO over AtariPreNet), not for %s: unset them"
+                         % (" / ".join(KNOBS), who))
+
+
+def split(B, K):
+    """K consecutive ranges [(lo, hi)] that cover [0, B): range j has B // K + (1 if j < B % K else 0) elements."""
+    B, K = int(B), int(K)
+    if K < 1 or B < K:
+        raise ValueError("PPO_MINIBATCHES = %d does not fit a batch of %d samples: every minibatch needs at least one" % (K, B))
+    base, extra = divmod(B, K)
+    out, lo = [], 0
+    for j in range(K):
+        hi = lo + base + (1 if j < extra else 0)
+        out.append((lo, hi))
+        lo = hi
+    return out
+
+
+_M64 = 2 ** 64 - 1
+
+
+def _mix(x):
+    """splitmix64's finaliser: neighbouring integers give unrelated seeds."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def epoch_order(seed, learn_call, epoch, B):
+    """int32 [B] on the host: the permutation of epoch `epoch` of the `learn_call`-th learn() of a net seeded with `seed`.
+    torch.randperm on a private CPU generator seeded from the three integers; the global generator is never touched."""
+    s = _mix(int(seed) & _M64)
+    s = _mix(s ^ (int(learn_call) & _M64))
+    s = _mix(s ^ (int(epoch) & _M64))
+    g = torch.Generator(device="cpu")
+    g.manual_seed(s & (2 ** 63 - 1))
+    return torch.randperm(int(B), generator=g, dtype=torch.int64).to(torch.int32)
+
+
+class Staging:
+    """The device buffers of the minibatch loop, kept by the net between learn calls: ONE minibatch of frames and columns (stream order
+    makes its reuse safe), one scratch advantage column of the whole batch, the three double sums, the affine pair and the moments'
+    workspace."""
+
+    def __init__(self, device, frame_shape, cap, B):
+        self.cap, self.B, self.frame_shape = int(cap), int(B), tuple(frame_shape)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.frames = torch.empty((self.cap,) + self.frame_shape, dtype=torch.uint8, device=device)
+        self.cols = torch.empty((4, self.cap), **f32)
+        self.adv = torch.empty(self.B, **f32)
+        self.sums = torch.zeros(3, dtype=torch.float64, device=device)
+        self.affine = torch.zeros(2, **f32)
+        self.ws = torch.empty(ops.moments_ws_floats(self.B), **f32)
+
+    def fits(self, frame_shape, cap, B):
+        return self.frame_shape == tuple(frame_shape) and self.cap >= cap and self.B >= B
+
+
+def advantage_affine(column, n, st, eps, group):
+    """st.affine <- (mean, 1 / (std + eps)) of the first n floats of `column` and of the other ranks' columns: the three sums of every
+    rank, summed over the group (dist.allreduce_flat: in place on RCCL ranks, through the host where gloo ranks share a GPU), then the
+    affine on the device."""
+    from ddrl4nav_amd.dist import allreduce_flat
+    ops.moments(column, sums=st.sums, ws=st.ws, n=n)
+    allreduce_flat(st.sums, group)
+    return ops.moments_affine(st.sums, eps, st.affine)
+
+
+def learn(net, data):
+    """The body of PPO.learn when a knob is set: a generator with learn's protocol."""
+    from ddrl4nav_amd.dist import global_batch
+    from ddrl4nav_amd.nn.atari_encoder import frames_u8
+    K, shuffle, mode, eps = net.minibatch
+    frames = frames_u8(data.states, net.device)
+    B = frames.shape[0]
+    ranges = split(B, K)                       # ValueError when K > B
+    cap = ranges[0][1] - ranges[0][0]          # the first minibatch is the largest
+    net._ensure_capacity(cap)
+    f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=net.device).contiguous()
+    actions, old_logps, advs, rets = f32(data.actions), f32(data.old_logps), f32(data.advs), f32(data.values)[0].contiguous()
+    assert rets.shape == (B,)
+    if net.target_kl is not None and net.deferred_stats:
+        raise ValueError("TARGET_KL needs the host after every step: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
+    hp, group, diag, deferred = net._hp, net._process_group, net.diagnostics, net.deferred_stats
+    st = net._mb_stage
+    if st is None or not st.fits(frames.shape[1:], cap, B):
+        st = net._mb_stage = Staging(net.device, frames.shape[1:], cap, B)
+    call = net.learn_calls
+    net.learn_calls += 1
+    rank = 0
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        rank = torch.distributed.get_rank(group)
+    affine = None
+    if mode == "batch":
+        affine = advantage_affine(advs, B, st, eps, group)
+        if not shuffle:                        # nothing is gathered: one pass into the scratch column
+            advs = ops.normalize(advs, affine, out=st.adv, n=B)[:B]
+            affine = None
+    epochs = net.training_iter_time
+    steps = epochs * K
+    if deferred:
+        if net._stats_rows is None or net._stats_rows.shape[0] < steps:
+            net._stats_rows = torch.empty((steps, 8), dtype=torch.float32).pin_memory()
+        if diag and (net._diag_rows is None or net._diag_rows.shape[0] < steps):
+            net._diag_rows = torch.empty((steps, ops.DIAG_SLOTS), dtype=torch.float64).pin_memory()
+            net._diag_dev = torch.zeros((steps, ops.DIAG_SLOTS), dtype=torch.float64, device=net.device)
+    b_globals = {}
+    t_all = time.time()
+    i = 0
+    for epoch in range(epochs):
+        order = epoch_order(net._seed + rank, call, epoch, B).to(net.device) if shuffle else None   # one int32 upload per epoch
+        for j, (lo, hi) in enumerate(ranges):
+            t0 = time.time()
+            n = hi - lo
+            if shuffle:
+                dst = [st.cols[k, :n] for k in range(4)]
+                ops.gather_minibatch(frames, order[lo:hi], st.frames, (actions, old_logps, advs, rets), dst, adv_affine=affine, n=n)
+                f, (a, o, ad, r) = st.frames[:n], dst
+            else:
+                f, a, o, ad, r = frames[lo:hi], actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
+            if mode == "minibatch":
+                advantage_affine(ad, n, st, eps, group)
+                ad = ops.normalize(ad, st.affine, out=ad if shuffle else st.adv, n=n)[:n]   # in place on the staged column
+            if j not in b_globals:             # the ranks' j-th sizes: one collective per j, in the first epoch
+                b_globals[j] = global_batch(n, group)
+            hp.ppo_iter(f, a, o, ad, r, b_global=b_globals[j])
+            if deferred:
+                if diag:
+                    net._diag_rows[i].copy_(hp.ppo_diag(a, o, r, out=net._diag_dev[i]), non_blocking=True)
+                hp.allreduce_grads()
+                hp.clip_adam_step()
+                hp.stats_async(net._stats_rows[i])
+                i += 1
+                continue
+            d = None
+            if diag:
+                d = ops.diag_dict(hp.diag_global(hp.ppo_diag(a, o, r)))
+                if ops.kl_stop(d, net.target_kl):
+                    return                     # ends the whole call; this step is not applied (as an iteration in nn/ppo.py)
+            hp.allreduce_grads()
+            hp.clip_adam_step()
+            net.update_time += 1
+            s = hp.stats()
+            loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
+                        "PpoBackUpTime": time.time() - t0}
+            if d is not None:
+                loss_log.update(d)
+            yield loss_log, net.update_time, True
+    if not deferred:
+        return
+    torch.cuda.current_stream().synchronize()   # the one synchronisation of the call
+    dt = (time.time() - t_all) / max(steps, 1)
+    for i in range(steps):
+        net.update_time += 1
+        s = hp.stats_dict(net._stats_rows[i])
+        loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
+                    "PpoBackUpTime": dt}
+        if diag:
+            loss_log.update(ops.diag_dict(hp.diag_global(net._diag_rows[i])))
+        yield loss_log, net.update_time, True

@@ -11,6 +11,7 @@ import time
 import torch
 
 from ddrl4nav_amd import ops
+from ddrl4nav_amd.nn import minibatch
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.engine import HotPath
 from ddrl4nav_amd.nn.base import Basenn
@@ -37,6 +38,10 @@ class PPO(Basenn):
         # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional, like DEFERRED_LOSS_READBACK): ApproxKL, ClipFraction, ExplainedVariance and
         # RatioMax in every loss dict, and KL early stopping (ValueError when TARGET_KL meets the deferred read-back)
         self.diagnostics, self.target_kl = ops.diag_options(config_nn)
+        # config_nn.PPO_MINIBATCHES / PPO_SHUFFLE / NORMALIZE_ADVANTAGE / ADV_NORM_EPS (optional, nn/minibatch.py): epochs of minibatch steps
+        self.minibatch = minibatch.minibatch_options(config_nn)
+        self._mb_stage = None
+        self.learn_calls = 0   # learn() calls that took the minibatch loop: the second integer of minibatch.epoch_order
         if hasattr(actor, "log_std"):
             raise NotImplementedError("the Atari fast path has a Categorical actor only (reference atari.yaml)")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -154,6 +159,9 @@ class PPO(Basenn):
 
     # ---- PPO.learn (ppo.py:77-146) -----------------------------------------------------------------
     def learn(self, data: Experience):
+        if self.minibatch != minibatch.DEFAULTS:   # a knob is set: TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py)
+            yield from minibatch.learn(self, data)
+            return
         frames = _frames_u8(data.states, self.device)
         B = frames.shape[0]
         self._ensure_capacity(B)

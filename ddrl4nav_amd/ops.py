@@ -175,6 +175,70 @@ def gather_rows_u8(src, idx, dst, labels_src=None, labels_dst=None, n=None):
     return dst
 
 
+def moments_ws_floats(n):
+    """Floats of scratch ddrl_op_moments needs for a column of n floats."""
+    f = c_int64()
+    check(_lib.load().ddrl_op_moments_ws_floats(int(n), byref(f)))
+    return f.value
+
+
+def moments(x, sums=None, accumulate=False, ws=None, n=None):
+    """(n, sum x, sum x^2) of the first n floats of x as 3 float64 on the device (include/ddrl.h ddrl_op_moments; csrc/minibatch.hip):
+    double sums in a fixed order.  accumulate: added to what `sums` holds.  Asynchronous on the current stream; returns sums."""
+    n = int(x.numel() if n is None else n)
+    assert x.numel() >= n
+    if sums is None:
+        assert not accumulate, "accumulate needs the sums of the earlier calls"
+        sums = torch.empty(3, dtype=torch.float64, device=x.device)
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 3
+    if ws is None:
+        ws = torch.empty(moments_ws_floats(n), dtype=torch.float32, device=x.device)
+    check(_lib.load().ddrl_op_moments(_p(_f32(x)), n, _p(sums), 1 if accumulate else 0, _p(_f32(ws)), _st()))
+    return sums
+
+
+def moments_affine(sums, eps, affine=None):
+    """(mean, 1 / (std + eps)) as 2 fp32 on the device from the sums of moments(), torch's unbiased std (include/ddrl.h
+    ddrl_op_moments_affine).  Nothing visits the host.  Returns affine."""
+    if affine is None:
+        affine = torch.empty(2, dtype=torch.float32, device=sums.device)
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 3 and affine.numel() == 2
+    check(_lib.load().ddrl_op_moments_affine(_p(sums), float(eps), _p(_f32(affine)), _st()))
+    return affine
+
+
+def normalize(x, affine, out=None, n=None):
+    """out[i] = (x[i] - affine[0]) * affine[1] for the first n floats (include/ddrl.h ddrl_op_normalize); out may be x.  Returns out."""
+    n = int(x.numel() if n is None else n)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=x.device)
+    assert x.numel() >= n and out.numel() >= n and affine.numel() == 2
+    check(_lib.load().ddrl_op_normalize(_p(_f32(x)), n, _p(_f32(affine)), _p(_f32(out)), _st()))
+    return out
+
+
+def gather_minibatch(frames, idx, frames_dst, columns=None, columns_dst=None, adv_affine=None, n=None):
+    """The collation of one minibatch in one launch (include/ddrl.h ddrl_op_gather_minibatch): frames_dst[i] = frames[idx[i]] for the
+    first n entries of idx (int32, on the device) as gather_rows_u8, and columns_dst[k][i] = columns[k][idx[i]] for the four fp32 columns
+    (actions, old_logps, advs, rets); entries may be None in both.  adv_affine (2 fp32 on the device): the advantage column is
+    normalised on the way, (adv - a[0]) * a[1].  Asynchronous on the current stream; returns frames_dst."""
+    n = int(idx.numel() if n is None else n)
+    assert frames.dtype == torch.uint8 and frames_dst.dtype == torch.uint8 and frames.is_contiguous() and frames_dst.is_contiguous() \
+        and frames.is_cuda and frames_dst.is_cuda, "expected contiguous uint8 device tensors"
+    assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() >= n, "idx: contiguous int32 on the device"
+    row_bytes = frames[0].numel()
+    assert frames_dst[0].numel() == row_bytes and frames_dst.shape[0] >= n, "frames_dst rows must match the frames' rows"
+    src, dst = list(columns or (None,) * 4), list(columns_dst or (None,) * 4)
+    assert len(src) == 4 and len(dst) == 4, "four columns: actions, old_logps, advs, rets"
+    for s, d in zip(src, dst):
+        assert (s is None) == (d is None), "a column comes with its destination"
+        assert s is None or (_f32(s).numel() >= frames.shape[0] and _f32(d).numel() >= n)
+    assert adv_affine is None or (_f32(adv_affine).numel() == 2 and src[2] is not None)
+    check(_lib.load().ddrl_op_gather_minibatch(_p(frames), frames.shape[0], row_bytes, _p(idx), n, _p(frames_dst), *[_p(t) for t in src],
+                                               *[_p(t) for t in dst], _p(adv_affine), _st()))
+    return frames_dst
+
+
 class Conv:
     """One Conv2d / Conv1d layer (torch weight layout [cout][cin][kh][kw]; Conv1d: h = kh = 1)."""
 

@@ -550,6 +550,39 @@ int32_t ddrl_op_heads_bc_loss(const float* w, const float* b, int32_t n_actions,
 int32_t ddrl_op_gather_rows_u8(const uint8_t* src, int64_t n_rows, int64_t row_bytes, const int32_t* idx, int32_t n, uint8_t* dst,
                                const float* labels_src, float* labels_dst, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PPO minibatch epochs (the reference runs full-batch iterations on raw advantages, ppo.py:77-146; added after round 6,
+ * additive: ABI 3).  All four need no context, allocate nothing and are asynchronous on `stream`; their argument checks run
+ * before anything touches HIP; no atomics, so a repeated call gives the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* sums3[0..3) (DEVICE memory, doubles, 8-byte aligned) = n, sum x, sum x^2 of the n floats of x: terms and partial sums in double,
+ * per-workgroup partial rows in `ws` folded in index order by a last stage (the scheme of ddrl_op_heads_diag).  accumulate != 0:
+ * added to what sums3 holds, so that micro-batches (or ranks) build one result.  ws = ddrl_op_moments_ws_floats(n) floats, 8-byte
+ * aligned; x, ws and sums3 do not overlap. */
+int32_t ddrl_op_moments_ws_floats(int64_t n, int64_t* floats);
+int32_t ddrl_op_moments(const float* x, int64_t n, double* sums3, int32_t accumulate, float* ws, void* stream);
+/* The affine pair of (x - x.mean()) / (x.std() + eps) with torch's unbiased std, from the sums of ddrl_op_moments, in double:
+ *   mean = S1 / n;  var = max(0, (S2 - S1 * S1 / n) / (n - 1)) for n >= 2, 0 for n < 2;
+ *   affine2[0] = (float)mean;  affine2[1] = (float)(1 / (sqrt(var) + eps))
+ * sums3 and affine2 (2 floats) are DEVICE memory: the divisor never visits the host.  eps >= 0. */
+int32_t ddrl_op_moments_affine(const double* sums3, double eps, float* affine2, void* stream);
+/* out[i] = (x[i] - affine2[0]) * affine2[1] for i < n, in fp32: a subtract, then a multiply (never fused).  out == x is allowed;
+ * any other overlap of x, affine2 and out is DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_normalize(const float* x, int64_t n, const float* affine2, float* out, void* stream);
+/* The collation of one minibatch of Experience in one launch:
+ *   frames_dst[i][0:row_bytes) = frames[idx[i]][0:row_bytes) for i < n   (the rules of ddrl_op_gather_rows_u8: row_bytes a multiple of
+ *   16, frames / frames_dst 16-byte aligned, idx int32 on the device),
+ *   X_dst[i] = X[idx[i]] for the four float columns X = actions, old_logps, advs, rets ([n_rows] -> [n]; a column is given with its
+ *   destination or both are NULL),
+ *   adv_affine != NULL (2 floats on the device, needs advs): advs_dst[i] = (advs[idx[i]] - adv_affine[0]) * adv_affine[1], the
+ *   arithmetic of ddrl_op_normalize bit for bit.
+ * An index outside [0, n_rows) reads nothing and yields a zero frame row and zeros in all four columns.  Nothing that is read (idx
+ * and adv_affine included) may overlap anything that is written, nor two destinations one another: DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_gather_minibatch(const uint8_t* frames, int64_t n_rows, int64_t row_bytes, const int32_t* idx, int32_t n,
+                                 uint8_t* frames_dst, const float* actions, const float* old_logps, const float* advs, const float* rets,
+                                 float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
