@@ -182,6 +182,10 @@ SIGNATURES = {
     "ddrl_op_normalize": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_gather_minibatch": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_frame_age": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_gather_frame_stacks": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,121 @@
+"""PlaneRollout: DeviceRollout (agent/rollout.py) with every Atari frame stored ONCE.
+
+DeviceRollout keeps whole stacks, uint8 [T+1, N, C, 84, 84]: with single-frame ingest (put_new_frames*) every frame that arrives is
+written C times.  Here the pool is
+
+  planes uint8 [H + T + 1, N, 84, 84]   H = C - 1 history rows; row H + t is the one frame that arrived for step t
+  age    uint8 [T + 1, N]               steps since env i's stack was last reset, saturated at C - 1 (csrc/fpool.hip ddrl_op_frame_age)
+
+a quarter of the bytes at C = 4 (0.47 GB against 1.86 GB at 256 envs x 256 steps), and a stack is assembled where it is read
+(ddrl_op_gather_frame_stacks): act(t) gathers slot t into one [N, C, 84, 84] scratch, the learner gathers its minibatches from
+batch().states[0], a data.FramePlanes.  Same life cycle and the same methods as DeviceRollout except the whole-stack puts; the same
+actions, log-probs, values and updates bit for bit (tests/test_plane_pool_gpu.py).  The ring-fed put needs no staging buffers and no
+per-parity events: the DMA lands in the pool's plane row itself."""
+import torch
+
+from ddrl4nav_amd import ops
+from ddrl4nav_amd.agent.rollout import DeviceRollout
+from ddrl4nav_amd.agent.statistics import EpisodeReturns
+from ddrl4nav_amd.data import Experience, FramePlanes
+from ddrl4nav_amd.utils.staging import copy_into
+
+
+class PlaneRollout(DeviceRollout):
+    def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False):
+        # the pools of DeviceRollout.__init__ with `frames` replaced by planes + age (not called: it would allocate the stacked pool)
+        self.hp = net.hot_path if hasattr(net, "hot_path") else net
+        self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
+        if not 1 <= self.C <= 4:
+            raise ValueError("1 to 4 stacked frames, got %d" % self.C)
+        if self.T < self.C:
+            raise ValueError("horizon %d < channels %d: carry_over() moves pool rows T..T+C-1 to rows 0..C-1, which would overlap"
+                             % (self.T, self.C))
+        self.H = self.C - 1
+        self.gamma, self.landa = gamma, landa
+        dev = torch.device(device if device is not None else self.hp.device)
+        self.device = dev
+        N, T = self.N, self.T
+        self.planes = torch.empty((self.H + T + 1, N, 84, 84), dtype=torch.uint8, device=dev)
+        self.age = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
+        self._stack = torch.empty((N, self.C, 84, 84), dtype=torch.uint8, device=dev)   # the slot act(t) reads
+        self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
+        self._rewards = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
+        self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
+        self._actions = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
+        self._logps = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
+        self.rewards, self.dones = self._rewards[:T], self._dones[:T]
+        self.actions, self.logps = self._actions[:T], self._logps[:T]
+        self.adv = torch.empty((T, N), dtype=torch.float32, device=dev)
+        self.ret = torch.empty((T, N), dtype=torch.float32, device=dev)
+        self._probs = torch.empty((N, self.hp.n_actions), dtype=torch.float32, device=dev)
+        self.seed, self.rollouts, self.t = int(seed), 0, 0
+        self.t0 = 0
+        self.copy_stream = torch.cuda.Stream(device=dev)
+        self.returns = EpisodeReturns(N, dev) if track_returns else None
+        self._reset_buf = torch.ones((2, N), dtype=torch.uint8, device=dev)   # _reset_flags: 0 a caller's flags, 1 all ones
+        self._ring_rollout = -1            # the rollout (self.rollouts) whose first ring put ordered the copy stream
+
+    # ---- ingest ---------------------------------------------------------------------------------
+    def put_frames(self, t, frames):
+        raise ValueError("PlaneRollout stores single frames (put_new_frames*): whole stacks go to DeviceRollout")
+
+    def put_frames_from_ring(self, t, ring):
+        raise ValueError("PlaneRollout stores single frames (put_new_frames_from_ring): whole stacks go to DeviceRollout")
+
+    def _age(self, t, flags):
+        """age[t] from age[t-1] and the reset flags (t == 0: every env is reset, _reset_flags admits nothing else)."""
+        ops.frame_age(self.age[t - 1] if t > 0 else None, flags, self.age[t], self.C)
+
+    def put_new_frames(self, t, newest, reset=None):
+        """ONE new frame per env, uint8 [N,84,84] (device or pinned host) -> pool row H + t; `reset` as DeviceRollout.put_new_frames."""
+        flags = self._reset_flags(t, reset)
+        copy_into(self.planes[self.H + t], torch.as_tensor(newest))
+        self._age(t, flags)
+
+    def put_new_frames_from_ring(self, t, ring, reset=None):
+        """put_new_frames with the frame taken from a pinned ring whose slots hold N * 7056 bytes: hipMemcpyAsync on the copy stream straight
+        into pool row H + t, which nothing enqueued earlier in this rollout touches; the compute stream waits for it.  The FIRST such put
+        of a rollout, at whatever t, orders the copy stream behind the compute stream (the previous update and carry_over() still read
+        and write the pool); later puts do not wait again, so copy t + 1 runs under forward t."""
+        flags = self._reset_flags(t, reset)           # before the ring is touched: a refused call consumes no slot
+        cur = torch.cuda.current_stream()
+        if self._ring_rollout != self.rollouts:     # finish() counts the rollouts: one wait per rollout, none per slot
+            self.copy_stream.wait_stream(cur)
+            self._ring_rollout = self.rollouts
+        ring.pop_to(self.planes[self.H + t], stream=self.copy_stream)
+        cur.wait_stream(self.copy_stream)
+        self._age(t, flags)
+
+    # ---- acting ---------------------------------------------------------------------------------
+    def stacks(self, t, out=None):
+        """Slot t (0..T) assembled as uint8 [N, C, 84, 84], into `out` or the scratch act() reads."""
+        out = self._stack if out is None else out
+        return ops.gather_frame_stacks(self.planes, self.age, self.C, out, first=t * self.N, n=self.N)
+
+    def act(self, t):
+        """DeviceRollout.act on the gathered slot."""
+        if t < self.t0:
+            return self._actions[t]
+        self.hp.forward(self.stacks(t), seed=self.seed + self.rollouts, stream_id=t, probs=self._probs,
+                        value=self.values[t], action=self._actions[t], logp=self._logps[t])
+        return self._actions[t]
+
+    # ---- carry-over + learner batch ---------------------------------------------------------------
+    def carry_over(self, keep_step=False):
+        """DeviceRollout.carry_over: the last stored step's frame WITH its history (pool rows T..T+H -> 0..H, age[T] -> age[0])."""
+        T, H = self.T, self.H
+        self.planes[:H + 1].copy_(self.planes[T:T + H + 1])
+        self.age[0].copy_(self.age[T])
+        if keep_step:
+            self.values[0].copy_(self.values[T])
+            for pool in (self._rewards, self._dones, self._actions, self._logps):
+                pool[0].copy_(pool[T])
+            self.t0 = 1
+        else:
+            self.t0 = 0
+
+    def batch(self):
+        """DeviceRollout.batch with the states as FramePlanes over the pool (zero-copy)."""
+        B = self.N * self.T
+        return Experience(states=[FramePlanes(self.planes, self.age, self.T, self.N, self.C)], advs=self.adv.view(B),
+                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self.ret.view(1, B))

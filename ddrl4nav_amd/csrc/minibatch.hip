@@ -54,23 +54,14 @@ __global__ void moments_affine_kernel(const double* __restrict__ sums3, double e
   affine2[1] = (float)(1.0 / (sqrt(var) + eps));
 }
 
-// a subtract, then a multiply (the build keeps them apart: -ffp-contract=off); the one text both the column pass and the gather apply
-__device__ __forceinline__ float affine_apply(float x, float shift, float scale) { return (x - shift) * scale; }
-
 __global__ __launch_bounds__(256) void normalize_kernel(const float* x, int64_t n, const float* __restrict__ affine2, float* out) {
   const float shift = affine2[0], scale = affine2[1];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = affine_apply(x[i], shift, scale);
 }
 
 // ---- collation of one minibatch ---------------------------------------------------------------------------------------------------------
-// The row mover of rows.h on the frames; the workgroup of a row's first chunk also gathers that row's entry of the four columns, one
-// thread each (column k: src[k] -> dst[k], both null = not given).  An index outside [0, n_rows): a zero frame row, zeros in the columns.
-struct MinibatchColumns {
-  const float* src[4];
-  float* dst[4];
-};
-constexpr int COL_ADV = 2;  // actions, old_logps, advs, rets
-
+// The row mover of rows.h on the frames; the workgroup of a row's first chunk also gathers that row's entry of the four columns
+// (rows.h gather_columns).  An index outside [0, n_rows): a zero frame row, zeros in the columns.
 __global__ __launch_bounds__(GATHER_THREADS) void gather_minibatch_kernel(const uint4* __restrict__ frames, int64_t n_rows, int64_t row_vecs,
                                                                            int chunks, const int32_t* __restrict__ idx,
                                                                            uint4* __restrict__ frames_dst, MinibatchColumns cols,
@@ -79,17 +70,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_minibatch_kernel(const 
   const int64_t r = idx[i];
   const bool ok = r >= 0 && r < n_rows;
   gather_row_chunk(frames, r, ok, row_vecs, c, i, frames_dst);
-  if (c == 0 && threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    if (cols.dst[k] != nullptr) {
-      float v = 0.0f;
-      if (ok) {
-        v = cols.src[k][r];
-        if (k == COL_ADV && adv_affine != nullptr) v = affine_apply(v, adv_affine[0], adv_affine[1]);
-      }
-      cols.dst[k][i] = v;
-    }
-  }
+  if (c == 0) gather_columns(cols, r, ok, i, adv_affine);
 }
 
 }  // namespace ddrl
@@ -144,24 +125,14 @@ int32_t ddrl_op_gather_minibatch(const uint8_t* frames, int64_t n_rows, int64_t 
   if (!aligned16(frames) || !aligned16(frames_dst) || ((uintptr_t)idx & 3)) return DDRL_ERR_INVALID_ARG;
   if (n_rows > INT64_MAX / row_bytes) return DDRL_ERR_INVALID_ARG;
   const MinibatchColumns cols{{actions, old_logps, advs, rets}, {actions_dst, old_logps_dst, advs_dst, rets_dst}};
-  for (int k = 0; k < 4; ++k) {
-    if ((cols.src[k] == nullptr) != (cols.dst[k] == nullptr)) return DDRL_ERR_INVALID_ARG;
-    if (((uintptr_t)cols.src[k] & 3) || ((uintptr_t)cols.dst[k] & 3)) return DDRL_ERR_INVALID_ARG;
-  }
-  if (adv_affine && (!advs || ((uintptr_t)adv_affine & 3))) return DDRL_ERR_INVALID_ARG;
+  if (!columns_ok(cols, adv_affine)) return DDRL_ERR_INVALID_ARG;
   // what is read against what is written, and the destinations against one another
   const void* src[7] = {frames, actions, old_logps, advs, rets, idx, adv_affine};
   const uint64_t src_b[7] = {(uint64_t)n_rows * row_bytes, (uint64_t)n_rows * 4, (uint64_t)n_rows * 4, (uint64_t)n_rows * 4,
                              (uint64_t)n_rows * 4, (uint64_t)n * 4, 8};
-  const void* dst[5] = {frames_dst, actions_dst, old_logps_dst, advs_dst, rets_dst};
+  void* dst[5] = {frames_dst, actions_dst, old_logps_dst, advs_dst, rets_dst};
   const uint64_t dst_b[5] = {(uint64_t)n * row_bytes, (uint64_t)n * 4, (uint64_t)n * 4, (uint64_t)n * 4, (uint64_t)n * 4};
-  for (int d = 0; d < 5; ++d) {
-    if (!dst[d]) continue;
-    for (int s = 0; s < 7; ++s)
-      if (src[s] && overlap(src[s], dst[d], src_b[s], dst_b[d])) return DDRL_ERR_INVALID_ARG;
-    for (int e = d + 1; e < 5; ++e)
-      if (dst[e] && overlap(dst[d], dst[e], dst_b[d], dst_b[e])) return DDRL_ERR_INVALID_ARG;
-  }
+  if (!reads_and_writes_apart(src, src_b, 7, dst, dst_b, 5)) return DDRL_ERR_INVALID_ARG;
   int64_t row_vecs;
   int chunks;
   if (!gather_grid(row_bytes, n, &row_vecs, &chunks)) return DDRL_ERR_INVALID_ARG;

@@ -1,6 +1,6 @@
 // Rows of device memory that more than one translation unit moves or folds: the 16-byte row mover of the gathers (imit.hip
-// ddrl_op_gather_rows_u8, minibatch.hip ddrl_op_gather_minibatch) and the last stage of the fixed-order double sums (diag.hip's eight
-// diagnostics sums, minibatch.hip's three moments).
+// ddrl_op_gather_rows_u8, minibatch.hip ddrl_op_gather_minibatch, fpool.hip ddrl_op_gather_frame_stacks), the float columns the last two
+// carry along, and the last stage of the fixed-order double sums (diag.hip's eight diagnostics sums, minibatch.hip's three moments).
 #pragma once
 #include "common.h"
 
@@ -37,6 +37,50 @@ __device__ __forceinline__ void gather_row_chunk(const uint4* __restrict__ src, 
     const int64_t u = u0 + t * GATHER_THREADS;
     if (u < row_vecs) dst[(int64_t)i * row_vecs + u] = v[t];
   }
+}
+
+// ---- the four float columns of Experience that ride along with a gather of frames (minibatch.hip, fpool.hip) ----------------------------
+// a subtract, then a multiply (the build keeps them apart: -ffp-contract=off); the one text the column pass and both gathers apply
+__device__ __forceinline__ float affine_apply(float x, float shift, float scale) { return (x - shift) * scale; }
+
+struct MinibatchColumns {  // column k: src[k] -> dst[k], both null = not given
+  const float* src[4];
+  float* dst[4];
+};
+constexpr int COL_ADV = 2;  // actions, old_logps, advs, rets
+
+// entry i of the four columns from sample r (read only when ok, zeros otherwise), one thread each: threads 0..3 of one workgroup per entry
+__device__ __forceinline__ void gather_columns(const MinibatchColumns& cols, int64_t r, bool ok, int i, const float* __restrict__ adv_affine) {
+  if (threadIdx.x >= 4) return;
+  const int k = threadIdx.x;
+  if (cols.dst[k] == nullptr) return;
+  float v = 0.0f;
+  if (ok) {
+    v = cols.src[k][r];
+    if (k == COL_ADV && adv_affine != nullptr) v = affine_apply(v, adv_affine[0], adv_affine[1]);
+  }
+  cols.dst[k][i] = v;
+}
+
+// the host's checks of the columns: a column comes with its destination, floats are 4-byte aligned, the affine pair needs the advantages
+inline bool columns_ok(const MinibatchColumns& cols, const float* adv_affine) {
+  for (int k = 0; k < 4; ++k) {
+    if ((cols.src[k] == nullptr) != (cols.dst[k] == nullptr)) return false;
+    if (((uintptr_t)cols.src[k] & 3) || ((uintptr_t)cols.dst[k] & 3)) return false;
+  }
+  return !adv_affine || (cols.src[COL_ADV] && !((uintptr_t)adv_affine & 3));
+}
+
+// true when nothing that is read overlaps anything that is written, nor two destinations one another (null entries are not given)
+inline bool reads_and_writes_apart(const void* const* src, const uint64_t* src_b, int ns, void* const* dst, const uint64_t* dst_b, int nd) {
+  for (int d = 0; d < nd; ++d) {
+    if (!dst[d]) continue;
+    for (int s = 0; s < ns; ++s)
+      if (src[s] && overlap(src[s], dst[d], src_b[s], dst_b[d])) return false;
+    for (int e = d + 1; e < nd; ++e)
+      if (dst[e] && overlap(dst[d], dst[e], dst_b[d], dst_b[e])) return false;
+  }
+  return true;
 }
 
 // ---- fold of per-workgroup rows of doubles --------------------------------------------------------------------------------------------

@@ -296,6 +296,8 @@ class GAIL(Basenn):
             return self.discriminator(x)
 
     def learn(self, data: Experience):
+        from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
+        refuse_frame_planes(data.states, "NETWORK_TYPE='gail'")
         for loss_item, update_time, last in self._train_discriminator(data):
             yield loss_item, update_time, False
         for loss_item, update_time, last in self._train_generator(data):

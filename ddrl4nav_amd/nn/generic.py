@@ -755,6 +755,8 @@ class GenericPPO(Basenn):
         self._backward_both(dha, dhc, n)
 
     def learn(self, data: Experience):
+        from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
+        refuse_frame_planes(data.states, "the operator-composed GenericPPO")
         states = data.states if isinstance(data.states, (list, tuple)) else [data.states]
         B = int(torch.as_tensor(states[0]).shape[0])
         f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()

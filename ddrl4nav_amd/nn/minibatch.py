@@ -11,8 +11,9 @@ The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the Config
   ADV_NORM_EPS         1e-8    the eps above
 
 With all four at their defaults PPO.learn does not come here.  Per step, everything on the device and in stream order: one
-ddrl_op_gather_minibatch into ONE staging buffer (shuffle on; off: contiguous views, nothing is copied), the moments / affine /
-normalise operators of csrc/minibatch.hip where asked for, then ppo_iter -> ppo_diag -> allreduce_grads -> clip_adam_step as in
+ddrl_op_gather_minibatch into ONE staging buffer (shuffle on; off: contiguous views, nothing is copied; states given as
+data.FramePlanes: ddrl_op_gather_frame_stacks into the same buffer, shuffled or not), the moments / affine / normalise operators of
+csrc/minibatch.hip where asked for, then ppo_iter -> ppo_diag -> allreduce_grads -> clip_adam_step as in
 nn/ppo.py.  split() and epoch_order() are plain CPU functions: a test recomputes every minibatch from them.
 """
 import time
@@ -117,9 +118,11 @@ def advantage_affine(column, n, st, eps, group):
 def learn(net, data):
     """The body of PPO.learn when a knob is set: a generator with learn's protocol."""
     from ddrl4nav_amd.dist import global_batch
+    from ddrl4nav_amd.data.frame_planes import planes_of
     from ddrl4nav_amd.nn.atari_encoder import frames_u8
     K, shuffle, mode, eps = net.minibatch
-    frames = frames_u8(data.states, net.device)
+    planes = planes_of(data.states)            # frames stored once (agent/plane_rollout.py): every minibatch is assembled into st.frames
+    frames = planes if planes is not None else frames_u8(data.states, net.device)
     B = frames.shape[0]
     ranges = split(B, K)                       # ValueError when K > B
     cap = ranges[0][1] - ranges[0][0]          # the first minibatch is the largest
@@ -162,10 +165,14 @@ def learn(net, data):
             n = hi - lo
             if shuffle:
                 dst = [st.cols[k, :n] for k in range(4)]
-                ops.gather_minibatch(frames, order[lo:hi], st.frames, (actions, old_logps, advs, rets), dst, adv_affine=affine, n=n)
+                if planes is not None:
+                    planes.gather(st.frames, order[lo:hi], n=n, columns=(actions, old_logps, advs, rets), columns_dst=dst, adv_affine=affine)
+                else:
+                    ops.gather_minibatch(frames, order[lo:hi], st.frames, (actions, old_logps, advs, rets), dst, adv_affine=affine, n=n)
                 f, (a, o, ad, r) = st.frames[:n], dst
             else:
-                f, a, o, ad, r = frames[lo:hi], actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
+                f = planes.stacks(lo, hi, out=st.frames) if planes is not None else frames[lo:hi]
+                a, o, ad, r = actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
             if mode == "minibatch":
                 advantage_affine(ad, n, st, eps, group)
                 ad = ops.normalize(ad, st.affine, out=ad if shuffle else st.adv, n=n)[:n]   # in place on the staged column

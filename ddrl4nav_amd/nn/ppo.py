@@ -13,6 +13,7 @@ import torch
 from ddrl4nav_amd import ops
 from ddrl4nav_amd.nn import minibatch
 from ddrl4nav_amd.data import Experience
+from ddrl4nav_amd.data.frame_planes import planes_of
 from ddrl4nav_amd.engine import HotPath
 from ddrl4nav_amd.nn.base import Basenn
 from ddrl4nav_amd.nn.distribution import HipCategorical
@@ -41,6 +42,7 @@ class PPO(Basenn):
         # config_nn.PPO_MINIBATCHES / PPO_SHUFFLE / NORMALIZE_ADVANTAGE / ADV_NORM_EPS (optional, nn/minibatch.py): epochs of minibatch steps
         self.minibatch = minibatch.minibatch_options(config_nn)
         self._mb_stage = None
+        self._plane_batch = None   # FramePlanes states on the full-batch branch: the batch materialised once per learn call
         self.learn_calls = 0   # learn() calls that took the minibatch loop: the second integer of minibatch.epoch_order
         if hasattr(actor, "log_std"):
             raise NotImplementedError("the Atari fast path has a Categorical actor only (reference atari.yaml)")
@@ -157,12 +159,23 @@ class PPO(Basenn):
     def states_normalization(self, states):
         return states / 255
 
+    def _batch_frames(self, states):
+        """The whole batch as uint8 [B, C, 84, 84] on the device.  FramePlanes (agent/plane_rollout.py) are assembled into a buffer this
+        net keeps: every iteration of the full-batch branch reads contiguous stacks, so for the length of learn() the batch holds the
+        stacked size again (the plane pool's saving lasts through the update only with minibatch epochs, nn/minibatch.py)."""
+        fp = planes_of(states)
+        if fp is None:
+            return _frames_u8(states, self.device)
+        if self._plane_batch is None or self._plane_batch.shape[0] < len(fp) or tuple(self._plane_batch.shape[1:]) != fp.shape[1:]:
+            self._plane_batch = torch.empty(fp.shape, dtype=torch.uint8, device=self.device)
+        return fp.stacks(0, len(fp), out=self._plane_batch)
+
     # ---- PPO.learn (ppo.py:77-146) -----------------------------------------------------------------
     def learn(self, data: Experience):
         if self.minibatch != minibatch.DEFAULTS:   # a knob is set: TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py)
             yield from minibatch.learn(self, data)
             return
-        frames = _frames_u8(data.states, self.device)
+        frames = self._batch_frames(data.states)
         B = frames.shape[0]
         self._ensure_capacity(B)
         f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()

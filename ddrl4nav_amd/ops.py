@@ -239,6 +239,46 @@ def gather_minibatch(frames, idx, frames_dst, columns=None, columns_dst=None, ad
     return frames_dst
 
 
+def frame_age(prev_age, reset, age, channels):
+    """The age row of one step of the single-frame pool (include/ddrl.h ddrl_op_frame_age; csrc/fpool.hip): age[i] = 0 where reset[i] is
+    not zero, else min(prev_age[i] + 1, channels - 1).  reset None: no env is reset; prev_age None (with a reset array): every env is.
+    uint8 [n] on one device.  Asynchronous on the current stream; returns age."""
+    for t in (prev_age, reset, age):
+        assert t is None or (t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.numel() == age.numel()), \
+            "expected contiguous uint8 device tensors of one length"
+    check(_lib.load().ddrl_op_frame_age(_p(prev_age), _p(reset), age.numel(), int(channels), _p(age), _st()))
+    return age
+
+
+def gather_frame_stacks(planes, age, channels, stacks_dst, idx=None, first=0, n=None, columns=None, columns_dst=None, adv_affine=None,
+                        hist=None):
+    """Stacks assembled from the single-frame pool in one launch (include/ddrl.h ddrl_op_gather_frame_stacks; csrc/fpool.hip): planes uint8
+    [rows, N, 84, 84] with `hist` history rows in front (default channels - 1), age uint8 [rows - hist, N]; stacks_dst[j] [channels, 84,
+    84] = the stack of sample idx[j] (int32 on the device), or of sample first + j when idx is None, for j < n.  Columns and adv_affine as
+    in gather_minibatch, indexed by the same samples.  Asynchronous on the current stream; returns stacks_dst."""
+    C = int(channels)
+    hist = C - 1 if hist is None else int(hist)
+    for t in (planes, age, stacks_dst):
+        assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), "expected contiguous uint8 device tensors"
+    rows, N = planes.shape[0], planes.shape[1]
+    assert tuple(planes.shape[2:]) == (84, 84) and age.numel() >= (rows - hist) * N, "planes [rows,N,84,84], age [rows - hist, N]"
+    if idx is not None:
+        assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous(), "idx: contiguous int32 on the device"
+        n = int(idx.numel() if n is None else n)
+        assert idx.numel() >= n
+    n = int(n)
+    assert tuple(stacks_dst.shape[1:]) == (C, 84, 84) and stacks_dst.shape[0] >= n, "stacks_dst: [>= n, channels, 84, 84]"
+    src, dst = list(columns or (None,) * 4), list(columns_dst or (None,) * 4)
+    assert len(src) == 4 and len(dst) == 4, "four columns: actions, old_logps, advs, rets"
+    for s, d in zip(src, dst):
+        assert (s is None) == (d is None), "a column comes with its destination"
+        assert s is None or (_f32(s).numel() >= (rows - hist) * N and _f32(d).numel() >= n)
+    assert adv_affine is None or (_f32(adv_affine).numel() == 2 and src[2] is not None)
+    check(_lib.load().ddrl_op_gather_frame_stacks(_p(planes), rows, N, hist, _p(age), C, _p(idx), int(first), n, _p(stacks_dst),
+                                                  *[_p(t) for t in src], *[_p(t) for t in dst], _p(adv_affine), _st()))
+    return stacks_dst
+
+
 class Conv:
     """One Conv2d / Conv1d layer (torch weight layout [cout][cin][kh][kw]; Conv1d: h = kh = 1)."""
 

@@ -583,6 +583,33 @@ int32_t ddrl_op_gather_minibatch(const uint8_t* frames, int64_t n_rows, int64_t 
                                  float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
                                  void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Single-frame experience pool: every Atari frame stored ONCE (additive: ABI 3).  Instead of whole stacks
+ * [T+1][n_envs][C][84][84], the pool keeps
+ *   planes uint8 [hist + T + 1][n_envs][84][84]   row hist + t = the one frame that arrived for step t, hist >= C - 1 history rows
+ *   age    uint8 [T + 1][n_envs]                  steps since env i's stack was last reset, saturated at C - 1
+ * and channel c of sample b = t * n_envs + i is pool row  hist + t - min(C - 1 - c, age[b], hist + t)  of env i: the observation of
+ * FrameStackWrapper (warputils.py:112-131), what ddrl_frame_stack_push writes out.  The last term of the min is a clamp: whatever
+ * bytes `age` holds, no row below 0 is read.  Both need no context, allocate nothing and are asynchronous on `stream`; their
+ * argument checks run before anything touches HIP; no atomics, so a repeated call gives the same bits.  channels outside 1..4:
+ * DDRL_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+/* age[i] = 0 where reset[i] != 0, else min(prev_age[i] + 1, channels - 1), for i < n.  reset == NULL: no env is reset.
+ * prev_age == NULL (legal only together with a reset array): every env is reset.  age overlaps neither input. */
+int32_t ddrl_op_frame_age(const uint8_t* prev_age, const uint8_t* reset, int32_t n, int32_t channels, uint8_t* age, void* stream);
+/* stacks_dst[j] ([channels][84][84]) = the stack of sample idx[j] (idx int32 on the device), or of sample first + j when idx is NULL
+ * (a contiguous minibatch; the acting slot t: first = t * n_envs, n = n_envs), assembled by the rule above, for j < n.  `rows` is
+ * the number of pool rows given, rows > hist >= channels - 1; samples are valid in [0, (rows - hist) * n_envs), and `age` and
+ * every column given hold that many entries.  The four float columns and adv_affine are those of ddrl_op_gather_minibatch, bit for
+ * bit.  A sample outside the valid range reads nothing and yields a zero stack and zeros in all four columns.  planes and
+ * stacks_dst are 16-byte aligned, n >= 1; nothing that is read (age, idx and adv_affine included) may overlap anything that is
+ * written, nor two destinations one another: DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_gather_frame_stacks(const uint8_t* planes, int32_t rows, int32_t n_envs, int32_t hist, const uint8_t* age,
+                                    int32_t channels, const int32_t* idx, int64_t first, int32_t n, uint8_t* stacks_dst,
+                                    const float* actions, const float* old_logps, const float* advs, const float* rets,
+                                    float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
