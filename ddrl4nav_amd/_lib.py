@@ -186,6 +186,13 @@ SIGNATURES = {
     "ddrl_op_gather_frame_stacks": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),
+    "ddrl_ppo_iter_indexed": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,
+                                        c_void_p]),
+    "ddrl_op_frame_table_planes": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "ddrl_op_frame_table_stacks": (c_int32, [c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

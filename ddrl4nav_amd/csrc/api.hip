@@ -280,13 +280,17 @@ int32_t ddrl_episode_returns(const float* rewards, const uint8_t* dones, int32_t
   return launch_status();
 }
 
-int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions, const float* old_logps,
-                      const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream) {
+// One PPO iteration on B samples whose frames are either the contiguous [B][C][84][84] behind `frames` (tab null) or lie where the
+// frame table says, behind the plane base pointer `frames` (kernels.h EncCall::tab): the body of both entry points
+static int32_t ppo_iter_on(ddrl_ctx* ctx, const uint8_t* frames, const int32_t* tab, int64_t n_planes, const float* actions,
+                           const float* old_logps, const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream) {
   if (!ctx || !frames || !actions || !old_logps || !advs || !rets) return DDRL_ERR_INVALID_ARG;
   if (B < 1 || B > ctx->cfg.max_batch || B_global < B) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   ensure_packed(ctx, st);
   EncCall ec = ctx_enc_call(ctx, frames, B, ctx->profile ? ctx : nullptr);
+  ec.tab = tab;
+  ec.n_planes = n_planes;
   if (ctx->buckets) ec.bucket_ev = ctx->bucket_ev;
   ctx->acts_stored = true;
   launch_encoder_forward(ec, false, st);
@@ -301,6 +305,19 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
   ctx->iter_n = B;
   ctx->bucket_events_fresh = ctx->buckets;
   return launch_status();
+}
+
+int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions, const float* old_logps,
+                      const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream) {
+  return ppo_iter_on(ctx, frames, nullptr, 0, actions, old_logps, advs, rets, B, B_global, stream);
+}
+
+int32_t ddrl_ppo_iter_indexed(ddrl_ctx* ctx, const uint8_t* planes, int64_t n_planes, const int32_t* tab, const float* actions,
+                              const float* old_logps, const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream) {
+  // the frame source's own checks, before anything touches the context or HIP
+  if (!planes || !tab || !aligned16(planes) || ((uintptr_t)tab & 3) || n_planes < 1) return DDRL_ERR_INVALID_ARG;
+  if (n_planes > INT64_MAX / 7056) return DDRL_ERR_INVALID_ARG;
+  return ppo_iter_on(ctx, planes, tab, n_planes, actions, old_logps, advs, rets, B, B_global, stream);
 }
 
 // the diagnostics head on what ddrl_ppo_iter left behind: its features, and -- its head partials being reduced -- the front of their

@@ -42,11 +42,15 @@ struct Fwd1B {
   static constexpr size_t LDS_BYTES = 2 * STAGE_BYTES;
 };
 
-template <int NE>
+// IND: the frames are read in place through a frame table (kernels.h EncCall::tab): `frames` is the plane base pointer and the base of
+// (sample, channel) is a looked-up, clamped plane instead of b * (C * 7056) + ch * 7056.  A tile touches two samples at most, so its
+// eight bases are uniform per workgroup; the per-lane part is a 32-bit offset inside the plane and one bit that names the sample.
+template <int NE, bool IND = false>
 __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __restrict__ frames, const unsigned short* __restrict__ wp1b,
                                                                float* __restrict__ amax, const float* __restrict__ params, int64_t bias_off0,
                                                                int64_t bias_off1, float* __restrict__ out, int64_t out_es, int n,
-                                                               unsigned* __restrict__ m1, int64_t m1_es, int C) {
+                                                               unsigned* __restrict__ m1, int64_t m1_es, int C,
+                                                               const int32_t* __restrict__ tab, int64_t n_planes) {
   using K = Fwd1B<NE>;
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6, l31 = lane & 31, hi = lane >> 5;
@@ -68,10 +72,18 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
   if (blockIdx.x == 0 && tid < (AMAX_DH - AMAX_FIRST_ACT) * 2) amax[amax_idx(AMAX_FIRST_ACT, 0) + tid] = 0.0f;
   int64_t imsrc[6];
   int imdst[6];
+  int imoff[6];         // IND: byte offset inside the plane; bit j of imsel: the dword belongs to the tile's second sample
+  unsigned imsel = 0u;
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     const int idx = tid + 256 * j;
-    imsrc[j] = (idx >= nd_total) ? src0 : (idx < nd0 ? src0 + idx * 4 : src1 + (idx - nd0) * 4);
+    if constexpr (IND) {
+      const bool second = idx < nd_total && idx >= nd0;
+      imoff[j] = second ? (idx - nd0) * 4 : iy0_start * 84 + (idx < nd0 ? idx * 4 : 0);
+      imsel |= (second ? 1u : 0u) << j;
+    } else {
+      imsrc[j] = (idx >= nd_total) ? src0 : (idx < nd0 ? src0 + idx * 4 : src1 + (idx - nd0) * 4);
+    }
     imdst[j] = K::A_BYTES + (idx / 21) * K::PITCH + (idx % 21) * 8;  // 4 pixels -> 4 halfwords
   }
   int abase[NE], bbase[2];
@@ -88,10 +100,19 @@ __global__ __launch_bounds__(256) void conv_fwd1_planes_kernel(const uint8_t* __
   // the frame bytes of all four channels are requested at once (24 dwords per thread): with 48 short MFMAs per
   // k-block a one-block prefetch distance does not cover an HBM round trip
   unsigned imreg[4][6];
+  if constexpr (IND) {
 #pragma unroll
-  for (int ch = 0; ch < 4; ++ch)
+    for (int ch = 0; ch < 4; ++ch) {  // the table repeats the last channel for the missing ones: always four
+      const int64_t pb0 = frame_plane_base(tab, b0, ch, n_planes), pb1 = frame_plane_base(tab, b1, ch, n_planes);
 #pragma unroll
-    for (int j = 0; j < 6; ++j) imreg[ch][j] = *(const unsigned*)(frames + (ch < C ? ch : C - 1) * 7056 + imsrc[j]);  // unconditional, clamped
+      for (int j = 0; j < 6; ++j) imreg[ch][j] = *(const unsigned*)(frames + (((imsel >> j) & 1u) ? pb1 : pb0) + imoff[j]);
+    }
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) imreg[ch][j] = *(const unsigned*)(frames + (ch < C ? ch : C - 1) * 7056 + imsrc[j]);  // unconditional, clamped
+  }
   // the weight planes of a channel are a plain copy of global memory: LDS-direct, one k-block ahead (L2-resident)
   const int wave = wave_u();
   uint32_t woff[K::NAJ];
@@ -202,11 +223,14 @@ struct Fwd1R {
   static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 };
 
-template <int NE>
+// IND: as in conv_fwd1_planes_kernel; the eight plane bases of a tile are uniform per 256-thread group and are fetched (as uniform values)
+// in geometry(), i.e. together with the tile's request, one tile ahead of its use.
+template <int NE, bool IND = false>
 __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* __restrict__ frames, const unsigned short* __restrict__ wp1b,
                                                                  float* __restrict__ amax, const float* __restrict__ params, int64_t bias_off0,
                                                                  int64_t bias_off1, float* __restrict__ out, int64_t out_es, int n,
-                                                                 unsigned* __restrict__ m1, int64_t m1_es, int C) {
+                                                                 unsigned* __restrict__ m1, int64_t m1_es, int C,
+                                                                 const int32_t* __restrict__ tab, int64_t n_planes) {
   using K = Fwd1R<NE>;
   extern __shared__ __attribute__((aligned(16))) char ldsr[];
   const int tid = threadIdx.x, gq = tid >> 8, lt = tid & 255, lane = tid & 63, wc = (tid >> 6) & 3, l31 = lane & 31, hi = lane >> 5;
@@ -229,6 +253,7 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
   struct Geo {
     int c0, b0, iy0_start, nrows0, nd0, nd_total;
     int64_t src0, src1;
+    int64_t pb[2][4];  // IND: plane bases of the tile's two samples
   };
   auto geometry = [&](int t) {
     Geo g;
@@ -246,6 +271,15 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
     }
     g.nd0 = g.nrows0 * 21;
     g.nd_total = g.nd0 + nrows1 * 21;
+    if constexpr (IND) {
+      const int ub0 = __builtin_amdgcn_readfirstlane(g.b0), ub1 = __builtin_amdgcn_readfirstlane(b1);  // uniform per group of four waves
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        g.pb[0][ch] = frame_plane_base(tab, ub0, ch, n_planes);
+        g.pb[1][ch] = frame_plane_base(tab, ub1, ch, n_planes);
+      }
+      return g;
+    }
     g.src0 = (int64_t)g.b0 * (C * 7056) + g.iy0_start * 84;
     g.src1 = (int64_t)b1 * (C * 7056);
     return g;
@@ -255,6 +289,18 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       const int idx = lt + 256 * j;
+      if constexpr (IND) {
+        const bool second = idx < g.nd_total && idx >= g.nd0;
+        const int o = second ? (idx - g.nd0) * 4 : g.iy0_start * 84 + (idx < g.nd0 ? idx * 4 : 0);
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+          // both bases by VALUE before the select: a select between two by-reference captures becomes a load through a selected pointer
+          // and sends the captured arrays to scratch (wgrad2.hip, at gsj[])
+          const int64_t p0 = g.pb[0][ch], p1 = g.pb[1][ch];
+          imreg[ch][j] = *(const unsigned*)(frames + (second ? p1 : p0) + o);
+        }
+        continue;
+      }
       const int64_t o = (idx >= g.nd_total) ? g.src0 : (idx < g.nd0 ? g.src0 + idx * 4 : g.src1 + (idx - g.nd0) * 4);
 #pragma unroll
       for (int ch = 0; ch < 4; ++ch) imreg[ch][j] = *(const unsigned*)(frames + (ch < C ? ch : C - 1) * 7056 + o);
@@ -347,27 +393,36 @@ __global__ __launch_bounds__(512) void conv_fwd1_resident_kernel(const uint8_t* 
   }
 }
 
-template <int NE>
+template <int NE, bool IND>
 static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
   const Workspace& w = *c.ws;
   const ParamLayout& L = *c.L;
   if (!acting && (int64_t)c.n * C1_P >= 256 * 2048) {  // at least ~8 tiles per workgroup: the 64 KB weight copy pays
     using R = Fwd1R<NE>;
-    lds_limit_once<conv_fwd1_resident_kernel<NE>>((int)R::LDS_BYTES);
+    lds_limit_once<conv_fwd1_resident_kernel<NE, IND>>((int)R::LDS_BYTES);
     static const int cus = [] {
       int dev = 0;
       hipDeviceProp_t prop;
       return hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
     }();
-    hipLaunchKernelGGL(conv_fwd1_resident_kernel<NE>, dim3((unsigned)cus), dim3(512), R::LDS_BYTES, st, c.frames, w.wp1b, w.amax, c.params,
-                       L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n, w.m1, w.es(M1_N), L.C);
+    hipLaunchKernelGGL((conv_fwd1_resident_kernel<NE, IND>), dim3((unsigned)cus), dim3(512), R::LDS_BYTES, st, c.frames, w.wp1b, w.amax, c.params,
+                       L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n, w.m1, w.es(M1_N), L.C, c.tab, c.n_planes);
     return;
   }
   using K = Fwd1B<NE>;
-  lds_limit_once<conv_fwd1_planes_kernel<NE>>((int)K::LDS_BYTES);
-  hipLaunchKernelGGL(conv_fwd1_planes_kernel<NE>, dim3((unsigned)(((int64_t)c.n * C1_P + 255) / 256)), dim3(256), K::LDS_BYTES, st, c.frames,
+  lds_limit_once<conv_fwd1_planes_kernel<NE, IND>>((int)K::LDS_BYTES);
+  hipLaunchKernelGGL((conv_fwd1_planes_kernel<NE, IND>), dim3((unsigned)(((int64_t)c.n * C1_P + 255) / 256)), dim3(256), K::LDS_BYTES, st, c.frames,
                      w.wp1b, w.amax, c.params, L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n,
-                     acting ? (unsigned*)nullptr : w.m1, w.es(M1_N), L.C);
+                     acting ? (unsigned*)nullptr : w.m1, w.es(M1_N), L.C, c.tab, c.n_planes);
+}
+// the frame source picks the instantiation: a frame table (training launches only, api.hip) = the indirect one
+template <int NE>
+static void launch_fwd1(const EncCall& c, bool acting, hipStream_t st) {
+  if (c.tab != nullptr) {
+    launch_fwd1_planes<NE, true>(c, acting, st);
+  } else {
+    launch_fwd1_planes<NE, false>(c, acting, st);
+  }
 }
 
 // ================================================================================================
@@ -703,9 +758,9 @@ void launch_conv_forward(const EncCall& c, bool acting, hipStream_t st) {
   {
     ProfRange pr(c.prof, acting ? "ConvFwd1.act" : "ConvFwd1", st);
     if (c.L->NE == 2) {
-      launch_fwd1_planes<2>(c, acting, st);
+      launch_fwd1<2>(c, acting, st);
     } else {
-      launch_fwd1_planes<1>(c, acting, st);
+      launch_fwd1<1>(c, acting, st);
     }
   }
   {

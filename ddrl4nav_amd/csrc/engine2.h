@@ -321,6 +321,16 @@ __device__ __forceinline__ unsigned pixel_pair_sel(unsigned a, unsigned b) { ret
 __device__ __forceinline__ unsigned short pixel_one(unsigned a) { return __builtin_bit_cast(unsigned short, (_Float16)(float)a); }
 // the four pixels of one dword as two operand pairs
 __device__ __forceinline__ uint2 pixel_quad(unsigned v) { return make_uint2(pixel_pair_sel<0, 1>(v, v), pixel_pair_sel<2, 3>(v, v)); }
+// Frame table (include/ddrl.h ddrl_op_frame_table_*; EncCall::tab): byte offset of the plane that holds channel ch of sample b, from the
+// plane base pointer.  The clamp is part of the contract of the indirect conv1 kernels: whatever the table holds, nothing outside
+// [planes, planes + n_planes * 7056) is read.
+constexpr int FRAME_PLANE_BYTES = 84 * 84;
+__device__ __forceinline__ int64_t frame_plane_base(const int32_t* __restrict__ tab, int b, int ch, int64_t n_planes) {
+  int64_t p = tab[(int64_t)b * 4 + ch];
+  p = p < 0 ? 0 : p;
+  p = p > n_planes - 1 ? n_planes - 1 : p;
+  return p * FRAME_PLANE_BYTES;
+}
 __host__ __device__ inline void planes_of(float w, float scale, unsigned short (&p)[NPL]) {
   const float ws = w * scale;
   const _Float16 h0 = (_Float16)ws;

@@ -614,11 +614,15 @@ struct Wgrad1B {
   static constexpr size_t LDS_BYTES = 2 * A_BYTES + IMG_BYTES;
 };
 
-template <int NE>
+// IND: the frames are read in place through a frame table (kernels.h EncCall::tab): `frames` is the plane base pointer, and the base of a
+// thread's (sample, channel) -- fixed per staging unit, new once per sample pair -- is a looked-up, clamped plane kept in a register per
+// lane, fetched where gsj[] is fetched.
+template <int NE, bool IND = false>
 __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ dz,
                                                                  const unsigned* __restrict__ m1, int64_t m1_es, int64_t dz_es,
                                                                  const float* __restrict__ amax, const float* __restrict__ gsc, int64_t gsc_es,
-                                                                 float* __restrict__ part, int n, int nsplit, int C) {
+                                                                 float* __restrict__ part, int n, int nsplit, int C,
+                                                                 const int32_t* __restrict__ tab, int64_t n_planes) {
   using K = Wgrad1B<NE>;
   const int fs = C * 7056;  // bytes of one sample's C stacked frames (1..4); wave wc owns the 64 taps of channel wc and idles past C
   extern __shared__ __attribute__((aligned(16))) char ldsw[];
@@ -653,12 +657,14 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
   // i.e. the second group = the k = 1 units of threads 0 .. 127, a lone group = the k = 0 units of waves 0 .. 2
   uint32_t imoff[2];
   int bdst[2];
-  unsigned im_s1 = 0, im_g1 = 0, im_ok1 = 0, im_ok2 = 0, im_tail = 0;
+  unsigned im_s1 = 0, im_g1 = 0, im_ok1 = 0, im_ok2 = 0, im_tail = 0, im_ch = 0;
+  int64_t imbase[2] = {0, 0};  // IND: byte offset of the plane of unit k's (sample, channel) in the present pair
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int u = tid + 256 * k, uc = min(u, 383);
     const int R = uc / 6, g = uc % 6, gsel = R >> 5, smp = (R >> 4) & 1, ch = min((R >> 2) & 3, C - 1), r = R & 3;  // missing channels re-read the last one
-    imoff[k] = (uint32_t)(smp * fs + ch * 7056 + (4 * gsel + r) * 84 + (g < 5 ? g * 16 : 68));  // g = 5: bytes 68..83, last dword
+    imoff[k] = (uint32_t)((IND ? 0 : smp * fs + ch * 7056) + (4 * gsel + r) * 84 + (g < 5 ? g * 16 : 68));  // g = 5: bytes 68..83, last dword
+    im_ch |= (unsigned)ch << (2 * k);
     bdst[k] = K::IMG_OFF + ((smp * 4 + ch) * 16 + r) * 192 + (g < 5 ? g * 8 : 40);              // + ring group * 4 * 192
     im_s1 |= (unsigned)smp << k;
     im_g1 |= (unsigned)gsel << k;
@@ -704,11 +710,16 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
     if (imfirst) {  // wave-uniform: the 20 k-blocks of a sample pair share their scales
 #pragma unroll
       for (int j = 0; j < K::NDZ_J; ++j) gsj[j] = ld_gs(gs, min(2 * pair + (int)((dz_s1 >> j) & 1u), n - 1));
+      if constexpr (IND) {  // the odd batch tail looks up its first sample again, as the contiguous form re-reads it
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+          imbase[k] = frame_plane_base(tab, min(2 * pair + (int)((im_s1 >> k) & 1u), n - 1), (int)((im_ch >> (2 * k)) & 3u), n_planes);
+      }
     }
     const int64_t sb = ew * dz_es + (int64_t)pair * (2 * A1_N) + oy * 20;
     const char* dzb = (const char*)(dz + sb);
     const char* mb = (const char*)(m1 + ew * m1_es + (int64_t)pair * (2 * M1_N) + oy * 20);
-    const char* fp = (const char*)frames + (int64_t)pair * (2 * fs) + (oy + gfirst) * 336;
+    const char* fp = (const char*)frames + (IND ? (int64_t)0 : (int64_t)pair * (2 * fs)) + (oy + gfirst) * 336;
     // odd batch tail: the second sample does not exist -> its slots read the first sample, commit() zeroes its dz
 #pragma unroll
     for (int j = 0; j < K::NDZ_J; ++j) {
@@ -721,8 +732,8 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
     for (int k = 0; k < 2; ++k) {
       // wave-uniform skips: a lone group has no k = 1 units and none in wave 3 (their loads were the cost, not the conversion)
       if (!imfirst && (k == 1 || !lone_group_wave)) continue;
-      const uint32_t o = full ? imoff[k] : imoff[k] - ((im_s1 >> k) & 1u) * (uint32_t)fs;
-      const unsigned* q = (const unsigned*)(fp + o);  // 4-byte aligned
+      const uint32_t o = (IND || full) ? imoff[k] : imoff[k] - ((im_s1 >> k) & 1u) * (uint32_t)fs;
+      const unsigned* q = (const unsigned*)(fp + (IND ? imbase[k] : (int64_t)0) + o);  // 4-byte aligned
       imr[k] = (u4w){q[0], q[1], q[2], q[3]};
     }
   };
@@ -847,13 +858,22 @@ __global__ __launch_bounds__(256) void conv_wgrad1_planes_kernel(const uint8_t* 
   }
 }
 
-template <int NE>
+template <int NE, bool IND>
 static void launch_wgrad1_planes(const EncCall& c, int S, hipStream_t st) {
   using K = Wgrad1B<NE>;
   const Workspace& w = *c.ws;
-  lds_limit_once<conv_wgrad1_planes_kernel<NE>>((int)K::LDS_BYTES);
-  hipLaunchKernelGGL(conv_wgrad1_planes_kernel<NE>, dim3(1, S, 1), dim3(256), K::LDS_BYTES, st, c.frames, w.dz1, w.m1, w.es(M1_N),
-                     w.es(A1_N), w.amax, w.gsc, w.es(1), w.wpart, c.n, S, c.L->C);
+  lds_limit_once<conv_wgrad1_planes_kernel<NE, IND>>((int)K::LDS_BYTES);
+  hipLaunchKernelGGL((conv_wgrad1_planes_kernel<NE, IND>), dim3(1, S, 1), dim3(256), K::LDS_BYTES, st, c.frames, w.dz1, w.m1, w.es(M1_N),
+                     w.es(A1_N), w.amax, w.gsc, w.es(1), w.wpart, c.n, S, c.L->C, c.tab, c.n_planes);
+}
+// the frame source picks the instantiation: a frame table (api.hip ddrl_ppo_iter_indexed) = the indirect one
+template <int NE>
+static void launch_wgrad1(const EncCall& c, int S, hipStream_t st) {
+  if (c.tab != nullptr) {
+    launch_wgrad1_planes<NE, true>(c, S, st);
+  } else {
+    launch_wgrad1_planes<NE, false>(c, S, st);
+  }
 }
 
 void launch_conv_wgrad1(const EncCall& c, float* grads, hipStream_t st) {
@@ -863,9 +883,9 @@ void launch_conv_wgrad1(const EncCall& c, float* grads, hipStream_t st) {
   {
     ProfRange pr(c.prof, "ConvWgrad1", st);
     if (L.NE == 2) {
-      launch_wgrad1_planes<2>(c, S, st);
+      launch_wgrad1<2>(c, S, st);
     } else {
-      launch_wgrad1_planes<1>(c, S, st);
+      launch_wgrad1<1>(c, S, st);
     }
   }
   ProfRange pr(c.prof, "reduce_partials", st);

@@ -5,7 +5,8 @@
 
 Sample b = t * N + i (the order of DeviceRollout.batch()) is the stack whose channel c is pool row H + t - min(C - 1 - c, age[b], H + t)
 of env i; csrc/fpool.hip (ddrl_op_gather_frame_stacks) assembles it where it is read.  Only the Atari fast path (nn/ppo.py PPO) reads
-this form: nn/minibatch.py gathers every minibatch from it, the full-batch branch materialises the batch once per learn call."""
+this form: nn/minibatch.py gathers every minibatch from it, the full-batch branch materialises the batch once per learn call -- or,
+with config_nn.FRAMES_IN_PLACE, both read the planes where they lie through a frame table (table(); csrc/ftable.hip)."""
 import torch
 
 from ddrl4nav_amd import ops
@@ -38,6 +39,19 @@ class FramePlanes:
         H = self.C - 1
         return ops.gather_frame_stacks(self.planes[:H + self.T], self.age[:self.T], self.C, out, idx=idx, first=first, n=n,
                                        columns=columns, columns_dst=columns_dst, adv_affine=adv_affine)
+
+    @property
+    def pool(self):
+        """The planes a table of table() counts from: the rows of the batch (history included, the bootstrap row not)."""
+        return self.planes[:self.C - 1 + self.T]
+
+    def table(self, tab=None, idx=None, first=0, n=None, columns=None, columns_dst=None, adv_affine=None):
+        """tab int32 [>= n, 4]: where the stack of sample idx[j] (or first + j) lies in `pool`, for HotPath.ppo_iter_indexed, with the
+        columns of ops.gather_minibatch riding along (ops.frame_table_planes).  No frame is moved.  Returns tab."""
+        if tab is None:
+            tab = torch.empty((int(idx.numel() if n is None else n), 4), dtype=torch.int32, device=self.planes.device)
+        return ops.frame_table_planes(self.pool, self.age[:self.T], self.C, tab, idx=idx, first=first, n=n, columns=columns,
+                                      columns_dst=columns_dst, adv_affine=adv_affine)
 
     def stacks(self, lo, hi, out=None):
         """Samples lo..hi-1 materialised as uint8 [hi - lo, C, 84, 84] (into the front of `out` when given); returns that view."""

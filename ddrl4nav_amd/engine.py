@@ -164,6 +164,19 @@ class HotPath:
         check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames), _p(actions), _p(old_logps), _p(advs), _p(rets),
                                      B, int(b_global if b_global is not None else B), _st()))
 
+    def ppo_iter_indexed(self, planes, tab, actions, old_logps, advs, rets, b_global=None):
+        """ppo_iter on frames read where they lie (include/ddrl.h ddrl_ppo_iter_indexed): `planes` is any contiguous uint8 device tensor
+        of whole 84 x 84 planes (a single-frame pool, or stacked frames) and tab int32 [>= B, 4] (ops.frame_table_planes /
+        frame_table_stacks) names the plane of every channel of the B = actions.numel() samples.  Bit-identical to ppo_iter on the
+        materialised frames."""
+        B = actions.numel()
+        for t in (actions, old_logps, advs, rets):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
+        assert planes.dtype == torch.uint8 and planes.is_cuda and planes.is_contiguous() and planes.numel() % (84 * 84) == 0
+        assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * B
+        check(self.lib.ddrl_ppo_iter_indexed(self.ctx, _p(planes), planes.numel() // (84 * 84), _p(tab), _p(actions), _p(old_logps),
+                                             _p(advs), _p(rets), B, int(b_global if b_global is not None else B), _st()))
+
     def ppo_diag(self, actions, old_logps, rets, out=None):
         """The eight diagnostics sums (ops.diag_dict) of THIS rank's batch on the features the last ppo_iter left behind, i.e. for the
         policy its loss was evaluated with; call between ppo_iter and clip_adam_step.  Reads only.  Returns 8 float64 on the device

@@ -10,6 +10,10 @@ The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the Config
                                "minibatch": over every (global) minibatch
   ADV_NORM_EPS         1e-8    the eps above
 
+  FRAMES_IN_PLACE      False   True: no minibatch of frames is staged; the conv1 kernels read the batch where it lies through a frame
+                               table (csrc/ftable.hip, ddrl_ppo_iter_indexed).  Same bits.  Not one of the four knobs that bring
+                               PPO.learn here: on the full-batch branch it keeps FramePlanes states from being materialised (nn/ppo.py)
+
 With all four at their defaults PPO.learn does not come here.  Per step, everything on the device and in stream order: one
 ddrl_op_gather_minibatch into ONE staging buffer (shuffle on; off: contiguous views, nothing is copied; states given as
 data.FramePlanes: ddrl_op_gather_frame_stacks into the same buffer, shuffled or not), the moments / affine / normalise operators of
@@ -41,6 +45,21 @@ def minibatch_options(config_nn):
     if not eps >= 0.0:
         raise ValueError("ADV_NORM_EPS must be >= 0, got %r" % (eps,))
     return int(k), bool(getattr(config_nn, "PPO_SHUFFLE", False)), mode, eps
+
+
+def frames_in_place_option(config_nn):
+    """config_nn.FRAMES_IN_PLACE (optional, default False) as a bool; ValueError for anything but True / False."""
+    v = getattr(config_nn, "FRAMES_IN_PLACE", False)
+    if not isinstance(v, bool):
+        raise ValueError("FRAMES_IN_PLACE must be True or False, got %r" % (v,))
+    return v
+
+
+def refuse_frames_in_place(config_nn, who):
+    """GenericPPO and GAIL run operator-composed encoders on float states: no conv1 kernel there reads a frame table."""
+    if frames_in_place_option(config_nn):
+        raise ValueError("FRAMES_IN_PLACE is built for the Atari fast path alone (nn/ppo.py PPO over AtariPreNet), not for %s: unset it"
+                         % who)
 
 
 def refuse_minibatch_options(config_nn, who):
@@ -91,18 +110,20 @@ class Staging:
     makes its reuse safe), one scratch advantage column of the whole batch, the three double sums, the affine pair and the moments'
     workspace."""
 
-    def __init__(self, device, frame_shape, cap, B):
-        self.cap, self.B, self.frame_shape = int(cap), int(B), tuple(frame_shape)
+    def __init__(self, device, frame_shape, cap, B, in_place=False):
+        self.cap, self.B, self.frame_shape, self.in_place = int(cap), int(B), tuple(frame_shape), bool(in_place)
         f32 = dict(dtype=torch.float32, device=device)
-        self.frames = torch.empty((self.cap,) + self.frame_shape, dtype=torch.uint8, device=device)
+        # FRAMES_IN_PLACE: no frame buffer at all, one frame table of a minibatch instead (16 bytes per sample)
+        self.frames = None if in_place else torch.empty((self.cap,) + self.frame_shape, dtype=torch.uint8, device=device)
+        self.tab = torch.empty((self.cap, 4), dtype=torch.int32, device=device) if in_place else None
         self.cols = torch.empty((4, self.cap), **f32)
         self.adv = torch.empty(self.B, **f32)
         self.sums = torch.zeros(3, dtype=torch.float64, device=device)
         self.affine = torch.zeros(2, **f32)
         self.ws = torch.empty(ops.moments_ws_floats(self.B), **f32)
 
-    def fits(self, frame_shape, cap, B):
-        return self.frame_shape == tuple(frame_shape) and self.cap >= cap and self.B >= B
+    def fits(self, frame_shape, cap, B, in_place=False):
+        return self.frame_shape == tuple(frame_shape) and self.cap >= cap and self.B >= B and self.in_place == bool(in_place)
 
 
 def advantage_affine(column, n, st, eps, group):
@@ -133,9 +154,10 @@ def learn(net, data):
     if net.target_kl is not None and net.deferred_stats:
         raise ValueError("TARGET_KL needs the host after every step: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
     hp, group, diag, deferred = net._hp, net._process_group, net.diagnostics, net.deferred_stats
+    in_place = getattr(net, "frames_in_place", False)
     st = net._mb_stage
-    if st is None or not st.fits(frames.shape[1:], cap, B):
-        st = net._mb_stage = Staging(net.device, frames.shape[1:], cap, B)
+    if st is None or not st.fits(frames.shape[1:], cap, B, in_place):
+        st = net._mb_stage = Staging(net.device, frames.shape[1:], cap, B, in_place)
     call = net.learn_calls
     net.learn_calls += 1
     rank = 0
@@ -163,7 +185,19 @@ def learn(net, data):
         for j, (lo, hi) in enumerate(ranges):
             t0 = time.time()
             n = hi - lo
-            if shuffle:
+            tab = None                         # FRAMES_IN_PLACE: the step's frame table; ppo_iter_indexed reads the batch where it lies
+            if in_place and shuffle:
+                dst = [st.cols[k, :n] for k in range(4)]
+                if planes is not None:
+                    tab = planes.table(st.tab, idx=order[lo:hi], n=n, columns=(actions, old_logps, advs, rets), columns_dst=dst, adv_affine=affine)
+                else:
+                    tab = ops.frame_table_stacks(frames, st.tab, idx=order[lo:hi], n=n, columns=(actions, old_logps, advs, rets),
+                                                 columns_dst=dst, adv_affine=affine)
+                a, o, ad, r = dst
+            elif in_place and planes is not None:
+                tab = planes.table(st.tab, first=lo, n=n)
+                a, o, ad, r = actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
+            elif shuffle:
                 dst = [st.cols[k, :n] for k in range(4)]
                 if planes is not None:
                     planes.gather(st.frames, order[lo:hi], n=n, columns=(actions, old_logps, advs, rets), columns_dst=dst, adv_affine=affine)
@@ -178,7 +212,10 @@ def learn(net, data):
                 ad = ops.normalize(ad, st.affine, out=ad if shuffle else st.adv, n=n)[:n]   # in place on the staged column
             if j not in b_globals:             # the ranks' j-th sizes: one collective per j, in the first epoch
                 b_globals[j] = global_batch(n, group)
-            hp.ppo_iter(f, a, o, ad, r, b_global=b_globals[j])
+            if tab is not None:
+                hp.ppo_iter_indexed(planes.pool if planes is not None else frames, tab, a, o, ad, r, b_global=b_globals[j])
+            else:
+                hp.ppo_iter(f, a, o, ad, r, b_global=b_globals[j])
             if deferred:
                 if diag:
                     net._diag_rows[i].copy_(hp.ppo_diag(a, o, r, out=net._diag_dev[i]), non_blocking=True)

@@ -41,6 +41,10 @@ class PPO(Basenn):
         self.diagnostics, self.target_kl = ops.diag_options(config_nn)
         # config_nn.PPO_MINIBATCHES / PPO_SHUFFLE / NORMALIZE_ADVANTAGE / ADV_NORM_EPS (optional, nn/minibatch.py): epochs of minibatch steps
         self.minibatch = minibatch.minibatch_options(config_nn)
+        # config_nn.FRAMES_IN_PLACE (optional, nn/minibatch.py): no batch or minibatch of frames is materialised; the conv1 kernels read
+        # them where they lie through a frame table (ddrl_ppo_iter_indexed).  Same bits; off by default
+        self.frames_in_place = minibatch.frames_in_place_option(config_nn)
+        self._frame_tab = None
         self._mb_stage = None
         self._plane_batch = None   # FramePlanes states on the full-batch branch: the batch materialised once per learn call
         self.learn_calls = 0   # learn() calls that took the minibatch loop: the second integer of minibatch.epoch_order
@@ -175,8 +179,17 @@ class PPO(Basenn):
         if self.minibatch != minibatch.DEFAULTS:   # a knob is set: TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py)
             yield from minibatch.learn(self, data)
             return
-        frames = self._batch_frames(data.states)
-        B = frames.shape[0]
+        fp = planes_of(data.states) if self.frames_in_place else None
+        if fp is not None:   # FRAMES_IN_PLACE: one frame table per learn call, every iteration reads the planes where they lie
+            B = len(fp)
+            if self._frame_tab is None or self._frame_tab.shape[0] < B:
+                self._frame_tab = torch.empty((B, 4), dtype=torch.int32, device=self.device)
+            pool, tab = fp.pool, fp.table(self._frame_tab, first=0, n=B)
+            ppo_iter = lambda *cols, **kw: self._hp.ppo_iter_indexed(pool, tab, *cols, **kw)
+        else:
+            frames = self._batch_frames(data.states)
+            B = frames.shape[0]
+            ppo_iter = lambda *cols, **kw: self._hp.ppo_iter(frames, *cols, **kw)
         self._ensure_capacity(B)
         f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
         actions, old_logps, advs = f32(data.actions), f32(data.old_logps), f32(data.advs)
@@ -205,7 +218,7 @@ class PPO(Basenn):
                 self._diag_dev = torch.zeros((k, ops.DIAG_SLOTS), dtype=torch.float64, device=self.device)
             t0 = time.time()
             for i in range(k):
-                self._hp.ppo_iter(frames, actions, old_logps, advs, rets, b_global=b_global)
+                ppo_iter(actions, old_logps, advs, rets, b_global=b_global)
                 if diag:
                     self._diag_rows[i].copy_(self._hp.ppo_diag(actions, old_logps, rets, out=self._diag_dev[i]), non_blocking=True)
                 self._hp.allreduce_grads()
@@ -224,7 +237,7 @@ class PPO(Basenn):
             return
         for _ in range(self.training_iter_time):
             t0 = time.time()
-            self._hp.ppo_iter(frames, actions, old_logps, advs, rets, b_global=b_global)
+            ppo_iter(actions, old_logps, advs, rets, b_global=b_global)
             d = None
             if diag:
                 # read before anything is applied: the sums describe the policy this iteration's loss was evaluated with, combined

@@ -279,6 +279,51 @@ def gather_frame_stacks(planes, age, channels, stacks_dst, idx=None, first=0, n=
     return stacks_dst
 
 
+def _table_args(tab, idx, first, n, n_samples, columns, columns_dst, adv_affine):
+    """The arguments both frame-table builders share, checked: (tab, idx, first, n, column sources, column destinations)."""
+    if idx is not None:
+        assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous(), "idx: contiguous int32 on the device"
+        n = int(idx.numel() if n is None else n)
+        assert idx.numel() >= n
+    n = int(n)
+    assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * n, "tab: contiguous int32 [>= n, 4]"
+    src, dst = list(columns or (None,) * 4), list(columns_dst or (None,) * 4)
+    assert len(src) == 4 and len(dst) == 4, "four columns: actions, old_logps, advs, rets"
+    for s, d in zip(src, dst):
+        assert (s is None) == (d is None), "a column comes with its destination"
+        assert s is None or (_f32(s).numel() >= n_samples and _f32(d).numel() >= n)
+    assert adv_affine is None or (_f32(adv_affine).numel() == 2 and src[2] is not None)
+    return n, src, dst
+
+
+def frame_table_planes(planes, age, channels, tab, idx=None, first=0, n=None, columns=None, columns_dst=None, adv_affine=None, hist=None):
+    """The frame table of n samples of the single-frame pool (include/ddrl.h ddrl_op_frame_table_planes; csrc/ftable.hip): tab int32
+    [>= n, 4], tab[j][c] = index of the plane of `planes` (uint8 [rows, N, 84, 84], `hist` history rows in front, default channels - 1)
+    that holds channel c of sample idx[j] (int32 on the device), or of sample first + j when idx is None, by the rule of
+    gather_frame_stacks.  Columns and adv_affine as in gather_minibatch.  A sample outside the valid range is CLAMPED to it (the
+    gathers return zeros).  No frame is touched.  Asynchronous on the current stream; returns tab."""
+    C = int(channels)
+    hist = C - 1 if hist is None else int(hist)
+    assert age.dtype == torch.uint8 and age.is_cuda and age.is_contiguous(), "age: contiguous uint8 on the device"
+    rows, N = planes.shape[0], planes.shape[1]
+    assert tuple(planes.shape[2:]) == (84, 84) and age.numel() >= (rows - hist) * N, "planes [rows,N,84,84], age [rows - hist, N]"
+    n, src, dst = _table_args(tab, idx, first, n, (rows - hist) * N, columns, columns_dst, adv_affine)
+    check(_lib.load().ddrl_op_frame_table_planes(rows, N, hist, _p(age), C, _p(idx), int(first), n, _p(tab), *[_p(t) for t in src],
+                                                 *[_p(t) for t in dst], _p(adv_affine), _st()))
+    return tab
+
+
+def frame_table_stacks(frames, tab, idx=None, first=0, n=None, columns=None, columns_dst=None, adv_affine=None):
+    """The frame table of n samples of stacked frames uint8 [n_rows, C, 84, 84] (include/ddrl.h ddrl_op_frame_table_stacks):
+    tab[j][c] = b * C + c for sample b = idx[j] or first + j, clamped to [0, n_rows); entries c >= C repeat entry C - 1.  Columns and
+    adv_affine as in gather_minibatch.  Asynchronous on the current stream; returns tab."""
+    assert frames.dim() == 4 and tuple(frames.shape[2:]) == (84, 84), "frames [n_rows, C, 84, 84]"
+    n, src, dst = _table_args(tab, idx, first, n, frames.shape[0], columns, columns_dst, adv_affine)
+    check(_lib.load().ddrl_op_frame_table_stacks(frames.shape[0], frames.shape[1], _p(idx), int(first), n, _p(tab),
+                                                 *[_p(t) for t in src], *[_p(t) for t in dst], _p(adv_affine), _st()))
+    return tab
+
+
 class Conv:
     """One Conv2d / Conv1d layer (torch weight layout [cout][cin][kh][kw]; Conv1d: h = kh = 1)."""
 

@@ -169,6 +169,17 @@ int32_t ddrl_ppo_iter(ddrl_ctx* ctx, const uint8_t* frames, const float* actions
                       const float* old_logps, const float* advs, const float* rets, int32_t B,
                       int64_t B_global, void* stream);
 
+/* ddrl_ppo_iter on frames read where they lie (additive: ABI 3): instead of a contiguous [B][C][84][84], `planes` is a plane base
+ * pointer with n_planes planes of 7,056 bytes behind it and `tab` (int32 [B][4] on the device, from ddrl_op_frame_table_planes /
+ * ddrl_op_frame_table_stacks below) names, for every sample of the call, the plane that holds each of its channels.  The conv1 kernels
+ * clamp every entry to [0, n_planes): whatever the table holds, nothing outside [planes, planes + n_planes * 7056) is read.  Same
+ * arithmetic on the same bytes: gradients, statistics, activations and sign masks are bit-identical to ddrl_ppo_iter on the materialised
+ * frames, and ddrl_ppo_diag, the gradient buckets and ddrl_clip_adam_step work after it exactly as after ddrl_ppo_iter.
+ * planes 16-byte aligned, tab 4-byte aligned with B * 4 entries, n_planes >= 1; otherwise DDRL_ERR_INVALID_ARG (checked before anything
+ * touches the context or HIP). */
+int32_t ddrl_ppo_iter_indexed(ddrl_ctx* ctx, const uint8_t* planes, int64_t n_planes, const int32_t* tab, const float* actions,
+                              const float* old_logps, const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream);
+
 /* The sums of ddrl_op_heads_diag (below; sums8 = 8 doubles of device memory, overwritten) on the features the last ddrl_ppo_iter left
  * in the context, i.e. for the policy that iteration's loss was evaluated with.  Run between ddrl_ppo_iter and ddrl_clip_adam_step;
  * reads only, so gradients and statistics are untouched.  DDRL_ERR_INVALID_ARG when B is not that call's B (or no ddrl_ppo_iter
@@ -609,6 +620,33 @@ int32_t ddrl_op_gather_frame_stacks(const uint8_t* planes, int32_t rows, int32_t
                                     const float* actions, const float* old_logps, const float* advs, const float* rets,
                                     float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
                                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frame tables: where the frames of a training call lie, for ddrl_ppo_iter_indexed (additive: ABI 3).  tab int32 [n][4] on the device:
+ * tab[j][c] = index of the 7,056-byte plane, counted from a plane base pointer, that holds channel c of sample j of the call; entries
+ * c >= channels repeat entry channels - 1.  Sample j of the call is sample idx[j] (idx int32 on the device), or first + j when idx is
+ * NULL.  The four float columns and adv_affine are those of ddrl_op_gather_minibatch, bit for bit: one launch collates a minibatch
+ * without touching a frame.  THE ONE DIFFERENCE from the gathers: a sample index outside the valid range is CLAMPED to it before
+ * anything is read -- age, the columns and the table entry all use the clamped sample -- where the gathers return zeros for such a
+ * sample.  Both need no context, allocate nothing and are asynchronous on `stream`; their argument checks run before anything touches
+ * HIP; no atomics, so a repeated call gives the same bits.  channels outside 1..4: DDRL_ERR_UNSUPPORTED.  tab and idx 4-byte aligned,
+ * n >= 1, the plane count fits an int32; nothing that is read (age, idx and adv_affine included) may overlap anything that is written,
+ * nor two destinations one another: DDRL_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+/* The single-frame pool (above): the rule of ddrl_op_gather_frame_stacks, its clamp against a hostile `age` included:
+ *   tab[j][c] = (hist + t - min(channels - 1 - c, age[b], hist + t)) * n_envs + env   for sample b = t * n_envs + env,
+ * counted from the pool's `planes` pointer (rows * n_envs planes).  rows > hist >= channels - 1; samples are valid in
+ * [0, (rows - hist) * n_envs), and `age` and every column given hold that many entries. */
+int32_t ddrl_op_frame_table_planes(int32_t rows, int32_t n_envs, int32_t hist, const uint8_t* age, int32_t channels, const int32_t* idx,
+                                   int64_t first, int32_t n, int32_t* tab, const float* actions, const float* old_logps,
+                                   const float* advs, const float* rets, float* actions_dst, float* old_logps_dst, float* advs_dst,
+                                   float* rets_dst, const float* adv_affine, void* stream);
+/* Stacked frames uint8 [n_rows][channels][84][84]: tab[j][c] = b * channels + c, counted from the frames' pointer (n_rows * channels
+ * planes); samples are valid in [0, n_rows). */
+int32_t ddrl_op_frame_table_stacks(int64_t n_rows, int32_t channels, const int32_t* idx, int64_t first, int32_t n, int32_t* tab,
+                                   const float* actions, const float* old_logps, const float* advs, const float* rets,
+                                   float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
+                                   void* stream);
 
 #ifdef __cplusplus
 }
