@@ -777,35 +777,153 @@ void launch_conv_forward(const EncCall& c, bool acting, hipStream_t st) {
 // conv3 data gradient as plane products, gather form (see conv_fwd3_planes_kernel, whose mirror image it is):
 //   dz2[b][ic][y][x] = leaky'(a2) * sum_{oc,ky,kx} dz3[b][oc][y-ky][x-kx] W3[oc][ic][ky][kx]
 // dz3 is staged channel-innermost into zero-bordered 11 x 11 images (data at +2, +2; [plane][sample][pixel][16 oc] 16-bit),
-// one MFMA k-group = one tap x 16 oc; tile = 64 ic x 3 whole samples (243 columns, wave w = columns 64 w .., 2 x 2 fragment
-// tiles), k-block = 16 oc = 9 k-groups, 4 k-blocks, one LDS stage.
+// one MFMA k-group = one tap x 16 oc; tile = 64 ic x 3 whole samples (243 columns = 8 column tiles of 32, 2 row tiles of 32 ic:
+// 16 accumulator tiles, four per wave), k-block = 16 oc = 9 k-groups, 4 k-blocks, one LDS stage.
 // (Requesting the a2 values of the mask before the last k-block instead of in the epilogue: no gain, 4.37 vs 4.33 ms.)
-// It walks all 81 x 9 tap products of which 49 x 9 are non-zero (the scatter form, conv_dgrad3_scatter_kernel, does
-// not) and still wins: 192 instead of 512 matrix-pipe cycles per 16 k.
+// Of the 81 x 9 (output pixel, tap) products of a sample 49 x 9 read a dz3 pixel, the others the zero border.  The columns are
+// ordered (output row y, sample, x) -- Dgrad3Rows below -- so that a column tile covers one or two output rows of all three samples
+// and the tap rows ky that no row of the tile receives (y - ky outside 0..6) are not issued: 60 instead of 72 (column tile, tap)
+// products per row tile and k-block, shared out 30 to each wave; every dropped product had an all-zero B fragment, so dz2 is bit
+// for bit what walking all 72 gives (SQ_INSTS_MFMA per launch 75.5 M -> 62.9 M, executed / algorithmic 1.74 -> 1.45).  The x
+// border is still walked: column tiles span all x.  (The scatter form, conv_dgrad3_scatter_kernel, walks no border at all and
+// loses: 512 matrix-pipe cycles per 16 k against 160 here.)
+// The epilogue leaves through the stage as whole channel rows, 16 bytes per lane: with the row order a direct store instruction
+// would write three or four 36-byte runs per channel instead of one 128-byte run (measured 2.36 ms direct, 2.18 through LDS; the
+// column-per-sample order it replaces: 2.43, profiles/r07_dgrad3_rows_ab.txt).
+// 240 VGPRs, no scratch, 60,096 B of LDS: two workgroups per CU as before (-Rpass-analysis=kernel-resource-usage).
 // Weights: wd3b[e][k-block 4][tap 9][plane][ic 64][oc half 2][oc 8] (optim.hip).
 // ================================================================================================
+// The tiling of the 3 x 81 output pixels of a workgroup, in one place, checked by the compiler from first principles.
+struct Dgrad3Rows {
+  static constexpr int SPT = 3, NCOL = SPT * 81, NT = 8, ROWW = SPT * 9;  // columns, column tiles of 32, columns per output row
+  // column c -> (y, sample, x): output row y of the three samples is columns 27 y .. 27 y + 26
+  static constexpr int col_y(int c) { return c / ROWW; }
+  static constexpr int col_s(int c) { return c % ROWW / 9; }
+  static constexpr int col_x(int c) { return c % 9; }
+  // tap t = 3 ky + kx reads dz3[y - ky][x - kx]: bit t of a column tile's mask is set where the tile issues it.  Tap row ky is
+  // needed by output rows ky .. ky + 6; tile t covers rows (32 t) / 27 .. min(32 t + 31, 242) / 27
+  static constexpr int tile_y0(int t) { return col_y(32 * t); }
+  static constexpr int tile_y1(int t) { return col_y(32 * t + 31 < NCOL ? 32 * t + 31 : NCOL - 1); }
+  static constexpr bool tile_has_tap(int t, int tap) { return tap / 3 <= tile_y1(t) && tap / 3 + 6 >= tile_y0(t); }
+  static constexpr int tile_taps(int t) {
+    int m = 0;
+    for (int tap = 0; tap < 9; ++tap) m |= (int)tile_has_tap(t, tap) << tap;
+    return m;
+  }
+  // wave -> its column tiles (-1: none) and its four units = accumulator tiles (row tile i of 32 ic, column tile WAVE_TILE[w][j]):
+  //   wave 0: {i0, i1} x {t0, t1}   12 + 18 = 30 unit-taps        wave 2: {i0, i1} x t2, i0 x t3, i0 x t7   18 + 9 + 3 = 30
+  //   wave 1: {i0, i1} x {t5, t6}   18 + 12 = 30                  wave 3: {i0, i1} x t4, i1 x t3, i1 x t7   18 + 9 + 3 = 30
+  // A barrier closes every k-block: the skipped products only pay if the four waves stay level.
+  static constexpr int WT = 3, NU = 4;
+  static constexpr int WAVE_TILE[4][WT] = {{0, 1, -1}, {5, 6, -1}, {2, 3, 7}, {4, 3, 7}};
+  static constexpr int UNIT_I[4][NU] = {{0, 1, 0, 1}, {0, 1, 0, 1}, {0, 1, 0, 0}, {0, 1, 1, 1}};
+  static constexpr int UNIT_J[4][NU] = {{0, 0, 1, 1}, {0, 0, 1, 1}, {0, 0, 1, 2}, {0, 0, 1, 2}};
+  static constexpr int unit_tile(int w, int u) { return WAVE_TILE[w][UNIT_J[w][u]]; }
+  static constexpr int popcount9(int m) {
+    int c = 0;
+    for (int b = 0; b < 9; ++b) c += m >> b & 1;
+    return c;
+  }
+
+  // ---- the proofs (brute force over the 243 columns and 9 taps)
+  // a (tile, tap) that is not issued has no column that reads a dz3 pixel through it; one that is issued has
+  static constexpr bool tap_feeds_tile(int t, int tap) {
+    for (int c = 32 * t; c < 32 * t + 32 && c < NCOL; ++c) {
+      const int sy = col_y(c) - tap / 3, sx = col_x(c) - tap % 3;
+      if (sy >= 0 && sy <= 6 && sx >= 0 && sx <= 6) return true;
+    }
+    return false;
+  }
+  static constexpr bool masks_are_exact() {
+    for (int t = 0; t < NT; ++t)
+      for (int tap = 0; tap < 9; ++tap)
+        if (tap_feeds_tile(t, tap) != tile_has_tap(t, tap)) return false;
+    return true;
+  }
+  // the columns are the 243 (sample, pixel) pairs, each once
+  static constexpr bool columns_are_a_permutation() {
+    bool seen[NCOL] = {};
+    for (int c = 0; c < NCOL; ++c) {
+      const int k = col_s(c) * 81 + col_y(c) * 9 + col_x(c);
+      if (col_s(c) >= SPT || col_y(c) >= 9 || seen[k]) return false;
+      seen[k] = true;
+    }
+    return true;
+  }
+  static constexpr int owners(int i, int t) {
+    int n = 0;
+    for (int w = 0; w < 4; ++w)
+      for (int u = 0; u < NU; ++u) n += UNIT_I[w][u] == i && UNIT_J[w][u] < WT && unit_tile(w, u) == t;
+    return n;
+  }
+  static constexpr bool every_unit_has_one_owner() {
+    for (int i = 0; i < 2; ++i)
+      for (int t = 0; t < NT; ++t)
+        if (owners(i, t) != 1) return false;
+    return true;
+  }
+  static constexpr int wave_unit_taps(int w) {
+    int n = 0;
+    for (int u = 0; u < NU; ++u) n += popcount9(tile_taps(unit_tile(w, u)));
+    return n;
+  }
+  static constexpr int row_tile_taps() {
+    int n = 0;
+    for (int t = 0; t < NT; ++t) n += popcount9(tile_taps(t));
+    return n;
+  }
+};
+static_assert(Dgrad3Rows::NT * 32 >= Dgrad3Rows::NCOL && (Dgrad3Rows::NT - 1) * 32 < Dgrad3Rows::NCOL, "8 column tiles of 32");
+static_assert(Dgrad3Rows::columns_are_a_permutation(), "every (sample, pixel) is one column");
+static_assert(Dgrad3Rows::masks_are_exact(), "a skipped (tile, tap) reads only the zero border, an issued one reads a dz3 pixel");
+static_assert(Dgrad3Rows::every_unit_has_one_owner(), "each of the 16 accumulator tiles belongs to exactly one wave (four each)");
+static_assert(Dgrad3Rows::row_tile_taps() == 60, "60 of 72 (column tile, tap) products per row tile");
+static_assert(Dgrad3Rows::wave_unit_taps(0) == 30 && Dgrad3Rows::wave_unit_taps(1) == 30 && Dgrad3Rows::wave_unit_taps(2) == 30 &&
+                  Dgrad3Rows::wave_unit_taps(3) == 30, "the waves are level: 30 unit-taps = 90 MFMAs per k-block each");
+
+template <int V>
+struct RoleC {
+  static constexpr int value = V;
+};
+// f(RoleC<w>) for the wave-uniform w: every wave runs the instantiation of its own units and taps
+template <class F>
+__device__ __forceinline__ void by_wave_role(int w, F&& f) {
+  switch (w) {
+    case 0: f(RoleC<0>{}); break;
+    case 1: f(RoleC<1>{}); break;
+    case 2: f(RoleC<2>{}); break;
+    default: f(RoleC<3>{}); break;
+  }
+}
+
 struct Dgrad3B {
   // one MFMA k-group = ONE tap x 16 oc (lane half h = oc 8 h .. 8 h + 7): nine k-groups per k-block of 16 oc, no padded tenth tap
   // (tap pairs x 8 oc walked ten: executed / algorithmic 1.84 -> 1.65), the tap shift is a compile-time LDS offset, four k-blocks
   // instead of eight.  Weights: wd3b[e][k-block 4][tap 9][plane NPL][ic 64][oc half 2][oc 8] (optim.hip pack_dgrad3_planes_kernel).
   // four waves / 3 samples per workgroup, two workgroups per CU.  Eight waves / 6 samples sharing one copy of the k-block's 37 KB of
   // weights (one workgroup per CU) measured 2.52 vs 2.43 ms, not kept -- unlike conv2's data gradient.
-  // 2 x 2 fragment tiles, 3 samples per tile: 4.19 vs 4.27 ms for 2 x 4 / 6 samples (re-measured under f16 planes: 2.54 vs 2.60)
-  static constexpr int THREADS = 256, TN = 2, SPT = ((THREADS / 64) * 32 * TN) / 81;  // column tiles per wave, whole samples per tile
+  // four accumulator tiles per wave, 3 samples per tile: 4.19 vs 4.27 ms for 2 x 4 / 6 samples (re-measured under f16 planes: 2.54 vs 2.60)
+  using R = Dgrad3Rows;  // which column is which pixel, which wave owns which accumulator tile, which taps a tile issues
+  static constexpr int THREADS = 256, SPT = R::SPT;  // whole samples per tile: 243 of the four waves' 4 x 2 x 32 columns
   static constexpr int KOC = 16, NKB = 64 / KOC, PIXB = 2 * KOC;  // oc per k-block, k-blocks, bytes per pixel and plane
   static constexpr int IMG_PLANE = SPT * 121 * PIXB;              // 11,616 B
   static constexpr int W_OFF = NPL * IMG_PLANE, W_BYTES = 9 * NPL * 64 * 32;
   static constexpr int NIU = SPT * 49, NIJ = (NIU + THREADS - 1) / THREADS;  // pixel units (16 oc each): 147 -> 1 per thread
   static constexpr int NWQ = W_BYTES / 16, NWJ = (NWQ + THREADS - 1) / THREADS;  // 2,304 weight quads -> 9 per thread
   static constexpr size_t LDS_BYTES = W_OFF + W_BYTES;
+  // epilogue through the stage: one row tile at a time, [sample][32 channels][81 pixels] fp32; 16 pad words per sample put the three
+  // samples' runs of nine pixels on banks 0.., 48.., 32..
+  static constexpr int OSS = 32 * C2_P + 16, OQS = 32 * C2_P / 4, NOJ = (SPT * OQS + THREADS - 1) / THREADS;  // 648 quads per sample
+  static_assert(SPT * OSS * 4 <= (int)LDS_BYTES && (32 * C2_P) % 4 == 0 && OSS % 4 == 0 && A2_N % 4 == 0, "the staged half fits, 16-byte rows");
 };
 
 __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_dgrad3_planes_kernel(
     const float* __restrict__ dz3, int64_t dz_es, const unsigned short* __restrict__ wd3b, float* __restrict__ amax, const unsigned* __restrict__ m2,
     float* __restrict__ out, int64_t out_es, int n) {
   using K = Dgrad3B;
+  using R = K::R;
   extern __shared__ __attribute__((aligned(16))) char ldsd3[];
-  const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, wc = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5;
   const int e = blockIdx.z, b0 = blockIdx.x * K::SPT;
   const float sa = plane_scale(amax[amax_idx(AMAX_DZ3, e)]), inv = 1.0f / (sa * plane_scale(amax[amax_idx(AMAX_W3, e)]));
   for (int i = tid; i < K::W_OFF / 16; i += K::THREADS) *(f4*)(ldsd3 + i * 16) = zero4();  // images incl. their zero borders
@@ -821,16 +939,18 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
   }
   const unsigned short* wsrc = wd3b + (int64_t)e * (K::NKB * 9 * NPL * 64 * 16) + tid * 8;  // + kb * 9 * NPL * 1024 + j * THREADS * 8
   // ---- operand bases
-  int aA[2], bB[K::TN];
+  int aA[2], bB[R::WT];
 #pragma unroll
   for (int i = 0; i < 2; ++i) aA[i] = K::W_OFF + (i * 32 + l31) * 32 + hi * 16;
+  by_wave_role(wc, [&](auto role) {
+    constexpr int W = decltype(role)::value;
 #pragma unroll
-  for (int j = 0; j < K::TN; ++j) {
-    int c = wc * (32 * K::TN) + j * 32 + l31;
-    if (c >= K::SPT * 81) c = 0;
-    const int s = c / 81, pix = c % 81;
-    bB[j] = (s * 121 + (pix / 9 + 2) * 11 + pix % 9 + 2) * K::PIXB + hi * 16;
-  }
+    for (int j = 0; j < R::WT; ++j) {
+      int c = R::WAVE_TILE[W][j] * 32 + l31;
+      if (R::WAVE_TILE[W][j] < 0 || c >= R::NCOL) c = 0;  // t7's 13 pad columns multiply column 0's pixels and are not stored
+      bB[j] = (R::col_s(c) * 121 + R::col_y(c) * 11 + R::col_x(c)) * K::PIXB + hi * 16;  // the pixel tap (2, 2) reads: taps add >= 0
+    }
+  });
   float ir[K::NIJ][K::KOC];
   f4 wr[K::NWJ];
   auto fetch = [&](int kb) {
@@ -861,65 +981,98 @@ __global__ __launch_bounds__(Dgrad3B::THREADS) __attribute__((amdgpu_waves_per_e
     for (int j = 0; j < K::NWJ; ++j)
       if (j + 1 < K::NWJ || tid + K::THREADS * j < K::NWQ) *(f4*)(ldsd3 + K::W_OFF + (tid + K::THREADS * j) * 16) = wr[j];
   };
-  f32x16 acc[2][K::TN];
+  f32x16 acc[R::NU];  // unit u of this wave: rows 32 UNIT_I .., column tile WAVE_TILE[UNIT_J]
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int u = 0; u < R::NU; ++u)
 #pragma unroll
-    for (int j = 0; j < K::TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-  fetch(0);
-  __syncthreads();  // zero fill complete
-  commit();
-  fetch(1);
-  __syncthreads();
-  for (int kb = 0; kb < K::NKB; ++kb) {
+    for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
+  // one k-block of this wave's units.  Any one accumulator receives its products in the order k-block, tap 0..8 (minus the tap rows
+  // its tile skips), plane product 0..2: the skipped ones would have added exact zeros, so dz2 is bit for bit what walking all
+  // nine taps gives.  The wave's role is a template argument: which fragments are read and which products are issued is fixed at
+  // compile time, and units that share a row tile or a column tile share its fragment (8-10 LDS reads per 12 MFMAs; a run-time tap
+  // mask over four (row tile, column tile) slots would read every unit's fragments apiece, 16 per 12).  The k-block loop sits INSIDE
+  // the role: with the switch inside the loop one role's accumulators were copied at every k-block (2.37 vs 2.36 ms).  All four
+  // paths pass the same two barriers per k-block.
+  auto mma = [&](auto role) {
+    constexpr int W = decltype(role)::value;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {  // tap (ky, kx) = (t / 3, t % 3): source pixel (y - ky, x - kx)
       constexpr int ROW11 = 11;
-      const int toff = ((t / 3) * ROW11 + t % 3) * K::PIXB;
-      frag8 af[NPL][2], bfr[NPL][K::TN];
+      const int toff = ((2 - t / 3) * ROW11 + 2 - t % 3) * K::PIXB;
+      frag8 af[NPL][2], bfr[NPL][R::WT];
 #pragma unroll
       for (int p = 0; p < NPL; ++p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) af[p][i] = *(const frag8*)(ldsd3 + aA[i] + (t * NPL + p) * 2048);
 #pragma unroll
-        for (int j = 0; j < K::TN; ++j) bfr[p][j] = *(const frag8*)(ldsd3 + bB[j] - toff + p * K::IMG_PLANE);
+        for (int j = 0; j < R::WT; ++j)
+          if (R::WAVE_TILE[W][j] >= 0 && R::tile_has_tap(R::WAVE_TILE[W][j], t)) bfr[p][j] = *(const frag8*)(ldsd3 + bB[j] + toff + p * K::IMG_PLANE);
       }
 #pragma unroll
       for (int m = 0; m < NPROD; ++m)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < K::TN; ++j) acc[i][j] = mfma_planes(af[PA[m]][i], bfr[PB[m]][j], acc[i][j]);
+        for (int u = 0; u < R::NU; ++u)
+          if (R::tile_has_tap(R::unit_tile(W, u), t)) acc[u] = mfma_planes(af[PA[m]][R::UNIT_I[W][u]], bfr[PB[m]][R::UNIT_J[W][u]], acc[u]);
     }
-    __syncthreads();  // every wave is done with the stage
-    if (kb + 1 < K::NKB) {
-      commit();
-      if (kb + 2 < K::NKB) fetch(kb + 2);
-    }
-    __syncthreads();
-  }
-  // dz2 = leaky'(a2) * sum
-  float big = 0.0f;
-#pragma unroll
-  for (int j = 0; j < K::TN; ++j) {
-    const int c = wc * (32 * K::TN) + j * 32 + l31;
-    const int s = c / 81, pix = c % 81;
-    if (c >= K::SPT * 81 || b0 + s >= n) continue;
-    const int64_t off = (int64_t)(b0 + s) * A2_N + pix + hi * (4 * C2_P);
-    float* op = out + e * out_es + off;
-    // the signs of a2 at this lane's 32 (channel, pixel) positions: one word written by conv2's forward, whose tile layout
-    // this epilogue shares (common.h Workspace::m2) -- not 32 reads of a2
-    const unsigned mw = m2[(e * (out_es / A2_N) + b0 + s) * M2_N + pix * 2 + hi];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float g = leaky_bit(mw, 16 * i + 15 - r, acc[i][j][r] * inv);
-        op[(i * 32 + acc_row(r, 0)) * C2_P] = g;
-        big = fmaxf(big, fabsf(g));
+  };
+  fetch(0);
+  __syncthreads();  // zero fill complete
+  commit();
+  fetch(1);
+  __syncthreads();
+  by_wave_role(wc, [&](auto role) {
+    for (int kb = 0; kb < K::NKB; ++kb) {
+      mma(role);
+      __syncthreads();  // every wave is done with the stage
+      if (kb + 1 < K::NKB) {
+        commit();
+        if (kb + 2 < K::NKB) fetch(kb + 2);
       }
+      __syncthreads();
+    }
+  });
+  // dz2 = leaky'(a2) * sum, through the stage (dead after the last k-block) so that it leaves as whole channel rows: the 32
+  // channels x 81 pixels of a row tile are 10,368 contiguous bytes per sample
+  float big = 0.0f;
+  float* ob = (float*)ldsd3;
+  unsigned mw[R::WT];
+  int ocol[R::WT];  // word offset of the lane's (sample, channel 4 hi, pixel) in the staged half, or -1: pad column / sample beyond n
+  by_wave_role(wc, [&](auto role) {
+    constexpr int W = decltype(role)::value;
+#pragma unroll
+    for (int j = 0; j < R::WT; ++j) {
+      const int c = R::WAVE_TILE[W][j] * 32 + l31;
+      const int s = R::col_s(c), pix = R::col_y(c) * 9 + R::col_x(c);
+      const bool live = R::WAVE_TILE[W][j] >= 0 && c < R::NCOL && b0 + s < n;
+      ocol[j] = live ? s * K::OSS + hi * (4 * C2_P) + pix : -1;
+      // the signs of a2 at this lane's 32 (channel, pixel) positions: one word written by conv2's forward, whose tile layout
+      // this epilogue shares (common.h Workspace::m2) -- not 32 reads of a2
+      mw[j] = live ? m2[(e * (out_es / A2_N) + b0 + s) * M2_N + pix * 2 + hi] : 0u;
+    }
+  });
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if (i) __syncthreads();  // row tile 0 has left the stage
+    by_wave_role(wc, [&](auto role) {
+      constexpr int W = decltype(role)::value;
+#pragma unroll
+      for (int u = 0; u < R::NU; ++u) {
+        const int j = R::UNIT_J[W][u];
+        if (R::UNIT_I[W][u] != i || ocol[j] < 0) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float g = leaky_bit(mw[j], 16 * i + 15 - r, acc[u][r] * inv);
+          ob[ocol[j] + acc_row(r, 0) * C2_P] = g;
+          big = fmaxf(big, fabsf(g));
+        }
+      }
+    });
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K::NOJ; ++k) {
+      const int q = tid + K::THREADS * k, s = q / K::OQS, w4 = q % K::OQS * 4;
+      if (q < K::SPT * K::OQS && b0 + s < n) *(f4*)(out + e * out_es + (int64_t)(b0 + s) * A2_N + i * (32 * C2_P) + w4) = *(const f4*)(ob + s * K::OSS + w4);
+    }
   }
   amax_update(big, amax + amax_idx(AMAX_DZ2, e));
 }
