@@ -5,8 +5,9 @@
 
 Sample b = t * N + i (the order of DeviceRollout.batch()) is the stack whose channel c is pool row H + t - min(C - 1 - c, age[b], H + t)
 of env i; csrc/fpool.hip (ddrl_op_gather_frame_stacks) assembles it where it is read.  Only the Atari fast path (nn/ppo.py PPO) reads
-this form: nn/minibatch.py gathers every minibatch from it, the full-batch branch materialises the batch once per learn call -- or,
-with config_nn.FRAMES_IN_PLACE, both read the planes where they lie through a frame table (table(); csrc/ftable.hip)."""
+this form, through the one frame source over it (nn/update_loop.py PlaneFrames): a minibatch step gathers its stacks from it, the
+full-batch step materialises the batch once per learn call -- or, with config_nn.FRAMES_IN_PLACE, both read the planes where they lie
+through a frame table (table(); csrc/ftable.hip)."""
 import torch
 
 from ddrl4nav_amd import ops

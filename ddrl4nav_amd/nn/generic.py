@@ -807,12 +807,7 @@ class GenericPPO(Basenn):
                                              self._step, _p(self._adam_ws), _st()))
             self._dirty = True
             self.update_time += 1
-            s = self.stats()
-            loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                        "PpoBackUpTime": time.time() - t0}
-            if d is not None:
-                loss_log.update(d)
-            yield loss_log, self.update_time, True
+            yield ops.loss_dict(self.stats(), time.time() - t0, d), self.update_time, True
 
     def stats(self):
         return ops.stats_dict(self.grads[self.n_params:self.n_params + 6].cpu())

@@ -10,18 +10,17 @@ The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the Config
                                "minibatch": over every (global) minibatch
   ADV_NORM_EPS         1e-8    the eps above
 
-  FRAMES_IN_PLACE      False   True: no minibatch of frames is staged; the conv1 kernels read the batch where it lies through a frame
-                               table (csrc/ftable.hip, ddrl_ppo_iter_indexed).  Same bits.  Not one of the four knobs that bring
-                               PPO.learn here: on the full-batch branch it keeps FramePlanes states from being materialised (nn/ppo.py)
+  FRAMES_IN_PLACE      False   True: no batch or minibatch of frames is staged; the conv1 kernels read the frames where they lie
+                               through a frame table (csrc/ftable.hip, ddrl_ppo_iter_indexed).  Same bits.  Not one of the four knobs
+                               that choose the step source: the frame source of either reads it (nn/update_loop.py)
 
-With all four at their defaults PPO.learn does not come here.  Per step, everything on the device and in stream order: one
-ddrl_op_gather_minibatch into ONE staging buffer (shuffle on; off: contiguous views, nothing is copied; states given as
-data.FramePlanes: ddrl_op_gather_frame_stacks into the same buffer, shuffled or not), the moments / affine / normalise operators of
-csrc/minibatch.hip where asked for, then ppo_iter -> ppo_diag -> allreduce_grads -> clip_adam_step as in
-nn/ppo.py.  split() and epoch_order() are plain CPU functions: a test recomputes every minibatch from them.
+PPO.learn runs one loop (nn/update_loop.py run()) over one of two step sources: with all four knobs at their defaults its own single
+full-batch step, otherwise steps() below.  Per step, everything on the device and in stream order: shuffle on, one gather of frames
+and columns into ONE staging buffer (or, in place, one frame table); off, contiguous views of the columns and of stacked frames
+(FramePlanes: the stacks assembled into the same buffer); the moments / affine / normalise operators of csrc/minibatch.hip where
+asked for; then the launch and what run() does after it.  split() and epoch_order() are plain CPU functions: a test recomputes
+every minibatch from them.
 """
-import time
-
 import torch
 
 from ddrl4nav_amd import ops
@@ -106,7 +105,7 @@ def epoch_order(seed, learn_call, epoch, B):
 
 
 class Staging:
-    """The device buffers of the minibatch loop, kept by the net between learn calls: ONE minibatch of frames and columns (stream order
+    """The device buffers of steps(), kept by the net between learn calls: ONE minibatch of frames and columns (stream order
     makes its reuse safe), one scratch advantage column of the whole batch, the three double sums, the affine pair and the moments'
     workspace."""
 
@@ -136,28 +135,22 @@ def advantage_affine(column, n, st, eps, group):
     return ops.moments_affine(st.sums, eps, st.affine)
 
 
-def learn(net, data):
-    """The body of PPO.learn when a knob is set: a generator with learn's protocol."""
+def steps(net, frames, columns):
+    """PPO.learn's step source when a knob is set: TRAINING_ITER_TIME epochs of the K minibatches of split(), one Step each.  `frames`:
+    uint8 [B, C, 84, 84] or data.FramePlanes; `columns`: actions, old_logps, advs, rets, fp32 [B] on the device."""
     from ddrl4nav_amd.dist import global_batch
-    from ddrl4nav_amd.data.frame_planes import planes_of
-    from ddrl4nav_amd.nn.atari_encoder import frames_u8
+    from ddrl4nav_amd.nn.update_loop import Step, frame_source
     K, shuffle, mode, eps = net.minibatch
-    planes = planes_of(data.states)            # frames stored once (agent/plane_rollout.py): every minibatch is assembled into st.frames
-    frames = planes if planes is not None else frames_u8(data.states, net.device)
-    B = frames.shape[0]
+    actions, old_logps, advs, rets = columns
+    B = len(frames)
     ranges = split(B, K)                       # ValueError when K > B
     cap = ranges[0][1] - ranges[0][0]          # the first minibatch is the largest
     net._ensure_capacity(cap)
-    f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=net.device).contiguous()
-    actions, old_logps, advs, rets = f32(data.actions), f32(data.old_logps), f32(data.advs), f32(data.values)[0].contiguous()
-    assert rets.shape == (B,)
-    if net.target_kl is not None and net.deferred_stats:
-        raise ValueError("TARGET_KL needs the host after every step: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
-    hp, group, diag, deferred = net._hp, net._process_group, net.diagnostics, net.deferred_stats
-    in_place = getattr(net, "frames_in_place", False)
+    group, in_place = net._process_group, net.frames_in_place
     st = net._mb_stage
     if st is None or not st.fits(frames.shape[1:], cap, B, in_place):
         st = net._mb_stage = Staging(net.device, frames.shape[1:], cap, B, in_place)
+    src = frame_source(net._hp, frames, in_place, st.frames, st.tab)
     call = net.learn_calls
     net.learn_calls += 1
     rank = 0
@@ -169,84 +162,20 @@ def learn(net, data):
         if not shuffle:                        # nothing is gathered: one pass into the scratch column
             advs = ops.normalize(advs, affine, out=st.adv, n=B)[:B]
             affine = None
-    epochs = net.training_iter_time
-    steps = epochs * K
-    if deferred:
-        if net._stats_rows is None or net._stats_rows.shape[0] < steps:
-            net._stats_rows = torch.empty((steps, 8), dtype=torch.float32).pin_memory()
-        if diag and (net._diag_rows is None or net._diag_rows.shape[0] < steps):
-            net._diag_rows = torch.empty((steps, ops.DIAG_SLOTS), dtype=torch.float64).pin_memory()
-            net._diag_dev = torch.zeros((steps, ops.DIAG_SLOTS), dtype=torch.float64, device=net.device)
     b_globals = {}
-    t_all = time.time()
-    i = 0
-    for epoch in range(epochs):
+    for epoch in range(net.training_iter_time):
         order = epoch_order(net._seed + rank, call, epoch, B).to(net.device) if shuffle else None   # one int32 upload per epoch
         for j, (lo, hi) in enumerate(ranges):
-            t0 = time.time()
             n = hi - lo
-            tab = None                         # FRAMES_IN_PLACE: the step's frame table; ppo_iter_indexed reads the batch where it lies
-            if in_place and shuffle:
-                dst = [st.cols[k, :n] for k in range(4)]
-                if planes is not None:
-                    tab = planes.table(st.tab, idx=order[lo:hi], n=n, columns=(actions, old_logps, advs, rets), columns_dst=dst, adv_affine=affine)
-                else:
-                    tab = ops.frame_table_stacks(frames, st.tab, idx=order[lo:hi], n=n, columns=(actions, old_logps, advs, rets),
-                                                 columns_dst=dst, adv_affine=affine)
-                a, o, ad, r = dst
-            elif in_place and planes is not None:
-                tab = planes.table(st.tab, first=lo, n=n)
-                a, o, ad, r = actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
-            elif shuffle:
-                dst = [st.cols[k, :n] for k in range(4)]
-                if planes is not None:
-                    planes.gather(st.frames, order[lo:hi], n=n, columns=(actions, old_logps, advs, rets), columns_dst=dst, adv_affine=affine)
-                else:
-                    ops.gather_minibatch(frames, order[lo:hi], st.frames, (actions, old_logps, advs, rets), dst, adv_affine=affine, n=n)
-                f, (a, o, ad, r) = st.frames[:n], dst
+            if shuffle:
+                a, o, ad, r = dst = [st.cols[k, :n] for k in range(4)]
+                launch = src.gathered(order[lo:hi], n, (actions, old_logps, advs, rets), dst, affine)
             else:
-                f = planes.stacks(lo, hi, out=st.frames) if planes is not None else frames[lo:hi]
+                launch = src.contiguous(lo, hi)
                 a, o, ad, r = actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
             if mode == "minibatch":
                 advantage_affine(ad, n, st, eps, group)
                 ad = ops.normalize(ad, st.affine, out=ad if shuffle else st.adv, n=n)[:n]   # in place on the staged column
             if j not in b_globals:             # the ranks' j-th sizes: one collective per j, in the first epoch
                 b_globals[j] = global_batch(n, group)
-            if tab is not None:
-                hp.ppo_iter_indexed(planes.pool if planes is not None else frames, tab, a, o, ad, r, b_global=b_globals[j])
-            else:
-                hp.ppo_iter(f, a, o, ad, r, b_global=b_globals[j])
-            if deferred:
-                if diag:
-                    net._diag_rows[i].copy_(hp.ppo_diag(a, o, r, out=net._diag_dev[i]), non_blocking=True)
-                hp.allreduce_grads()
-                hp.clip_adam_step()
-                hp.stats_async(net._stats_rows[i])
-                i += 1
-                continue
-            d = None
-            if diag:
-                d = ops.diag_dict(hp.diag_global(hp.ppo_diag(a, o, r)))
-                if ops.kl_stop(d, net.target_kl):
-                    return                     # ends the whole call; this step is not applied (as an iteration in nn/ppo.py)
-            hp.allreduce_grads()
-            hp.clip_adam_step()
-            net.update_time += 1
-            s = hp.stats()
-            loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                        "PpoBackUpTime": time.time() - t0}
-            if d is not None:
-                loss_log.update(d)
-            yield loss_log, net.update_time, True
-    if not deferred:
-        return
-    torch.cuda.current_stream().synchronize()   # the one synchronisation of the call
-    dt = (time.time() - t_all) / max(steps, 1)
-    for i in range(steps):
-        net.update_time += 1
-        s = hp.stats_dict(net._stats_rows[i])
-        loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                    "PpoBackUpTime": dt}
-        if diag:
-            loss_log.update(ops.diag_dict(hp.diag_global(net._diag_rows[i])))
-        yield loss_log, net.update_time, True
+            yield Step(launch, a, o, ad, r, b_globals[j])

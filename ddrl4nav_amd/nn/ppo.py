@@ -4,19 +4,20 @@ Same constructor arguments, same ``forward(states, act=None, play_mode=False)`` 
 same ``learn(data)`` generator protocol and loss-dict keys, same ``state_dict()`` key names and
 nn2redis blob -- but every tensor op of the reference is replaced by the HIP kernels behind
 include/ddrl.h.  The module's parameters are views into one flat fp32 arena (the reference's
-named_parameters() order), which is what the kernels, the Adam step and the RCCL all-reduce use.
+named_parameters() order), which is what the kernels, the Adam step and the RCCL all-reduce use.  learn() is one loop over one of two
+step sources, and one frame source decides where a step's frames are read (nn/update_loop.py).
 """
-import time
-
 import torch
 
 from ddrl4nav_amd import ops
 from ddrl4nav_amd.nn import minibatch
 from ddrl4nav_amd.data import Experience
-from ddrl4nav_amd.data.frame_planes import planes_of
+from ddrl4nav_amd.data.frame_planes import FramePlanes, planes_of
+from ddrl4nav_amd.dist import global_batch
 from ddrl4nav_amd.engine import HotPath
 from ddrl4nav_amd.nn.base import Basenn
 from ddrl4nav_amd.nn.distribution import HipCategorical
+from ddrl4nav_amd.nn.update_loop import Step, frame_source, run
 
 
 from ddrl4nav_amd.nn.atari_encoder import frames_u8 as _frames_u8  # noqa: E402
@@ -44,10 +45,10 @@ class PPO(Basenn):
         # config_nn.FRAMES_IN_PLACE (optional, nn/minibatch.py): no batch or minibatch of frames is materialised; the conv1 kernels read
         # them where they lie through a frame table (ddrl_ppo_iter_indexed).  Same bits; off by default
         self.frames_in_place = minibatch.frames_in_place_option(config_nn)
-        self._frame_tab = None
+        self._frame_tab = None      # FramePlanes states, full-batch step, in place: int32 [B, 4]
         self._mb_stage = None
-        self._plane_batch = None   # FramePlanes states on the full-batch branch: the batch materialised once per learn call
-        self.learn_calls = 0   # learn() calls that took the minibatch loop: the second integer of minibatch.epoch_order
+        self._plane_batch = None   # FramePlanes states, full-batch step, staged: the batch materialised once per learn call
+        self.learn_calls = 0   # learn() calls with a minibatch knob set: the second integer of minibatch.epoch_order
         if hasattr(actor, "log_std"):
             raise NotImplementedError("the Atari fast path has a Categorical actor only (reference atari.yaml)")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -163,95 +164,36 @@ class PPO(Basenn):
     def states_normalization(self, states):
         return states / 255
 
-    def _batch_frames(self, states):
-        """The whole batch as uint8 [B, C, 84, 84] on the device.  FramePlanes (agent/plane_rollout.py) are assembled into a buffer this
-        net keeps: every iteration of the full-batch branch reads contiguous stacks, so for the length of learn() the batch holds the
-        stacked size again (the plane pool's saving lasts through the update only with minibatch epochs, nn/minibatch.py)."""
-        fp = planes_of(states)
-        if fp is None:
-            return _frames_u8(states, self.device)
-        if self._plane_batch is None or self._plane_batch.shape[0] < len(fp) or tuple(self._plane_batch.shape[1:]) != fp.shape[1:]:
-            self._plane_batch = torch.empty(fp.shape, dtype=torch.uint8, device=self.device)
-        return fp.stacks(0, len(fp), out=self._plane_batch)
-
     # ---- PPO.learn (ppo.py:77-146) -----------------------------------------------------------------
-    def learn(self, data: Experience):
-        if self.minibatch != minibatch.DEFAULTS:   # a knob is set: TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py)
-            yield from minibatch.learn(self, data)
-            return
-        fp = planes_of(data.states) if self.frames_in_place else None
-        if fp is not None:   # FRAMES_IN_PLACE: one frame table per learn call, every iteration reads the planes where they lie
-            B = len(fp)
+    def _full_batch_steps(self, frames, columns):
+        """The step source with every minibatch knob at its default: ONE step over the whole batch, prepared once per learn call and
+        handed out TRAINING_ITER_TIME times.  Stacked frames are read as they are.  FramePlanes are materialised into _plane_batch (for
+        the length of learn() the batch holds the stacked size again: the plane pool's saving lasts through the update only with
+        minibatch epochs or in place) or, with FRAMES_IN_PLACE, tabled into _frame_tab and read where they lie."""
+        B = len(frames)
+        self._ensure_capacity(B)
+        if isinstance(frames, FramePlanes) and self.frames_in_place:
             if self._frame_tab is None or self._frame_tab.shape[0] < B:
                 self._frame_tab = torch.empty((B, 4), dtype=torch.int32, device=self.device)
-            pool, tab = fp.pool, fp.table(self._frame_tab, first=0, n=B)
-            ppo_iter = lambda *cols, **kw: self._hp.ppo_iter_indexed(pool, tab, *cols, **kw)
-        else:
-            frames = self._batch_frames(data.states)
-            B = frames.shape[0]
-            ppo_iter = lambda *cols, **kw: self._hp.ppo_iter(frames, *cols, **kw)
-        self._ensure_capacity(B)
-        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
-        actions, old_logps, advs = f32(data.actions), f32(data.old_logps), f32(data.advs)
-        rets = f32(data.values)[0].contiguous()
-        assert rets.shape == (B,)
+        elif isinstance(frames, FramePlanes):
+            if self._plane_batch is None or self._plane_batch.shape[0] < B or tuple(self._plane_batch.shape[1:]) != frames.shape[1:]:
+                self._plane_batch = torch.empty(frames.shape, dtype=torch.uint8, device=self.device)
+        launch = frame_source(self._hp, frames, self.frames_in_place, self._plane_batch, self._frame_tab).contiguous(0, B)
         # data-parallel: every rank scales by 1 / (sum of the ranks' batch sizes) -- shards may be uneven
-        from ddrl4nav_amd.dist import global_batch
-        b_global = global_batch(B, self._process_group)
-        diag = self.diagnostics
-        if self.target_kl is not None and self.deferred_stats:   # net.deferred_stats switched on after construction
-            raise ValueError("TARGET_KL needs the host after every iteration: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
-        if self.deferred_stats:
-            # All TRAINING_ITER_TIME iterations are enqueued back to back; every iteration's 8-float statistics tail goes to its own
-            # pinned host row by an asynchronous copy and ONE synchronisation precedes the yields (the reference syncs four times per
-            # iteration, ppo.py:132-137).  Same keys, same values, same update_time per yield; what differs is that the weights are
-            # already those of the LAST iteration when the first item is yielded -- the reference's consumer (backward.py:189-209)
-            # publishes at update_time % 10 == 0 only, i.e. after the last one either way.  With N > 1 ranks this also keeps a slow
-            # host from stalling the other ranks' collectives once per iteration.
-            k = self.training_iter_time
-            if self._stats_rows is None or self._stats_rows.shape[0] < k:
-                self._stats_rows = torch.empty((k, 8), dtype=torch.float32).pin_memory()
-            if diag and (self._diag_rows is None or self._diag_rows.shape[0] < k):
-                # the eight diagnostics sums of every iteration: a device row each (the next iteration must not overwrite what a copy
-                # still reads) and a pinned host row next to the statistics row
-                self._diag_rows = torch.empty((k, ops.DIAG_SLOTS), dtype=torch.float64).pin_memory()
-                self._diag_dev = torch.zeros((k, ops.DIAG_SLOTS), dtype=torch.float64, device=self.device)
-            t0 = time.time()
-            for i in range(k):
-                ppo_iter(actions, old_logps, advs, rets, b_global=b_global)
-                if diag:
-                    self._diag_rows[i].copy_(self._hp.ppo_diag(actions, old_logps, rets, out=self._diag_dev[i]), non_blocking=True)
-                self._hp.allreduce_grads()
-                self._hp.clip_adam_step()
-                self._hp.stats_async(self._stats_rows[i])
-            torch.cuda.current_stream().synchronize()
-            dt = (time.time() - t0) / max(k, 1)
-            for i in range(k):
-                self.update_time += 1
-                s = self._hp.stats_dict(self._stats_rows[i])
-                loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"], "EntLoss": s["EntLoss"],
-                            "PpoBackUpTime": dt}
-                if diag:   # the ranks' rows are combined after the one synchronisation (a collective per iteration, on the host)
-                    loss_log.update(ops.diag_dict(self._hp.diag_global(self._diag_rows[i])))
-                yield loss_log, self.update_time, True
-            return
+        step = Step(launch, *columns, global_batch(B, self._process_group))
         for _ in range(self.training_iter_time):
-            t0 = time.time()
-            ppo_iter(actions, old_logps, advs, rets, b_global=b_global)
-            d = None
-            if diag:
-                # read before anything is applied: the sums describe the policy this iteration's loss was evaluated with, combined
-                # over the ranks so that every rank takes the same decision (a rank that stopped alone would leave the others
-                # waiting in the gradient all-reduce)
-                d = ops.diag_dict(self._hp.diag_global(self._hp.ppo_diag(actions, old_logps, rets)))
-                if ops.kl_stop(d, self.target_kl):
-                    return   # this iteration's step is not applied: no all-reduce, no Adam, no yield, update_time as it was
-            self._hp.allreduce_grads()
-            self._hp.clip_adam_step()
-            self.update_time += 1
-            s = self._hp.stats()  # one device->host copy (the reference does four .item() syncs)
-            loss_log = {"PpoTotalLoss": s["PpoTotalLoss"], "ActorLoss": s["ActorLoss"], "VLoss": s["VLoss"],
-                        "EntLoss": s["EntLoss"], "PpoBackUpTime": time.time() - t0}
-            if d is not None:
-                loss_log.update(d)
-            yield loss_log, self.update_time, True
+            yield step
+
+    def learn(self, data: Experience):
+        """One loop (nn/update_loop.py run()) over one of two step sources: the single full-batch step above, or, with a minibatch knob
+        set, TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py steps())."""
+        fp = planes_of(data.states)
+        frames = fp if fp is not None else _frames_u8(data.states, self.device)
+        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+        columns = f32(data.actions), f32(data.old_logps), f32(data.advs), f32(data.values)[0].contiguous()
+        assert columns[3].shape == (len(frames),)
+        if self.minibatch != minibatch.DEFAULTS:
+            steps, n_steps = minibatch.steps(self, frames, columns), self.training_iter_time * self.minibatch[0]
+        else:
+            steps, n_steps = self._full_batch_steps(frames, columns), self.training_iter_time
+        yield from run(self, steps, n_steps)

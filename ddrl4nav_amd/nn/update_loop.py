@@ -1,0 +1,107 @@
+"""The one update loop of the Atari fast path (nn/ppo.py PPO.learn): where a step's frames come from, and what follows its launch.
+
+A Step is one optimiser step that a step source has prepared: its launcher and columns.  The sources are PPO._full_batch_steps (all
+knobs at their defaults: ONE step, handed out TRAINING_ITER_TIME times) and minibatch.steps (epochs of K minibatches).  Both take
+their launchers from a frame source -- StackedFrames over uint8 [B, C, 84, 84], PlaneFrames over data.FramePlanes -- which alone
+decides between the staged and the in-place form (config_nn.FRAMES_IN_PLACE) and alone calls HotPath.ppo_iter / ppo_iter_indexed.
+run() owns everything after the launch: diagnostics, KL stop, gradient all-reduce, Adam step, statistics read-back, loss dict.
+"""
+import collections
+import time
+from functools import partial
+
+import torch
+
+from ddrl4nav_amd import ops
+from ddrl4nav_amd.data.frame_planes import FramePlanes
+
+# launch(actions, old_logps, advs, rets, b_global=) enqueues the step's ppo_iter on its frames; ppo_diag reads actions, old_logps, rets
+Step = collections.namedtuple("Step", "launch actions old_logps advs rets b_global")
+
+
+class StackedFrames:
+    """Frames uint8 [B, C, 84, 84] on the device.  stage: uint8 [>= n, C, 84, 84] that gathered() fills (staged); tab: int32 [>= n, 4]
+    (in place).  Both methods return a launcher, the HotPath call with its frames bound; what they enqueue precedes it in stream order."""
+
+    def __init__(self, hp, frames, in_place, stage=None, tab=None):
+        self.hp, self.frames, self.in_place, self.stage, self.tab = hp, frames, in_place, stage, tab
+
+    def contiguous(self, lo, hi):
+        """Samples lo..hi-1 in storage order: a view, in place or not."""
+        return partial(self.hp.ppo_iter, self.frames[lo:hi])
+
+    def gathered(self, idx, n, columns, columns_dst, adv_affine):
+        """The n samples idx names; the four float columns ride along into columns_dst (the advantages through adv_affine if given)."""
+        if self.in_place:
+            tab = ops.frame_table_stacks(self.frames, self.tab, idx=idx, n=n, columns=columns, columns_dst=columns_dst, adv_affine=adv_affine)
+            return partial(self.hp.ppo_iter_indexed, self.frames, tab)
+        ops.gather_minibatch(self.frames, idx, self.stage, columns, columns_dst, adv_affine=adv_affine, n=n)
+        return partial(self.hp.ppo_iter, self.stage[:n])
+
+
+class PlaneFrames(StackedFrames):
+    """data.FramePlanes, every frame stored once: stacks are assembled into `stage`, or read where they lie through `tab`."""
+
+    def contiguous(self, lo, hi):
+        if self.in_place:
+            return partial(self.hp.ppo_iter_indexed, self.frames.pool, self.frames.table(self.tab, first=lo, n=hi - lo))
+        return partial(self.hp.ppo_iter, self.frames.stacks(lo, hi, out=self.stage))
+
+    def gathered(self, idx, n, columns, columns_dst, adv_affine):
+        if self.in_place:
+            tab = self.frames.table(self.tab, idx=idx, n=n, columns=columns, columns_dst=columns_dst, adv_affine=adv_affine)
+            return partial(self.hp.ppo_iter_indexed, self.frames.pool, tab)
+        self.frames.gather(self.stage, idx, n=n, columns=columns, columns_dst=columns_dst, adv_affine=adv_affine)
+        return partial(self.hp.ppo_iter, self.stage[:n])
+
+
+def frame_source(hp, frames, in_place, stage=None, tab=None):
+    return (PlaneFrames if isinstance(frames, FramePlanes) else StackedFrames)(hp, frames, in_place, stage, tab)
+
+
+def run(net, steps, n_steps):
+    """learn()'s protocol over the n_steps Steps of `steps`.  Eager: one host synchronisation per step, the weights match update_time at
+    every yield (the reference's protocol).  net.deferred_stats (config_nn.DEFERRED_LOSS_READBACK): every step is enqueued back to back,
+    its statistics tail and diagnostics sums go to pinned host rows of their own by asynchronous copies, and ONE synchronisation
+    precedes the yields -- same keys, values and update_time per yield, but the weights are already the last step's at the first yield
+    (the reference's consumer, backward.py:189-209, publishes after the last one either way), and with N > 1 ranks a slow host does not
+    stall the others' collectives once per step."""
+    diag, deferred = net.diagnostics, net.deferred_stats
+    if net.target_kl is not None and deferred:   # net.deferred_stats switched on after construction
+        raise ValueError("TARGET_KL needs the host after every step: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
+    if deferred and (net._stats_rows is None or net._stats_rows.shape[0] < n_steps):
+        net._stats_rows = torch.empty((n_steps, 8), dtype=torch.float32).pin_memory()
+    if deferred and diag and (net._diag_rows is None or net._diag_rows.shape[0] < n_steps):
+        # a device row per step as well: the next step must not overwrite what a copy still reads
+        net._diag_rows = torch.empty((n_steps, ops.DIAG_SLOTS), dtype=torch.float64).pin_memory()
+        net._diag_dev = torch.zeros((n_steps, ops.DIAG_SLOTS), dtype=torch.float64, device=net.device)
+    t_all = t0 = time.time()
+    for i, s in enumerate(steps):
+        hp = net._hp   # read per step: the step source ensures the capacity, which may rebuild the hot path
+        s.launch(s.actions, s.old_logps, s.advs, s.rets, b_global=s.b_global)
+        d = None
+        if diag and deferred:
+            net._diag_rows[i].copy_(hp.ppo_diag(s.actions, s.old_logps, s.rets, out=net._diag_dev[i]), non_blocking=True)
+        elif diag:
+            # read before anything is applied: the sums describe the policy this step's loss was evaluated with, combined over the
+            # ranks so that every rank takes the same decision (one that stopped alone would leave the others in the all-reduce)
+            d = ops.diag_dict(hp.diag_global(hp.ppo_diag(s.actions, s.old_logps, s.rets)))
+            if ops.kl_stop(d, net.target_kl):
+                return   # ends the whole call; this step is not applied: no all-reduce, no Adam, no yield, update_time as it was
+        hp.allreduce_grads()
+        hp.clip_adam_step()
+        if deferred:
+            hp.stats_async(net._stats_rows[i])
+            continue
+        net.update_time += 1
+        yield ops.loss_dict(hp.stats(), time.time() - t0, d), net.update_time, True   # one device->host copy
+        t0 = time.time()
+    if not deferred:
+        return
+    torch.cuda.current_stream().synchronize()   # the one synchronisation of the call
+    dt = (time.time() - t_all) / max(n_steps, 1)
+    for i in range(n_steps):
+        net.update_time += 1
+        # the ranks' diagnostics rows are combined after the synchronisation (a collective per step, on the host)
+        d = ops.diag_dict(net._hp.diag_global(net._diag_rows[i])) if diag else None
+        yield ops.loss_dict(ops.stats_dict(net._stats_rows[i]), dt, d), net.update_time, True

@@ -55,6 +55,16 @@ def diag_dict(sums):
     return {"ApproxKL": s[1] / n, "ClipFraction": s[2] / n, "ExplainedVariance": ev, "RatioMax": s[7]}
 
 
+def loss_dict(stats, backup_time, diag=None):
+    """The item a learn() generator yields (reference ppo.py:131-146): four losses of stats_dict, PpoBackUpTime, and the diagnostics of
+    diag_dict when given."""
+    out = {"PpoTotalLoss": stats["PpoTotalLoss"], "ActorLoss": stats["ActorLoss"], "VLoss": stats["VLoss"], "EntLoss": stats["EntLoss"],
+           "PpoBackUpTime": backup_time}
+    if diag is not None:
+        out.update(diag)
+    return out
+
+
 def combine_diag_sums(rows):
     """One global row from the ranks' (or micro-batches') rows, combined in the order given: slots 0-6 summed, slot 7 the largest.
     Every rank that folds the same rows in the same order ends with the same bits."""
