@@ -193,6 +193,9 @@ SIGNATURES = {
                                              c_void_p]),
     "ddrl_op_frame_table_stacks": (c_int32, [c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_forward_indexed": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_frame_slot": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

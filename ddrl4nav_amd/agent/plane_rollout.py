@@ -10,7 +10,12 @@ a quarter of the bytes at C = 4 (0.47 GB against 1.86 GB at 256 envs x 256 steps
 (ddrl_op_gather_frame_stacks): act(t) gathers slot t into one [N, C, 84, 84] scratch, the learner gathers its minibatches from
 batch().states[0], a data.FramePlanes.  Same life cycle and the same methods as DeviceRollout except the whole-stack puts; the same
 actions, log-probs, values and updates bit for bit (tests/test_plane_pool_gpu.py).  The ring-fed put needs no staging buffers and no
-per-parity events: the DMA lands in the pool's plane row itself."""
+per-parity events: the DMA lands in the pool's plane row itself.
+
+act_in_place (None: the net's config_nn.ACT_IN_PLACE, nn/minibatch.py; off by default): act(t) gathers nothing.  The put's age launch is
+ops.frame_slot, which also writes the slot's frame table (int32 [N, 4], 16 bytes per env instead of the N * C * 7056 of the scratch), and
+act(t) is HotPath.forward_indexed on the pool through that table: the same four launches per step as DeviceRollout, the same bits as the
+gathered path (tests/test_act_in_place_gpu.py).  The scratch is then allocated only when stacks() is asked for without `out`."""
 import torch
 
 from ddrl4nav_amd import ops
@@ -21,7 +26,8 @@ from ddrl4nav_amd.utils.staging import copy_into
 
 
 class PlaneRollout(DeviceRollout):
-    def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False):
+    def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False,
+                 act_in_place=None):
         # the pools of DeviceRollout.__init__ with `frames` replaced by planes + age (not called: it would allocate the stacked pool)
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
         self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
@@ -37,7 +43,11 @@ class PlaneRollout(DeviceRollout):
         N, T = self.N, self.T
         self.planes = torch.empty((self.H + T + 1, N, 84, 84), dtype=torch.uint8, device=dev)
         self.age = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
-        self._stack = torch.empty((N, self.C, 84, 84), dtype=torch.uint8, device=dev)   # the slot act(t) reads
+        self.act_in_place = bool(getattr(net, "act_in_place", False) if act_in_place is None else act_in_place)
+        # the slot act(t) reads: gathered into _stack, or in place through _slot_tab, the frame table of slot _slot_t (-1: of none)
+        self._stack = None if self.act_in_place else torch.empty((N, self.C, 84, 84), dtype=torch.uint8, device=dev)
+        self._slot_tab = torch.empty((N, 4), dtype=torch.int32, device=dev) if self.act_in_place else None
+        self._slot_t = -1
         self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
         self._rewards = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
         self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
@@ -64,7 +74,12 @@ class PlaneRollout(DeviceRollout):
 
     def _age(self, t, flags):
         """age[t] from age[t-1] and the reset flags (t == 0: every env is reset, _reset_flags admits nothing else)."""
-        ops.frame_age(self.age[t - 1] if t > 0 else None, flags, self.age[t], self.C)
+        prev = self.age[t - 1] if t > 0 else None
+        if self.act_in_place:   # the same launch also tables slot t for act(t)
+            ops.frame_slot(self.planes.shape[0], self.C, t, prev, flags, self.age[t], self._slot_tab)
+            self._slot_t = t
+        else:
+            ops.frame_age(prev, flags, self.age[t], self.C)
 
     def put_new_frames(self, t, newest, reset=None):
         """ONE new frame per env, uint8 [N,84,84] (device or pinned host) -> pool row H + t; `reset` as DeviceRollout.put_new_frames."""
@@ -88,13 +103,24 @@ class PlaneRollout(DeviceRollout):
 
     # ---- acting ---------------------------------------------------------------------------------
     def stacks(self, t, out=None):
-        """Slot t (0..T) assembled as uint8 [N, C, 84, 84], into `out` or the scratch act() reads."""
-        out = self._stack if out is None else out
+        """Slot t (0..T) assembled as uint8 [N, C, 84, 84], into `out` or the scratch act() reads (acting in place: allocated here, at
+        the first call without `out`)."""
+        if out is None:
+            if self._stack is None:
+                self._stack = torch.empty((self.N, self.C, 84, 84), dtype=torch.uint8, device=self.device)
+            out = self._stack
         return ops.gather_frame_stacks(self.planes, self.age, self.C, out, first=t * self.N, n=self.N)
 
     def act(self, t):
-        """DeviceRollout.act on the gathered slot."""
+        """DeviceRollout.act on the gathered slot, or (act_in_place) on the pool through the slot's frame table."""
         if t < self.t0:
+            return self._actions[t]
+        if self.act_in_place:
+            if self._slot_t != t:   # no put tabled this slot (act(0) after carry_over(), a slot acted on again): table it from age[t]
+                ops.frame_table_planes(self.planes, self.age, self.C, self._slot_tab, first=t * self.N, n=self.N)
+                self._slot_t = t
+            self.hp.forward_indexed(self.planes, self._slot_tab, self.N, seed=self.seed + self.rollouts, stream_id=t, probs=self._probs,
+                                    value=self.values[t], action=self._actions[t], logp=self._logps[t])
             return self._actions[t]
         self.hp.forward(self.stacks(t), seed=self.seed + self.rollouts, stream_id=t, probs=self._probs,
                         value=self.values[t], action=self._actions[t], logp=self._logps[t])
@@ -106,6 +132,7 @@ class PlaneRollout(DeviceRollout):
         T, H = self.T, self.H
         self.planes[:H + 1].copy_(self.planes[T:T + H + 1])
         self.age[0].copy_(self.age[T])
+        self._slot_t = -1          # slot 0 now holds another step's frames: whatever the table describes is stale
         if keep_step:
             self.values[0].copy_(self.values[T])
             for pool in (self._rewards, self._dones, self._actions, self._logps):

@@ -49,6 +49,9 @@ struct ActArgs {
   int64_t a1_es, a2_es, a3_es;
   float* a3max;  // [e][a3max_es]: largest |a3| of every sample
   int a3max_es, n, C, NE;
+  // IND (a frame table, kernels.h EncCall::tab): `frames` is the plane base pointer with n_planes planes of 7,056 bytes behind it
+  const int32_t* tab;
+  int64_t n_planes;
 };
 
 struct ActG {
@@ -81,7 +84,9 @@ __device__ __forceinline__ uint2 bytes_to_f16(unsigned v) {
   return make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
 }
 
-template <bool KEEP>
+// IND: the frames are read in place through a frame table, as in conv_fwd1_planes_kernel (conv2.hip): the four plane bases of the
+// workgroup's sample are looked up and clamped with blockIdx.x alone, i.e. as scalars; the per-lane part is the offset inside the plane.
+template <bool KEEP, bool IND = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void act_convs_kernel(const ActArgs A) {
   using K = ActG;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -99,7 +104,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
   // ---------------- phase 0: requests
   unsigned fr[4][4];
-  {
+  if constexpr (IND) {
+    // four separately named bases (an array of them indexed in the loop became a load through a selected pointer and went to scratch
+    // in the conv1 kernels); the table repeats the last channel for the missing ones: always four
+    const uint8_t* const f0 = A.frames + frame_plane_base(A.tab, b, 0, A.n_planes);
+    const uint8_t* const f1 = A.frames + frame_plane_base(A.tab, b, 1, A.n_planes);
+    const uint8_t* const f2 = A.frames + frame_plane_base(A.tab, b, 2, A.n_planes);
+    const uint8_t* const f3 = A.frames + frame_plane_base(A.tab, b, 3, A.n_planes);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int off = min(tid + 512 * j, 1763) * 4;
+      fr[0][j] = *(const unsigned*)(f0 + off);
+      fr[1][j] = *(const unsigned*)(f1 + off);
+      fr[2][j] = *(const unsigned*)(f2 + off);
+      fr[3][j] = *(const unsigned*)(f3 + off);
+    }
+  } else {
     const uint8_t* fsrc = A.frames + (size_t)b * ((size_t)C * 7056);
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch)
@@ -389,16 +409,24 @@ void launch_act_convs(const EncCall& c, hipStream_t st) {
   const ParamLayout& L = *c.L;
   lds_limit_once<act_convs_kernel<false>>((int)K::LDS_BYTES);
   lds_limit_once<act_convs_kernel<true>>((int)K::LDS_BYTES);
+  lds_limit_once<act_convs_kernel<false, true>>((int)K::LDS_BYTES);
+  lds_limit_once<act_convs_kernel<true, true>>((int)K::LDS_BYTES);
   ActArgs a{c.frames, w.wp1b, w.wp2b, w.wp3b, w.amax, c.params,
             {L.enc_base[0] + L.enc.c1b, L.enc_base[L.NE - 1] + L.enc.c1b},
             {L.enc_base[0] + L.enc.c2b, L.enc_base[L.NE - 1] + L.enc.c2b},
             {L.enc_base[0] + L.enc.c3b, L.enc_base[L.NE - 1] + L.enc.c3b},
-            w.a1, w.a2, w.a3, w.es(A1_N), w.es(A2_N), w.es(A3_N), w.actmax, ACT_FUSED_MAX, c.n, L.C, L.NE};
+            w.a1, w.a2, w.a3, w.es(A1_N), w.es(A2_N), w.es(A3_N), w.actmax, ACT_FUSED_MAX, c.n, L.C, L.NE, c.tab, c.n_planes};
   ProfRange pr(c.prof, "ActConvs", st);
-  if (c.keep_acts)
-    hipLaunchKernelGGL(act_convs_kernel<true>, dim3((unsigned)c.n, (unsigned)L.NE), dim3(K::THREADS), K::LDS_BYTES, st, a);
+  const dim3 grid((unsigned)c.n, (unsigned)L.NE);
+  if (c.tab != nullptr) {  // the frame source picks the instantiation, as launch_fwd1 does (conv2.hip)
+    if (c.keep_acts)
+      hipLaunchKernelGGL((act_convs_kernel<true, true>), grid, dim3(K::THREADS), K::LDS_BYTES, st, a);
+    else
+      hipLaunchKernelGGL((act_convs_kernel<false, true>), grid, dim3(K::THREADS), K::LDS_BYTES, st, a);
+  } else if (c.keep_acts)
+    hipLaunchKernelGGL(act_convs_kernel<true>, grid, dim3(K::THREADS), K::LDS_BYTES, st, a);
   else
-    hipLaunchKernelGGL(act_convs_kernel<false>, dim3((unsigned)c.n, (unsigned)L.NE), dim3(K::THREADS), K::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(act_convs_kernel<false>, grid, dim3(K::THREADS), K::LDS_BYTES, st, a);
 }
 
 }  // namespace ddrl

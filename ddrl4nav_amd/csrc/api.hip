@@ -217,8 +217,10 @@ static EncCall ctx_enc_call(ddrl_ctx* ctx, const uint8_t* frames, int n, Profile
   return EncCall{prof, &ctx->ws, &ctx->L, &ctx->splits, ctx->params, frames, n};
 }
 
-int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const float* act_in, uint64_t seed,
-                     uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out, void* stream) {
+// An acting forward on n samples whose frames are either the contiguous [n][C][84][84] behind `frames` (tab null) or lie where the frame
+// table says, behind the plane base pointer `frames` (kernels.h EncCall::tab): the body of both entry points
+static int32_t forward_on(ddrl_ctx* ctx, const uint8_t* frames, const int32_t* tab, int64_t n_planes, int32_t n, const float* act_in,
+                          uint64_t seed, uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out, void* stream) {
   if (!ctx || !frames || !value) return DDRL_ERR_INVALID_ARG;
   if (n < 1 || n > ctx->cfg.max_batch) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -227,6 +229,8 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
   // record drains the queue): the acting path is only timed when asked for explicitly (on = 1)
   Profiler* prof = ctx->profile && ctx->profile_acting ? ctx : nullptr;
   EncCall ec = ctx_enc_call(ctx, frames, n, prof);
+  ec.tab = tab;
+  ec.n_planes = n_planes;
   ec.keep_acts = ctx->keep_acts;
   ctx->acts_stored = ctx->keep_acts || n > ACT_FUSED_MAX;
   launch_encoder_forward(ec, true, st);
@@ -237,6 +241,20 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
   ctx->last_n = n;
   ctx->iter_n = 0;
   return launch_status();
+}
+
+int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const float* act_in, uint64_t seed,
+                     uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out, void* stream) {
+  return forward_on(ctx, frames, nullptr, 0, n, act_in, seed, stream_id, probs, value, action_out, logp_out, stream);
+}
+
+int32_t ddrl_forward_indexed(ddrl_ctx* ctx, const uint8_t* planes, int64_t n_planes, const int32_t* tab, int32_t n, const float* act_in,
+                             uint64_t seed, uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out,
+                             void* stream) {
+  // the frame source's own checks, before anything touches the context or HIP
+  if (!planes || !tab || !aligned16(planes) || ((uintptr_t)tab & 3) || n_planes < 1) return DDRL_ERR_INVALID_ARG;
+  if (n_planes > INT64_MAX / 7056) return DDRL_ERR_INVALID_ARG;
+  return forward_on(ctx, planes, tab, n_planes, n, act_in, seed, stream_id, probs, value, action_out, logp_out, stream);
 }
 
 int32_t ddrl_categorical_stats(const float* probs, int32_t n, int32_t A, float* p_hat, float* logits, float* entropy,

@@ -415,7 +415,8 @@ static void launch_fwd1_planes(const EncCall& c, bool acting, hipStream_t st) {
                      w.wp1b, w.amax, c.params, L.enc_base[0] + L.enc.c1b, L.enc_base[NE - 1] + L.enc.c1b, w.a1, w.es(A1_N), c.n,
                      acting ? (unsigned*)nullptr : w.m1, w.es(M1_N), L.C, c.tab, c.n_planes);
 }
-// the frame source picks the instantiation: a frame table (training launches only, api.hip) = the indirect one
+// the frame source picks the instantiation: a frame table (ddrl_ppo_iter_indexed, and ddrl_forward_indexed of more than ACT_FUSED_MAX
+// samples: acting = true, no sign mask) = the indirect one
 template <int NE>
 static void launch_fwd1(const EncCall& c, bool acting, hipStream_t st) {
   if (c.tab != nullptr) {

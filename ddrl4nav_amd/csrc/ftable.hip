@@ -8,6 +8,8 @@
 // The four float columns and the advantage affine of the gathers ride along (rows.h gather_columns): one launch collates a minibatch
 // without touching a frame.  A sample index outside the valid range is CLAMPED to it before anything is read (the gathers return zeros
 // for such a sample).  Context-free, no allocation, no atomics: repeats are bit-identical.
+// ddrl_op_frame_slot: the table of ONE acting slot of the single-frame pool together with the slot's age row (fpool.hip frame_age_kernel),
+// one launch per acting step, for ddrl_forward_indexed.
 #include "rows.h"
 
 namespace ddrl {
@@ -57,6 +59,30 @@ static int32_t frame_table(int64_t n_samples, int64_t n_planes, int n_envs, int 
   return launch_status();
 }
 
+// ---- acting slot t of the single-frame pool: age[i] by the rule of frame_age_kernel (fpool.hip), then the four entries of env i by the
+// rule above with newest = hist + t, written as one 16-byte store.  One thread per env.
+constexpr int SLOT_THREADS = 64;
+using i4v = __attribute__((ext_vector_type(4))) int;
+__global__ __launch_bounds__(SLOT_THREADS) void frame_slot_kernel(int n_envs, int newest, int channels, const uint8_t* __restrict__ prev,
+                                                                  const uint8_t* __restrict__ reset, uint8_t* __restrict__ age,
+                                                                  int32_t* __restrict__ tab) {
+  const unsigned i = blockIdx.x * (unsigned)SLOT_THREADS + threadIdx.x;
+  if (i >= (unsigned)n_envs) return;
+  const int cap = channels - 1;
+  int a = 0;
+  if (prev != nullptr && (reset == nullptr || reset[i] == 0)) a = (int)prev[i] + 1 < cap ? (int)prev[i] + 1 : cap;
+  age[i] = (uint8_t)a;
+  i4v e;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int back = cap - (c < channels ? c : cap);
+    back = a < back ? a : back;
+    back = newest < back ? newest : back;  // the rule's own clamp: row >= 0 (a <= cap already)
+    e[c] = (newest - back) * n_envs + (int)i;
+  }
+  *(i4v*)(tab + (int64_t)i * 4) = e;
+}
+
 }  // namespace ddrl
 
 using namespace ddrl;
@@ -83,6 +109,24 @@ int32_t ddrl_op_frame_table_stacks(int64_t n_rows, int32_t channels, const int32
   if (n_rows < 1 || n_rows > INT32_MAX / channels) return DDRL_ERR_INVALID_ARG;
   const MinibatchColumns cols{{actions, old_logps, advs, rets}, {actions_dst, old_logps_dst, advs_dst, rets_dst}};
   return frame_table(n_rows, n_rows * channels, 1, 0, nullptr, channels, idx, first, n, tab, cols, adv_affine, stream);
+}
+
+int32_t ddrl_op_frame_slot(int32_t rows, int32_t n_envs, int32_t hist, int32_t channels, int32_t t, const uint8_t* prev_age,
+                           const uint8_t* reset, uint8_t* age, int32_t* tab, void* stream) {
+  if (channels < 1 || channels > 4) return DDRL_ERR_UNSUPPORTED;
+  if (!age || !tab || (!prev_age && !reset) || n_envs < 1 || hist < channels - 1) return DDRL_ERR_INVALID_ARG;
+  if (t < 0 || (int64_t)hist + t >= rows) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(tab)) return DDRL_ERR_INVALID_ARG;                         // an env's four entries are one 16-byte store
+  if ((int64_t)rows * n_envs > INT32_MAX) return DDRL_ERR_INVALID_ARG;  // an entry is an int32
+  const uint64_t nb = (uint64_t)n_envs;
+  const void* src[2] = {prev_age, reset};
+  const uint64_t src_b[2] = {nb, nb};
+  void* dst[2] = {age, tab};
+  const uint64_t dst_b[2] = {nb, nb * 16};
+  if (!reads_and_writes_apart(src, src_b, 2, dst, dst_b, 2)) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(frame_slot_kernel, dim3((unsigned)((n_envs - 1) / SLOT_THREADS + 1)), dim3(SLOT_THREADS), 0, (hipStream_t)stream, n_envs,
+                     hist + t, channels, prev_age, reset, age, tab);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -37,9 +37,9 @@ struct EncCall {
   int n;
   hipEvent_t* bucket_ev = nullptr;  // [GRAD_BUCKETS] or null (single rank: nothing to overlap)
   bool keep_acts = false;           // acting launches: also store a1 / a2 (ddrl_debug_keep_activations; the fused kernel of act.hip keeps them on chip)
-  // training launches reading frames in place (ddrl_ppo_iter_indexed): tab [n][4] = index of the 7,056-byte plane behind `frames`
-  // that holds channel c of sample b (entries c >= C repeat entry C - 1), n_planes = planes behind `frames`; the conv1 kernels clamp
-  // every entry to [0, n_planes).  null = `frames` is the contiguous [n][C][84][84]
+  // launches reading frames in place (ddrl_ppo_iter_indexed, ddrl_forward_indexed): tab [n][4] = index of the 7,056-byte plane behind
+  // `frames` that holds channel c of sample b (entries c >= C repeat entry C - 1), n_planes = planes behind `frames`; the conv1 kernels
+  // and the fused acting kernel (act.hip) clamp every entry to [0, n_planes).  null = `frames` is the contiguous [n][C][84][84]
   const int32_t* tab = nullptr;
   int64_t n_planes = 0;
 };

@@ -130,6 +130,27 @@ class HotPath:
                                     _p(action) if act is None else c_void_p(0), _p(logp), _st()))
         return probs, value, action, logp
 
+    def forward_indexed(self, planes, tab, n, act=None, seed=0, stream_id=0, probs=None, value=None, action=None, logp=None):
+        """forward on frames read where they lie (include/ddrl.h ddrl_forward_indexed): `planes` is any contiguous uint8 device tensor of
+        whole 84 x 84 planes (a single-frame pool, or stacked frames) and tab int32 [>= n, 4] (ops.frame_slot / frame_table_planes /
+        frame_table_stacks) names the plane of every channel of the n samples.  Bit-identical to forward on the materialised stacks."""
+        n = int(n)
+        assert planes.dtype == torch.uint8 and planes.is_cuda and planes.is_contiguous() and planes.numel() % (84 * 84) == 0
+        assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * n
+        dev = planes.device
+        probs = torch.empty((n, self.n_actions), dtype=torch.float32, device=dev) if probs is None else probs
+        value = torch.empty(n, dtype=torch.float32, device=dev) if value is None else value
+        logp = torch.empty(n, dtype=torch.float32, device=dev) if logp is None else logp
+        if act is None:
+            action = torch.empty(n, dtype=torch.float32, device=dev) if action is None else action
+        else:
+            assert act.dtype == torch.float32 and act.is_contiguous() and act.numel() == n
+            action = act
+        check(self.lib.ddrl_forward_indexed(self.ctx, _p(planes), planes.numel() // (84 * 84), _p(tab), n, _p(act),
+                                            int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), _p(probs), _p(value),
+                                            _p(action) if act is None else c_void_p(0), _p(logp), _st()))
+        return probs, value, action, logp
+
     def categorical_stats(self, probs):
         return ops.categorical_stats(probs)
 

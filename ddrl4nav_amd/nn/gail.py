@@ -259,6 +259,8 @@ class GAIL(Basenn):
         refuse_minibatch_options(discriminator.config_nn, "NETWORK_TYPE='gail'")
         from ddrl4nav_amd.nn.minibatch import refuse_frames_in_place
         refuse_frames_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
+        from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
+        refuse_act_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
         if getattr(generator, "diagnostics", False):
             raise NotImplementedError("the generator was built with PPO_DIAGNOSTICS / TARGET_KL, which GAIL does not support")
         self.device = discriminator.device

@@ -490,6 +490,8 @@ class GenericPPO(Basenn):
         refuse_minibatch_options(config_nn, "the operator-composed GenericPPO")
         from ddrl4nav_amd.nn.minibatch import refuse_frames_in_place
         refuse_frames_in_place(config_nn, "the operator-composed GenericPPO")
+        from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
+        refuse_act_in_place(config_nn, "the operator-composed GenericPPO")
         if rnd is not None:
             raise NotImplementedError("RND is disabled in the reference defaults (USE_RND=False) and out of scope")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):

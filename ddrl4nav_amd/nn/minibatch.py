@@ -14,6 +14,10 @@ The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the Config
                                through a frame table (csrc/ftable.hip, ddrl_ppo_iter_indexed).  Same bits.  Not one of the four knobs
                                that choose the step source: the frame source of either reads it (nn/update_loop.py)
 
+  ACT_IN_PLACE         False   True: PlaneRollout.act reads its slot of the single-frame pool where it lies (one ddrl_op_frame_slot launch
+                               for the age row and the slot's frame table, then ddrl_forward_indexed) instead of gathering it into a
+                               scratch first.  Same bits.  Its own knob: FRAMES_IN_PLACE alone changes nothing about acting
+
 PPO.learn runs one loop (nn/update_loop.py run()) over one of two step sources: with all four knobs at their defaults its own single
 full-batch step, otherwise steps() below.  Per step, everything on the device and in stream order: shuffle on, one gather of frames
 and columns into ONE staging buffer (or, in place, one frame table); off, contiguous views of the columns and of stacked frames
@@ -58,6 +62,21 @@ def refuse_frames_in_place(config_nn, who):
     """GenericPPO and GAIL run operator-composed encoders on float states: no conv1 kernel there reads a frame table."""
     if frames_in_place_option(config_nn):
         raise ValueError("FRAMES_IN_PLACE is built for the Atari fast path alone (nn/ppo.py PPO over AtariPreNet), not for %s: unset it"
+                         % who)
+
+
+def act_in_place_option(config_nn):
+    """config_nn.ACT_IN_PLACE (optional, default False) as a bool; ValueError for anything but True / False."""
+    v = getattr(config_nn, "ACT_IN_PLACE", False)
+    if not isinstance(v, bool):
+        raise ValueError("ACT_IN_PLACE must be True or False, got %r" % (v,))
+    return v
+
+
+def refuse_act_in_place(config_nn, who):
+    """GenericPPO and GAIL act on float states through operator-composed encoders: no acting kernel there reads a frame table."""
+    if act_in_place_option(config_nn):
+        raise ValueError("ACT_IN_PLACE is built for the Atari fast path alone (nn/ppo.py PPO over AtariPreNet), not for %s: unset it"
                          % who)
 
 

@@ -45,6 +45,8 @@ class PPO(Basenn):
         # config_nn.FRAMES_IN_PLACE (optional, nn/minibatch.py): no batch or minibatch of frames is materialised; the conv1 kernels read
         # them where they lie through a frame table (ddrl_ppo_iter_indexed).  Same bits; off by default
         self.frames_in_place = minibatch.frames_in_place_option(config_nn)
+        # config_nn.ACT_IN_PLACE (optional, nn/minibatch.py): a PlaneRollout over this net acts on its pool in place (agent/plane_rollout.py)
+        self.act_in_place = minibatch.act_in_place_option(config_nn)
         self._frame_tab = None      # FramePlanes states, full-batch step, in place: int32 [B, 4]
         self._mb_stage = None
         self._plane_batch = None   # FramePlanes states, full-batch step, staged: the batch materialised once per learn call

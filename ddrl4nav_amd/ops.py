@@ -334,6 +334,22 @@ def frame_table_stacks(frames, tab, idx=None, first=0, n=None, columns=None, col
     return tab
 
 
+def frame_slot(rows, channels, t, prev_age, reset, age, tab, hist=None):
+    """One acting step of the single-frame pool in one launch (include/ddrl.h ddrl_op_frame_slot; csrc/ftable.hip): age (uint8 [N]) as
+    frame_age(prev_age, reset, age, channels), and tab (int32 [>= N, 4], 16-byte aligned) as frame_table_planes(first=t * N, n=N) of a
+    pool of `rows` plane rows with `hist` history rows in front (default channels - 1), bit for bit.  The table is what
+    HotPath.forward_indexed reads slot t through.  Asynchronous on the current stream; returns tab."""
+    C = int(channels)
+    hist = C - 1 if hist is None else int(hist)
+    N = age.numel()
+    for x in (prev_age, reset, age):
+        assert x is None or (x.dtype == torch.uint8 and x.is_cuda and x.is_contiguous() and x.numel() == N), \
+            "expected contiguous uint8 device tensors of one length"
+    assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * N, "tab: contiguous int32 [>= N, 4]"
+    check(_lib.load().ddrl_op_frame_slot(int(rows), N, hist, C, int(t), _p(prev_age), _p(reset), _p(age), _p(tab), _st()))
+    return tab
+
+
 class Conv:
     """One Conv2d / Conv1d layer (torch weight layout [cout][cin][kh][kw]; Conv1d: h = kh = 1)."""
 

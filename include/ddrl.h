@@ -121,6 +121,19 @@ int32_t ddrl_forward(ddrl_ctx* ctx, const uint8_t* frames, int32_t n, const floa
                      uint64_t seed, uint64_t stream_id, float* probs, float* value,
                      float* action_out, float* logp_out, void* stream);
 
+/* ddrl_forward on frames read where they lie (additive: ABI 3): instead of a contiguous [n][C][84][84], `planes` is a plane base
+ * pointer with n_planes planes of 7,056 bytes behind it and `tab` (int32 [n][4] on the device, from ddrl_op_frame_table_planes /
+ * ddrl_op_frame_table_stacks / ddrl_op_frame_slot below) names, for every sample of the call, the plane that holds each of its
+ * channels.  The kernels that read the frames (the fused acting kernel up to 512 samples, the conv1 forward above) clamp every entry
+ * to [0, n_planes): whatever the table holds, nothing outside [planes, planes + n_planes * 7056) is read.  Same arithmetic on the
+ * same bytes: the outputs, the features ddrl_last_features returns and, with ddrl_debug_keep_activations, a1 / a2 are bit-identical to
+ * ddrl_forward on the materialised stacks; the context is left as ddrl_forward leaves it.  planes 16-byte aligned, tab 4-byte aligned
+ * with n * 4 entries, 1 <= n_planes <= INT64_MAX / 7056; otherwise DDRL_ERR_INVALID_ARG (checked before anything touches the context
+ * or HIP). */
+int32_t ddrl_forward_indexed(ddrl_ctx* ctx, const uint8_t* planes, int64_t n_planes, const int32_t* tab, int32_t n, const float* act_in,
+                             uint64_t seed, uint64_t stream_id, float* probs, float* value, float* action_out, float* logp_out,
+                             void* stream);
+
 /* torch.distributions.Categorical(probs) derived quantities (actor.py:97 + forward.py:137-138,
  * ppo.py:106): p_hat = p/sum(p), logits = log(clamp(p_hat, eps, 1-eps)), entropy. */
 int32_t ddrl_categorical_stats(const float* probs, int32_t n, int32_t n_actions, float* p_hat,
@@ -647,6 +660,18 @@ int32_t ddrl_op_frame_table_stacks(int64_t n_rows, int32_t channels, const int32
                                    const float* actions, const float* old_logps, const float* advs, const float* rets,
                                    float* actions_dst, float* old_logps_dst, float* advs_dst, float* rets_dst, const float* adv_affine,
                                    void* stream);
+/* One acting step of the single-frame pool in one launch (additive: ABI 3), for ddrl_forward_indexed: the age row of step t and the
+ * frame table of its n_envs samples,
+ *   age[i]    = 0 where reset[i] != 0, else min(prev_age[i] + 1, channels - 1)            (ddrl_op_frame_age, bit for bit)
+ *   tab[i][c] = (hist + t - min(channels - 1 - c, age[i], hist + t)) * n_envs + i          (ddrl_op_frame_table_planes with
+ *               first = t * n_envs, n = n_envs and no columns, bit for bit; entries c >= channels repeat entry channels - 1)
+ * reset == NULL: no env is reset; prev_age == NULL (legal only together with a reset array): every env is.  prev_age, reset and age
+ * hold n_envs bytes, tab n_envs * 4 entries; `rows` is the number of pool rows, rows > hist + t, t >= 0, hist >= channels - 1,
+ * rows * n_envs fits an int32.  tab is 16-byte aligned (an env's four entries are one store); age and tab overlap neither input nor
+ * one another: DDRL_ERR_INVALID_ARG.  channels outside 1..4: DDRL_ERR_UNSUPPORTED.  Needs no context, allocates nothing, no atomics,
+ * asynchronous on `stream`; the argument checks run before anything touches HIP. */
+int32_t ddrl_op_frame_slot(int32_t rows, int32_t n_envs, int32_t hist, int32_t channels, int32_t t, const uint8_t* prev_age,
+                           const uint8_t* reset, uint8_t* age, int32_t* tab, void* stream);
 
 #ifdef __cplusplus
 }
