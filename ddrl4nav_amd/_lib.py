@@ -51,6 +51,17 @@ class HeadsDesc(Structure):
                 ("critic_b", c_int64), ("n_params", c_int64)]
 
 
+class LossOptions(Structure):
+    """ddrl_loss_options (include/ddrl.h)."""
+    _fields_ = [("value_clip", c_float), ("entropy_split", c_int32), ("reserved", c_int32 * 2)]
+
+
+class PpoBatch(Structure):
+    """ddrl_ppo_batch (include/ddrl.h)."""
+    _fields_ = [("frames_or_planes", c_void_p), ("n_planes", c_int64), ("tab", c_void_p), ("actions", c_void_p),
+                ("old_logps", c_void_p), ("advs", c_void_p), ("rets", c_void_p), ("old_values", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/ddrl.h declares
 SIGNATURES = {
     "ddrl_abi_version": (c_int32, []),
@@ -196,6 +207,12 @@ SIGNATURES = {
     "ddrl_forward_indexed": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "ddrl_op_frame_slot": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_ppo_iter_opt": (c_int32, [c_void_p, POINTER(PpoBatch), POINTER(LossOptions), c_int32, c_int64, c_void_p]),
+    "ddrl_op_heads_loss_opt": (c_int32, [POINTER(HeadsDesc), POINTER(Config), c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, POINTER(LossOptions), c_void_p, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "ddrl_set_rates": (c_int32, [c_void_p, c_float, c_float, c_float, c_float]),
+    "ddrl_op_gather_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@ class PlaneRollout(DeviceRollout):
                  act_in_place=None):
         # the pools of DeviceRollout.__init__ with `frames` replaced by planes + age (not called: it would allocate the stacked pool)
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
+        self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
         if not 1 <= self.C <= 4:
             raise ValueError("1 to 4 stacked frames, got %d" % self.C)
@@ -145,4 +146,4 @@ class PlaneRollout(DeviceRollout):
         """DeviceRollout.batch with the states as FramePlanes over the pool (zero-copy)."""
         B = self.N * self.T
         return Experience(states=[FramePlanes(self.planes, self.age, self.T, self.N, self.C)], advs=self.adv.view(B),
-                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self.ret.view(1, B))
+                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self._value_rows(B))

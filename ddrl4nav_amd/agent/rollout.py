@@ -27,9 +27,19 @@ from ddrl4nav_amd.ops import frame_stack_push
 from ddrl4nav_amd.utils.staging import copy_into
 
 
+def value_rows(ret, values, T, B, with_old_values):
+    """Experience.values of a rollout's batch: row 0 the return targets (a view of `ret`); for a net that clips its value loss
+    (net.wants_old_values, VALUE_CLIP) also row 1, the T rows of values the collecting policy predicted (a copy: carry_over rewrites
+    values[0])."""
+    if not with_old_values:
+        return ret.view(1, B)
+    return torch.stack([ret.view(B), values[:T].reshape(B)])
+
+
 class DeviceRollout:
     def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False):
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
+        self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
         self.gamma, self.landa = gamma, landa
         dev = torch.device(device if device is not None else self.hp.device)
@@ -182,11 +192,14 @@ class DeviceRollout:
         else:
             self.t0 = 0
 
+    def _value_rows(self, B):
+        return value_rows(self.ret, self.values, self.T, B, self.with_old_values)
+
     def batch(self):
         """Zero-copy views in the layout net.learn expects (sample order is irrelevant to the maths)."""
         B = self.N * self.T
         return Experience(states=[self.frames[:self.T].view(B, self.C, 84, 84)], advs=self.adv.view(B),
-                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self.ret.view(1, B))
+                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self._value_rows(B))
 
 
 class StateRollout:
@@ -197,6 +210,7 @@ class StateRollout:
 
     def __init__(self, net, n_envs, state_shapes, horizon=256, gamma=0.99, landa=0.95, device=None, track_returns=False):
         self.net = net
+        self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T = int(n_envs), int(horizon)
         self.gamma, self.landa = gamma, landa
         dev = torch.device(device if device is not None else net.device)
@@ -274,8 +288,11 @@ class StateRollout:
         else:
             self.t0 = 0
 
+    def _value_rows(self, B):
+        return value_rows(self.ret, self.values, self.T, B, self.with_old_values)
+
     def batch(self):
         B = self.N * self.T
         return Experience(states=[p[:self.T].reshape((B,) + tuple(p.shape[2:])) for p in self.states],
                           advs=self.adv.view(B), actions=self.actions.view((B,) + tuple(self.actions.shape[2:])),
-                          old_logps=self.logps.view(B), values=self.ret.view(1, B))
+                          old_logps=self.logps.view(B), values=self._value_rows(B))

@@ -300,8 +300,10 @@ int32_t ddrl_episode_returns(const float* rewards, const uint8_t* dones, int32_t
 
 // One PPO iteration on B samples whose frames are either the contiguous [B][C][84][84] behind `frames` (tab null) or lie where the
 // frame table says, behind the plane base pointer `frames` (kernels.h EncCall::tab): the body of both entry points
+// opt: null = the plain loss kernels (ddrl_ppo_iter / _indexed); else the OPT instantiations with these options (ddrl_ppo_iter_opt)
 static int32_t ppo_iter_on(ddrl_ctx* ctx, const uint8_t* frames, const int32_t* tab, int64_t n_planes, const float* actions,
-                           const float* old_logps, const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream) {
+                           const float* old_logps, const float* advs, const float* rets, int32_t B, int64_t B_global, void* stream,
+                           const LossOptions* opt = nullptr, const float* old_values = nullptr) {
   if (!ctx || !frames || !actions || !old_logps || !advs || !rets) return DDRL_ERR_INVALID_ARG;
   if (B < 1 || B > ctx->cfg.max_batch || B_global < B) return DDRL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -315,7 +317,9 @@ static int32_t ppo_iter_on(ddrl_ctx* ctx, const uint8_t* frames, const int32_t* 
   launch_backward_amax_reset(ec, st);
   {
     ProfRange ps(ctx->profile ? ctx : nullptr, "heads_loss", st);
-    launch_heads_loss(ctx_heads_call(ctx, B, false), actions, old_logps, advs, rets, (float)(1.0 / (double)B_global), ctx->grads, st);
+    const float inv_b = (float)(1.0 / (double)B_global);
+    if (opt) launch_heads_loss_opt(ctx_heads_call(ctx, B, false), actions, old_logps, advs, rets, *opt, old_values, inv_b, ctx->grads, st);
+    else launch_heads_loss(ctx_heads_call(ctx, B, false), actions, old_logps, advs, rets, inv_b, ctx->grads, st);
   }
   bucket_done(ec, BUCKET_HEADS, st);  // head-layer gradients and the three loss shares of the tail are final
   launch_encoder_backward(ec, ctx->grads, st, true);
@@ -336,6 +340,34 @@ int32_t ddrl_ppo_iter_indexed(ddrl_ctx* ctx, const uint8_t* planes, int64_t n_pl
   if (!planes || !tab || !aligned16(planes) || ((uintptr_t)tab & 3) || n_planes < 1) return DDRL_ERR_INVALID_ARG;
   if (n_planes > INT64_MAX / 7056) return DDRL_ERR_INVALID_ARG;
   return ppo_iter_on(ctx, planes, tab, n_planes, actions, old_logps, advs, rets, B, B_global, stream);
+}
+
+int32_t ddrl_ppo_iter_opt(ddrl_ctx* ctx, const ddrl_ppo_batch* batch, const ddrl_loss_options* opt, int32_t B, int64_t B_global,
+                          void* stream) {
+  // the batch's and the options' own checks, before anything touches the context or HIP
+  if (!batch || !opt) return DDRL_ERR_INVALID_ARG;
+  if (!(opt->value_clip >= 0.0f) || opt->value_clip > 3.0e38f || opt->reserved[0] != 0 || opt->reserved[1] != 0) return DDRL_ERR_INVALID_ARG;
+  if (opt->value_clip > 0.0f && (!batch->old_values || ((uintptr_t)batch->old_values & 3))) return DDRL_ERR_INVALID_ARG;
+  if (batch->tab) {
+    if (!batch->frames_or_planes || !aligned16(batch->frames_or_planes) || ((uintptr_t)batch->tab & 3) || batch->n_planes < 1)
+      return DDRL_ERR_INVALID_ARG;
+    if (batch->n_planes > INT64_MAX / 7056) return DDRL_ERR_INVALID_ARG;
+  }
+  const LossOptions lo{opt->value_clip, opt->entropy_split != 0 ? 1 : 0};
+  return ppo_iter_on(ctx, batch->frames_or_planes, batch->tab, batch->tab ? batch->n_planes : 0, batch->actions, batch->old_logps,
+                     batch->advs, batch->rets, B, B_global, stream, &lo, batch->old_values);
+}
+
+int32_t ddrl_set_rates(ddrl_ctx* ctx, float actor_lr, float critic_lr, float learning_rate, float ppo_clip) {
+  const float r[4] = {actor_lr, critic_lr, learning_rate, ppo_clip};
+  for (float x : r)
+    if (!(x >= 0.0f) || x > 3.0e38f) return DDRL_ERR_INVALID_ARG;  // negative, NaN or infinite
+  if (!ctx) return DDRL_ERR_INVALID_ARG;
+  ctx->cfg.actor_lr = actor_lr;
+  ctx->cfg.critic_lr = critic_lr;
+  ctx->cfg.learning_rate = learning_rate;
+  ctx->cfg.ppo_clip = ppo_clip;
+  return DDRL_OK;
 }
 
 // the diagnostics head on what ddrl_ppo_iter left behind: its features, and -- its head partials being reduced -- the front of their

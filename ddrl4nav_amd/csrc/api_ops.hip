@@ -450,10 +450,11 @@ int32_t ddrl_op_heads_act(const ddrl_heads_desc* d, const float* params, const f
   return launch_status();
 }
 
-int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
-                           const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
-                           const float* rets, int64_t B_global, float* dh_actor, float* dh_critic, float* grads, float* ws,
-                           void* stream) {
+// opt: null = the plain loss kernels (ddrl_op_heads_loss); else the OPT instantiations (ddrl_op_heads_loss_opt)
+static int32_t heads_loss_on(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                             const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
+                             const float* rets, int64_t B_global, float* dh_actor, float* dh_critic, float* grads, float* ws,
+                             void* stream, const LossOptions* opt, const float* old_values) {
   if (!heads_ok(d) || !cfg || !params || !h_actor || !h_critic || !actions || !old_logps || !advs || !rets || !dh_actor ||
       !grads || !ws || n < 1 || B_global < n)
     return DDRL_ERR_INVALID_ARG;
@@ -464,16 +465,41 @@ int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, con
   const float inv_b = (float)(1.0 / (double)B_global);
   const HeadLayout L = head_layout(d);
   if (d->continuous) {
-    launch_gauss_loss(L, *cfg, params, h_actor, d->shared ? h_actor : h_critic, n, actions, old_logps, advs,
-                      rets, inv_b, dh_actor, dh_critic, hw.dlogits, hw.dvalue, hw.hpart, grads, st);
+    if (opt)
+      launch_gauss_loss_opt(L, *cfg, params, h_actor, d->shared ? h_actor : h_critic, n, actions, old_logps, advs, rets, *opt, old_values,
+                            inv_b, dh_actor, dh_critic, hw.dlogits, hw.dvalue, hw.hpart, grads, st);
+    else
+      launch_gauss_loss(L, *cfg, params, h_actor, d->shared ? h_actor : h_critic, n, actions, old_logps, advs,
+                        rets, inv_b, dh_actor, dh_critic, hw.dlogits, hw.dvalue, hw.hpart, grads, st);
     return launch_status();
   }
   const ParamLayout PL = head_param_layout(L);
   HeadsCall hc{&PL, cfg, params, n, h_actor, d->shared ? 0 : (int64_t)(h_critic - h_actor), dh_actor,
                d->shared ? 0 : (int64_t)(dh_critic - dh_actor)};
   hc.dlogits = hw.dlogits, hc.dvalue = hw.dvalue, hc.hpart = hw.hpart;
-  launch_heads_loss(hc, actions, old_logps, advs, rets, inv_b, grads, st);
+  if (opt) launch_heads_loss_opt(hc, actions, old_logps, advs, rets, *opt, old_values, inv_b, grads, st);
+  else launch_heads_loss(hc, actions, old_logps, advs, rets, inv_b, grads, st);
   return launch_status();
+}
+
+int32_t ddrl_op_heads_loss(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                           const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
+                           const float* rets, int64_t B_global, float* dh_actor, float* dh_critic, float* grads, float* ws,
+                           void* stream) {
+  return heads_loss_on(d, cfg, params, h_actor, h_critic, n, actions, old_logps, advs, rets, B_global, dh_actor, dh_critic, grads, ws,
+                       stream, nullptr, nullptr);
+}
+
+int32_t ddrl_op_heads_loss_opt(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                               const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
+                               const float* rets, const ddrl_loss_options* opt, const float* old_values, int64_t B_global,
+                               float* dh_actor, float* dh_critic, float* grads, float* ws, void* stream) {
+  if (!opt || !(opt->value_clip >= 0.0f) || opt->value_clip > 3.0e38f || opt->reserved[0] != 0 || opt->reserved[1] != 0)
+    return DDRL_ERR_INVALID_ARG;
+  if (opt->value_clip > 0.0f && (!old_values || ((uintptr_t)old_values & 3))) return DDRL_ERR_INVALID_ARG;
+  const LossOptions lo{opt->value_clip, opt->entropy_split != 0 ? 1 : 0};
+  return heads_loss_on(d, cfg, params, h_actor, h_critic, n, actions, old_logps, advs, rets, B_global, dh_actor, dh_critic, grads, ws,
+                       stream, &lo, old_values);
 }
 
 int32_t ddrl_op_heads_diag_ws_floats(const ddrl_heads_desc* d, int32_t max_n, int64_t* floats) {

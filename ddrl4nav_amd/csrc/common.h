@@ -83,6 +83,12 @@ inline ParamLayout make_layout(int A, int C, bool shared = false) {
 
 // The actor + critic head layers inside ANY flat arena, as ddrl_heads_desc gives them (api_ops.hip head_layout): the Categorical
 // (n <= 18 actions) and the Gaussian (n <= 8 action dims, + log_std) heads alike.
+// update options of the loss block (include/ddrl.h ddrl_loss_options): the argument of the loss kernels' OPT instantiations
+struct LossOptions {
+  float value_clip;   // > 0: the value loss is max(e(ret - v), e(ret - v_c)), v_c = v_old + clamp(v - v_old, -c, c)
+  int entropy_split;  // != 0: with two encoders the actor side differentiates actor_loss - theta_e * entropy
+};
+
 struct HeadLayout {
   int n;
   int shared;  // 1: total_loss is differentiated (shared prenet), both heads read the actor's features and feed its dh

@@ -90,17 +90,24 @@ __global__ __launch_bounds__(256) void gauss_act_kernel(const float* __restrict_
 }
 
 // hpart per workgroup: [D*512 dWa][512 dwc][D dba][1 dbc][D dlog_std][actor_sum, v_sum, ent_sum]
+// OPT / X: the update options, as heads.hip heads_loss_kernel
+template <bool OPT = false, class... X>
 __global__ __launch_bounds__(256) void gauss_loss_kernel(
     const float* __restrict__ h_actor, const float* __restrict__ h_critic, const float* __restrict__ params, HeadLayout L,
     ddrl_config cfg, int n, const float* __restrict__ actions, const float* __restrict__ old_logps,
     const float* __restrict__ advs, const float* __restrict__ rets, float inv_b, float* __restrict__ dh_actor,
     float* __restrict__ dh_critic, float* __restrict__ dmu_out, float* __restrict__ dvalue, float* __restrict__ hpart,
-    int64_t hstride) {
+    int64_t hstride, X... x) {
+  static_assert(sizeof...(X) == (OPT ? 2 : 0), "the options and old_values come with OPT only");
   __shared__ float red[(MAXD + 1) * FEAT + 3 * MAXD + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
   const int D = L.n;
   const bool shared = L.shared != 0;
+  const LossOptions opt = loss_options(x...);
+  const float* __restrict__ old_values = loss_old_values(x...);  // OPT: never null (the launcher passes rets where the clip is off)
+  bool ent_grad = shared;  // the entropy term is differentiated
+  if constexpr (OPT) ent_grad = shared || opt.entropy_split != 0;
   GHeadRegs R;
   gload_weights(R, params, L, lane);
   float gwa[MAXD][8], gwc[8], gba[MAXD], gls[MAXD], gbc = 0.0f;
@@ -141,7 +148,9 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(
     const SurrogateTerm sg = ppo_surrogate(logp, old_logps[b], adv, cfg, inv_b);
     s_actor += (double)sg.term;
     const float err = rets[b] - v;
-    const float gv_unit = value_loss_element(err, cfg, s_v);
+    float gv_unit;
+    if constexpr (OPT) gv_unit = opt.value_clip > 0.0f ? value_loss_element_clipped(rets[b], v, old_values[b], opt.value_clip, cfg, s_v) : value_loss_element(err, cfg, s_v);
+    else gv_unit = value_loss_element(err, cfg, s_v);
     s_ent += (double)ent_b;
     const float g_logp = sg.g_logp;
     const float gv = shared ? gv_unit * inv_b * cfg.v_loss_theta : gv_unit * inv_b;
@@ -151,7 +160,7 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(
       dmu[d] = (d < D) ? g_logp * (diff[d] / R.var[d]) : 0.0f;
       // d logp / d log_std = diff^2 / var - 1 ; entropy term only when total_loss is differentiated
       float gl = (d < D) ? g_logp * ((diff[d] * diff[d]) / R.var[d] - 1.0f) : 0.0f;
-      if (shared && d < D) gl += -cfg.ent_loss_theta * inv_b / (float)D;
+      if (ent_grad && d < D) gl += -cfg.ent_loss_theta * inv_b / (float)D;
       gls[d] += gl;
       gba[d] += dmu[d];
     }
@@ -226,14 +235,31 @@ void launch_gauss_act(const HeadLayout& L, const float* params, const float* h_a
                      mu_out, value, action_out, logp_out);
 }
 
+template <bool OPT, class... X>
+static void launch_gauss_loss_with(const HeadLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
+                                   const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
+                                   const float* rets, float inv_b, float* dh_actor, float* dh_critic, float* dmu, float* dvalue,
+                                   float* hpart, float* grads, hipStream_t st, X... x) {
+  const int64_t hs = gauss_hpart_stride(L.n);
+  hipLaunchKernelGGL((gauss_loss_kernel<OPT, X...>), dim3(HEAD_WG), dim3(256), 0, st, h_actor, h_critic, params, L, cfg, n, actions,
+                     old_logps, advs, rets, inv_b, dh_actor, dh_critic, dmu, dvalue, hpart, hs, x...);
+  launch_head_reduce(hpart, hs, HEAD_WG, PpoHeadsReduce{L, L.n, inv_b, cfg.smooth_l1_loss, grads}, st);
+}
+
 void launch_gauss_loss(const HeadLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
                        const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
                        const float* rets, float inv_b, float* dh_actor, float* dh_critic, float* dmu, float* dvalue,
                        float* hpart, float* grads, hipStream_t st) {
-  const int64_t hs = gauss_hpart_stride(L.n);
-  hipLaunchKernelGGL(gauss_loss_kernel, dim3(HEAD_WG), dim3(256), 0, st, h_actor, h_critic, params, L, cfg, n, actions,
-                     old_logps, advs, rets, inv_b, dh_actor, dh_critic, dmu, dvalue, hpart, hs);
-  launch_head_reduce(hpart, hs, HEAD_WG, PpoHeadsReduce{L, L.n, inv_b, cfg.smooth_l1_loss, grads}, st);
+  launch_gauss_loss_with<false>(L, cfg, params, h_actor, h_critic, n, actions, old_logps, advs, rets, inv_b, dh_actor, dh_critic, dmu,
+                                dvalue, hpart, grads, st);
+}
+
+void launch_gauss_loss_opt(const HeadLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
+                           const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
+                           const float* rets, const LossOptions& opt, const float* old_values, float inv_b, float* dh_actor,
+                           float* dh_critic, float* dmu, float* dvalue, float* hpart, float* grads, hipStream_t st) {
+  launch_gauss_loss_with<true>(L, cfg, params, h_actor, h_critic, n, actions, old_logps, advs, rets, inv_b, dh_actor, dh_critic, dmu,
+                               dvalue, hpart, grads, st, opt, opt.value_clip > 0.0f ? old_values : rets);
 }
 
 }  // namespace ddrl

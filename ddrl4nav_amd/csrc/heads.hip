@@ -205,13 +205,16 @@ constexpr int LOSS_WAVES = 4;      // waves per workgroup of heads_loss: one per
 constexpr int LOSS_WAVES6 = 8;     // A <= 6 (Pong): the weight rows live in LDS, 245 registers -> two waves per SIMD (round 6)
 constexpr int LOSS_NS = 4;         // samples per wave and turn (a power of two): the scalar chain of the loss block runs once per NS samples
 // GREG: the actor head's weight / bias gradient is accumulated in registers (else: head_wgrad_kernel, A > 8)
-template <int MAXA, bool WLDS, bool GREG = !WLDS, int WAVES = LOSS_WAVES>
+// OPT: the update options (common.h LossOptions).  X = (LossOptions, const float* old_values) for the OPT instantiations,
+// empty otherwise: the plain instantiations keep their argument list and their code.
+template <int MAXA, bool WLDS, bool GREG = !WLDS, int WAVES = LOSS_WAVES, bool OPT = false, class... X>
 __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
     const float* __restrict__ h, int64_t h_es, const float* __restrict__ params, ParamLayout L, ddrl_config cfg, int n,
     const float* __restrict__ actions, const float* __restrict__ old_logps, const float* __restrict__ advs,
     const float* __restrict__ rets, float inv_b, float* __restrict__ dh, int64_t dh_es, float* __restrict__ dlogits,
     float* __restrict__ dvalue, float* __restrict__ hpart, int64_t hstride, float* __restrict__ gsc, int64_t gsc_es,
-    float* __restrict__ amax) {
+    float* __restrict__ amax, X... x) {
+  static_assert(sizeof...(X) == (OPT ? 2 : 0), "the options and old_values come with OPT only");
   __shared__ float red[(MAXA + 1) * FEAT + 2 * MAXA + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gw = blockIdx.x * WAVES + wave;
@@ -265,6 +268,10 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
   // v_loss.backward() only -- no theta_v, no entropy gradient.
   const bool shared = (L.NE == 1);
   const int ec = L.NE - 1;
+  const LossOptions opt = loss_options(x...);
+  const float* __restrict__ old_values = loss_old_values(x...);  // OPT: never null (the launcher passes rets where the clip is off)
+  bool ent_grad = shared;  // the entropy term is differentiated
+  if constexpr (OPT) ent_grad = shared || opt.entropy_split != 0;
   // A wave takes NS samples per turn (round 6; one per turn before: 1,046 vector instructions per sample, most of them the softmax /
   // log / divide chain that all 64 lanes executed on the same wave-uniform numbers).  Phases of a turn:
   //   A  the NS x (A + 1) dot products: 8 features per lane, then wave reductions (TR below: all of them together);
@@ -301,6 +308,8 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
     const int bl = min(b0 + ls, n - 1);
     const bool live = b0 + ls < n && owner;           // this lane's phase-B results count (the other lanes repeat them or work on junk)
     const float s_act = actions[bl], s_adv = advs[bl], s_olp = old_logps[bl], s_ret = rets[bl];
+    float s_vold = 0.0f;
+    if constexpr (OPT) s_vold = old_values[bl];
     // ---- phase A (a lane keeps only the results of ITS sample of phase B: no [NS][A + 1] array of logits in registers)
     float zl[MAXA], v = 0.0f;
 #pragma unroll
@@ -370,7 +379,9 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
     const SurrogateTerm sg = ppo_surrogate(logp, s_olp, adv, cfg, inv_b);
     const float err = s_ret - v;
     double v_el = 0.0;
-    const float gv_unit = value_loss_element(err, cfg, v_el);  // d(v_loss element)/d(v) before the 1/B
+    float gv_unit;  // d(v_loss element)/d(v) before the 1/B
+    if constexpr (OPT) gv_unit = opt.value_clip > 0.0f ? value_loss_element_clipped(s_ret, v, s_vold, opt.value_clip, cfg, v_el) : value_loss_element(err, cfg, v_el);
+    else gv_unit = value_loss_element(err, cfg, v_el);
     float ent = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXA; ++j)
@@ -390,7 +401,7 @@ __global__ __launch_bounds__(WAVES * 64) void heads_loss_kernel(
     float gp[MAXA], dot = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXA; ++j) gp[j] = ((j == a) ? g_qa / d.ps : 0.0f) + g_ps;
-    if (shared) {
+    if (ent_grad) {
       // -theta_e * mean(H), H = -sum_j q_j * log(clamp(q_j)): dH/dq_j = -(lc_j + q_j * [in range] / clamp(q_j))
       const float g_h = -cfg.ent_loss_theta * inv_b;
       float gq[MAXA], gps_e = 0.0f;
@@ -603,21 +614,35 @@ void launch_heads_act(const HeadsCall& c, const float* act_in, uint64_t seed, ui
                      c.n, act_in, seed, stream_id, probs, value, action_out, logp_out);
 }
 
-void launch_heads_loss(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs,
-                       const float* rets, float inv_b, float* grads, hipStream_t st) {
+// x: nothing, or (LossOptions, old_values) for the OPT instantiations
+template <bool OPT, class... X>
+static void launch_heads_loss_with(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs,
+                                   const float* rets, float inv_b, float* grads, hipStream_t st, X... x) {
   const ParamLayout& L = *c.L;
   const int64_t hs = hpart_stride(L.A);
   const bool large = L.A > MAXA_SMALL;
   // A <= 6 (Pong's six actions): the four samples' 7 x 4 dot products are reduced together (TR in the kernel), weight rows in LDS, eight waves
   const bool six = L.A <= 6;
-  auto kern = large ? heads_loss_kernel<MAXA_LARGE, true> : (six ? heads_loss_kernel<6, LOSS_WAVES6 == 8, true, LOSS_WAVES6> : heads_loss_kernel<MAXA_SMALL, false>);
+  auto kern = large ? heads_loss_kernel<MAXA_LARGE, true, false, LOSS_WAVES, OPT, X...>
+                    : (six ? heads_loss_kernel<6, LOSS_WAVES6 == 8, true, LOSS_WAVES6, OPT, X...> : heads_loss_kernel<MAXA_SMALL, false, true, LOSS_WAVES, OPT, X...>);
   hipLaunchKernelGGL(kern, dim3(HEAD_WG), dim3((six ? LOSS_WAVES6 : LOSS_WAVES) * 64), 0, st, c.h, c.h_es, c.params, L, *c.cfg, c.n,
-                     actions, old_logps, advs, rets, inv_b, c.dh, c.dh_es, c.dlogits, c.dvalue, c.hpart, hs, c.gsc, c.gsc_es, c.amax);
+                     actions, old_logps, advs, rets, inv_b, c.dh, c.dh_es, c.dlogits, c.dvalue, c.hpart, hs, c.gsc, c.gsc_es, c.amax, x...);
   if (large)
     hipLaunchKernelGGL(head_wgrad_kernel<MAXA_LARGE>, dim3(HEAD_WG), dim3(256), 0, st, c.h, (int64_t)FEAT, (const float*)c.dlogits, c.n,
                        L.A, c.hpart, hs, (L.A + 1) * FEAT);
   const HeadLayout hl{L.A, L.NE == 1, L.actor_w, L.actor_b, 0, L.critic_w, L.critic_b, L.n_params};
   launch_head_reduce(c.hpart, hs, HEAD_WG, PpoHeadsReduce{hl, 0, inv_b, c.cfg->smooth_l1_loss, grads}, st);
+}
+
+void launch_heads_loss(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs,
+                       const float* rets, float inv_b, float* grads, hipStream_t st) {
+  launch_heads_loss_with<false>(c, actions, old_logps, advs, rets, inv_b, grads, st);
+}
+
+void launch_heads_loss_opt(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs, const float* rets,
+                           const LossOptions& opt, const float* old_values, float inv_b, float* grads, hipStream_t st) {
+  // the kernel loads its fifth column without a branch: where the clip is off (old_values may be null) it reads the returns again
+  launch_heads_loss_with<true>(c, actions, old_logps, advs, rets, inv_b, grads, st, opt, opt.value_clip > 0.0f ? old_values : rets);
 }
 
 void launch_categorical_stats(const float* probs, int n, int A, float* p_hat, float* logits, float* entropy,

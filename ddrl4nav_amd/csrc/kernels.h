@@ -114,6 +114,9 @@ void launch_heads_act(const HeadsCall& c, const float* act_in, uint64_t seed, ui
 void launch_heads_loss(const HeadsCall& c, const float* actions, const float* old_logps,
                        const float* advs, const float* rets, float inv_bglobal, float* grads,
                        hipStream_t st);
+// the same with the update options (common.h LossOptions): old_values [n] is read when opt.value_clip > 0 only
+void launch_heads_loss_opt(const HeadsCall& c, const float* actions, const float* old_logps, const float* advs, const float* rets,
+                           const LossOptions& opt, const float* old_values, float inv_bglobal, float* grads, hipStream_t st);
 void launch_categorical_sample(const float* probs, int n, int A, uint64_t seed, uint64_t stream_id, float* action,
                                float* logp, hipStream_t st);
 void launch_categorical_stats(const float* probs, int n, int A, float* p_hat, float* logits,

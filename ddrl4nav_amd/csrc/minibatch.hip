@@ -73,6 +73,16 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_minibatch_kernel(const 
   if (c == 0) gather_columns(cols, r, ok, i, adv_affine);
 }
 
+// ---- one more float column (old_values: the four-column gathers' signatures are fixed) -------------------------------------------------
+// dst[j] = src[idx[j]], or src[first + j] without an index; a sample outside [0, n_rows) reads nothing and gives zero
+__global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict__ src, int64_t n_rows, const int32_t* __restrict__ idx,
+                                                         int64_t first, int n, float* __restrict__ dst) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int64_t r = idx ? (int64_t)idx[j] : first + j;
+  dst[j] = (r >= 0 && r < n_rows) ? src[r] : 0.0f;
+}
+
 }  // namespace ddrl
 
 using namespace ddrl;
@@ -138,6 +148,17 @@ int32_t ddrl_op_gather_minibatch(const uint8_t* frames, int64_t n_rows, int64_t 
   if (!gather_grid(row_bytes, n, &row_vecs, &chunks)) return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(gather_minibatch_kernel, dim3((unsigned)(n * chunks)), dim3(GATHER_THREADS), 0, (hipStream_t)stream,
                      (const uint4*)frames, n_rows, row_vecs, chunks, idx, (uint4*)frames_dst, cols, adv_affine);
+  return launch_status();
+}
+
+int32_t ddrl_op_gather_f32(const float* src, int64_t n_rows, const int32_t* idx, int64_t first, int32_t n, float* dst, void* stream) {
+  if (!src || !dst || n < 1 || n_rows < 1 || n_rows > INT64_MAX / 4) return DDRL_ERR_INVALID_ARG;
+  if (((uintptr_t)src & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)idx & 3)) return DDRL_ERR_INVALID_ARG;
+  if (!idx && (first < INT64_MIN / 2 || first > INT64_MAX / 2)) return DDRL_ERR_INVALID_ARG;  // first + j cannot overflow
+  const uint64_t sb = (uint64_t)n_rows * 4, db = (uint64_t)n * 4;
+  if (overlap(src, dst, sb, db) || (idx && overlap(idx, dst, db, db))) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, n_rows, idx, first, n,
+                     dst);
   return launch_status();
 }
 

@@ -149,5 +149,9 @@ void launch_gauss_loss(const HeadLayout& L, const ddrl_config& cfg, const float*
                        const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
                        const float* rets, float inv_b, float* dh_actor, float* dh_critic, float* dmu, float* dvalue,
                        float* hpart, float* grads, hipStream_t st);
+void launch_gauss_loss_opt(const HeadLayout& L, const ddrl_config& cfg, const float* params, const float* h_actor,
+                           const float* h_critic, int n, const float* actions, const float* old_logps, const float* advs,
+                           const float* rets, const LossOptions& opt, const float* old_values, float inv_b, float* dh_actor,
+                           float* dh_critic, float* dmu, float* dvalue, float* hpart, float* grads, hipStream_t st);
 
 }  // namespace ddrl

@@ -159,4 +159,27 @@ __device__ __forceinline__ float value_loss_element(float err, const ddrl_config
   return -err;
 }
 
+// ---- update options of the loss block (include/ddrl.h ddrl_loss_options) -----------------------------------------
+// Only the OPT instantiations of the loss kernels take them, as two trailing kernel arguments (common.h LossOptions by value, then
+// old_values); the plain instantiations' argument list, and with it their code, is the one without.
+__device__ __forceinline__ LossOptions loss_options() { return LossOptions{0.0f, 0}; }
+__device__ __forceinline__ LossOptions loss_options(LossOptions o, const float*) { return o; }
+__device__ __forceinline__ const float* loss_old_values() { return nullptr; }
+__device__ __forceinline__ const float* loss_old_values(LossOptions, const float* p) { return p; }
+
+// The clipped value-loss element of one sample: as value_loss_element, for max(L_u, L_c) with L_u = e(ret - v), L_c = e(ret - v_c).
+// torch.max splits the gradient evenly on a tie, torch.clamp passes it on the closed interval (the conventions at the head of this
+// file); a NaN in either element stays visible.
+__device__ __forceinline__ float value_loss_element_clipped(float ret, float v, float v_old, float c, const ddrl_config& cfg, double& sum) {
+  const float d = v - v_old;
+  const float d_c = fminf(fmaxf(d, -c), c);
+  const float v_c = v_old + d_c;
+  double l_u = 0.0, l_c = 0.0;
+  const float g_u = value_loss_element(ret - v, cfg, l_u);
+  float g_c = value_loss_element(ret - v_c, cfg, l_c);
+  if (!(d >= -c && d <= c)) g_c = 0.0f;
+  sum += (l_u < l_c || l_c != l_c) ? l_c : l_u;
+  return (l_u > l_c) ? g_u : ((l_u < l_c) ? g_c : 0.5f * (g_u + g_c));
+}
+
 }  // namespace ddrl

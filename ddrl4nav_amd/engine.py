@@ -44,6 +44,8 @@ class HotPath:
         self.process_group = process_group
         self.n_actions = int(n_actions)
         self.max_batch = int(max_batch)
+        # (value_clip, entropy_split) of the loss block (include/ddrl.h ddrl_loss_options); the default runs ddrl_ppo_iter / _indexed
+        self.loss_options = ops.NO_LOSS_OPTIONS
         self._ar_events = None  # (start, stop) event pairs around the gradient all-reduce while time_allreduce(True)
         self.comm = None        # dist.RcclComm: the C-ABI all-reduce (ddrl_grad_allreduce) instead of torch.distributed
         import os
@@ -177,15 +179,36 @@ class HotPath:
         return adv, ret
 
     # ---- learner ----------------------------------------------------------------------------
-    def ppo_iter(self, frames, actions, old_logps, advs, rets, b_global=None):
+    def _ppo_iter_opt(self, frames_or_planes, n_planes, tab, actions, old_logps, advs, rets, old_values, B, b_global):
+        """ddrl_ppo_iter_opt: either frame source, with self.loss_options (old_values [B] fp32: needed when the clip is on)."""
+        clip, split = self.loss_options
+        if clip:
+            if old_values is None:
+                raise ValueError("loss_options has a value clip: ppo_iter needs old_values")
+            assert old_values.dtype == torch.float32 and old_values.is_cuda and old_values.is_contiguous() and old_values.numel() == B
+        batch = _lib.PpoBatch(_p(frames_or_planes), int(n_planes), _p(tab), _p(actions), _p(old_logps), _p(advs), _p(rets),
+                              _p(old_values if clip else None))
+        opt = ops.loss_options(clip, split)
+        check(self.lib.ddrl_ppo_iter_opt(self.ctx, byref(batch), byref(opt), B, int(b_global if b_global is not None else B), _st()))
+
+    def set_rates(self, actor_lr, critic_lr, learning_rate, ppo_clip):
+        """Overwrite the two Adam groups' learning rates, the shared mode's and PPO_CLIP in the context (include/ddrl.h ddrl_set_rates):
+        the next ppo_iter / ppo_diag / clip_adam_step read them.  Host only."""
+        check(self.lib.ddrl_set_rates(self.ctx, float(actor_lr), float(critic_lr), float(learning_rate), float(ppo_clip)))
+        self.cfg.actor_lr, self.cfg.critic_lr = float(actor_lr), float(critic_lr)
+        self.cfg.learning_rate, self.cfg.ppo_clip = float(learning_rate), float(ppo_clip)
+
+    def ppo_iter(self, frames, actions, old_logps, advs, rets, b_global=None, old_values=None):
         B = frames.shape[0]
         for t in (actions, old_logps, advs, rets):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
         assert frames.dtype == torch.uint8 and frames.is_contiguous()
+        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
+            return self._ppo_iter_opt(frames, 0, None, actions, old_logps, advs, rets, old_values, B, b_global)
         check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames), _p(actions), _p(old_logps), _p(advs), _p(rets),
                                      B, int(b_global if b_global is not None else B), _st()))
 
-    def ppo_iter_indexed(self, planes, tab, actions, old_logps, advs, rets, b_global=None):
+    def ppo_iter_indexed(self, planes, tab, actions, old_logps, advs, rets, b_global=None, old_values=None):
         """ppo_iter on frames read where they lie (include/ddrl.h ddrl_ppo_iter_indexed): `planes` is any contiguous uint8 device tensor
         of whole 84 x 84 planes (a single-frame pool, or stacked frames) and tab int32 [>= B, 4] (ops.frame_table_planes /
         frame_table_stacks) names the plane of every channel of the B = actions.numel() samples.  Bit-identical to ppo_iter on the
@@ -195,6 +218,8 @@ class HotPath:
             assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
         assert planes.dtype == torch.uint8 and planes.is_cuda and planes.is_contiguous() and planes.numel() % (84 * 84) == 0
         assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * B
+        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
+            return self._ppo_iter_opt(planes, planes.numel() // (84 * 84), tab, actions, old_logps, advs, rets, old_values, B, b_global)
         check(self.lib.ddrl_ppo_iter_indexed(self.ctx, _p(planes), planes.numel() // (84 * 84), _p(tab), _p(actions), _p(old_logps),
                                              _p(advs), _p(rets), B, int(b_global if b_global is not None else B), _st()))
 

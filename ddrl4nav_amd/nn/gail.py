@@ -22,7 +22,7 @@ from ctypes import byref, c_int64
 import numpy as np
 import torch
 
-from ddrl4nav_amd import _lib
+from ddrl4nav_amd import _lib, ops
 from ddrl4nav_amd._lib import STATS_FLOATS, check
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.nn.base import Basenn
@@ -261,6 +261,11 @@ class GAIL(Basenn):
         refuse_frames_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
         from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
         refuse_act_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
+        from ddrl4nav_amd.nn.minibatch import refuse_loss_options
+        refuse_loss_options(discriminator.config_nn, "NETWORK_TYPE='gail'")
+        if tuple(getattr(generator, "loss_options", ops.NO_LOSS_OPTIONS)) != ops.NO_LOSS_OPTIONS:
+            raise ValueError("the generator was built with VALUE_CLIP / ENTROPY_BONUS_SPLIT, which GAIL does not support (its value loss "
+                             "sums two critics)")
         if getattr(generator, "diagnostics", False):
             raise NotImplementedError("the generator was built with PPO_DIAGNOSTICS / TARGET_KL, which GAIL does not support")
         self.device = discriminator.device

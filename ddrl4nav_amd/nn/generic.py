@@ -492,6 +492,13 @@ class GenericPPO(Basenn):
         refuse_frames_in_place(config_nn, "the operator-composed GenericPPO")
         from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
         refuse_act_in_place(config_nn, "the operator-composed GenericPPO")
+        # config_nn.VALUE_CLIP / ENTROPY_BONUS_SPLIT / LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL (optional; nn/minibatch.py)
+        from ddrl4nav_amd.nn import minibatch
+        self.loss_options = minibatch.loss_options(config_nn)
+        self.lr_anneal = minibatch.anneal_options(config_nn)
+        self.anneal_step = 0       # optimiser steps this net has applied: the schedule's u
+        self._base_rates = (float(config_nn.ACTOR_LEARNING_RATE), float(config_nn.CRITIC_LEARNING_RATE), float(config_nn.LEARNING_RATE),
+                            float(config_nn.PPO_CLIP))
         if rnd is not None:
             raise NotImplementedError("RND is disabled in the reference defaults (USE_RND=False) and out of scope")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -738,7 +745,12 @@ class GenericPPO(Basenn):
         return states / 255
 
     # ---- learn (ppo.py:77-146) -----------------------------------------------------------------------
-    def _iter_chunk(self, st, n, actions, old_logps, advs, rets, b_global, extra_rets=(), diag_first=None):
+    @property
+    def wants_old_values(self):
+        """True when learn() needs data.values row 1, the collecting policy's values (VALUE_CLIP): StateRollout.batch() then emits it."""
+        return self.loss_options[0] > 0.0
+
+    def _iter_chunk(self, st, n, actions, old_logps, advs, rets, b_global, extra_rets=(), diag_first=None, old_values=None):
         """forward + loss + backward of one micro-batch; gradients land in self.gtmp (overwritten).  diag_first (None: off): the
         diagnostics sums of the micro-batch are written to (True) or added to (False) self._diag_sums."""
         ha, hc = self._features(st, n)
@@ -747,9 +759,13 @@ class GenericPPO(Basenn):
                            accumulate=not diag_first, ws=self._diag_ws)
         dha = self._dh[0]
         dhc = dha if self.share_cnn_net else self._dh[1]
-        check(self.lib.ddrl_op_heads_loss(byref(self._hd), byref(self._cfg), _p(self.params), _p(ha), _p(hc), n, _p(actions),
-                                          _p(old_logps), _p(advs), _p(rets), b_global, _p(dha), _p(dhc), _p(self.gtmp),
-                                          _p(self._heads_ws), _st()))
+        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
+            ops.heads_loss_opt(self._hd, self._cfg, self.params, ha, hc, n, actions, old_logps, advs, rets, self.loss_options, old_values,
+                               b_global, dha, dhc, self.gtmp, self._heads_ws)
+        else:
+            check(self.lib.ddrl_op_heads_loss(byref(self._hd), byref(self._cfg), _p(self.params), _p(ha), _p(hc), n, _p(actions),
+                                              _p(old_logps), _p(advs), _p(rets), b_global, _p(dha), _p(dhc), _p(self.gtmp),
+                                              _p(self._heads_ws), _st()))
         # v_loss = ppov_loss + rndv_loss + gailv_loss (ppo.py:95-107): each extra head adds its loss share to the VLoss
         # slot of the statistics tail and its d(loss)/d(h) to the shared encoder's gradient
         for (crit, ws), xr in zip(self._extra, extra_rets):
@@ -771,6 +787,14 @@ class GenericPPO(Basenn):
         # ppo.py:97-104: the GAIL critic's targets are the LAST row of data.values (with RND unbuilt there is one extra head)
         assert len(self._extra) <= 1 and (not self._extra or vals.shape[0] >= 2), "data.values needs one row per critic"
         extra_rets = [vals[-1].contiguous()] if self._extra else []
+        old_values = None
+        if self.wants_old_values:
+            if self._extra:
+                raise ValueError("VALUE_CLIP is not built for a net with an extra critic (GAIL): its value loss sums two critics")
+            if vals.dim() != 2 or vals.shape[0] < 2:
+                raise ValueError("VALUE_CLIP needs the collecting policy's values as row 1 of data.values (row 0: the returns); this "
+                                 "batch has %d row(s)" % (vals.shape[0] if vals.dim() == 2 else 1))
+            old_values = vals[1].contiguous()
         import torch.distributed as dist
         from ddrl4nav_amd.dist import global_batch
         world = dist.get_world_size(self._process_group) if dist.is_available() and dist.is_initialized() else 1
@@ -785,10 +809,15 @@ class GenericPPO(Basenn):
         for _ in range(self.training_iter_time):
             t0 = time.time()
             self._ensure_packed()
+            if self.lr_anneal is not None:   # the rates of optimiser step number anneal_step, on this net's own configuration
+                from ddrl4nav_amd.nn.minibatch import annealed_rates
+                c = self._cfg
+                c.actor_lr, c.critic_lr, c.learning_rate, c.ppo_clip = annealed_rates(self._base_rates, self.anneal_step, *self.lr_anneal)
             for ci, lo in enumerate(range(0, B, self.cap)):
                 hi = min(B, lo + self.cap)
                 self._iter_chunk([s[lo:hi] for s in dstates], hi - lo, actions[lo:hi], old_logps[lo:hi], advs[lo:hi],
-                                 rets[lo:hi], b_global, [x[lo:hi] for x in extra_rets], diag_first=(ci == 0) if self.diagnostics else None)
+                                 rets[lo:hi], b_global, [x[lo:hi] for x in extra_rets], diag_first=(ci == 0) if self.diagnostics else None,
+                                 old_values=None if old_values is None else old_values[lo:hi])
                 if ci == 0:
                     self.grads.copy_(self.gtmp)
                 else:
@@ -804,6 +833,7 @@ class GenericPPO(Basenn):
                 from ddrl4nav_amd.dist import allreduce_flat
                 allreduce_flat(self.grads, self._process_group)
             self._step += 1
+            self.anneal_step += 1   # a step the KL stop skipped does not count
             check(self.lib.ddrl_op_clip_adam(byref(self._cfg), _p(self.params), _p(self.grads), _p(self.adam_m),
                                              _p(self.adam_v), self.n_params, self.n_actor, 1 if self.share_cnn_net else 0,
                                              self._step, _p(self._adam_ws), _st()))

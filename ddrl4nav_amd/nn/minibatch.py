@@ -18,6 +18,15 @@ The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the Config
                                for the age row and the slot's frame table, then ddrl_forward_indexed) instead of gathering it into a
                                scratch first.  Same bits.  Its own knob: FRAMES_IN_PLACE alone changes nothing about acting
 
+  VALUE_CLIP           None    c > 0: the value loss is clipped around the collecting policy's value, max(e(ret - v), e(ret - v_c)) with
+                               v_c = v_old + clamp(v - v_old, -c, c) (the loss kernels' option form, ddrl_ppo_iter_opt); data.values
+                               then carries v_old as its row 1
+  ENTROPY_BONUS_SPLIT  False   True: with two encoders the actor side differentiates actor_loss - ENTROPY_LOSS_THETA * entropy (the
+                               reference differentiates actor_loss alone there, so its entropy coefficient only shows in the logged total)
+  LR_ANNEAL_UPDATES    None    N >= 1: before optimiser step u (0-based, steps this net has applied) the three learning rates are
+  LR_ANNEAL_FLOOR      0.0     multiplied by max(LR_ANNEAL_FLOOR, 1 - u / N) (ddrl_set_rates);
+  CLIP_ANNEAL          False   True: PPO_CLIP as well
+
 PPO.learn runs one loop (nn/update_loop.py run()) over one of two step sources: with all four knobs at their defaults its own single
 full-batch step, otherwise steps() below.  Per step, everything on the device and in stream order: shuffle on, one gather of frames
 and columns into ONE staging buffer (or, in place, one frame table); off, contiguous views of the columns and of stacked frames
@@ -80,6 +89,69 @@ def refuse_act_in_place(config_nn, who):
                          % who)
 
 
+def value_clip_option(config_nn):
+    """config_nn.VALUE_CLIP (optional): a finite float > 0, or None (None / False = off); ValueError for anything else."""
+    v = getattr(config_nn, "VALUE_CLIP", None)
+    if v is None or v is False:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < float("inf"):
+        raise ValueError("VALUE_CLIP must be a finite number > 0, or None / False for off, got %r" % (v,))
+    return float(v)
+
+
+def entropy_split_option(config_nn):
+    """config_nn.ENTROPY_BONUS_SPLIT (optional, default False) as a bool; ValueError for anything but True / False."""
+    v = getattr(config_nn, "ENTROPY_BONUS_SPLIT", False)
+    if not isinstance(v, bool):
+        raise ValueError("ENTROPY_BONUS_SPLIT must be True or False, got %r" % (v,))
+    return v
+
+
+def loss_options(config_nn):
+    """(value_clip or 0.0, entropy_split): HotPath.loss_options / ops.heads_loss_opt's `options`; ops.NO_LOSS_OPTIONS when both are off."""
+    return (value_clip_option(config_nn) or 0.0, entropy_split_option(config_nn))
+
+
+def anneal_options(config_nn):
+    """(N, floor, clip too) from config_nn.LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL, or None when LR_ANNEAL_UPDATES is None;
+    ValueError for N < 1 or not an integer, a floor outside [0, 1], a CLIP_ANNEAL that is no bool, and for a floor or a clip switch set
+    without LR_ANNEAL_UPDATES."""
+    n = getattr(config_nn, "LR_ANNEAL_UPDATES", None)
+    floor = getattr(config_nn, "LR_ANNEAL_FLOOR", 0.0)
+    clip = getattr(config_nn, "CLIP_ANNEAL", False)
+    if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0.0 <= float(floor) <= 1.0:
+        raise ValueError("LR_ANNEAL_FLOOR must be a number in [0, 1], got %r" % (floor,))
+    if not isinstance(clip, bool):
+        raise ValueError("CLIP_ANNEAL must be True or False, got %r" % (clip,))
+    if n is None:
+        if clip or float(floor) != 0.0:
+            raise ValueError("CLIP_ANNEAL / LR_ANNEAL_FLOOR need LR_ANNEAL_UPDATES, the length of the schedule")
+        return None
+    if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or int(n) < 1:
+        raise ValueError("LR_ANNEAL_UPDATES must be an integer >= 1 or None, got %r" % (n,))
+    return int(n), float(floor), clip
+
+
+def anneal_factor(u, n, floor=0.0):
+    """max(floor, 1 - u / n) in double: the factor in front of optimiser step number u (0-based) of a schedule of n steps."""
+    return max(float(floor), 1.0 - float(u) / float(n))
+
+
+def annealed_rates(base, u, n, floor=0.0, clip_too=False):
+    """(actor_lr, critic_lr, learning_rate, ppo_clip) of step u from the base four: each product formed in double (Python floats)
+    and rounded once to fp32 where HotPath.set_rates hands it over; ppo_clip only with clip_too."""
+    s = anneal_factor(u, n, floor)
+    a, c, l, p = (float(x) for x in base)
+    return a * s, c * s, l * s, (p * s if clip_too else p)
+
+
+def refuse_loss_options(config_nn, who):
+    """The GAIL generator's value loss sums two critics (ppo.py:95-107): neither a clip around ONE old value nor the split backward is
+    defined for it."""
+    if loss_options(config_nn) != ops.NO_LOSS_OPTIONS:
+        raise ValueError("VALUE_CLIP / ENTROPY_BONUS_SPLIT are not built for %s (its value loss sums two critics): unset them" % who)
+
+
 def refuse_minibatch_options(config_nn, who):
     """GenericPPO and GAIL keep their states as float lists per encoder input: the frame-row collation does not serve them."""
     if minibatch_options(config_nn) != DEFAULTS:
@@ -135,6 +207,7 @@ class Staging:
         self.frames = None if in_place else torch.empty((self.cap,) + self.frame_shape, dtype=torch.uint8, device=device)
         self.tab = torch.empty((self.cap, 4), dtype=torch.int32, device=device) if in_place else None
         self.cols = torch.empty((4, self.cap), **f32)
+        self.old_values = None   # [cap], allocated by steps() when the net clips its value loss and shuffles
         self.adv = torch.empty(self.B, **f32)
         self.sums = torch.zeros(3, dtype=torch.float64, device=device)
         self.affine = torch.zeros(2, **f32)
@@ -154,9 +227,10 @@ def advantage_affine(column, n, st, eps, group):
     return ops.moments_affine(st.sums, eps, st.affine)
 
 
-def steps(net, frames, columns):
+def steps(net, frames, columns, old_values=None):
     """PPO.learn's step source when a knob is set: TRAINING_ITER_TIME epochs of the K minibatches of split(), one Step each.  `frames`:
-    uint8 [B, C, 84, 84] or data.FramePlanes; `columns`: actions, old_logps, advs, rets, fp32 [B] on the device."""
+    uint8 [B, C, 84, 84] or data.FramePlanes; `columns`: actions, old_logps, advs, rets, fp32 [B] on the device; old_values: the fifth
+    column of a net with VALUE_CLIP (a view in order, ops.gather_f32 when shuffled), else None."""
     from ddrl4nav_amd.dist import global_batch
     from ddrl4nav_amd.nn.update_loop import Step, frame_source
     K, shuffle, mode, eps = net.minibatch
@@ -169,6 +243,8 @@ def steps(net, frames, columns):
     st = net._mb_stage
     if st is None or not st.fits(frames.shape[1:], cap, B, in_place):
         st = net._mb_stage = Staging(net.device, frames.shape[1:], cap, B, in_place)
+    if old_values is not None and shuffle and st.old_values is None:
+        st.old_values = torch.empty(st.cap, dtype=torch.float32, device=net.device)
     src = frame_source(net._hp, frames, in_place, st.frames, st.tab)
     call = net.learn_calls
     net.learn_calls += 1
@@ -186,15 +262,20 @@ def steps(net, frames, columns):
         order = epoch_order(net._seed + rank, call, epoch, B).to(net.device) if shuffle else None   # one int32 upload per epoch
         for j, (lo, hi) in enumerate(ranges):
             n = hi - lo
+            vo = None
             if shuffle:
                 a, o, ad, r = dst = [st.cols[k, :n] for k in range(4)]
                 launch = src.gathered(order[lo:hi], n, (actions, old_logps, advs, rets), dst, affine)
+                if old_values is not None:
+                    vo = ops.gather_f32(old_values, st.old_values, idx=order[lo:hi], n=n)
             else:
                 launch = src.contiguous(lo, hi)
                 a, o, ad, r = actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi]
+                if old_values is not None:
+                    vo = old_values[lo:hi]
             if mode == "minibatch":
                 advantage_affine(ad, n, st, eps, group)
                 ad = ops.normalize(ad, st.affine, out=ad if shuffle else st.adv, n=n)[:n]   # in place on the staged column
             if j not in b_globals:             # the ranks' j-th sizes: one collective per j, in the first epoch
                 b_globals[j] = global_batch(n, group)
-            yield Step(launch, a, o, ad, r, b_globals[j])
+            yield Step(launch, a, o, ad, r, b_globals[j], vo)

@@ -47,6 +47,13 @@ class PPO(Basenn):
         self.frames_in_place = minibatch.frames_in_place_option(config_nn)
         # config_nn.ACT_IN_PLACE (optional, nn/minibatch.py): a PlaneRollout over this net acts on its pool in place (agent/plane_rollout.py)
         self.act_in_place = minibatch.act_in_place_option(config_nn)
+        # config_nn.VALUE_CLIP / ENTROPY_BONUS_SPLIT (optional, nn/minibatch.py): the loss block's option form (ddrl_ppo_iter_opt);
+        # LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL: linear schedules of the learning rates and PPO_CLIP (ddrl_set_rates)
+        self.loss_options = minibatch.loss_options(config_nn)
+        self.lr_anneal = minibatch.anneal_options(config_nn)
+        self.anneal_step = 0       # optimiser steps this net has applied: the schedule's u
+        self._base_rates = (float(config_nn.ACTOR_LEARNING_RATE), float(config_nn.CRITIC_LEARNING_RATE), float(config_nn.LEARNING_RATE),
+                            float(config_nn.PPO_CLIP))
         self._frame_tab = None      # FramePlanes states, full-batch step, in place: int32 [B, 4]
         self._mb_stage = None
         self._plane_batch = None   # FramePlanes states, full-batch step, staged: the batch materialised once per learn call
@@ -167,7 +174,12 @@ class PPO(Basenn):
         return states / 255
 
     # ---- PPO.learn (ppo.py:77-146) -----------------------------------------------------------------
-    def _full_batch_steps(self, frames, columns):
+    @property
+    def wants_old_values(self):
+        """True when learn() needs data.values row 1, the collecting policy's values (VALUE_CLIP): a rollout's batch() then emits it."""
+        return self.loss_options[0] > 0.0
+
+    def _full_batch_steps(self, frames, columns, old_values=None):
         """The step source with every minibatch knob at its default: ONE step over the whole batch, prepared once per learn call and
         handed out TRAINING_ITER_TIME times.  Stacked frames are read as they are.  FramePlanes are materialised into _plane_batch (for
         the length of learn() the batch holds the stacked size again: the plane pool's saving lasts through the update only with
@@ -182,20 +194,29 @@ class PPO(Basenn):
                 self._plane_batch = torch.empty(frames.shape, dtype=torch.uint8, device=self.device)
         launch = frame_source(self._hp, frames, self.frames_in_place, self._plane_batch, self._frame_tab).contiguous(0, B)
         # data-parallel: every rank scales by 1 / (sum of the ranks' batch sizes) -- shards may be uneven
-        step = Step(launch, *columns, global_batch(B, self._process_group))
+        step = Step(launch, *columns, global_batch(B, self._process_group), old_values)
         for _ in range(self.training_iter_time):
             yield step
 
     def learn(self, data: Experience):
         """One loop (nn/update_loop.py run()) over one of two step sources: the single full-batch step above, or, with a minibatch knob
         set, TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py steps())."""
+        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+        values = f32(data.values)
+        old_values = None
+        if self.wants_old_values:
+            # row 0 stays the return target; row 1 = what the collecting policy predicted (not derivable: ret = fl(v_old + adv) is rounded)
+            if values.dim() != 2 or values.shape[0] < 2:
+                raise ValueError("VALUE_CLIP needs the collecting policy's values as row 1 of data.values (row 0: the returns); this "
+                                 "batch has %d row(s) -- the rollouts emit it for a net with VALUE_CLIP, the Redis learner path cannot "
+                                 "(its workers overwrite their values with the returns)" % (values.shape[0] if values.dim() == 2 else 1))
+            old_values = values[1].contiguous()
         fp = planes_of(data.states)
         frames = fp if fp is not None else _frames_u8(data.states, self.device)
-        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
-        columns = f32(data.actions), f32(data.old_logps), f32(data.advs), f32(data.values)[0].contiguous()
+        columns = f32(data.actions), f32(data.old_logps), f32(data.advs), values[0].contiguous()
         assert columns[3].shape == (len(frames),)
         if self.minibatch != minibatch.DEFAULTS:
-            steps, n_steps = minibatch.steps(self, frames, columns), self.training_iter_time * self.minibatch[0]
+            steps, n_steps = minibatch.steps(self, frames, columns, old_values), self.training_iter_time * self.minibatch[0]
         else:
-            steps, n_steps = self._full_batch_steps(frames, columns), self.training_iter_time
+            steps, n_steps = self._full_batch_steps(frames, columns, old_values), self.training_iter_time
         yield from run(self, steps, n_steps)

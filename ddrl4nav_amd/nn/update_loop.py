@@ -14,9 +14,11 @@ import torch
 
 from ddrl4nav_amd import ops
 from ddrl4nav_amd.data.frame_planes import FramePlanes
+from ddrl4nav_amd.nn import minibatch
 
-# launch(actions, old_logps, advs, rets, b_global=) enqueues the step's ppo_iter on its frames; ppo_diag reads actions, old_logps, rets
-Step = collections.namedtuple("Step", "launch actions old_logps advs rets b_global")
+# launch(actions, old_logps, advs, rets, b_global=, old_values=) enqueues the step's ppo_iter on its frames; ppo_diag reads actions,
+# old_logps, rets.  old_values: the collecting policy's values, the fifth column of a net with VALUE_CLIP (None otherwise)
+Step = collections.namedtuple("Step", "launch actions old_logps advs rets b_global old_values", defaults=(None,))
 
 
 class StackedFrames:
@@ -78,7 +80,12 @@ def run(net, steps, n_steps):
     t_all = t0 = time.time()
     for i, s in enumerate(steps):
         hp = net._hp   # read per step: the step source ensures the capacity, which may rebuild the hot path
-        s.launch(s.actions, s.old_logps, s.advs, s.rets, b_global=s.b_global)
+        hp.loss_options = net.loss_options
+        if net.lr_anneal is not None:
+            # the rates of optimiser step number net.anneal_step (counted at enqueue: the deferred read-back sees the same numbers);
+            # host arithmetic and four words of the context, no synchronisation
+            hp.set_rates(*minibatch.annealed_rates(net._base_rates, net.anneal_step, *net.lr_anneal))
+        s.launch(s.actions, s.old_logps, s.advs, s.rets, b_global=s.b_global, old_values=s.old_values)
         d = None
         if diag and deferred:
             net._diag_rows[i].copy_(hp.ppo_diag(s.actions, s.old_logps, s.rets, out=net._diag_dev[i]), non_blocking=True)
@@ -90,6 +97,7 @@ def run(net, steps, n_steps):
                 return   # ends the whole call; this step is not applied: no all-reduce, no Adam, no yield, update_time as it was
         hp.allreduce_grads()
         hp.clip_adam_step()
+        net.anneal_step += 1   # a step the KL stop skipped does not count
         if deferred:
             hp.stats_async(net._stats_rows[i])
             continue

@@ -249,6 +249,36 @@ def gather_minibatch(frames, idx, frames_dst, columns=None, columns_dst=None, ad
     return frames_dst
 
 
+def gather_f32(src, dst, idx=None, first=0, n=None):
+    """One more float column next to the four of the gathers (include/ddrl.h ddrl_op_gather_f32; csrc/minibatch.hip): dst[j] =
+    src[idx[j]] (idx int32 on the device), or src[first + j] without an index, for j < n; a sample outside src gives zero.
+    Asynchronous on the current stream; returns dst[:n]."""
+    n = int((idx.numel() if idx is not None else dst.numel()) if n is None else n)
+    assert idx is None or (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() >= n), \
+        "idx: contiguous int32 on the device"
+    assert _f32(dst).numel() >= n
+    check(_lib.load().ddrl_op_gather_f32(_p(_f32(src)), src.numel(), _p(idx), int(first), n, _p(dst), _st()))
+    return dst[:n]
+
+
+NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off
+
+
+def loss_options(value_clip=0.0, entropy_split=False):
+    """ddrl_loss_options (include/ddrl.h) from the two update options; value_clip None / False / 0 = off."""
+    return _lib.LossOptions(float(value_clip or 0.0), 1 if entropy_split else 0)
+
+
+def heads_loss_opt(desc, cfg, params, h_actor, h_critic, n, actions, old_logps, advs, rets, options, old_values, b_global, dh_actor,
+                   dh_critic, grads, ws):
+    """ddrl_op_heads_loss with the update options (include/ddrl.h ddrl_op_heads_loss_opt): `options` = (value_clip, entropy_split),
+    old_values [n] fp32 (None unless the clip is on).  Asynchronous on the current stream."""
+    o = loss_options(*options)
+    check(_lib.load().ddrl_op_heads_loss_opt(byref(desc), byref(cfg), _p(params), _p(h_actor), _p(h_critic), int(n), _p(actions),
+                                             _p(old_logps), _p(advs), _p(rets), byref(o), _p(old_values), int(b_global), _p(dh_actor),
+                                             _p(dh_critic), _p(grads), _p(ws), _st()))
+
+
 def frame_age(prev_age, reset, age, channels):
     """The age row of one step of the single-frame pool (include/ddrl.h ddrl_op_frame_age; csrc/fpool.hip): age[i] = 0 where reset[i] is
     not zero, else min(prev_age[i] + 1, channels - 1).  reset None: no env is reset; prev_age None (with a reset array): every env is.

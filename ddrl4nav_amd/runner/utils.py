@@ -86,6 +86,8 @@ def _create_gail_net(config, config_nn, config_env, max_batch, process_group, ex
     refuse_frames_in_place(config_nn, "NETWORK_TYPE='gail'")
     from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
     refuse_act_in_place(config_nn, "NETWORK_TYPE='gail'")
+    from ddrl4nav_amd.nn.minibatch import refuse_loss_options
+    refuse_loss_options(config_nn, "NETWORK_TYPE='gail'")
     dim = config_nn.AC_INPUT_DIM
     actor = config_nn.ACTOR_CLASS(action_output_dim=config_nn.ACTION_OUTPUT_DIM, device=config_nn.DEVICE, last_input_dim=dim,
                                   soft_max_grid=config_nn.SOFT_MAX_GRID, nn_dtype=config_nn.MODULE_TENSOR_DTYPE)

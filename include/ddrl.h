@@ -673,6 +673,55 @@ int32_t ddrl_op_frame_table_stacks(int64_t n_rows, int32_t channels, const int32
 int32_t ddrl_op_frame_slot(int32_t rows, int32_t n_envs, int32_t hist, int32_t channels, int32_t t, const uint8_t* prev_age,
                            const uint8_t* reset, uint8_t* age, int32_t* tab, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PPO update options (the reference has none of them, ppo.py:82-129; additive: ABI 3).  ddrl_config and every
+ * entry point above are unchanged: the options arrive through entry points of their own, and with all options off those compute, bit
+ * for bit, what the entry points above compute.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ddrl_loss_options {
+  float value_clip;      /* c > 0: per sample, with e(x) the value-loss element (x^2, halved by the mean, or smooth-L1 with beta 1),
+                            d = v - v_old, v_c = v_old + clamp(d, -c, c), the element is max(e(ret - v), e(ret - v_c)); its gradient
+                            follows torch.max (a tie splits evenly) and torch.clamp (passes on the closed interval).  0 = off */
+  int32_t entropy_split; /* != 0: with two encoders the actor side differentiates actor_loss - ent_loss_theta * entropy (the reference
+                            differentiates actor_loss alone there, ppo.py:118-129): the entropy gradient reaches the actor head, the
+                            actor's encoder and log_std, nothing else; with a shared prenet total_loss carries the term already and
+                            the option changes nothing.  The three statistics and the total are the same either way */
+  int32_t reserved[2];   /* must be 0 */
+} ddrl_loss_options;
+
+/* One training batch of the Atari context.  tab == NULL: frames_or_planes is the contiguous uint8 [B][C][84][84] of ddrl_ppo_iter and
+ * n_planes is not read; otherwise it is the plane base pointer of ddrl_ppo_iter_indexed with n_planes planes behind it and tab its
+ * frame table (the same rules: planes 16-byte aligned, tab 4-byte aligned with B * 4 entries, 1 <= n_planes <= INT64_MAX / 7056).
+ * old_values [B] = the values the collecting policy predicted: required, 4-byte aligned, when value_clip > 0; not read otherwise. */
+typedef struct ddrl_ppo_batch {
+  const uint8_t* frames_or_planes;
+  int64_t n_planes;
+  const int32_t* tab;
+  const float *actions, *old_logps, *advs, *rets, *old_values;
+} ddrl_ppo_batch;
+
+/* ddrl_ppo_iter / ddrl_ppo_iter_indexed with the options: the same launches, the loss kernel in its option form.  ddrl_ppo_diag, the
+ * gradient buckets and ddrl_clip_adam_step work after it exactly as after ddrl_ppo_iter.  value_clip negative, NaN or infinite, a
+ * non-zero reserved word, a missing or misaligned old_values under value_clip > 0: DDRL_ERR_INVALID_ARG (every check runs before
+ * anything touches the context or HIP). */
+int32_t ddrl_ppo_iter_opt(ddrl_ctx* ctx, const ddrl_ppo_batch* batch, const ddrl_loss_options* opt, int32_t B, int64_t B_global,
+                          void* stream);
+/* ddrl_op_heads_loss with the options, both head families (Gaussian: the entropy term's gradient is -ent_loss_theta / (B D) per
+ * log_std entry); old_values [n] as above. */
+int32_t ddrl_op_heads_loss_opt(const ddrl_heads_desc* d, const ddrl_config* cfg, const float* params, const float* h_actor,
+                               const float* h_critic, int32_t n, const float* actions, const float* old_logps, const float* advs,
+                               const float* rets, const ddrl_loss_options* opt, const float* old_values, int64_t B_global,
+                               float* dh_actor, float* dh_critic, float* grads, float* ws, void* stream);
+/* Overwrite actor_lr, critic_lr, learning_rate and ppo_clip of the context's configuration (learning-rate and clip schedules): the loss
+ * kernels, ddrl_ppo_diag and ddrl_clip_adam_step read them at every launch, so the next call of each sees the new values.  Host only,
+ * no synchronisation.  A negative or non-finite value: DDRL_ERR_INVALID_ARG, and the context is unchanged. */
+int32_t ddrl_set_rates(ddrl_ctx* ctx, float actor_lr, float critic_lr, float learning_rate, float ppo_clip);
+/* dst[j] = src[idx[j]] (idx int32 on the device), or src[first + j] when idx is NULL, for j < n: one more float column (old_values)
+ * next to the four that the gathers and the frame tables above carry.  src holds n_rows floats; a sample outside [0, n_rows) reads
+ * nothing and yields zero.  src, dst and idx 4-byte aligned, dst overlaps neither src nor idx: DDRL_ERR_INVALID_ARG.  Needs no
+ * context, allocates nothing, no atomics, asynchronous on `stream`; the argument checks run before anything touches HIP. */
+int32_t ddrl_op_gather_f32(const float* src, int64_t n_rows, const int32_t* idx, int64_t first, int32_t n, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
