@@ -213,6 +213,12 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p]),
     "ddrl_set_rates": (c_int32, [c_void_p, c_float, c_float, c_float, c_float]),
     "ddrl_op_gather_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_column_moments_ws_floats": (c_int32, [c_int64, c_int32, POINTER(c_int64)]),
+    "ddrl_op_column_moments": (c_int32, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_running_merge": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_running_affine": (c_int32, [c_void_p, c_int32, c_double, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_normalize_columns": (c_int32, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
+    "ddrl_op_discounted_returns": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@ gathered path (tests/test_act_in_place_gpu.py).  The scratch is then allocated o
 import torch
 
 from ddrl4nav_amd import ops
+from ddrl4nav_amd.agent.normalize import check_knobs
 from ddrl4nav_amd.agent.rollout import DeviceRollout
 from ddrl4nav_amd.agent.statistics import EpisodeReturns
 from ddrl4nav_amd.data import Experience, FramePlanes
@@ -27,8 +28,9 @@ from ddrl4nav_amd.utils.staging import copy_into
 
 class PlaneRollout(DeviceRollout):
     def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False,
-                 act_in_place=None):
+                 act_in_place=None, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
         # the pools of DeviceRollout.__init__ with `frames` replaced by planes + age (not called: it would allocate the stacked pool)
+        check_knobs(norm_eps, reward_clip)
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
         self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
@@ -65,6 +67,7 @@ class PlaneRollout(DeviceRollout):
         self.returns = EpisodeReturns(N, dev) if track_returns else None
         self._reset_buf = torch.ones((2, N), dtype=torch.uint8, device=dev)   # _reset_flags: 0 a caller's flags, 1 all ones
         self._ring_rollout = -1            # the rollout (self.rollouts) whose first ring put ordered the copy stream
+        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
 
     # ---- ingest ---------------------------------------------------------------------------------
     def put_frames(self, t, frames):

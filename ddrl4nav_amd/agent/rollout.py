@@ -21,6 +21,7 @@ sample is on-policy for the weights the update starts from."""
 import torch
 
 from ddrl4nav_amd.agent.agent import gae_device
+from ddrl4nav_amd.agent.normalize import ReturnNorm, RunningNorm, check_knobs, obs_norm_flags
 from ddrl4nav_amd.agent.statistics import EpisodeReturns
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.ops import frame_stack_push
@@ -36,8 +37,41 @@ def value_rows(ret, values, T, B, with_old_values):
     return torch.stack([ret.view(B), values[:T].reshape(B)])
 
 
-class DeviceRollout:
-    def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False):
+class _ReturnScaling:
+    """What DeviceRollout, PlaneRollout and StateRollout share of normalize_returns (agent/normalize.py ReturnNorm; DESIGN.md section
+    6.6): off (the default) nothing is allocated, nothing is launched and finish() runs GAE on the raw rewards as before."""
+    ret_norm = None
+    rewards_norm = None
+
+    def _init_return_scaling(self, normalize_returns, reward_clip, norm_eps):
+        """After N, T, gamma and device are set."""
+        if normalize_returns:
+            self.ret_norm = ReturnNorm(self.N, self.T, self.gamma, self.device, eps=norm_eps, clip=reward_clip)
+            self.rewards_norm = self.ret_norm.rewards_norm
+
+    def _gae(self):
+        """finish(): GAE over rows 0..T-1, on the scaled rewards when normalize_returns is on.  Those rows are every step exactly once,
+        also with carry_over(keep_step=True) (row T becomes row 0 of the next rollout), as for EpisodeReturns; the raw rewards stay.
+        Under an initialised process group the commit of the return statistics is an all-reduce (through the host on gloo): finish()
+        is then a synchronising collective that every rank has to call."""
+        rewards = self.rewards if self.ret_norm is None else self.ret_norm.scale(self.rewards, self.dones)
+        gae_device(self.values, rewards, self.dones, self.gamma, self.landa, adv=self.adv, ret=self.ret)
+
+    def state_dict(self):
+        """The running statistics a checkpoint has to carry next to the net's (host tensors): the return scaling's state and carry."""
+        return {"ret_norm": None if self.ret_norm is None else self.ret_norm.state_dict()}
+
+    def load_state_dict(self, sd):
+        if (sd.get("ret_norm") is None) != (self.ret_norm is None):
+            raise ValueError("normalize_returns differs between the saved rollout and this one")
+        if self.ret_norm is not None:
+            self.ret_norm.load_state_dict(sd["ret_norm"])
+
+
+class DeviceRollout(_ReturnScaling):
+    def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False,
+                 normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
+        check_knobs(norm_eps, reward_clip)
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
         self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
@@ -67,6 +101,7 @@ class DeviceRollout:
         self._reset_buf = None             # uint8 [2, N]: 0 a caller's reset flags brought to the device, 1 all ones (reset=True)
         self._pushed = [None, None]        # events: the push kernel that read _newest[parity] is through
         self._ring_rollout = -1            # the rollout (self.rollouts) whose first single-frame ring put ordered the copy stream
+        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
 
     # ---- ingest ---------------------------------------------------------------------------------
     def put_frames(self, t, frames):
@@ -173,7 +208,7 @@ class DeviceRollout:
 
     # ---- GAE + learner batch ----------------------------------------------------------------------
     def finish(self):
-        gae_device(self.values, self.rewards, self.dones, self.gamma, self.landa, adv=self.adv, ret=self.ret)
+        self._gae()
         if self.returns is not None:  # Status.update_reward_status over rows 0..T-1: every step once, also with keep_step
             self.returns.update(self.rewards, self.dones)
         self.rollouts += 1
@@ -202,13 +237,26 @@ class DeviceRollout:
                           actions=self.actions.view(B), old_logps=self.logps.view(B), values=self._value_rows(B))
 
 
-class StateRollout:
+class StateRollout(_ReturnScaling):
     """DeviceRollout for the operator-composed nets (nn/generic.py): the observation is a LIST of
     float tensors per env (e.g. robot_nav: laser [1,960], vector [5], pedestrian image [3,48,48]) and
     the action may be continuous.  Same pool layout idea ([time][env] major, everything on the GPU),
-    same life cycle: put_states(t, ...) -> act(t) -> record(t, ...) ... bootstrap() -> finish() -> batch()."""
+    same life cycle: put_states(t, ...) -> act(t) -> record(t, ...) ... bootstrap() -> finish() -> batch().
 
-    def __init__(self, net, n_envs, state_shapes, horizon=256, gamma=0.99, landa=0.95, device=None, track_returns=False):
+    normalize_obs (True, or one bool per component; off by default): every put stores the slot as it arrived, adds its RAW rows to the
+    pending sums of the component's RunningNorm (the public ``obs_norm[k]``; None for a component left raw), then normalises the slot IN
+    PLACE with the affine frozen at the last finish() -- before the first finish() that of a fresh state, or of whatever the host warmed
+    ``obs_norm[k]`` with (update / commit / freeze, or load_state_dict).  act() and batch() therefore read the same numbers and stay
+    zero-copy.  finish() commits and freezes.  carry_over() moves a slot that is normalised already: it is neither counted nor
+    normalised again, so slot 0 of the next rollout carries the statistics of one finish() earlier than slots 1..T (DESIGN.md
+    section 6.6).  normalize_returns: see _ReturnScaling."""
+
+    def __init__(self, net, n_envs, state_shapes, horizon=256, gamma=0.99, landa=0.95, device=None, track_returns=False,
+                 normalize_obs=None, obs_clip=10.0, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
+        state_shapes = [tuple(int(d) for d in shape) for shape in state_shapes]
+        flags = obs_norm_flags(normalize_obs, len(state_shapes))
+        check_knobs(norm_eps, obs_clip)
+        check_knobs(norm_eps, reward_clip)
         self.net = net
         self.with_old_values = bool(getattr(net, "wants_old_values", False))
         self.N, self.T = int(n_envs), int(horizon)
@@ -231,19 +279,38 @@ class StateRollout:
         self.t0 = 0
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.returns = EpisodeReturns(N, dev) if track_returns else None
+        self.obs_norm = None
+        self._ring_ordered = False         # normalize_obs: a ring put has ordered the copy stream since the last finish()
+        if any(flags):
+            self.obs_norm = [RunningNorm(shape, dev, eps=norm_eps, clip=obs_clip) if on else None
+                             for on, shape in zip(flags, state_shapes)]
+        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
+
+    def _normalize_slot(self, t, index):
+        """Slot t of component `index` holds raw rows: count them, then normalise them in place with the frozen affine."""
+        norm = self.obs_norm[index] if self.obs_norm is not None else None
+        if norm is not None:
+            slot = self.states[index][t]
+            norm.update(slot)
+            norm.apply(slot, out=slot)
 
     def put_states(self, t, states):
         """Device or pinned-host tensors, one per observation component -> pool slot t."""
-        for pool, s in zip(self.states, states):
+        for k, (pool, s) in enumerate(zip(self.states, states)):
             copy_into(pool[t], torch.as_tensor(s).reshape(pool[t].shape))
+            self._normalize_slot(t, k)
 
     def put_state_from_ring(self, t, index, ring):
         """Component `index` of slot t from a pinned ring (raw fp32 bytes), on the copy stream (the first slot of a rollout orders the
-        copy stream behind the compute stream, as put_frames_from_ring)."""
-        if t <= self.t0:
+        copy stream behind the compute stream, as put_frames_from_ring).  With normalize_obs the compute stream also WRITES the slots
+        (the in-place normalisation of the previous rollout's puts), so the first ring put behind a finish() orders the copy stream
+        as well, at whatever t: after carry_over() that put is t == 1."""
+        if t <= self.t0 or (self.obs_norm is not None and not self._ring_ordered):
             self.copy_stream.wait_stream(torch.cuda.current_stream())
+            self._ring_ordered = True
         ring.pop_to(self.states[index][t], stream=self.copy_stream)
         torch.cuda.current_stream().wait_stream(self.copy_stream)
+        self._normalize_slot(t, index)
 
     def act(self, t):
         if t < self.t0:  # carried over as a complete step (DeviceRollout.act)
@@ -271,12 +338,37 @@ class StateRollout:
         copy_into(self._dones[t], dones)
 
     def finish(self):
-        gae_device(self.values, self.rewards, self.dones, self.gamma, self.landa, adv=self.adv, ret=self.ret)
+        """GAE over the rollout; with normalize_obs / normalize_returns first the commits of the statistics.  Under an initialised
+        process group every commit is one small all-reduce (through the host on gloo): finish() is then a synchronising collective that
+        EVERY rank has to call, once per normalised component and once for the returns, in this order."""
+        for norm in self.obs_norm or ():
+            if norm is not None:
+                norm.commit()
+                norm.freeze()
+        self._ring_ordered = False
+        self._gae()
         if self.returns is not None:
             self.returns.update(self.rewards, self.dones)
 
+    def state_dict(self):
+        """_ReturnScaling.state_dict plus the observation statistics, one entry (or None) per component."""
+        sd = super().state_dict()
+        sd["obs_norm"] = None if self.obs_norm is None else [None if n is None else n.state_dict() for n in self.obs_norm]
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        saved = sd.get("obs_norm")
+        mine = self.obs_norm
+        if [n is None for n in saved or ()] != [n is None for n in mine or ()]:
+            raise ValueError("normalize_obs differs between the saved rollout and this one")
+        for n, s in zip(mine or (), saved or ()):
+            if n is not None:
+                n.load_state_dict(s)
+
     def carry_over(self, keep_step=False):
-        """DeviceRollout.carry_over: keep_step=True keeps the whole (T+1)-th step as the reference does (agent.py:286-292)."""
+        """DeviceRollout.carry_over: keep_step=True keeps the whole (T+1)-th step as the reference does (agent.py:286-292).  A slot
+        normalised at its put moves as it is (class docstring)."""
         T = self.T
         for p in self.states:
             p[0].copy_(p[T])

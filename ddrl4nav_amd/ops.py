@@ -4,6 +4,7 @@ frame-stack push (ddrl_frame_stack_push).  torch supplies memory
 and streams only; the arithmetic runs in csrc/gconv.hip and csrc/glinear.hip.  Used by
 ddrl4nav_amd.nn.generic to compose the reference's non-Atari encoders
 (USTC_lab/nn/nav_encoder.py, mlp_encoder.py)."""
+import functools
 import math
 from ctypes import byref, c_int32, c_int64, c_void_p
 
@@ -259,6 +260,98 @@ def gather_f32(src, dst, idx=None, first=0, n=None):
     assert _f32(dst).numel() >= n
     check(_lib.load().ddrl_op_gather_f32(_p(_f32(src)), src.numel(), _p(idx), int(first), n, _p(dst), _st()))
     return dst[:n]
+
+
+def _rows2d(x, d):
+    """(n, ld) of a fp32 device matrix whose rows hold d used columns: a contiguous tensor of n * d floats, or a 2-D view whose rows
+    are ld >= d floats apart."""
+    assert x.dtype == torch.float32 and x.is_cuda, "expected a fp32 device tensor"
+    if x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == d and x.stride(0) >= d:
+        return x.shape[0], x.stride(0)
+    assert x.is_contiguous() and x.numel() % d == 0, "expected [n, d] rows (contiguous, or a 2-D view with a row stride)"
+    return x.numel() // d, d
+
+
+@functools.lru_cache(maxsize=256)
+def column_moments_ws_floats(n, d):
+    """Floats of scratch ddrl_op_column_moments needs for n rows of d columns (a function of the two numbers alone: remembered, a
+    rollout asks for the same few shapes at every step)."""
+    f = c_int64()
+    check(_lib.load().ddrl_op_column_moments_ws_floats(int(n), int(d), byref(f)))
+    return f.value
+
+
+def column_moments(x, d, sums=None, accumulate=False, ws=None):
+    """(n, sum x_j, sum x_j^2) of the d columns of x ([n, d] rows, see _rows2d) as 1 + 2 d float64 on the device (include/ddrl.h
+    ddrl_op_column_moments; csrc/runnorm.hip): double sums in an order the shape alone fixes.  accumulate: added to what `sums`
+    holds.  Asynchronous on the current stream; returns sums."""
+    d = int(d)
+    n, ld = _rows2d(x, d)
+    if sums is None:
+        assert not accumulate, "accumulate needs the sums of the earlier calls"
+        sums = torch.empty(1 + 2 * d, dtype=torch.float64, device=x.device)
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 1 + 2 * d
+    need = column_moments_ws_floats(n, d)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=x.device)
+    assert _f32(ws).numel() >= need, "ws: column_moments_ws_floats(n, d) floats"
+    check(_lib.load().ddrl_op_column_moments(_p(x), n, d, ld, _p(sums), 1 if accumulate else 0, _p(ws), _st()))
+    return sums
+
+
+def running_state(d, device):
+    """A fresh running state, float64 [1 + 2 d] = (count 0, mean 0..., var 1...): the defaults of the reference's RunningMeanStd."""
+    s = torch.zeros(1 + 2 * int(d), dtype=torch.float64, device=device)
+    s[1 + int(d):] = 1.0
+    return s
+
+
+def running_merge(sums, state):
+    """RunningMeanStd.update (warputils.py:94-109) of `state` with the pending batch `sums` (include/ddrl.h ddrl_op_running_merge);
+    both float64 [1 + 2 d] on the device.  Returns state."""
+    d = (sums.numel() - 1) // 2
+    for t in (sums, state):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() == 1 + 2 * d
+    check(_lib.load().ddrl_op_running_merge(_p(sums), d, _p(state), _st()))
+    return state
+
+
+def running_affine(state, eps, center=True, affine=None):
+    """affine fp32 [2, d] = (shift, scale) of a running state: shift = mean (0 without center), scale = 1 / sqrt(var + eps)
+    (include/ddrl.h ddrl_op_running_affine).  Returns affine."""
+    d = (state.numel() - 1) // 2
+    assert state.dtype == torch.float64 and state.is_cuda and state.is_contiguous() and state.numel() == 1 + 2 * d
+    if affine is None:
+        affine = torch.empty((2, d), dtype=torch.float32, device=state.device)
+    assert _f32(affine).numel() == 2 * d
+    check(_lib.load().ddrl_op_running_affine(_p(state), d, float(eps), 1 if center else 0, _p(affine), _st()))
+    return affine
+
+
+def normalize_columns(x, affine, clip, out=None):
+    """out[r][j] = clamp((x[r][j] - shift_j) * scale_j, -clip, clip) with affine = (shift, scale) fp32 [2, d] (include/ddrl.h
+    ddrl_op_normalize_columns).  x and out: [n, d] rows (see _rows2d); out may be x, and defaults to a new tensor of x's shape.
+    Returns out."""
+    d = _f32(affine).numel() // 2
+    n, ld_x = _rows2d(x, d)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    n_out, ld_out = _rows2d(out, d)
+    assert n_out == n, "out must hold the rows of x"
+    check(_lib.load().ddrl_op_normalize_columns(_p(x), n, d, ld_x, _p(affine), float(clip), _p(out), ld_out, _st()))
+    return out
+
+
+def discounted_returns(rewards, dones, gamma, carry, trace=None):
+    """trace[t] = carry * gamma + rewards[t]; carry = 0 where dones[t] else trace[t], over the T rows of rewards / dones [T, N]
+    (include/ddrl.h ddrl_op_discounted_returns); carry fp32 [N] persists between calls.  Returns trace."""
+    T, N = rewards.shape
+    assert tuple(dones.shape) == (T, N) and dones.dtype == torch.uint8 and dones.is_cuda and dones.is_contiguous()
+    if trace is None:
+        trace = torch.empty((T, N), dtype=torch.float32, device=rewards.device)
+    assert _f32(carry).numel() == N and tuple(_f32(trace).shape) == (T, N)
+    check(_lib.load().ddrl_op_discounted_returns(_p(_f32(rewards)), _p(dones), T, N, float(gamma), _p(carry), _p(trace), _st()))
+    return trace
 
 
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off

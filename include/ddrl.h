@@ -722,6 +722,40 @@ int32_t ddrl_set_rates(ddrl_ctx* ctx, float actor_lr, float critic_lr, float lea
  * context, allocates nothing, no atomics, asynchronous on `stream`; the argument checks run before anything touches HIP. */
 int32_t ddrl_op_gather_f32(const float* src, int64_t n_rows, const int32_t* idx, int64_t first, int32_t n, float* dst, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Running observation and return normalisation (the reference defines RunningMeanStd, warputils.py:83-109, and uses it nowhere;
+ * additive: ABI 3).  All five need no context, allocate nothing and are asynchronous on `stream`; their argument
+ * checks run before anything touches HIP: a null pointer, a misaligned one (floats 4 bytes, doubles 8), an overlap of anything read
+ * with anything written, n < 1, d < 1 or ld < d is DDRL_ERR_INVALID_ARG.  No atomics; a result depends on the arguments and the data
+ * alone -- not on the launch geometry, not on whether a pointer allows 16-byte loads -- and a repeated call gives the same bits.
+ *   sums   double [1 + 2 d]  n, sum x_j (d entries), sum x_j^2 (d entries): a PENDING batch, additive over calls and over ranks
+ *   state  double [1 + 2 d]  count, mean[d], var[d] (population variance); a fresh state is (0, 0..., 1...)
+ *   affine float  [2][d]     shift[d], scale[d]
+ * ------------------------------------------------------------------------------------------ */
+/* sums of the columns [0, d) of x, fp32 [n][ld] (columns [d, ld) are never read): terms and partial sums in double; the rows are cut
+ * into slabs whose partial rows go to `ws` (ddrl_op_column_moments_ws_floats(n, d) floats, 8-byte aligned) and are folded in slab
+ * order.  accumulate != 0: added to what `sums` holds.  n <= INT64_MAX / 8 and d <= 2^28 in both. */
+int32_t ddrl_op_column_moments_ws_floats(int64_t n, int32_t d, int64_t* floats);
+int32_t ddrl_op_column_moments(const float* x, int64_t n, int32_t d, int64_t ld, double* sums, int32_t accumulate, float* ws, void* stream);
+/* RunningMeanStd.update (warputils.py:94-109) with the pending batch of `sums`, in double, per feature j:
+ *   n = sums[0];  bm = S1_j / n;  bv = max(0, S2_j / n - bm^2);  delta = bm - mean_j;  tot = count + n
+ *   mean_j += delta * n / tot;  var_j = (var_j * count + bv * n + delta^2 * count * n / tot) / tot;  count = tot
+ * n == 0 leaves the state unchanged.  `sums` is not modified. */
+int32_t ddrl_op_running_merge(const double* sums, int32_t d, double* state, void* stream);
+/* shift_j = center ? (float)mean_j : 0;  scale_j = (float)(1 / sqrt(var_j + eps)), formed in double.  eps >= 0. */
+int32_t ddrl_op_running_affine(const double* state, int32_t d, double eps, int32_t center, float* affine, void* stream);
+/* out[r][j] = clamp((x[r][j] - shift_j) * scale_j, -clip, clip) for r < n, j < d, in fp32: a subtract, then a multiply (never fused),
+ * then v < -clip ? -clip : (v > clip ? clip : v), so that a NaN stays a NaN and an infinity goes to the clip.  clip > 0, +inf
+ * allowed.  x is [n][ld_x], out [n][ld_out]; out == x with ld_out == ld_x is allowed, any other overlap is refused; the padding columns
+ * [d, ld_out) of out are never written. */
+int32_t ddrl_op_normalize_columns(const float* x, int64_t n, int32_t d, int64_t ld_x, const float* affine, float clip, float* out,
+                                  int64_t ld_out, void* stream);
+/* The discounted return that reward scaling takes its variance of, over the T steps of a rollout ([T][N], like ddrl_gae), one lane per
+ * env, forward in time, never fused:  g = carry[n] * gamma + rewards[t][n];  trace[t][n] = g;  carry[n] = dones[t][n] ? 0 : g.
+ * carry [N] persists between calls: two chained calls equal one call on the concatenation.  0 <= gamma <= 1. */
+int32_t ddrl_op_discounted_returns(const float* rewards, const uint8_t* dones, int32_t T, int32_t N, float gamma, float* carry, float* trace,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
