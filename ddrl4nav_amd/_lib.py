@@ -219,6 +219,10 @@ SIGNATURES = {
     "ddrl_op_running_affine": (c_int32, [c_void_p, c_int32, c_double, c_int32, c_void_p, c_void_p]),
     "ddrl_op_normalize_columns": (c_int32, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     "ddrl_op_discounted_returns": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_env_state_ints": (c_int32, []),
+    "ddrl_op_env_reset": (c_int32, [c_int32, c_void_p, c_int32, c_int64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_env_step": (c_int32, [c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.c_uint32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -86,10 +86,20 @@ class PlaneRollout(DeviceRollout):
             ops.frame_age(prev, flags, self.age[t], self.C)
 
     def put_new_frames(self, t, newest, reset=None):
-        """ONE new frame per env, uint8 [N,84,84] (device or pinned host) -> pool row H + t; `reset` as DeviceRollout.put_new_frames."""
+        """ONE new frame per env, uint8 [N,84,84] (device or pinned host) -> pool row H + t; `reset` as DeviceRollout.put_new_frames.
+        `newest` may be new_frame_row(t) itself, already filled: then only the age / slot launch runs."""
         flags = self._reset_flags(t, reset)
-        copy_into(self.planes[self.H + t], torch.as_tensor(newest))
+        row = self.planes[self.H + t]
+        n = torch.as_tensor(newest)
+        # a producer on the device (env/device_env.py) may have rendered into new_frame_row(t) itself: nothing is left to copy
+        if not (n.is_cuda and n.data_ptr() == row.data_ptr() and n.shape == row.shape and n.dtype == row.dtype and n.is_contiguous()):
+            copy_into(row, n)
         self._age(t, flags)
+
+    def new_frame_row(self, t):
+        """Pool row H + t, uint8 [N, 84, 84] (16-byte aligned): where put_new_frames(t, ...) stores the frame.  A device producer writes
+        it there and passes this very tensor to put_new_frames, which then copies nothing."""
+        return self.planes[self.H + t]
 
     def put_new_frames_from_ring(self, t, ring, reset=None):
         """put_new_frames with the frame taken from a pinned ring whose slots hold N * 7056 bytes: hipMemcpyAsync on the copy stream straight

@@ -354,6 +354,53 @@ def discounted_returns(rewards, dones, gamma, carry, trace=None):
     return trace
 
 
+ENV_GAMES = {"pong": 0, "catch": 1}   # include/ddrl.h ddrl_op_env_reset / ddrl_op_env_step `game`
+ENV_PLANE = 84 * 84
+
+
+@functools.lru_cache(maxsize=None)
+def env_state_ints():
+    """The int32 words of one device env's state (include/ddrl.h ddrl_op_env_state_ints; a constant of the library: remembered)."""
+    return int(_lib.load().ddrl_op_env_state_ints())
+
+
+def _env_args(game, state, frame):
+    """(game id, n) of a device-env call after the checks both operators share: state int32 [n, env_state_ints()], frame uint8
+    [n, 84, 84], contiguous, on one device, the frame's base 16-byte aligned."""
+    if game not in ENV_GAMES:
+        raise ValueError("game must be one of %s, got %r" % (sorted(ENV_GAMES), game))
+    assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 \
+        and state.shape[1] == env_state_ints(), "state: contiguous int32 [n, env_state_ints()] on the device"
+    n = state.shape[0]
+    assert frame.dtype == torch.uint8 and frame.is_cuda and frame.is_contiguous() and tuple(frame.shape) == (n, 84, 84) \
+        and frame.device == state.device, "frame: contiguous uint8 [n, 84, 84] on the state's device"
+    assert frame.data_ptr() % 16 == 0, "frame: the base must be 16-byte aligned"
+    return ENV_GAMES[game], n
+
+
+def env_reset(game, state, frame, env0=0, seed=0, mask=None):
+    """A new first episode for every env of `state`, or for those with a non-zero byte in mask (uint8 [n]), and their first frames
+    (include/ddrl.h ddrl_op_env_reset; csrc/denv.hip).  Asynchronous on the current stream; returns frame."""
+    g, n = _env_args(game, state, frame)
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == n
+                            and mask.device == state.device), "mask: contiguous uint8 [n] on the state's device"
+    check(_lib.load().ddrl_op_env_reset(g, _p(state), n, int(env0), int(seed) & 0xFFFFFFFF, _p(mask), _p(frame), _st()))
+    return frame
+
+
+def env_step(game, state, actions, frame, reward, done, env0=0, n_actions=6, points=21, max_steps=10000, seed=0):
+    """One step of every env (include/ddrl.h ddrl_op_env_step; csrc/denv.hip): actions fp32 [n] -> state (in place), frame uint8
+    [n, 84, 84], reward fp32 [n], done uint8 [n].  Asynchronous on the current stream; returns (frame, reward, done)."""
+    g, n = _env_args(game, state, frame)
+    assert _f32(actions).numel() == n and _f32(reward).numel() == n and actions.device == state.device \
+        and reward.device == state.device, "actions / reward: fp32 [n] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
+        and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
+    check(_lib.load().ddrl_op_env_step(g, _p(state), n, int(env0), int(n_actions), int(points), int(max_steps), int(seed) & 0xFFFFFFFF,
+                                       _p(actions), _p(frame), _p(reward), _p(done), _st()))
+    return frame, reward, done
+
+
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off
 
 

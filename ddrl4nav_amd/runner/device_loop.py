@@ -1,0 +1,54 @@
+"""The closed loop on one GPU: a DeviceRollout / PlaneRollout driven by a DeviceEnv (env/device_env.py), then net.learn on its batch.
+
+Every tensor that moves between acting, the env and the pools is a device tensor and every call is asynchronous on the current stream:
+a rollout adds no host synchronisation to what act(), record() and the puts do already (none, for device arguments).  On a PlaneRollout
+the env renders straight into the pool row the frame belongs to (PlaneRollout.new_frame_row), so the put copies nothing."""
+
+
+def _row(ro, t):
+    """Where the env should render the frame of slot t: the plane pool's own row, or None (the env's buffer, which the put copies)."""
+    return ro.new_frame_row(t) if hasattr(ro, "new_frame_row") else None
+
+
+def collect(ro, env, keep_step=False, reset=None):
+    """One rollout of `ro` on `env`: act(t) -> env.step -> record(t, reward, done) -> put_new_frames(t + 1, frame) for t = t0 .. T - 1,
+    then bootstrap() and finish().
+
+    reset (None: True for ro's first rollout, ro.rollouts == 0 with nothing carried over): the env is reset and its first frame put as
+    slot 0.  Otherwise slot 0 is what carry_over() left there.
+    keep_step: the caller will close this rollout with carry_over(keep_step=True) -- the bootstrap action is then sent to the env as
+    well and its reward and done recorded in row T; the frame it produced stays in env.frame and becomes slot 1 of the next rollout,
+    which starts at ro.t0 == 1 with the kept action already played."""
+    T = ro.T
+    if env.N != ro.N:
+        raise ValueError("the env has %d envs, the rollout %d" % (env.N, ro.N))
+    if reset is None:
+        reset = ro.rollouts == 0 and ro.t0 == 0
+    if reset:
+        if ro.t0 != 0:
+            raise ValueError("a rollout that carried a whole step over cannot restart its env")
+        ro.put_new_frames(0, env.reset(frame_out=_row(ro, 0)), reset=True)
+    elif ro.t0 == 1:
+        # the kept step's action was played at the end of the previous rollout: env.frame is the observation of slot 1
+        ro.put_new_frames(1, env.frame)
+    for t in range(ro.t0, T):
+        frame, reward, done = env.step(ro.act(t), frame_out=_row(ro, t + 1))
+        ro.record(t, reward, done)
+        ro.put_new_frames(t + 1, frame)
+    action = ro.bootstrap()
+    if keep_step:
+        _, reward, done = env.step(action)
+        ro.record(T, reward, done)
+    ro.finish()
+
+
+def train(net, env, ro, updates, keep_step=False):
+    """A generator over `updates` PPO updates: collect(ro, env), net.learn(ro.batch()), carry_over(keep_step).  Yields, per update,
+    (the last loss dict of net.learn, ro.returns.mean_return() -- None without track_returns)."""
+    for _ in range(int(updates)):
+        collect(ro, env, keep_step=keep_step)
+        losses = None
+        for item in net.learn(ro.batch()):
+            losses = item[0]
+        yield losses, (ro.returns.mean_return() if ro.returns is not None else None)
+        ro.carry_over(keep_step=keep_step)

@@ -756,6 +756,30 @@ int32_t ddrl_op_normalize_columns(const float* x, int64_t n, int32_t d, int64_t 
 int32_t ddrl_op_discounted_returns(const float* rewards, const uint8_t* dones, int32_t T, int32_t N, float gamma, float* carry, float* trace,
                                    void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device environments: Pong and Catch stepped and rendered on the GPU (additive: ABI 3; the rules are
+ * tests/device_env_ref.py, in integers only, and the kernels reproduce them bit for bit).  Context-free, no allocation, no atomics,
+ * asynchronous on `stream`; the same arguments and data give the same bits.  One launch serves all n envs.
+ *   game    0 = Pong, 1 = Catch
+ *   state   int32 [n][ddrl_op_env_state_ints()], 16-byte aligned: ball, velocity, paddles, scores, step and event counters
+ *   env0    the global index of local env 0 (the random draws hash (seed, env0 + i, event counter)): 0 <= env0, env0 + n <= 2^32
+ *   frame   uint8 [n][84][84], 16-byte aligned: background 87, objects 236; env i is written at frame + i * 7056 and nowhere else
+ * A null pointer (the mask excepted), n < 1, an unknown game, a misaligned state or frame, an overlap of two arguments: DDRL_ERR_INVALID_ARG,
+ * decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+/* the int32 words of one env's state (16) */
+int32_t ddrl_op_env_state_ints(void);
+/* A new first episode (all counters zero) for every env, or for those with a non-zero byte in mask (uint8 [n], NULL = all); their first
+ * frames are rendered.  The state and frame of an env whose mask byte is zero are not touched. */
+int32_t ddrl_op_env_reset(int32_t game, int32_t* state, int32_t n, int64_t env0, uint32_t seed, const uint8_t* mask, uint8_t* frame,
+                          void* stream);
+/* One step of every env: actions float32 [n] (k = (int)a % 3: stay / negative / positive direction; not finite, negative or >= n_actions:
+ * stay) -> the new state, its frame, reward float32 [n] in {-1, 0, 1} and done uint8 [n].  A finished env (a score of `points` in
+ * Pong, the landed ball in Catch, or max_steps steps) starts its next episode in the same launch: the frame is that episode's first and
+ * done is the reset flag.  2 <= n_actions <= 18, points >= 1, max_steps >= 1; actions and reward 4-byte aligned. */
+int32_t ddrl_op_env_step(int32_t game, int32_t* state, int32_t n, int64_t env0, int32_t n_actions, int32_t points, int32_t max_steps,
+                         uint32_t seed, const float* actions, uint8_t* frame, float* reward, uint8_t* done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
