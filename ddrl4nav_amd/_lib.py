@@ -223,6 +223,12 @@ SIGNATURES = {
     "ddrl_op_env_reset": (c_int32, [c_int32, c_void_p, c_int32, c_int64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_env_step": (c_int32, [c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.c_uint32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_nav_env_state_ints": (c_int32, []),
+    "ddrl_op_nav_env_trig": (c_int32, [c_void_p]),
+    "ddrl_op_nav_env_reset": (c_int32, [c_void_p, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "ddrl_op_nav_env_step": (c_int32, [c_void_p, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -277,6 +277,7 @@ class StateRollout(_ReturnScaling):
         self.adv = torch.empty((T, N), **f)
         self.ret = torch.empty((T, N), **f)
         self.t0 = 0
+        self.rollouts = 0                  # finish() counts them (runner/device_loop.collect_states resets its env before the first)
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.returns = EpisodeReturns(N, dev) if track_returns else None
         self.obs_norm = None
@@ -298,6 +299,17 @@ class StateRollout(_ReturnScaling):
         """Device or pinned-host tensors, one per observation component -> pool slot t."""
         for k, (pool, s) in enumerate(zip(self.states, states)):
             copy_into(pool[t], torch.as_tensor(s).reshape(pool[t].shape))
+            self._normalize_slot(t, k)
+
+    def state_rows(self, t):
+        """The pool rows of slot t, one [N, ...] view per component: where a device producer (env/device_nav_env.py) renders the
+        observation of slot t, followed by put_states_in_place(t)."""
+        return [pool[t] for pool in self.states]
+
+    def put_states_in_place(self, t):
+        """Slot t was written through state_rows(t) by a producer on the current stream: nothing is copied.  With normalize_obs the raw
+        rows are counted and normalised in place exactly as put_states does; otherwise a no-op."""
+        for k in range(len(self.states)):
             self._normalize_slot(t, k)
 
     def put_state_from_ring(self, t, index, ring):
@@ -349,6 +361,7 @@ class StateRollout(_ReturnScaling):
         self._gae()
         if self.returns is not None:
             self.returns.update(self.rewards, self.dones)
+        self.rollouts += 1
 
     def state_dict(self):
         """_ReturnScaling.state_dict plus the observation statistics, one entry (or None) per component."""

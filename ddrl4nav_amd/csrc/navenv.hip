@@ -1,0 +1,390 @@
+// Device navigation env: a differential-drive robot, up to 10 static circular obstacles and up to 5 walking pedestrians in a round
+// arena, stepped and observed on the GPU (include/ddrl.h ddrl_op_nav_env_*).  tests/nav_env_ref.py is the rule
+// book: integer arithmetic only (the one double-precision square root is an estimate that an integer fix-up makes the exact floor), so
+// every state word, lidar range, vector entry, map cell, reward and done equals the model's.  Context-free, no allocation, no atomics;
+// the same arguments give the same bits.
+//
+// One 256-thread workgroup per env.  Threads 0..63 load one state word each, bring it into its range and park it in LDS; after a barrier
+// thread 0 plays the (workgroup-uniform) step on the LDS copy -- pedestrians, robot, collision, goal, the new episode of a finished env
+// -- and stores the reward and the done; after a second barrier thread 0 stores the 256 bytes of state and every thread renders from
+// the LDS copy: a thread owns 4 consecutive beams (240 threads, one 16-byte store each) and 16-byte chunks of the 3 x 48 x 48 map (1,728
+// chunks).  Render is a gather: every address written is a function of the env index alone, and no table index depends on a word that
+// has not been through nav_sanitize_word.
+#include <cstring>
+
+#include "rows.h"
+
+namespace ddrl {
+
+constexpr int NAV_STATE_INTS = 64, NAV_THREADS = 256;
+constexpr int NAV_HEADINGS = 3840, NAV_BEAMS = 960, NAV_BEAM_STEP = 4, NAV_Q = 14;
+constexpr int NAV_MAX_OBS = 10, NAV_MAX_PEDS = 5;
+constexpr int NAV_ARENA_R = 2560, NAV_ROBOT_R = 64, NAV_PED_R = 77, NAV_OBS_R_MIN = 77, NAV_OBS_R_MAX = 128;
+constexpr int NAV_RANGE_MAX = 1536, NAV_GOAL_TOL = 77, NAV_CELL = 608;
+constexpr int NAV_V_MAX = 32, NAV_W_MAX = 64, NAV_SPEED_MIN = 8, NAV_SPEED_MAX = 24, NAV_DPREV_MAX = 8191;
+constexpr int NAV_BONUS = 15 * 256;
+constexpr int NAV_MAP = 48, NAV_MAP_CELL = 64, NAV_MAP_FLOATS = 3 * NAV_MAP * NAV_MAP, NAV_MAP_CHUNKS = NAV_MAP_FLOATS / 4;
+constexpr int NAV_VECTOR = 5;
+enum { NS_X = 0, NS_Y, NS_H, NS_V, NS_W, NS_GX, NS_GY, NS_DPREV, NS_STEPS, NS_EVENTS, NS_OBS0 = 10, NS_PED0 = 40, NS_USED = 60 };
+static_assert(NAV_BEAMS == 4 * 240 && NAV_BEAMS * NAV_BEAM_STEP == NAV_HEADINGS, "four beams a thread, one turn");
+static_assert(NS_OBS0 + 3 * NAV_MAX_OBS == NS_PED0 && NS_PED0 + 4 * NAV_MAX_PEDS == NS_USED, "state layout");
+
+// Q14 cos[3840] then sin[3840] (tools/gen_nav_trig.py): the copy the kernels index and the copy ddrl_op_nav_env_trig hands out
+__device__ const int32_t nav_trig_dev[2 * NAV_HEADINGS] = {
+#include "nav_trig.inc"
+};
+static const int32_t nav_trig_host[2 * NAV_HEADINGS] = {
+#include "nav_trig.inc"
+};
+
+__device__ __forceinline__ int nav_cos(int h) { return nav_trig_dev[h]; }  // h in 0..3839: sanitised or reduced by the caller
+__device__ __forceinline__ int nav_sin(int h) { return nav_trig_dev[NAV_HEADINGS + h]; }
+__device__ __forceinline__ int nav_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int nav_heading(int v) {  // any int -> 0..3839
+  const int m = v % NAV_HEADINGS;
+  return m < 0 ? m + NAV_HEADINGS : m;
+}
+
+// section 6.7's counter-based hash (denv.hip env_hash, tests/device_env_ref.py hash32), word for word
+__device__ __forceinline__ uint32_t nav_hash(uint32_t seed, uint32_t env, uint32_t counter) {
+  uint32_t x = seed ^ (env * 0x9E3779B1u) ^ (counter * 0x85EBCA77u);
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 16;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// floor(sqrt(x)), 0 <= x < 2^62: the double estimate is within one of it, the loops settle the rest in either direction
+__device__ __forceinline__ int64_t nav_isqrt(int64_t x) {
+  int64_t r = (int64_t)sqrt((double)x);
+  while (r * r > x) --r;
+  while ((r + 1) * (r + 1) <= x) ++r;
+  return r;
+}
+
+// word k of a loaded state brought into its range (NavEnvRef.sanitize): a no-op on every state the rules produce
+__device__ __forceinline__ int nav_sanitize_word(int k, int v, int n_obs, int n_peds) {
+  if (k == NS_X || k == NS_Y || k == NS_GX || k == NS_GY) return nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R);
+  if (k == NS_H) return nav_heading(v);
+  if (k == NS_V) return nav_clamp(v, 0, NAV_V_MAX);
+  if (k == NS_W) return nav_clamp(v, -NAV_W_MAX, NAV_W_MAX);
+  if (k == NS_DPREV) return nav_clamp(v, 0, NAV_DPREV_MAX);
+  if (k == NS_STEPS || k == NS_EVENTS) return v;
+  if (k < NS_PED0) {
+    const int q = k - NS_OBS0, o = q / 3, f = q - 3 * o;
+    if (o >= n_obs) return 0;
+    return f < 2 ? nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R) : nav_clamp(v, NAV_OBS_R_MIN, NAV_OBS_R_MAX);
+  }
+  if (k < NS_USED) {
+    const int q = k - NS_PED0, p = q >> 2, f = q & 3;
+    if (p >= n_peds) return 0;
+    if (f < 2) return nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R);
+    return f == 2 ? nav_heading(v) : nav_clamp(v, NAV_SPEED_MIN, NAV_SPEED_MAX);
+  }
+  return 0;
+}
+
+__device__ __forceinline__ uint32_t nav_draw(int* s, uint32_t seed, uint32_t genv) {
+  const uint32_t h = nav_hash(seed, genv, (uint32_t)s[NS_EVENTS]);
+  s[NS_EVENTS] = (int)((uint32_t)s[NS_EVENTS] + 1u);
+  return h;
+}
+
+__device__ __forceinline__ int nav_distance(const int* s) {
+  const int64_t dx = s[NS_GX] - s[NS_X], dy = s[NS_GY] - s[NS_Y];
+  return (int)nav_isqrt(dx * dx + dy * dy);
+}
+
+// NavEnvRef._new_episode on the LDS copy: 3 + n_obs + n_peds draws, every slot in a cell of its own
+__device__ void nav_new_episode(int* s, int n_obs, int n_peds, uint32_t seed, uint32_t genv) {
+  uint32_t h = nav_draw(s, seed, genv);
+  const uint32_t m = h % 20u;
+  const int a = (int)(1u + m + m / 4u);  // the m-th of 1..24 that is no multiple of 5
+  const int b = (int)((h >> 8) % 25u);
+  int slot = 0;
+  auto centre = [&](int* cx, int* cy) {
+    const int cell = (a * slot + b) % 25;
+    ++slot;
+    *cx = (cell % 5 - 2) * NAV_CELL;
+    *cy = (cell / 5 - 2) * NAV_CELL;
+  };
+  int cx, cy;
+  for (int k = 0; k < n_obs; ++k) {
+    h = nav_draw(s, seed, genv);
+    centre(&cx, &cy);
+    s[NS_OBS0 + 3 * k] = cx + (int)((h >> 8) % 257u) - 128;
+    s[NS_OBS0 + 3 * k + 1] = cy + (int)((h >> 17) % 257u) - 128;
+    s[NS_OBS0 + 3 * k + 2] = NAV_OBS_R_MIN + (int)(h % 52u);
+  }
+  h = nav_draw(s, seed, genv);
+  centre(&cx, &cy);
+  s[NS_X] = cx;
+  s[NS_Y] = cy;
+  s[NS_H] = (int)(h % (uint32_t)NAV_HEADINGS);
+  h = nav_draw(s, seed, genv);
+  centre(&cx, &cy);
+  s[NS_GX] = cx + (int)((h >> 8) % 257u) - 128;
+  s[NS_GY] = cy + (int)((h >> 17) % 257u) - 128;
+  for (int j = 0; j < n_peds; ++j) {
+    h = nav_draw(s, seed, genv);
+    centre(&cx, &cy);
+    s[NS_PED0 + 4 * j] = cx;
+    s[NS_PED0 + 4 * j + 1] = cy;
+    s[NS_PED0 + 4 * j + 2] = (int)(h % (uint32_t)NAV_HEADINGS);
+    s[NS_PED0 + 4 * j + 3] = NAV_SPEED_MIN + (int)((h >> 12) % 17u);
+  }
+  s[NS_V] = s[NS_W] = s[NS_STEPS] = 0;
+  s[NS_DPREV] = nav_distance(s);
+}
+
+__device__ __forceinline__ bool nav_finite(float a) { return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u; }
+
+// one step of the rules on the LDS copy (NavEnvRef.step), the new episode of a finished env included; every product fits 32 bits
+__device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t genv, int* units_out,
+                            int* done_out) {
+  a0 = nav_finite(a0) ? a0 : 0.0f;
+  a1 = nav_finite(a1) ? a1 : 0.0f;
+  a0 = a0 < 0.0f ? 0.0f : (a0 > 1.0f ? 1.0f : a0);
+  a1 = a1 < -1.0f ? -1.0f : (a1 > 1.0f ? 1.0f : a1);
+  const int v = (int)floorf(a0 * 32.0f), w = (int)truncf(a1 * 64.0f);
+  // 1. the pedestrians, in index order
+  for (int j = 0; j < n_peds; ++j) {
+    int* p = s + NS_PED0 + 4 * j;
+    const int cx = p[0] + ((p[3] * nav_cos(p[2])) >> NAV_Q), cy = p[1] + ((p[3] * nav_sin(p[2])) >> NAV_Q);
+    bool refused = cx * cx + cy * cy > (NAV_ARENA_R - NAV_PED_R) * (NAV_ARENA_R - NAV_PED_R);
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - s[NS_OBS0 + 3 * k], dy = cy - s[NS_OBS0 + 3 * k + 1], rr = NAV_PED_R + s[NS_OBS0 + 3 * k + 2];
+      refused = refused || dx * dx + dy * dy < rr * rr;
+    }
+    if (refused) {
+      p[2] = (int)(nav_draw(s, seed, genv) % (uint32_t)NAV_HEADINGS);
+    } else {
+      p[0] = cx;
+      p[1] = cy;
+    }
+  }
+  // 2. the robot
+  const int h = nav_heading(s[NS_H] + w);
+  const int x = s[NS_X] + ((v * nav_cos(h)) >> NAV_Q), y = s[NS_Y] + ((v * nav_sin(h)) >> NAV_Q);
+  s[NS_X] = x;
+  s[NS_Y] = y;
+  s[NS_H] = h;
+  s[NS_V] = v;
+  s[NS_W] = w;
+  s[NS_STEPS] = (int)((uint32_t)s[NS_STEPS] + 1u);
+  // 3. distance and reward units
+  const int d = nav_distance(s);
+  int units = 2 * (s[NS_DPREV] - d);
+  s[NS_DPREV] = d;
+  // 4. collision  5. goal  6. truncation
+  bool collision = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
+  for (int k = 0; k < n_obs; ++k) {
+    const int dx = x - s[NS_OBS0 + 3 * k], dy = y - s[NS_OBS0 + 3 * k + 1], rr = NAV_ROBOT_R + s[NS_OBS0 + 3 * k + 2];
+    collision = collision || dx * dx + dy * dy < rr * rr;
+  }
+  for (int j = 0; j < n_peds; ++j) {
+    const int dx = x - s[NS_PED0 + 4 * j], dy = y - s[NS_PED0 + 4 * j + 1];
+    collision = collision || dx * dx + dy * dy < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
+  }
+  bool done = collision;
+  if (collision) {
+    units -= NAV_BONUS;
+  } else if (d <= NAV_GOAL_TOL) {
+    units += NAV_BONUS;
+    done = true;
+  } else if (s[NS_STEPS] >= max_steps) {
+    done = true;
+  }
+  if (done) nav_new_episode(s, n_obs, n_peds, seed, genv);
+  *units_out = units;
+  *done_out = done ? 1 : 0;
+}
+
+// the nearest hit of four beams on the circle at (mx, my) from the robot, radius rad (NavEnvRef.lidar; |d|^2 counts as 2^28)
+__device__ __forceinline__ void nav_cast(int mx, int my, int rad, const int* dx, const int* dy, int* rng) {
+  const int cc = mx * mx + my * my - rad * rad;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int t = NAV_RANGE_MAX;
+    if (cc <= 0) {
+      t = 0;
+    } else {
+      const int64_t b = (int64_t)mx * dx[q] + (int64_t)my * dy[q];
+      const int64_t disc = b * b - (int64_t)cc * ((int64_t)1 << 28);
+      if (b > 0 && disc >= 0) t = (int)((b - nav_isqrt(disc)) >> NAV_Q);
+    }
+    rng[q] = min(rng[q], t);
+  }
+}
+
+// Everything behind the step: thread 0 stores the state, then all threads render the observation of the LDS copy `s`.  `ped` is LDS
+// scratch [NAV_MAX_PEDS][4].  Called by every thread of the workgroup, behind a barrier that made `s` final.
+__device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4], int n_obs, int n_peds, int32_t* __restrict__ st,
+                                                     float* __restrict__ laser, float* __restrict__ vector, float* __restrict__ image) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    int4* o = reinterpret_cast<int4*>(st);
+#pragma unroll
+    for (int k = 0; k < NAV_STATE_INTS / 4; ++k) o[k] = make_int4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+  }
+  const int x = s[NS_X], y = s[NS_Y], h = s[NS_H];
+  const int c = nav_cos(h), sn = nav_sin(h);
+  if (tid < n_peds) {  // pedestrian tid in the robot's frame: position, velocity in ticks / step
+    const int* p = s + NS_PED0 + 4 * tid;
+    const int qx = p[0] - x, qy = p[1] - y, rel = nav_heading(p[2] - h);
+    ped[tid][0] = (qx * c + qy * sn) >> NAV_Q;
+    ped[tid][1] = (-qx * sn + qy * c) >> NAV_Q;
+    ped[tid][2] = (p[3] * nav_cos(rel)) >> NAV_Q;
+    ped[tid][3] = (p[3] * nav_sin(rel)) >> NAV_Q;
+  }
+  __syncthreads();
+  // laser: beams 4 tid .. 4 tid + 3
+  if (tid < NAV_BEAMS / 4) {
+    int dx[4], dy[4], rng[4];
+    const int cw = x * x + y * y - NAV_ARENA_R * NAV_ARENA_R;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      int hb = h + NAV_BEAM_STEP * (4 * tid + q);  // below 2 * 3840
+      hb = hb >= NAV_HEADINGS ? hb - NAV_HEADINGS : hb;
+      dx[q] = nav_cos(hb);
+      dy[q] = nav_sin(hb);
+      int t = 0;
+      if (cw < 0) {  // the wall from inside
+        const int64_t b = -((int64_t)x * dx[q] + (int64_t)y * dy[q]);
+        t = (int)((b + nav_isqrt(b * b - (int64_t)cw * ((int64_t)1 << 28))) >> NAV_Q);
+      }
+      rng[q] = t;
+    }
+    for (int k = 0; k < n_obs; ++k) nav_cast(s[NS_OBS0 + 3 * k] - x, s[NS_OBS0 + 3 * k + 1] - y, s[NS_OBS0 + 3 * k + 2], dx, dy, rng);
+    for (int j = 0; j < n_peds; ++j) nav_cast(s[NS_PED0 + 4 * j] - x, s[NS_PED0 + 4 * j + 1] - y, NAV_PED_R, dx, dy, rng);
+    float4 out;
+    out.x = (float)nav_clamp(rng[0], 0, NAV_RANGE_MAX) * 0.00390625f;
+    out.y = (float)nav_clamp(rng[1], 0, NAV_RANGE_MAX) * 0.00390625f;
+    out.z = (float)nav_clamp(rng[2], 0, NAV_RANGE_MAX) * 0.00390625f;
+    out.w = (float)nav_clamp(rng[3], 0, NAV_RANGE_MAX) * 0.00390625f;
+    reinterpret_cast<float4*>(laser)[tid] = out;
+  } else if (tid == NAV_THREADS - 1) {  // vector: goal in the robot's frame, the last action, the distance
+    const int gx = s[NS_GX] - x, gy = s[NS_GY] - y;
+    vector[0] = (float)((gx * c + gy * sn) >> NAV_Q) * 0.00390625f;
+    vector[1] = (float)((-gx * sn + gy * c) >> NAV_Q) * 0.00390625f;
+    vector[2] = (float)s[NS_V] * 0.03125f;
+    vector[3] = (float)s[NS_W] * 0.015625f;
+    vector[4] = (float)s[NS_DPREV] * 0.00390625f;
+  }
+  // pedestrian map: chunk = 4 consecutive cells of one row of one channel; the lowest pedestrian index that covers a cell wins
+  for (int ck = tid; ck < NAV_MAP_CHUNKS; ck += NAV_THREADS) {
+    const int ch = ck / (NAV_MAP * NAV_MAP / 4), rem = ck - ch * (NAV_MAP * NAV_MAP / 4);
+    const int row = rem / (NAV_MAP / 4), col0 = (rem - row * (NAV_MAP / 4)) * 4;
+    const int fwd = (NAV_MAP / 2 - row) * NAV_MAP_CELL - NAV_MAP_CELL / 2;
+    float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int j = n_peds - 1; j >= 0; --j) {
+      const int df = fwd - ped[j][0];
+      const float pv = ch == 0 ? 1.0f : (float)ped[j][ch + 1] * 0.03125f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int dl = (NAV_MAP / 2 - (col0 + q)) * NAV_MAP_CELL - NAV_MAP_CELL / 2 - ped[j][1];
+        if (df * df + dl * dl <= NAV_PED_R * NAV_PED_R) val[q] = pv;
+      }
+    }
+    reinterpret_cast<float4*>(image)[ck] = make_float4(val[0], val[1], val[2], val[3]);
+  }
+}
+
+__global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
+                                                                   int n_peds, int max_steps, const float* __restrict__ actions,
+                                                                   float* __restrict__ laser, float* __restrict__ vector,
+                                                                   float* __restrict__ image, float* __restrict__ reward,
+                                                                   uint8_t* __restrict__ done) {
+  __shared__ int s[NAV_STATE_INTS];
+  __shared__ int ped[NAV_MAX_PEDS][4];
+  const int64_t i = blockIdx.x;
+  const int tid = threadIdx.x;
+  int32_t* st = state + i * NAV_STATE_INTS;
+  if (tid < NAV_STATE_INTS) s[tid] = nav_sanitize_word(tid, st[tid], n_obs, n_peds);
+  __syncthreads();  // the old state is in LDS: nothing reads the env's global words after this, thread 0 alone writes them
+  if (tid == 0) {
+    int units, d;
+    nav_advance(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, (uint32_t)(env0 + i), &units, &d);
+    reward[i] = (float)units * 0.00390625f;
+    done[i] = (uint8_t)d;
+  }
+  __syncthreads();  // the new state is final
+  nav_store_and_render(s, ped, n_obs, n_peds, st, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
+}
+
+__global__ __launch_bounds__(NAV_THREADS) void nav_env_reset_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
+                                                                    int n_peds, const uint8_t* __restrict__ mask,
+                                                                    float* __restrict__ laser, float* __restrict__ vector,
+                                                                    float* __restrict__ image) {
+  __shared__ int s[NAV_STATE_INTS];
+  __shared__ int ped[NAV_MAX_PEDS][4];
+  const int64_t i = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (mask != nullptr && mask[i] == 0) return;  // uniform over the workgroup; the env's state and observation stay as they are
+  if (tid < NAV_STATE_INTS) s[tid] = 0;
+  __syncthreads();
+  if (tid == 0) nav_new_episode(s, n_obs, n_peds, seed, (uint32_t)(env0 + i));
+  __syncthreads();
+  nav_store_and_render(s, ped, n_obs, n_peds, state + i * NAV_STATE_INTS, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR,
+                       image + i * NAV_MAP_FLOATS);
+}
+
+// what both operators check of n, env0 and the populations: 1 <= n, global env indices inside 32 bits
+inline bool nav_range_ok(int32_t n, int64_t env0, int32_t n_obs, int32_t n_peds) {
+  return n >= 1 && env0 >= 0 && env0 + (int64_t)n <= ((int64_t)1 << 32) && n_obs >= 0 && n_obs <= NAV_MAX_OBS && n_peds >= 0 &&
+         n_peds <= NAV_MAX_PEDS;
+}
+
+}  // namespace ddrl
+
+using namespace ddrl;
+
+extern "C" {
+
+// every check comes before the first HIP call: a host without a GPU gets the same answers
+
+int32_t ddrl_op_nav_env_state_ints(void) { return NAV_STATE_INTS; }
+
+int32_t ddrl_op_nav_env_trig(int32_t* cos_sin_host) {
+  if (!cos_sin_host) return DDRL_ERR_INVALID_ARG;
+  memcpy(cos_sin_host, nav_trig_host, sizeof(nav_trig_host));
+  return DDRL_OK;
+}
+
+int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                              const uint8_t* mask, float* laser, float* vector, float* image, void* stream) {
+  if (!state || !laser || !vector || !image || !nav_range_ok(n, env0, n_obstacles, n_peds)) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3)) return DDRL_ERR_INVALID_ARG;
+  const void* src[1] = {mask};
+  const uint64_t src_b[1] = {(uint64_t)n};
+  void* dst[4] = {state, laser, vector, image};
+  const uint64_t dst_b[4] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
+                             (uint64_t)n * NAV_MAP_FLOATS * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 4)) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(nav_env_reset_kernel, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed, n_obstacles,
+                     n_peds, mask, laser, vector, image);
+  return launch_status();
+}
+
+int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
+                             const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream) {
+  if (!state || !actions || !laser || !vector || !image || !reward || !done || !nav_range_ok(n, env0, n_obstacles, n_peds))
+    return DDRL_ERR_INVALID_ARG;
+  if (max_steps < 1) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
+      ((uintptr_t)reward & 3))
+    return DDRL_ERR_INVALID_ARG;
+  const void* src[1] = {actions};
+  const uint64_t src_b[1] = {(uint64_t)n * 8};
+  void* dst[6] = {state, laser, vector, image, reward, done};
+  const uint64_t dst_b[6] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
+                             (uint64_t)n * NAV_MAP_FLOATS * 4, (uint64_t)n * 4, (uint64_t)n};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 6)) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(nav_env_step_kernel, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed, n_obstacles,
+                     n_peds, max_steps, actions, laser, vector, image, reward, done);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@ a trajectory is reproducible bit for bit from (game, seed, global env index, act
 import torch
 
 from ddrl4nav_amd import ops
+from ddrl4nav_amd.env.device_nav_env import NAV_ENV_NAME, make_device_nav_env
 
 ENV_NAMES = {"DevicePong-v0": "pong", "DeviceCatch-v0": "catch"}
 _PARAMS = ("game", "n_envs", "seed", "n_actions", "points", "max_steps", "env0")
@@ -76,10 +77,13 @@ class DeviceEnv:
 
 def make_device_env(config_env, device=None, env0=0):
     """The DeviceEnv of a config_env dict: env_name "DevicePong-v0" / "DeviceCatch-v0", env_num, and the optional knobs env_seed,
-    discrete_actions (its length is n_actions), env_points, env_max_steps."""
+    discrete_actions (its length is n_actions), env_points, env_max_steps; or the DeviceNavEnv of env_name "DeviceNav-v0" with env_num,
+    env_seed, env_obstacles, env_peds, env_max_steps (env/device_nav_env.py)."""
     name = config_env.get("env_name")
+    if name == NAV_ENV_NAME:
+        return make_device_nav_env(config_env, device=device, env0=env0)
     if name not in ENV_NAMES:
-        raise ValueError("env_name must be one of %s, got %r" % (sorted(ENV_NAMES), name))
+        raise ValueError("env_name must be one of %s, got %r" % (sorted(ENV_NAMES) + [NAV_ENV_NAME], name))
     if "env_num" not in config_env:
         raise ValueError("config_env needs env_num")
     actions = config_env.get("discrete_actions")

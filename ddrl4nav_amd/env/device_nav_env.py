@@ -1,0 +1,89 @@
+"""DeviceNavEnv: 2-D robot navigation stepped and observed on the GPU (csrc/navenv.hip).
+
+The reference's robot_nav task talks to a ROS simulator (img_env) that is not part of its tree.  A DeviceNavEnv stands where it stood:
+a differential-drive robot, static circular obstacles and walking pedestrians in a round arena, and the three observation components
+NavPreNet1D reads -- laser [1, 960], vector [5], pedestrian map [3, 48, 48], fp32 -- written by one launch per step for all N envs.
+The rules are integer-only (tests/nav_env_ref.py is the rule book), so a trajectory is reproducible bit for bit from (seed, global env
+index, populations, actions)."""
+import torch
+
+from ddrl4nav_amd import ops
+
+NAV_ENV_NAME = "DeviceNav-v0"
+_PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
+
+
+class DeviceNavEnv:
+    state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
+
+    def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0):
+        """n_obstacles 0..10 static circles, n_peds 0..5 pedestrians; an episode ends at a collision, at the goal or after max_steps
+        steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv."""
+        self.N, self.seed, self.env0 = int(n_envs), int(seed), int(env0)
+        self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
+        if self.N < 1:
+            raise ValueError("n_envs must be at least 1, got %d" % self.N)
+        if not 0 <= self.n_obstacles <= 10:
+            raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
+        if not 0 <= self.n_peds <= 5:
+            raise ValueError("n_peds must be in 0..5, got %d" % self.n_peds)
+        if self.max_steps < 1:
+            raise ValueError("max_steps must be at least 1, got %d" % self.max_steps)
+        if not 0 <= self.seed < 2 ** 32:
+            raise ValueError("seed must fit 32 bits, got %d" % self.seed)
+        if self.env0 < 0 or self.env0 + self.N > 2 ** 32:
+            raise ValueError("global env indices env0 .. env0 + n_envs - 1 must fit 32 bits")
+        dev = torch.device("cuda" if device is None else device)
+        self.device = dev
+        self.state = torch.zeros((self.N, ops.nav_env_state_ints()), dtype=torch.int32, device=dev)
+        self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
+        self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
+        self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
+
+    @property
+    def n_envs(self):
+        return self.N
+
+    def _obs_out(self, obs_out):
+        return self.obs if obs_out is None else list(obs_out)
+
+    def reset(self, mask=None, obs_out=None):
+        """A new first episode for every env, or for those with a non-zero entry in mask (uint8 [N] on the device); returns the
+        observation [laser, vector, image] (the env's own tensors, or obs_out: contiguous fp32 device tensors of those shapes, laser and
+        image 16-byte aligned -- the rows of a StateRollout's pools are).  A masked-out env's rows are not written."""
+        return ops.nav_env_reset(self.state, self._obs_out(obs_out), env0=self.env0, seed=self.seed, n_obstacles=self.n_obstacles,
+                                 n_peds=self.n_peds, mask=mask)
+
+    def step(self, actions, obs_out=None):
+        """actions fp32 [N, 2] on the device (what a Gaussian actor's act() returns) -> ([laser, vector, image], reward fp32 [N], done
+        uint8 [N]): device tensors the env owns, valid until the next step (obs_out: render there instead).  A finished env has already
+        begun its next episode: the observation is that episode's first and done is the reset flag.  Asynchronous."""
+        return ops.nav_env_step(self.state, actions, self._obs_out(obs_out), self.reward, self.done, env0=self.env0, seed=self.seed,
+                                n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)
+
+    def state_dict(self):
+        """The state words (a host tensor) and the parameters: an env loaded from it continues bit-identically."""
+        sd = {k: getattr(self, k) for k in _PARAMS}
+        sd["state"] = self.state.cpu()
+        return sd
+
+    def load_state_dict(self, sd):
+        for k in _PARAMS:
+            if sd[k] != getattr(self, k):
+                raise ValueError("%s differs between the saved env (%r) and this one (%r)" % (k, sd[k], getattr(self, k)))
+        s = torch.as_tensor(sd["state"])
+        if s.dtype != torch.int32 or tuple(s.shape) != tuple(self.state.shape):
+            raise ValueError("state must be int32 %s, got %s %s" % (tuple(self.state.shape), s.dtype, tuple(s.shape)))
+        self.state.copy_(s)
+
+
+def make_device_nav_env(config_env, device=None, env0=0):
+    """The DeviceNavEnv of a config_env dict: env_name "DeviceNav-v0", env_num, and the optional knobs env_obstacles, env_peds,
+    env_max_steps, env_seed."""
+    if config_env.get("env_name") != NAV_ENV_NAME:
+        raise ValueError("env_name must be %r, got %r" % (NAV_ENV_NAME, config_env.get("env_name")))
+    if "env_num" not in config_env:
+        raise ValueError("config_env needs env_num")
+    return DeviceNavEnv(int(config_env["env_num"]), device=device, seed=int(config_env.get("env_seed", 0)),
+                        n_obstacles=int(config_env.get("env_obstacles", 10)), n_peds=int(config_env.get("env_peds", 5)),
+                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0)

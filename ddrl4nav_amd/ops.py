@@ -401,6 +401,62 @@ def env_step(game, state, actions, frame, reward, done, env0=0, n_actions=6, poi
     return frame, reward, done
 
 
+NAV_ENV_SHAPES = [(1, 960), (5,), (3, 48, 48)]   # laser, vector, pedestrian map: what ddrl_op_nav_env_* write per env, fp32
+NAV_ENV_HEADINGS = 3840
+
+
+@functools.lru_cache(maxsize=None)
+def nav_env_state_ints():
+    """The int32 words of one navigation env's state (include/ddrl.h ddrl_op_nav_env_state_ints; a constant of the library)."""
+    return int(_lib.load().ddrl_op_nav_env_state_ints())
+
+
+def nav_env_trig():
+    """The Q14 table the navigation kernels index, as a host tensor int32 [2, 3840] (cos, sin) (include/ddrl.h ddrl_op_nav_env_trig)."""
+    out = torch.empty((2, NAV_ENV_HEADINGS), dtype=torch.int32)
+    check(_lib.load().ddrl_op_nav_env_trig(c_void_p(out.data_ptr())))
+    return out
+
+
+def _nav_env_args(state, obs):
+    """n of a navigation-env call after the checks both operators share: state int32 [n, nav_env_state_ints()] and the three observation
+    components fp32 [n, 1, 960], [n, 5], [n, 3, 48, 48], contiguous, on one device, laser and image 16-byte aligned."""
+    assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 \
+        and state.shape[1] == nav_env_state_ints(), "state: contiguous int32 [n, nav_env_state_ints()] on the device"
+    n = state.shape[0]
+    assert len(obs) == 3, "obs: [laser, vector, image]"
+    for name, t, shape in zip(("laser", "vector", "image"), obs, NAV_ENV_SHAPES):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (n,) + shape \
+            and t.device == state.device, "%s: contiguous fp32 %s on the state's device" % (name, ("n",) + shape)
+    assert obs[0].data_ptr() % 16 == 0 and obs[2].data_ptr() % 16 == 0, "laser / image: the base must be 16-byte aligned"
+    return n
+
+
+def nav_env_reset(state, obs, env0=0, seed=0, n_obstacles=10, n_peds=5, mask=None):
+    """A new first episode for every env of `state`, or for those with a non-zero byte in mask (uint8 [n]), and their first observations
+    obs = [laser, vector, image] (include/ddrl.h ddrl_op_nav_env_reset; csrc/navenv.hip).  Asynchronous on the current stream; returns
+    obs."""
+    n = _nav_env_args(state, obs)
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == n
+                            and mask.device == state.device), "mask: contiguous uint8 [n] on the state's device"
+    check(_lib.load().ddrl_op_nav_env_reset(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), _p(mask),
+                                            _p(obs[0]), _p(obs[1]), _p(obs[2]), _st()))
+    return obs
+
+
+def nav_env_step(state, actions, obs, reward, done, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
+    """One step of every env (include/ddrl.h ddrl_op_nav_env_step; csrc/navenv.hip): actions fp32 [n, 2] -> state (in place), obs =
+    [laser, vector, image], reward fp32 [n], done uint8 [n].  Asynchronous on the current stream; returns (obs, reward, done)."""
+    n = _nav_env_args(state, obs)
+    assert tuple(_f32(actions).shape) == (n, 2) and _f32(reward).numel() == n and actions.device == state.device \
+        and reward.device == state.device, "actions fp32 [n, 2], reward fp32 [n] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
+        and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
+    check(_lib.load().ddrl_op_nav_env_step(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps),
+                                           _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward), _p(done), _st()))
+    return obs, reward, done
+
+
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off
 
 

@@ -1,8 +1,10 @@
-"""The closed loop on one GPU: a DeviceRollout / PlaneRollout driven by a DeviceEnv (env/device_env.py), then net.learn on its batch.
+"""The closed loop on one GPU: a DeviceRollout / PlaneRollout driven by a DeviceEnv (env/device_env.py), or a StateRollout driven by a
+DeviceNavEnv (env/device_nav_env.py; collect_states / train_states), then net.learn on its batch.
 
 Every tensor that moves between acting, the env and the pools is a device tensor and every call is asynchronous on the current stream:
 a rollout adds no host synchronisation to what act(), record() and the puts do already (none, for device arguments).  On a PlaneRollout
-the env renders straight into the pool row the frame belongs to (PlaneRollout.new_frame_row), so the put copies nothing."""
+the env renders straight into the pool row the frame belongs to (PlaneRollout.new_frame_row), so the put copies nothing; on a
+StateRollout it renders into StateRollout.state_rows."""
 
 
 def _row(ro, t):
@@ -47,6 +49,51 @@ def train(net, env, ro, updates, keep_step=False):
     (the last loss dict of net.learn, ro.returns.mean_return() -- None without track_returns)."""
     for _ in range(int(updates)):
         collect(ro, env, keep_step=keep_step)
+        losses = None
+        for item in net.learn(ro.batch()):
+            losses = item[0]
+        yield losses, (ro.returns.mean_return() if ro.returns is not None else None)
+        ro.carry_over(keep_step=keep_step)
+
+
+def collect_states(ro, env, keep_step=False, reset=None):
+    """collect() for a StateRollout `ro` and an env whose observation is a list of fp32 components (DeviceNavEnv): act(t) ->
+    env.step(obs_out=ro.state_rows(t + 1)) -> record(t, reward, done) -> put_states_in_place(t + 1) for t = t0 .. T - 1, then
+    bootstrap() and finish().  The env renders into the pool rows, so no observation is copied.
+
+    reset (None: True for ro's first rollout, ro.rollouts == 0 with nothing carried over): the env is reset into slot 0.  Otherwise
+    slot 0 is what carry_over() left there.
+    keep_step: as for collect() -- bootstrap(sample=True) draws the (T + 1)-th action, the env plays it into its own tensors and its
+    reward and done are recorded in row T; the next rollout starts at ro.t0 == 1 and copies that observation into slot 1."""
+    T = ro.T
+    if env.N != ro.N:
+        raise ValueError("the env has %d envs, the rollout %d" % (env.N, ro.N))
+    if reset is None:
+        reset = ro.rollouts == 0 and ro.t0 == 0
+    if reset:
+        if ro.t0 != 0:
+            raise ValueError("a rollout that carried a whole step over cannot restart its env")
+        env.reset(obs_out=ro.state_rows(0))
+        ro.put_states_in_place(0)
+    elif ro.t0 == 1:
+        # the kept step's action was played at the end of the previous rollout: env.obs is the observation of slot 1
+        ro.put_states(1, env.obs)
+    for t in range(ro.t0, T):
+        _, reward, done = env.step(ro.act(t), obs_out=ro.state_rows(t + 1))
+        ro.record(t, reward, done)
+        ro.put_states_in_place(t + 1)
+    action = ro.bootstrap(sample=keep_step)
+    if keep_step:
+        _, reward, done = env.step(action)
+        ro.record(T, reward, done)
+    ro.finish()
+
+
+def train_states(net, env, ro, updates, keep_step=False):
+    """train() for a StateRollout: collect_states(ro, env), net.learn(ro.batch()), carry_over(keep_step).  Yields, per update, (the last
+    loss dict of net.learn, ro.returns.mean_return() -- None without track_returns)."""
+    for _ in range(int(updates)):
+        collect_states(ro, env, keep_step=keep_step)
         losses = None
         for item in net.learn(ro.batch()):
             losses = item[0]

@@ -780,6 +780,36 @@ int32_t ddrl_op_env_reset(int32_t game, int32_t* state, int32_t n, int64_t env0,
 int32_t ddrl_op_env_step(int32_t game, int32_t* state, int32_t n, int64_t env0, int32_t n_actions, int32_t points, int32_t max_steps,
                          uint32_t seed, const float* actions, uint8_t* frame, float* reward, uint8_t* done, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device navigation env: a differential-drive robot, up to 10 static circular obstacles and up to 5 walking pedestrians in a round
+ * arena, stepped and observed on the GPU (additive: ABI 3; the rules are tests/nav_env_ref.py, in integers only,
+ * and the kernels reproduce them bit for bit).  Context-free, no allocation, no atomics, asynchronous on `stream`; the same arguments and
+ * data give the same bits.  One launch serves all n envs.  The observation is what NavPreNet1D reads:
+ *   laser   float32 [n][1][960], 16-byte aligned: ranges in metres (0 .. 6), beam 0 straight ahead, counter-clockwise
+ *   vector  float32 [n][5]: the goal in the robot's frame (m), the last v / 32 and w / 64, the distance to the goal (m)
+ *   image   float32 [n][3][48][48], 16-byte aligned: the egocentric pedestrian map (occupancy, velocity forward / left)
+ *   state   int32 [n][ddrl_op_nav_env_state_ints()], 16-byte aligned
+ *   env0    the global index of local env 0 (the random draws hash (seed, env0 + i, event counter)): 0 <= env0, env0 + n <= 2^32
+ * Env i is written at laser + i * 960, vector + i * 5, image + i * 6912 and nowhere else.  A null pointer (the mask excepted), n < 1,
+ * n_obstacles outside 0..10, n_peds outside 0..5, a misaligned state, laser or image, an overlap of two arguments:
+ * DDRL_ERR_INVALID_ARG, decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+/* the int32 words of one env's state (64) */
+int32_t ddrl_op_nav_env_state_ints(void);
+/* Host only: copies out the Q14 table the kernels index, cos[3840] then sin[3840] of 2 pi k / 3840 (7,680 words). */
+int32_t ddrl_op_nav_env_trig(int32_t* cos_sin_host);
+/* A new first episode (all counters zero) for every env, or for those with a non-zero byte in mask (uint8 [n], NULL = all); their first
+ * observations are rendered.  The state and observation of an env whose mask byte is zero are not touched. */
+int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                              const uint8_t* mask, float* laser, float* vector, float* image, void* stream);
+/* One step of every env: actions float32 [n][2] (v = floor(clamp(a0, 0, 1) * 32) ticks of 1/256 m, w = trunc(clamp(a1, -1, 1) * 64)
+ * heading steps of 2 pi / 3840; a component that is not finite counts as 0) -> the new state, its observation, reward float32 [n] (a
+ * multiple of 1/256: twice the progress towards the goal in metres, -15 for a collision, +15 at the goal) and done uint8 [n].  A
+ * finished env (collision, goal, or max_steps steps) starts its next episode in the same launch: the observation is that episode's first
+ * and done is the reset flag.  max_steps >= 1; actions, vector and reward 4-byte aligned. */
+int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
+                             const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,143 @@
+#!/usr/bin/env python
+"""What the device navigation env costs (env/device_nav_env.py, csrc/navenv.hip), on one box in one process, the
+legs of each measurement alternating:
+
+  (a) kernel   ddrl_op_nav_env_step for N envs against a plain device-to-device copy of the same N * 31,508 observation bytes -- what a
+               rollout spends to take a ready-made device observation.  `calls` launches between one pair of device events give one
+               sample (time per call); the samples of the two legs alternate.
+  (b) acting   one rollout's acting phase on a StateRollout of BASELINE config 4's net (NavPreNet1D x2 + GaussionActor(2)), T steps
+               between one pair of events: act -> env.step rendering into the pool rows -> record -> put_states_in_place, against the
+               same phase on observations that are in the pool already (act -> record), and against the T act() calls and the T
+               env.step calls alone.  env.step against act() at the same N is the comparison DESIGN.md reports.
+
+Every leg is warmed up first; a leg reports the median, the p95 and the extremes of its samples.  Prints one JSON line.
+
+    python tools/bench_device_nav_env.py [--envs 512] [--steps 256] [--calls 200] [--samples 30] [--runs 10] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import sys
+import types
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tools.bench_device_env import summary, timed  # noqa: E402
+
+OBS_FLOATS = 960 + 5 + 3 * 48 * 48
+
+
+def make_net(max_batch, seed=0, **config_nn):
+    """BASELINE config 4's net through create_net, as tools/bench_nav.py builds it; config_nn: ConfigNN fields to override."""
+    from ddrl4nav_amd.config import BaseConfig, ConfigNN
+    from ddrl4nav_amd.runner import create_net
+    env = {"env_type": "gym", "env_name": "PongNoFrameskip-v4", "env_num": 8, "discrete_action": False, "act_dim": 2, "image_batch": 1,
+           "ped_sim": {"total": 3}}
+    cfg = BaseConfig(types.SimpleNamespace(task="bench_device_nav_env", ip="127.0.0.1"), env)
+    cfg.TASK_TYPE = "robot_nav"
+    cfg_nn = ConfigNN(env)
+    cfg_nn.SHARE_CNN_NET = False
+    for name, value in config_nn.items():
+        setattr(cfg_nn, name, value)
+    torch.manual_seed(seed)
+    return create_net({"config": cfg, "config_nn": cfg_nn, "config_env": env}, max_batch=max_batch)
+
+
+def kernel_legs(args):
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N = args.envs
+    env = DeviceNavEnv(N, device="cuda", seed=1)
+    env.reset()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
+    src = torch.rand((N, OBS_FLOATS), device="cuda", generator=g)
+    dst = torch.empty_like(src)
+
+    def steps():
+        for _ in range(args.calls):
+            env.step(actions)
+
+    def copies():
+        for _ in range(args.calls):
+            dst.copy_(src)
+
+    for _ in range(args.warmup):
+        steps()
+        copies()
+    torch.cuda.synchronize()
+    ms = {"env_step": [], "d2d_copy": []}
+    for _ in range(args.samples):
+        ms["env_step"].append(timed(steps))
+        ms["d2d_copy"].append(timed(copies))
+    out = {k: summary(v, per=args.calls) for k, v in ms.items()}
+    out["bytes_per_call"] = N * OBS_FLOATS * 4
+    out["step_over_copy"] = round(out["env_step"]["median_us"] / out["d2d_copy"]["median_us"], 3)
+    return out
+
+
+def acting_legs(args):
+    from ddrl4nav_amd.agent import StateRollout
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N, T = args.envs, args.steps
+    net = make_net(N)
+    env = DeviceNavEnv(N, device="cuda", seed=1)
+    ro = StateRollout(net, N, env.state_shapes, horizon=T)
+    env.reset(obs_out=ro.state_rows(0))
+    ro.put_states_in_place(0)
+
+    def with_env():
+        for t in range(T):
+            _, r, d = env.step(ro.act(t), obs_out=ro.state_rows(t + 1))
+            ro.record(t, r, d)
+            ro.put_states_in_place(t + 1)
+
+    def in_pool():                      # the observations the env left in the pool, its last reward and done
+        for t in range(T):
+            ro.act(t)
+            ro.record(t, env.reward, env.done)
+
+    def act_only():
+        for t in range(T):
+            ro.act(t)
+
+    def env_only():
+        for t in range(T):
+            env.step(ro._actions[t], obs_out=ro.state_rows(t + 1))
+
+    legs = {"device_env": with_env, "observations_in_pool": in_pool, "act_only": act_only, "env_step_only": env_only}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.runs):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    out = {k: summary(v, unit="ms") for k, v in ms.items()}
+    out["device_env_over_in_pool"] = round(out["device_env"]["median_ms"] / out["observations_in_pool"]["median_ms"], 4)
+    out["env_step_over_act"] = round(out["env_step_only"]["median_ms"] / out["act_only"]["median_ms"], 4)
+    out["env_steps_per_s_device_env"] = round(N * T / (out["device_env"]["median_ms"] / 1000.0))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--calls", type=int, default=200, help="launches per sample of the kernel legs")
+    ap.add_argument("--samples", type=int, default=30)
+    ap.add_argument("--runs", type=int, default=10, help="timed acting phases per leg")
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_device_nav_env needs a GPU: there is nothing to measure without one")
+    out = {"tool": "bench_device_nav_env", "N": args.envs, "T": args.steps, "device": torch.cuda.get_device_name(0),
+           "kernel": kernel_legs(args), "acting": acting_legs(args)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

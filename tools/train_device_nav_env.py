@@ -1,0 +1,102 @@
+#!/usr/bin/env python
+"""Train BASELINE config 4's net (NavPreNet1D x2 + GaussionActor(2)) on the device navigation env (env/device_nav_env.py; DESIGN.md
+section 6.8): the whole loop -- acting, the env, GAE, the update -- on one GPU through runner/device_loop.train_states.  Writes the
+mean-return curve as JSON: per update the env steps so far, the mean return of the envs' latest finished episodes
+(EpisodeReturns.mean_return) and the last loss dict of the update; next to it the return of the uniform-random policy (a0 ~ U(0, 1),
+a1 ~ U(-1, 1)) on the same env, measured first on the device over --baseline-steps steps.
+
+    python tools/train_device_nav_env.py [--envs 256] [--horizon 64] [--updates 100] [--obstacles 10] [--peds 5] [--max-steps 500]
+                                         [--iters 4] [--actor-lr R] [--critic-lr R] [--normalize-obs] [--seed 0] [--out curve.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tools.bench_device_nav_env import make_net  # noqa: E402
+
+
+def random_policy_return(env, steps, seed):
+    """(mean return per finished episode, mean reward per env per 1,000 steps) of uniform-random actions; leaves the env reset."""
+    g = torch.Generator(device=env.device).manual_seed(seed)
+    scale, shift = torch.tensor([1.0, 2.0], device=env.device), torch.tensor([0.0, 1.0], device=env.device)
+    env.reset()
+    total = torch.zeros((), dtype=torch.float64, device=env.device)
+    episodes = torch.zeros((), dtype=torch.float64, device=env.device)
+    for _ in range(steps):
+        _, r, d = env.step(torch.rand((env.N, 2), device=env.device, generator=g) * scale - shift)
+        total += r.sum()
+        episodes += d.sum()
+    env.reset()
+    total, episodes = float(total.item()), float(episodes.item())
+    return (total / episodes if episodes else float("nan")), 1000.0 * total / (env.N * steps)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--horizon", type=int, default=64)
+    ap.add_argument("--updates", type=int, default=100)
+    ap.add_argument("--obstacles", type=int, default=10)
+    ap.add_argument("--peds", type=int, default=5)
+    ap.add_argument("--max-steps", type=int, default=500)
+    ap.add_argument("--iters", type=int, default=4, help="TRAINING_ITER_TIME: passes over a rollout's batch")
+    ap.add_argument("--micro-batch", type=int, default=4096, help="the net's max_batch: samples per launch of the update")
+    ap.add_argument("--actor-lr", type=float, default=None)
+    ap.add_argument("--critic-lr", type=float, default=None)
+    ap.add_argument("--normalize-obs", action="store_true", help="StateRollout(normalize_obs=True)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--baseline-steps", type=int, default=1000)
+    ap.add_argument("--log-every", type=int, default=10)
+    ap.add_argument("--out", default=None, help="the curve as JSON (default: printed only)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("train_device_nav_env needs a GPU")
+
+    from ddrl4nav_amd.agent import StateRollout
+    from ddrl4nav_amd.env import make_device_env
+    from ddrl4nav_amd.runner.device_loop import train_states
+
+    knobs = {"TRAINING_ITER_TIME": args.iters}
+    for name, value in (("ACTOR_LEARNING_RATE", args.actor_lr), ("CRITIC_LEARNING_RATE", args.critic_lr)):
+        if value is not None:
+            knobs[name] = value
+    net = make_net(max(args.micro_batch, args.envs), seed=args.seed, **knobs)
+    env = make_device_env({"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
+                           "env_peds": args.peds, "env_max_steps": args.max_steps}, device=net.device)
+    ro = StateRollout(net, args.envs, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None)
+
+    per_episode, per_1000 = random_policy_return(env, args.baseline_steps, args.seed + 1)
+    out = {"tool": "train_device_nav_env", "N": args.envs, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
+           "max_steps": args.max_steps, "iters": args.iters, "normalize_obs": bool(args.normalize_obs),
+           "device": torch.cuda.get_device_name(0),
+           "random_policy": {"return_per_episode": per_episode, "reward_per_env_per_1000_steps": per_1000, "steps": args.baseline_steps},
+           "curve": []}
+    print("random policy: %.3f per episode, %.2f per env per 1,000 steps" % (per_episode, per_1000), flush=True)
+    t0 = time.time()
+    for u, (losses, mean_return) in enumerate(train_states(net, env, ro, args.updates), 1):
+        out["curve"].append({"update": u, "env_steps": u * args.envs * args.horizon, "mean_return": mean_return,
+                             "losses": {k: v for k, v in losses.items() if k != "PpoBackUpTime"}})
+        if u % args.log_every == 0 or u == args.updates:
+            print("update %4d  steps %9d  mean return %8.3f  VLoss %.4f  EntLoss %.4f  %.0f s"
+                  % (u, u * args.envs * args.horizon, mean_return, losses["VLoss"], losses["EntLoss"], time.time() - t0), flush=True)
+    out["seconds"] = round(time.time() - t0, 1)
+    out["env_steps_per_s_end_to_end"] = round(args.updates * args.envs * args.horizon / max(out["seconds"], 1e-9))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f)
+    brief = {k: v for k, v in out.items() if k != "curve"}
+    brief["first_return"] = next((c["mean_return"] for c in out["curve"] if c["mean_return"] == c["mean_return"]), None)
+    brief["last_return"] = out["curve"][-1]["mean_return"] if out["curve"] else None
+    print(json.dumps(brief))
+
+
+if __name__ == "__main__":
+    main()
