@@ -171,6 +171,14 @@ constexpr int AMAX_WL = 0, AMAX_W2 = 1, AMAX_W3 = 2, AMAX_W1 = 3, AMAX_A1 = 4, A
 // absolute error floor of the planes (2^-25 of their unit) does not rise against the per-tensor scheme.
 constexpr float WGRAD_HEADROOM = 4.0f;
 constexpr int GSC_EXP_MIN = -60, GSC_EXP_MAX = 60;  // clamp of log2 g_s: keeps plane_scale / g_max and g_max / scales inside fp32
+// ... together with PLANE_SCALE_EXP_MAX.  A sample whose largest |gradient| lies below 2^GSC_EXP_MIN keeps g_s = 2^-60 and a normalised
+// maximum BELOW 1 -- as far below as fp32 goes, 2^-89 -- and when every sample of a batch is like that (a collapsed policy under the
+// split entropy bonus: d(loss)/d(features) ~ theta e^-gap, 1e-34 at a logit gap of 70) the slot's plane scale grew to 2^101 and
+// WGRAD_HEADROOM x plane_scale / g_max to infinity: inf x 0 in the staging, NaN in every gradient of that encoder.  No plane scale
+// above 2^40: 4 x 2^40 / 2^-60 = 2^102, and times an activation's plane scale (<= 2^23 for a maximum of 2^-10 or more) still a number.
+// Below a normalised maximum of 2^-27 the planes then hold fewer bits (down to fp16's subnormals: raw magnitudes to 2^-129, fp32's
+// own limit) instead of none.  Nothing changes for a tensor whose largest magnitude is 2^-27 or more.
+constexpr int PLANE_SCALE_EXP_MAX = 40;
 // AMAX_A1 is not measured: pixels / 255 lie in [0, 1], so |a1[oc]| <= sum_k |w1[oc][k]| + |b1[oc]|; pack_weights stores the largest
 // such bound with the weight slots (a few times the measured maximum: two of the sixteen spare binades of the fp16 planes),
 // which spares conv1's epilogue a maximum per output and an atomic per wave
@@ -180,7 +188,7 @@ __host__ __device__ inline float f16_scale(float m) {
   if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f;
   int e;
   frexpf(m, &e);  // m = f * 2^e, f in [0.5, 1)
-  return ldexpf(1.0f, 13 - e);
+  return ldexpf(1.0f, 13 - e < PLANE_SCALE_EXP_MAX ? 13 - e : PLANE_SCALE_EXP_MAX);
 }
 constexpr int HEAD_WG = 256;   // workgroups of the heads/loss kernel (fixed -> deterministic)
 constexpr int NORM_WG = 1024;  // workgroups of the grad-norm kernel

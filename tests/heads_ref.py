@@ -97,11 +97,22 @@ def make_case(continuous, A, n, shared, smooth, hyper=None, seed=0, B_global=Non
     else:
         a = torch.arange(n) % A                          # every action present (n >= A), in a shuffled order
         c.actions = a[torch.randperm(n, generator=g)].float()
-    _, logp64, _, v64, _ = forward(c, ha64, hc64, P64, torch.float64)
     pairs = _pairs(RATIOS[round(hyper["ppo_clip"], 3)])
-    idx = torch.arange(n)
     sign = torch.tensor([pairs[i % 18][0] for i in range(n)], dtype=torch.float64)
     target = torch.tensor([pairs[i % 18][1] for i in range(n)], dtype=torch.float64)
+    _place(c, g, sign, target)
+    return c
+
+
+def _place(c, g, sign, target):
+    """The batch columns that depend on the policy, placed from the float64 forward of the case's features, parameters and actions:
+    advantages of the given signs, old_logps for the target ratios, returns at the Huber cycle of distances from the value."""
+    n, hyper = c.n, c.hyper
+    P64 = {k: v.double() for k, v in c.params.items()}
+    ha64 = c.ha.double()
+    hc64 = ha64 if c.shared else c.hc.double()
+    _, logp64, _, v64, _ = forward(c, ha64, hc64, P64, torch.float64)
+    idx = torch.arange(n)
     mag = torch.randn(n, generator=g).double().abs() * torch.where(idx % 10 == 7, 1e-4, 1.0)
     adv = sign * mag
     if n >= 16:
@@ -118,11 +129,12 @@ def make_case(continuous, A, n, shared, smooth, hyper=None, seed=0, B_global=Non
     return c
 
 
-def check_recipe(c):
+def check_recipe(c, every_action=True):
     """The recipe's own promises (a CPU test runs them for every case of the GPU grid): every sample's float64 ratio sits
     more than 1e-3 from each branch boundary, so the fp32 ratio a kernel forms (|log-prob error| ~1e-6) lands in the same
     branch; the batch holds every outcome (a fixed subset below 64 samples); with the Huber loss all three pieces of its
-    gradient occur and no |err| is within 1e-3 of 1."""
+    gradient occur and no |err| is within 1e-3 of 1.  every_action = False: the batch need not hold every action (the
+    peaked recipe below draws them at random)."""
     h = c.hyper
     bounds = torch.tensor([1.0 - h["ppo_clip"], 1.0 + h["ppo_clip"], h["dual_clip"]], dtype=torch.float64)
     margin = (c.r64[:, None] - bounds[None, :]).abs().min().item()
@@ -134,12 +146,147 @@ def check_recipe(c):
     if c.n >= 64:
         faint = (c.advs != 0) & (c.advs.abs() < 1e-3)
         assert faint.any() and (c.advs.abs() > 1e-2).any()
-        if not c.continuous:
+        if not c.continuous and every_action:
             assert set(int(a) for a in c.actions) == set(range(c.A))
     ae = c.err64.abs()
     assert ((ae - 1.0).abs() > 1e-3).all(), float((ae - 1.0).abs().min())
     if c.n >= 7:
         assert (c.err64 > 1.0).any() and (c.err64 < -1.0).any() and ((ae < 1.0) & (ae > 0.1)).any() and (ae < 1e-5).any()
+
+
+# ---- peaked and collapsed policies ------------------------------------------------------------------------------------------------------
+# make_case draws logits with a standard deviation of about 0.6: every policy is close to uniform and no q_j comes near a clamp of
+# log(clamp(q, eps, 1 - eps)).  The recipe below PLACES the logits: one `top` action at 0, the others at -gap, so that every clamp, the
+# subnormal range of expf and its underflow are met at a stated distance.
+LOG_EPS = math.log(CAT_EPS)
+FAR_RATIOS = (2.0 ** 20, 2.0 ** -20, 2.0 ** 10, 2.0 ** -10)
+ENTRY_MARGIN = 0.05      # |log q_j - log eps| of every entry: fp32 logits are off by ~1e-5 at most, 5,000 times less
+TAIL_MARGIN = 1.5        # |log(sum_{j != top} q_j) - log eps|: below 1 the fp32 spacing is 2^-24 = eps / 2, so q_top = 1 - tail is resolved
+                         # to a QUARTER of eps and 1 - eps itself is a number: a tail within a factor of ~3 of eps can round onto the closed
+                         # boundary (flips seen at a log-margin of 0.29, none from 0.69 up)
+UNDERFLOW_GAPS = (95.0, 120.0)    # class (e): expf(-95) = 5.5e-42 is an fp32 subnormal, expf(-120) is 0
+
+
+def peaked_gaps(A):
+    """The gaps the samples cycle through, rare classes first (a batch of three holds a saturated, a peaked and -- A >= 8 -- a class (c)
+    row).  Classes: (a) near uniform: 0, 3; (b) peaked, every clamp in range: 9, 13 (and 14.25 for A = 2); (c) every tail entry below
+    eps while the top is still below 1 - eps: needs e^-gap < eps e^-ENTRY_MARGIN and (A - 1) e^-gap > eps e^TAIL_MARGIN, that is
+    15.99 < gap < 15.94 + log(A - 1) - 1.5, empty below A = 8 (log 7 = 1.95) -- 16.2 for A >= 8, left out for smaller A; (d) both
+    saturated: 20.5, 30, 40.  A = 2 cannot take 16.2 at all: its one tail entry would sit 0.26 from eps."""
+    if A == 2:
+        return (20.5, 13.0, 0.0, 40.0, 9.0, 3.0, 30.0, 14.25)
+    if A < 8:
+        return (20.5, 13.0, 0.0, 40.0, 9.0, 3.0, 30.0)
+    return (20.5, 13.0, 16.2, 0.0, 40.0, 9.0, 3.0, 30.0)
+
+
+def control_columns(A):
+    """One feature column per action, reserved to steer its logit."""
+    return [7 + 29 * j for j in range(A)]
+
+
+def make_peaked_case(A, n, shared, smooth, hyper=None, seed=0, B_global=None, gaps=None):
+    """make_case(0, ...) with PLACED logits.  Features, weights, advantages and returns stay dense and random; actor_w[:, K] = I and
+    critic_w[K] = 0 on the control columns K, and ha[b, K_j] = target[b, j] - z0[b, j] formed in float64 (z0: the logits without the
+    control features), so the float64 logits are the targets up to the fp32 rounding of that one feature and the fp32 logits differ from
+    them by dot-product rounding only.  Target of sample b: `top` at 0, the other actions at -gap_b, plus one shift per sample from
+    U[-1, 1].  gap_b cycles through `gaps` (default peaked_gaps(A); UNDERFLOW_GAPS is class (e), kept in cases of its own because its rows
+    carry a wider tolerance, peaked_row_tol).  Every third sample takes `top`, the others a uniform action -- tail actions with
+    q < eps included.  Ratios: the 18-pair cycle of make_case, but every ninth sample takes a far ratio 2^+-20, 2^+-10 with alternating
+    sign of the advantage instead -- never where the advantage is exactly 0 (inf * 0 is torch's answer there too)."""
+    c = make_case(0, A, n, shared, smooth, hyper, seed=seed, B_global=B_global)
+    g = torch.Generator().manual_seed(7919 * seed + 37 * A + n + 1)
+    gaps = tuple(peaked_gaps(A) if gaps is None else gaps)
+    L = len(gaps)
+    K = control_columns(A)
+    c.params["actor_w"][:, K] = torch.eye(A)
+    c.params["critic_w"][K] = 0.0
+    c.gaps = gaps
+    c.gap = torch.tensor([gaps[(b + b // L) % L] for b in range(n)], dtype=torch.float64)     # one step more per round: no lock-step with the other cycles
+    c.top = torch.randint(0, A, (n,), generator=g)
+    shift = 2.0 * torch.rand(n, generator=g).double() - 1.0
+    target = -c.gap[:, None].repeat(1, A)
+    target[torch.arange(n), c.top] = 0.0
+    target = target + shift[:, None]
+    ha64 = c.ha.double()
+    ha64[:, K] = 0.0
+    z0 = ha64 @ c.params["actor_w"].double().T + c.params["actor_b"].double()
+    c.ha[:, K] = (target - z0).float()
+    uniform = torch.randint(0, A, (n,), generator=g)
+    c.actions = torch.where(torch.arange(n) % 3 == 0, c.top, uniform).float()
+    pairs = _pairs(RATIOS[round(c.hyper["ppo_clip"], 3)])
+    sign = [float(pairs[i % 18][0]) for i in range(n)]
+    ratio = [float(pairs[i % 18][1]) for i in range(n)]
+    k = 0
+    c.far = torch.zeros(n, dtype=torch.bool)
+    for i in range(n):
+        if i % 9 == 4 and not (n >= 16 and i % 16 == 15):
+            sign[i], ratio[i] = (1.0, -1.0)[k % 2], FAR_RATIOS[(k // 2) % 4]
+            c.far[i] = True
+            k += 1
+    _place(c, g, torch.tensor(sign, dtype=torch.float64), torch.tensor(ratio, dtype=torch.float64))
+    P64 = {k_: v.double() for k_, v in c.params.items()}
+    c.z64 = c.ha.double() @ P64["actor_w"].T + P64["actor_b"]
+    return c
+
+
+def ulp32(x):
+    """Spacing of float32 at |x| (float64 tensor in, float64 out)."""
+    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))
+    return torch.ldexp(torch.ones_like(x), e - 24)
+
+
+def peaked_row_tol(c, base):
+    """Per-row tolerance of a peaked case: a row's relative gradient error is about the ABSOLUTE error of its logit gaps, and the last
+    roundings of a logit -- the six levels of a 64-lane butterfly plus the bias add, half an ulp each, for the two logits of a gap -- happen
+    at magnitude max_j |z_bj|: base + 8 ulp32(max_j |z_bj|).  Within 10 % of `base` = 2e-5 for |z| < 4, 5e-5 at |z| = 41, 8e-5 at 121."""
+    return base + 8.0 * ulp32(c.z64.abs().amax(1))
+
+
+def check_peaked_recipe(c):
+    """The peaked recipe's promises, in float64 (a CPU test runs them for every case of the GPU grid): every entry's log q_j more than
+    ENTRY_MARGIN from log eps; every row's log tail sum (summed directly, not 1 - q_top) more than TAIL_MARGIN from log eps; torch's own
+    fp32 forward puts every q_j < eps and q_j > 1 - eps comparison on the side float64 puts it; the ratio and Huber margins of
+    check_recipe; from 64 samples up all eight outcomes of the surrogate, far ratios of both directions under advantages of both signs
+    (all four far ratios from 257 up), a taken action with q < eps and one with q > 1 - eps -- or, in a class (e) case, a tail entry
+    that is a positive fp32 subnormal after exp and one that is exactly 0."""
+    check_recipe(c, every_action=False)
+    n, A = c.n, c.A
+    logq = torch.log_softmax(c.z64, dim=-1)
+    q = torch.exp(logq)
+    entry = float((logq - LOG_EPS).abs().min())
+    assert entry > ENTRY_MARGIN, entry
+    not_top = torch.ones(n, A, dtype=torch.bool)
+    not_top[torch.arange(n), c.top] = False
+    tail = (q * not_top).sum(1)
+    tmargin = float((torch.log(tail) - LOG_EPS).abs().min())
+    assert tmargin > TAIL_MARGIN, tmargin
+    P32 = {k: v.float() for k, v in c.params.items()}
+    probs32, _, _, _, z32 = forward(c, c.ha, c.ha if c.shared else c.hc, P32, torch.float32)
+    q32 = probs32 / probs32.sum(-1, keepdim=True)
+    eps32 = torch.tensor(CAT_EPS, dtype=torch.float32)
+    assert torch.equal(q32 < eps32, q < CAT_EPS), "fp32 crosses the lower clamp"
+    assert torch.equal(q32 > 1.0 - eps32, q > 1.0 - CAT_EPS), "fp32 crosses the upper clamp"
+    assert not bool(((c.advs == 0) & c.far).any())
+    qa = q.gather(1, c.actions.long()[:, None])[:, 0]
+    e32 = torch.exp(z32 - z32.amax(1, keepdim=True))
+    underflow = set(c.gaps) <= set(UNDERFLOW_GAPS)
+    if underflow:
+        assert bool((c.z64.abs().amax(1) > 90.0).all())
+    if n < 64:
+        return
+    assert set(c.outcomes) == set(OUTCOMES)
+    far = c.r64[c.far]
+    adv = c.advs[c.far]
+    for want in FAR_RATIOS[:2] if n < 257 else FAR_RATIOS:
+        hit = (far / want - 1.0).abs() < 1e-3
+        assert bool((hit & (adv > 0)).any()) and bool((hit & (adv < 0)).any()), want
+    assert bool((qa < CAT_EPS).any()) and bool((qa > 1.0 - CAT_EPS).any())
+    if underflow:
+        assert bool(((e32 > 0) & (e32 < 2.0 ** -126)).any()) and bool((e32 == 0).any())
+    else:
+        have = set(float(x) for x in c.gap)
+        assert have == set(c.gaps), sorted(set(c.gaps) - have)
 
 
 def loss_block(c, dtype):

@@ -27,10 +27,14 @@ def d_index(i):
 
 def make_case(continuous, A, n, shared, smooth, options, hyper=None, seed=0, B_global=None):
     """heads_ref.make_case plus c.value_clip, c.entropy_split and c.old_values = fp32(v64 - d), d / c cycling through D_OVER_C."""
-    c = H.make_case(continuous, A, n, shared, smooth, hyper, seed=seed, B_global=B_global)
+    return attach_options(H.make_case(continuous, A, n, shared, smooth, hyper, seed=seed, B_global=B_global), options)
+
+
+def attach_options(c, options):
+    """The option fields and the fifth column on a finished case of heads_ref (make_case or make_peaked_case)."""
     c.value_clip, c.entropy_split = float(options[0]), bool(options[1])
     v64 = c.rets.double() - c.err64
-    c.d_over_c = torch.tensor([D_OVER_C[d_index(i)] for i in range(n)], dtype=torch.float64)
+    c.d_over_c = torch.tensor([D_OVER_C[d_index(i)] for i in range(c.n)], dtype=torch.float64)
     c.old_values = (v64 - c.d_over_c * VALUE_CLIP).float()
     c.v64 = v64
     return c
@@ -70,6 +74,11 @@ def check_recipe(c):
     forms lands on the same side of the clamp), every clipped sample's two elements more than 1e-4 apart (the same maximum), with
     smooth-L1 no |ret - v_c| within 1e-3 of 1, and from 64 samples up all four outcomes."""
     H.check_recipe(c)
+    check_clip_recipe(c)
+
+
+def check_clip_recipe(c):
+    """The fifth column's promises alone (check_recipe; the peaked cases check theirs with heads_ref.check_peaked_recipe)."""
     d, l_u, l_c, err_c = clip_terms64(c)
     assert torch.isfinite(c.old_values).all()
     assert float(((d.abs() - VALUE_CLIP).abs()).min()) > 1e-3, float(((d.abs() - VALUE_CLIP).abs()).min())
@@ -179,6 +188,10 @@ def atari_losses(net, x, actions, old_logps, advs, rets, old_values, smooth_l1, 
     """oracle.ppo_losses with the clipped value loss (value_clip 0: its own expressions): (actor_loss, v_loss, entropy)."""
     from oracle import ddrl_oracle as O
     _, p_hat, logits, v = net(x)
+    # the oracle clamps with the eps of its OWN dtype (torch.distributions' rule): run in float64 it would shut its gradients at 2.2e-16
+    # where the definition the kernels implement (include/ddrl.h) says 2^-23.  The float32 eps whatever the dtype; inside the interval --
+    # every cell but the saturated one -- these are the same numbers
+    logits = torch.log(torch.clamp(p_hat, O.EPS, 1.0 - O.EPS))
     v = v.squeeze(-1)
     log_p = O.categorical_log_prob(logits, actions)
     ratio = torch.exp(log_p - old_logps)

@@ -10,6 +10,7 @@ copies what was measured, with the limit of its kind beside it, so that the head
 usage: python tools/update_margins.py [--source gpurun_out/margins_measured.json] [--note "r04, MI355X"]
 
 --only PREFIX: the source holds a run of some test files only; replace the records whose test name starts with PREFIX and keep the rest.
+--keys TEXT: keep the whole record and write only the measured keys that contain TEXT (new keys of one test record, say "_peaked_").
 """
 import argparse
 import json
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--source", default=os.path.join(ROOT, "gpurun_out", "margins_measured.json"))
     ap.add_argument("--note", default="")
     ap.add_argument("--only", default=None, help="replace the records of tests whose name starts with this; keep every other record")
+    ap.add_argument("--keys", default=None, help="keep every record; write only the measured keys that contain this text")
     args = ap.parse_args()
     import parity_util as P
     measured = json.load(open(args.source))
@@ -35,6 +37,10 @@ def main():
     if args.only is not None:
         out.update({t: d for t, d in json.load(open(path)).items() if t != "_doc" and not t.startswith(args.only)})
         measured = {t: d for t, d in measured.items() if t.startswith(args.only)}
+    if args.keys is not None:
+        out.update({t: d for t, d in json.load(open(path)).items() if t != "_doc"})
+        measured = {t: {k: v for k, v in d.items() if args.keys in k} for t, d in measured.items()}
+        measured = {t: d for t, d in measured.items() if d}
     over = []
     for test, d in sorted(measured.items()):
         slot = out.setdefault(test, {})
