@@ -22,7 +22,7 @@ import torch
 
 from ddrl4nav_amd.agent.agent import gae_device
 from ddrl4nav_amd.agent.normalize import ReturnNorm, RunningNorm, check_knobs, obs_norm_flags
-from ddrl4nav_amd.agent.statistics import EpisodeReturns
+from ddrl4nav_amd.agent.statistics import EpisodeReturns, NavStatus
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.ops import frame_stack_push
 from ddrl4nav_amd.utils.staging import copy_into
@@ -249,10 +249,13 @@ class StateRollout(_ReturnScaling):
     ``obs_norm[k]`` with (update / commit / freeze, or load_state_dict).  act() and batch() therefore read the same numbers and stay
     zero-copy.  finish() commits and freezes.  carry_over() moves a slot that is normalised already: it is neither counted nor
     normalised again, so slot 0 of the next rollout carries the statistics of one finish() earlier than slots 1..T (DESIGN.md
-    section 6.6).  normalize_returns: see _ReturnScaling."""
+    section 6.6).  normalize_returns: see _ReturnScaling.
+
+    track_nav_status: record() also takes the env's info words (DeviceNavEnv(emit_info=True).info) into an int32 [T + 1, N] pool and
+    finish() feeds rows 0..T-1 to ``nav_status`` (agent.NavStatus), exactly where it feeds ``returns``."""
 
     def __init__(self, net, n_envs, state_shapes, horizon=256, gamma=0.99, landa=0.95, device=None, track_returns=False,
-                 normalize_obs=None, obs_clip=10.0, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
+                 normalize_obs=None, obs_clip=10.0, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8, track_nav_status=False):
         state_shapes = [tuple(int(d) for d in shape) for shape in state_shapes]
         flags = obs_norm_flags(normalize_obs, len(state_shapes))
         check_knobs(norm_eps, obs_clip)
@@ -280,6 +283,8 @@ class StateRollout(_ReturnScaling):
         self.rollouts = 0                  # finish() counts them (runner/device_loop.collect_states resets its env before the first)
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.returns = EpisodeReturns(N, dev) if track_returns else None
+        self.nav_status = NavStatus(N, dev) if track_nav_status else None
+        self._infos = torch.zeros((T + 1, N), dtype=torch.int32, device=dev) if track_nav_status else None
         self.obs_norm = None
         self._ring_ordered = False         # normalize_obs: a ring put has ordered the copy stream since the last finish()
         if any(flags):
@@ -343,9 +348,13 @@ class StateRollout(_ReturnScaling):
         self.values[self.T].copy_(values[0][:, 0])
         return None
 
-    def record(self, t, rewards, dones):
+    def record(self, t, rewards, dones, info=None):
         if t < self.t0:
             raise ValueError("step %d was carried over from the previous rollout with its reward and done" % t)
+        if self._infos is not None:
+            if info is None:
+                raise ValueError("this rollout tracks the navigation status: record() needs the env's info words")
+            copy_into(self._infos[t], info)
         copy_into(self._rewards[t], rewards)
         copy_into(self._dones[t], dones)
 
@@ -361,6 +370,8 @@ class StateRollout(_ReturnScaling):
         self._gae()
         if self.returns is not None:
             self.returns.update(self.rewards, self.dones)
+        if self.nav_status is not None:    # Status.update_nav_status over the same rows
+            self.nav_status.update(self._infos[:self.T])
         self.rollouts += 1
 
     def state_dict(self):
@@ -387,7 +398,7 @@ class StateRollout(_ReturnScaling):
             p[0].copy_(p[T])
         if keep_step:
             self.values[0].copy_(self.values[T])
-            for pool in (self._rewards, self._dones, self._actions, self._logps):
+            for pool in (self._rewards, self._dones, self._actions, self._logps) + (() if self._infos is None else (self._infos,)):
                 pool[0].copy_(pool[T])
             self.t0 = 1
         else:

@@ -141,9 +141,19 @@ __device__ void nav_new_episode(int* s, int n_obs, int n_peds, uint32_t seed, ui
 
 __device__ __forceinline__ bool nav_finite(float a) { return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u; }
 
-// one step of the rules on the LDS copy (NavEnvRef.step), the new episode of a finished env included; every product fits 32 bits
+// The info word of ddrl_op_nav_env_step_info (include/ddrl.h; tests/nav_status_ref.py spells it out): what the step just played did,
+// read off the moved robot and pedestrians before a finished env's new episode is drawn.
+constexpr int NAV_CLOSE = 512;  // "close to a pedestrian": centres within 2 m
+enum {
+  NI_DONE = 1 << 0, NI_GOAL = 1 << 1, NI_KIND_SHIFT = 2, NI_TRUNC = 1 << 4, NI_CLOSE = 1 << 5, NI_WALL = 1 << 6, NI_OBSTACLE = 1 << 7,
+  NI_V_SHIFT = 8, NI_W_SHIFT = 16
+};
+
+// one step of the rules on the LDS copy (NavEnvRef.step), the new episode of a finished env included; every product fits 32 bits.
+// INFO: *info_out receives the info word; the state, the units and the done are the same either way.
+template <bool INFO>
 __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t genv, int* units_out,
-                            int* done_out) {
+                            int* done_out, int* info_out) {
   a0 = nav_finite(a0) ? a0 : 0.0f;
   a1 = nav_finite(a1) ? a1 : 0.0f;
   a0 = a0 < 0.0f ? 0.0f : (a0 > 1.0f ? 1.0f : a0);
@@ -179,15 +189,19 @@ __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, i
   int units = 2 * (s[NS_DPREV] - d);
   s[NS_DPREV] = d;
   // 4. collision  5. goal  6. truncation
-  bool collision = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
+  // one flag per cause: the info word names them (INFO), the plain instantiation only needs their union
+  const bool wall = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
+  bool hit_o = false, hit_p = false, close = false;
   for (int k = 0; k < n_obs; ++k) {
     const int dx = x - s[NS_OBS0 + 3 * k], dy = y - s[NS_OBS0 + 3 * k + 1], rr = NAV_ROBOT_R + s[NS_OBS0 + 3 * k + 2];
-    collision = collision || dx * dx + dy * dy < rr * rr;
+    hit_o = hit_o || dx * dx + dy * dy < rr * rr;
   }
   for (int j = 0; j < n_peds; ++j) {
-    const int dx = x - s[NS_PED0 + 4 * j], dy = y - s[NS_PED0 + 4 * j + 1];
-    collision = collision || dx * dx + dy * dy < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
+    const int dx = x - s[NS_PED0 + 4 * j], dy = y - s[NS_PED0 + 4 * j + 1], dd = dx * dx + dy * dy;
+    hit_p = hit_p || dd < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
+    if (INFO) close = close || dd <= NAV_CLOSE * NAV_CLOSE;
   }
+  const bool collision = wall || hit_o || hit_p;
   bool done = collision;
   if (collision) {
     units -= NAV_BONUS;
@@ -196,6 +210,13 @@ __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, i
     done = true;
   } else if (s[NS_STEPS] >= max_steps) {
     done = true;
+  }
+  if (INFO) {
+    const int kind = (wall || hit_o) ? 1 : (hit_p ? 2 : 0);  // static wins
+    const bool goal = !collision && d <= NAV_GOAL_TOL;
+    *info_out = (done ? NI_DONE : 0) | (goal ? NI_GOAL : 0) | (kind << NI_KIND_SHIFT) | ((done && !collision && !goal) ? NI_TRUNC : 0) |
+                (close ? NI_CLOSE : 0) | (wall ? NI_WALL : 0) | (hit_o ? NI_OBSTACLE : 0) | (v << NI_V_SHIFT) |
+                ((w + NAV_W_MAX) << NI_W_SHIFT);
   }
   if (done) nav_new_episode(s, n_obs, n_peds, seed, genv);
   *units_out = units;
@@ -292,11 +313,13 @@ __device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4]
   }
 }
 
+// INFO: the instantiation behind ddrl_op_nav_env_step_info; `info` is not touched otherwise
+template <bool INFO>
 __global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
                                                                    int n_peds, int max_steps, const float* __restrict__ actions,
                                                                    float* __restrict__ laser, float* __restrict__ vector,
                                                                    float* __restrict__ image, float* __restrict__ reward,
-                                                                   uint8_t* __restrict__ done) {
+                                                                   uint8_t* __restrict__ done, int32_t* __restrict__ info) {
   __shared__ int s[NAV_STATE_INTS];
   __shared__ int ped[NAV_MAX_PEDS][4];
   const int64_t i = blockIdx.x;
@@ -305,10 +328,11 @@ __global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __re
   if (tid < NAV_STATE_INTS) s[tid] = nav_sanitize_word(tid, st[tid], n_obs, n_peds);
   __syncthreads();  // the old state is in LDS: nothing reads the env's global words after this, thread 0 alone writes them
   if (tid == 0) {
-    int units, d;
-    nav_advance(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, (uint32_t)(env0 + i), &units, &d);
+    int units, d, word = 0;
+    nav_advance<INFO>(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, (uint32_t)(env0 + i), &units, &d, &word);
     reward[i] = (float)units * 0.00390625f;
     done[i] = (uint8_t)d;
+    if (INFO) info[i] = word;
   }
   __syncthreads();  // the new state is final
   nav_store_and_render(s, ped, n_obs, n_peds, st, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
@@ -368,23 +392,43 @@ int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t 
   return launch_status();
 }
 
-int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
-                             const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream) {
+// both step entries: `info` is given (and checked like the other outputs) by ddrl_op_nav_env_step_info alone
+static int32_t nav_env_step_launch(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
+                                   uint8_t* done, int32_t* info, bool with_info, void* stream) {
   if (!state || !actions || !laser || !vector || !image || !reward || !done || !nav_range_ok(n, env0, n_obstacles, n_peds))
     return DDRL_ERR_INVALID_ARG;
+  if (with_info && (!info || ((uintptr_t)info & 3))) return DDRL_ERR_INVALID_ARG;
   if (max_steps < 1) return DDRL_ERR_INVALID_ARG;
   if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
       ((uintptr_t)reward & 3))
     return DDRL_ERR_INVALID_ARG;
   const void* src[1] = {actions};
   const uint64_t src_b[1] = {(uint64_t)n * 8};
-  void* dst[6] = {state, laser, vector, image, reward, done};
-  const uint64_t dst_b[6] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
-                             (uint64_t)n * NAV_MAP_FLOATS * 4, (uint64_t)n * 4, (uint64_t)n};
-  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 6)) return DDRL_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(nav_env_step_kernel, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed, n_obstacles,
-                     n_peds, max_steps, actions, laser, vector, image, reward, done);
+  void* dst[7] = {state, laser, vector, image, reward, done, with_info ? info : nullptr};
+  const uint64_t dst_b[7] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
+                             (uint64_t)n * NAV_MAP_FLOATS * 4, (uint64_t)n * 4, (uint64_t)n, (uint64_t)n * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 7)) return DDRL_ERR_INVALID_ARG;
+  if (with_info)
+    hipLaunchKernelGGL(nav_env_step_kernel<true>, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed,
+                       n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info);
+  else
+    hipLaunchKernelGGL(nav_env_step_kernel<false>, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed,
+                       n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, (int32_t*)nullptr);
   return launch_status();
+}
+
+int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
+                             const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream) {
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, nullptr,
+                             false, stream);
+}
+
+int32_t ddrl_op_nav_env_step_info(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                  int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
+                                  uint8_t* done, int32_t* info, void* stream) {
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info, true,
+                             stream);
 }
 
 }  // extern "C"

@@ -16,9 +16,11 @@ _PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
 class DeviceNavEnv:
     state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
-    def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0):
+    def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False):
         """n_obstacles 0..10 static circles, n_peds 0..5 pedestrians; an episode ends at a collision, at the goal or after max_steps
-        steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv."""
+        steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv.  emit_info: every step also
+        fills ``info`` (int32 [N]: why the step ended or did not, ops.nav_info_fields; agent.NavStatus accumulates it); the trajectory is
+        the same either way."""
         self.N, self.seed, self.env0 = int(n_envs), int(seed), int(env0)
         self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
         if self.N < 1:
@@ -39,6 +41,8 @@ class DeviceNavEnv:
         self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
         self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
         self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
+        self.emit_info = bool(emit_info)
+        self.info = torch.zeros(self.N, dtype=torch.int32, device=dev) if self.emit_info else None
 
     @property
     def n_envs(self):
@@ -57,7 +61,11 @@ class DeviceNavEnv:
     def step(self, actions, obs_out=None):
         """actions fp32 [N, 2] on the device (what a Gaussian actor's act() returns) -> ([laser, vector, image], reward fp32 [N], done
         uint8 [N]): device tensors the env owns, valid until the next step (obs_out: render there instead).  A finished env has already
-        begun its next episode: the observation is that episode's first and done is the reset flag.  Asynchronous."""
+        begun its next episode: the observation is that episode's first and done is the reset flag.  With emit_info, ``info`` describes the
+        step just played (the finished episode's last, not the new one's first).  Asynchronous."""
+        if self.emit_info:
+            return ops.nav_env_step_info(self.state, actions, self._obs_out(obs_out), self.reward, self.done, self.info, env0=self.env0,
+                                         seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
         return ops.nav_env_step(self.state, actions, self._obs_out(obs_out), self.reward, self.done, env0=self.env0, seed=self.seed,
                                 n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)
 
@@ -79,11 +87,11 @@ class DeviceNavEnv:
 
 def make_device_nav_env(config_env, device=None, env0=0):
     """The DeviceNavEnv of a config_env dict: env_name "DeviceNav-v0", env_num, and the optional knobs env_obstacles, env_peds,
-    env_max_steps, env_seed."""
+    env_max_steps, env_seed, env_info (emit_info)."""
     if config_env.get("env_name") != NAV_ENV_NAME:
         raise ValueError("env_name must be %r, got %r" % (NAV_ENV_NAME, config_env.get("env_name")))
     if "env_num" not in config_env:
         raise ValueError("config_env needs env_num")
     return DeviceNavEnv(int(config_env["env_num"]), device=device, seed=int(config_env.get("env_seed", 0)),
                         n_obstacles=int(config_env.get("env_obstacles", 10)), n_peds=int(config_env.get("env_peds", 5)),
-                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0)
+                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0, emit_info=bool(config_env.get("env_info", False)))

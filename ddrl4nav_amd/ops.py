@@ -457,6 +457,74 @@ def nav_env_step(state, actions, obs, reward, done, env0=0, seed=0, n_obstacles=
     return obs, reward, done
 
 
+def nav_env_step_info(state, actions, obs, reward, done, info, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
+    """nav_env_step plus the info word of every env, info int32 [n] (include/ddrl.h ddrl_op_nav_env_step_info): what the step just played
+    did -- done, goal, collision kind, truncation, closeness to a pedestrian, the decoded action (nav_info_fields unpacks it).  The other
+    outputs are bit-identical to nav_env_step's.  Asynchronous on the current stream; returns (obs, reward, done, info)."""
+    n = _nav_env_args(state, obs)
+    assert tuple(_f32(actions).shape) == (n, 2) and _f32(reward).numel() == n and actions.device == state.device \
+        and reward.device == state.device, "actions fp32 [n, 2], reward fp32 [n] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
+        and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
+    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (n,) \
+        and info.device == state.device, "info: contiguous int32 [n] on the state's device"
+    check(_lib.load().ddrl_op_nav_env_step_info(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds),
+                                                int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward), _p(done),
+                                                _p(info), _st()))
+    return obs, reward, done, info
+
+
+NAV_INFO_FIELDS = ("done", "goal", "collision", "truncated", "close", "wall_hit", "obstacle_hit", "v", "w")
+NAV_COLLISION_STATIC, NAV_COLLISION_PED = 1, 2    # the reference's coding of info["collision"]
+
+
+def nav_info_fields(info):
+    """The fields of info words (a host or device int32 tensor of any shape) as int32 tensors of that shape, by name: done, goal,
+    collision (0 none, 1 static, 2 pedestrian), truncated, close, wall_hit, obstacle_hit, and the decoded action v in 0..32 (ticks per
+    step) and w in -64..64 (heading steps per step)."""
+    w = torch.as_tensor(info)
+    assert w.dtype == torch.int32, "info: int32 words"
+    bit = lambda k: (w >> k) & 1
+    return {"done": bit(0), "goal": bit(1), "collision": (w >> 2) & 3, "truncated": bit(4), "close": bit(5), "wall_hit": bit(6),
+            "obstacle_hit": bit(7), "v": (w >> 8) & 63, "w": ((w >> 16) & 255) - 64}
+
+
+NAV_STATUS_ROWS, NAV_STATUS_RINGS, NAV_STATUS_WINDOW, NAV_STATUS_SUMMARY = 18, 5, 100, 22    # include/ddrl.h DDRL_NAV_STATUS_*
+
+
+def _nav_status_args(sums, episode_num, rings):
+    """N of a navigation-status call after the checks both operators share: sums fp32 [18, N], episode_num int32 [N], rings fp32
+    [5, 100, N], contiguous, on one device."""
+    assert sums.dtype == torch.float32 and sums.is_cuda and sums.is_contiguous() and sums.dim() == 2 \
+        and sums.shape[0] == NAV_STATUS_ROWS, "sums: contiguous fp32 [18, N] on the device"
+    N = sums.shape[1]
+    assert episode_num.dtype == torch.int32 and episode_num.is_contiguous() and tuple(episode_num.shape) == (N,) \
+        and episode_num.device == sums.device, "episode_num: contiguous int32 [N] on the sums' device"
+    assert rings.dtype == torch.float32 and rings.is_contiguous() and tuple(rings.shape) == (NAV_STATUS_RINGS, NAV_STATUS_WINDOW, N) \
+        and rings.device == sums.device, "rings: contiguous fp32 [5, 100, N] on the sums' device"
+    return N
+
+
+def nav_status_update(info, sums, episode_num, rings):
+    """T successive Status.update_nav_status calls over info int32 [T, N] in one launch (include/ddrl.h ddrl_op_nav_status_update;
+    csrc/navstat.hip); T == 0 is a no-op.  Asynchronous on the current stream."""
+    N = _nav_status_args(sums, episode_num, rings)
+    assert info.dtype == torch.int32 and info.is_contiguous() and info.dim() == 2 and info.shape[1] == N \
+        and info.device == sums.device, "info: contiguous int32 [T, N] on the sums' device"
+    check(_lib.load().ddrl_op_nav_status_update(_p(info) if info.shape[0] else c_void_p(0), int(info.shape[0]), N, _p(sums),
+                                                _p(episode_num), _p(rings), _st()))
+
+
+def nav_status_reduce(sums, episode_num, rings, summary):
+    """The (sum, count) pairs group_logger's means are made of, summary float64 [22] (include/ddrl.h ddrl_op_nav_status_reduce): a
+    fixed-order sum over the envs.  Asynchronous on the current stream; returns summary."""
+    N = _nav_status_args(sums, episode_num, rings)
+    assert summary.dtype == torch.float64 and summary.is_contiguous() and tuple(summary.shape) == (NAV_STATUS_SUMMARY,) \
+        and summary.device == sums.device, "summary: contiguous float64 [22] on the sums' device"
+    check(_lib.load().ddrl_op_nav_status_reduce(_p(sums), _p(episode_num), _p(rings), N, _p(summary), _st()))
+    return summary
+
+
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off
 
 

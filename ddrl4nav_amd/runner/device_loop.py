@@ -64,10 +64,17 @@ def collect_states(ro, env, keep_step=False, reset=None):
     reset (None: True for ro's first rollout, ro.rollouts == 0 with nothing carried over): the env is reset into slot 0.  Otherwise
     slot 0 is what carry_over() left there.
     keep_step: as for collect() -- bootstrap(sample=True) draws the (T + 1)-th action, the env plays it into its own tensors and its
-    reward and done are recorded in row T; the next rollout starts at ro.t0 == 1 and copies that observation into slot 1."""
+    reward and done are recorded in row T; the next rollout starts at ro.t0 == 1 and copies that observation into slot 1.
+
+    A rollout built with track_nav_status=True also records env.info, the info words of every step: the env must have been built with
+    emit_info=True (ValueError otherwise)."""
     T = ro.T
     if env.N != ro.N:
         raise ValueError("the env has %d envs, the rollout %d" % (env.N, ro.N))
+    tracks = getattr(ro, "nav_status", None) is not None
+    if tracks and getattr(env, "info", None) is None:
+        raise ValueError("the rollout tracks the navigation status but the env was built without emit_info")
+    info = {"info": env.info} if tracks else {}
     if reset is None:
         reset = ro.rollouts == 0 and ro.t0 == 0
     if reset:
@@ -80,18 +87,19 @@ def collect_states(ro, env, keep_step=False, reset=None):
         ro.put_states(1, env.obs)
     for t in range(ro.t0, T):
         _, reward, done = env.step(ro.act(t), obs_out=ro.state_rows(t + 1))
-        ro.record(t, reward, done)
+        ro.record(t, reward, done, **info)
         ro.put_states_in_place(t + 1)
     action = ro.bootstrap(sample=keep_step)
     if keep_step:
         _, reward, done = env.step(action)
-        ro.record(T, reward, done)
+        ro.record(T, reward, done, **info)
     ro.finish()
 
 
 def train_states(net, env, ro, updates, keep_step=False):
     """train() for a StateRollout: collect_states(ro, env), net.learn(ro.batch()), carry_over(keep_step).  Yields, per update, (the last
-    loss dict of net.learn, ro.returns.mean_return() -- None without track_returns)."""
+    loss dict of net.learn, ro.returns.mean_return() -- None without track_returns).  The navigation status of a tracking rollout is read
+    from ro.nav_status (summary() is its one device-to-host copy)."""
     for _ in range(int(updates)):
         collect_states(ro, env, keep_step=keep_step)
         losses = None

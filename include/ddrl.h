@@ -809,6 +809,41 @@ int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t 
  * and done is the reset flag.  max_steps >= 1; actions, vector and reward 4-byte aligned. */
 int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
                              const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream);
+/* ddrl_op_nav_env_step plus one output, info int32 [n] (4-byte aligned, apart from every other argument): what the step just played
+ * did, before a finished env's new episode is drawn.  State, observation, reward and done are bit-identical to ddrl_op_nav_env_step.
+ *   bit 0 done   bit 1 goal   bits 2-3 collision kind (0 none, 1 static: wall or obstacle, 2 pedestrian; static wins)
+ *   bit 4 truncated (max_steps reached without collision or goal)
+ *   bit 5 close to a pedestrian: after the move some pedestrian's centre is within 512 ticks (2 m) of the robot's
+ *   bit 6 wall hit   bit 7 obstacle hit   bits 8-13 the decoded v (0..32)   bits 16-23 the decoded w + 64 (0..128)   others zero */
+int32_t ddrl_op_nav_env_step_info(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                  int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
+                                  uint8_t* done, int32_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Navigation episode statistics (additive: ABI 3): the reference's Status.update_nav_status and the sums of its
+ * group_logger over the info words above, per env, on the device.  Context-free, no allocation, no atomics, asynchronous on `stream`;
+ * fixed-order sums, so the same data give the same bits.  The per-env state is three buffers the caller owns (zero = a fresh Status):
+ *   sums         float32 [18][N]: for every step, for the steps close to a pedestrian, for the steps in the open, six rows each:
+ *                v_speeds_sum, v_speeds_episode, w_speeds_sum, w_speeds_episode, steps_sum, steps_episode
+ *   episode_num  int32 [N]
+ *   rings        float32 [5][100][N]: arrive_num, coll_static_num, coll_ped_num, coll_robot_num, and the truncations kept the same way
+ * A null or misaligned pointer, N < 1, T < 0, an overlap of two arguments: DDRL_ERR_INVALID_ARG, decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+#define DDRL_NAV_STATUS_ROWS 18
+#define DDRL_NAV_STATUS_RINGS 5
+#define DDRL_NAV_STATUS_WINDOW 100
+#define DDRL_NAV_STATUS_SUMMARY 22
+/* T successive update_nav_status calls in one launch, one lane per env: info int32 [T][N] with arrive = bit 1, collision = bits 2-3,
+ * all_down = bit 0, speeds = (v / 32, w / 64) from the decoded fields (w = bits 16-23 less 64), bool_get_close_to_human = bit 5,
+ * is_clean = 1.  Every fp32 operation is exact, so the state equals the reference's bit for bit.  T == 0 is a no-op. */
+int32_t ddrl_op_nav_status_update(const int32_t* info, int32_t T, int32_t N, float* sums, int32_t* episode_num, float* rings,
+                                  void* stream);
+/* summary double [DDRL_NAV_STATUS_SUMMARY] (8-byte aligned), eleven (sum, count) pairs that add across ranks: reach, static-collision,
+ * pedestrian-collision and truncation rate (sum(ring) / clip(episode_num + 1, 1, 100), every env counts); linear and angular speed per
+ * step of the latest finished episode (fp32 quotient per env) over all steps, over the close steps and over the open steps, counting
+ * only envs whose step count is > 0; steps_episode (every env counts).  One workgroup, a fixed order. */
+int32_t ddrl_op_nav_status_reduce(const float* sums, const int32_t* episode_num, const float* rings, int32_t N, double* summary,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

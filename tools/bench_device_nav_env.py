@@ -10,6 +10,11 @@ legs of each measurement alternating:
                same phase on observations that are in the pool already (act -> record), and against the T act() calls and the T
                env.step calls alone.  env.step against act() at the same N is the comparison DESIGN.md reports.
 
+  (c) info     ddrl_op_nav_env_step_info against ddrl_op_nav_env_step on two envs of the same seed under the same actions (DESIGN.md
+               section 6.9), samples alternating as in (a).  The plain leg's samples are also split into its even and its odd ones: the
+               gap between the two halves' medians is the session's own run-to-run spread, which the info leg is held against.
+  (d) status   ddrl_op_nav_status_update over T x N info words and ddrl_op_nav_status_reduce, `calls` launches per sample.
+
 Every leg is warmed up first; a leg reports the median, the p95 and the extremes of its samples.  Prints one JSON line.
 
     python tools/bench_device_nav_env.py [--envs 512] [--steps 256] [--calls 200] [--samples 30] [--runs 10] [--warmup 2]
@@ -78,6 +83,70 @@ def kernel_legs(args):
     return out
 
 
+def info_legs(args):
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N = args.envs
+    plain, told = DeviceNavEnv(N, device="cuda", seed=1), DeviceNavEnv(N, device="cuda", seed=1, emit_info=True)
+    plain.reset()
+    told.reset()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
+
+    def leg(env):
+        def run():
+            for _ in range(args.calls):
+                env.step(actions)
+        return run
+
+    legs = {"env_step": leg(plain), "env_step_info": leg(told)}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.samples):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    out = {k: summary(v, per=args.calls) for k, v in ms.items()}
+    halves = [summary(ms["env_step"][h::2], per=args.calls)["median_us"] for h in (0, 1)]
+    out["env_step_halves_median_us"] = halves
+    out["env_step_spread_us"] = round(abs(halves[0] - halves[1]), 3)
+    out["info_minus_plain_us"] = round(out["env_step_info"]["median_us"] - out["env_step"]["median_us"], 3)
+    out["same_state"] = bool(torch.equal(plain.state, told.state))
+    return out
+
+
+def status_legs(args):
+    from ddrl4nav_amd.agent import NavStatus
+    N, T = args.envs, args.steps
+    g = torch.Generator(device="cuda").manual_seed(2)
+    done = (torch.rand((T, N), device="cuda", generator=g) < 0.02).to(torch.int32)
+    close = (torch.rand((T, N), device="cuda", generator=g) < 0.3).to(torch.int32)
+    v = torch.randint(0, 33, (T, N), device="cuda", generator=g, dtype=torch.int32)
+    w = torch.randint(0, 129, (T, N), device="cuda", generator=g, dtype=torch.int32)
+    info = (done | (done << 1) | (close << 5) | (v << 8) | (w << 16)).contiguous()
+    st = NavStatus(N, "cuda")
+
+    def updates():
+        for _ in range(args.calls):
+            st.update(info)
+
+    def reduces():
+        for _ in range(args.calls):
+            st.partial()
+
+    legs = {"status_update": updates, "status_reduce": reduces}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.samples):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    return {k: summary(v, per=args.calls) for k, v in ms.items()}
+
+
 def acting_legs(args):
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.env import DeviceNavEnv
@@ -135,7 +204,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_device_nav_env needs a GPU: there is nothing to measure without one")
     out = {"tool": "bench_device_nav_env", "N": args.envs, "T": args.steps, "device": torch.cuda.get_device_name(0),
-           "kernel": kernel_legs(args), "acting": acting_legs(args)}
+           "kernel": kernel_legs(args), "info": info_legs(args), "status": status_legs(args), "acting": acting_legs(args)}
     print(json.dumps(out))
 
 

@@ -7,6 +7,11 @@ a1 ~ U(-1, 1)) on the same env, measured first on the device over --baseline-ste
 
     python tools/train_device_nav_env.py [--envs 256] [--horizon 64] [--updates 100] [--obstacles 10] [--peds 5] [--max-steps 500]
                                          [--iters 4] [--actor-lr R] [--critic-lr R] [--normalize-obs] [--seed 0] [--out curve.json]
+                                         [--nav-status]
+
+--nav-status: the env emits its info words and the rollout keeps the reference's navigation statistics on the device (agent.NavStatus;
+DESIGN.md section 6.9); reach, collision and truncation rates over the envs' latest 100 episodes are printed next to the return and
+stored in the curve.  The loop gains no host synchronisation per step: the one copy is NavStatus.summary() at a logged update.
 """
 import argparse
 import json
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--actor-lr", type=float, default=None)
     ap.add_argument("--critic-lr", type=float, default=None)
     ap.add_argument("--normalize-obs", action="store_true", help="StateRollout(normalize_obs=True)")
+    ap.add_argument("--nav-status", action="store_true", help="track and print reach / collision / truncation rates (agent.NavStatus)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--baseline-steps", type=int, default=1000)
     ap.add_argument("--log-every", type=int, default=10)
@@ -69,8 +75,9 @@ def main():
             knobs[name] = value
     net = make_net(max(args.micro_batch, args.envs), seed=args.seed, **knobs)
     env = make_device_env({"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
-                           "env_peds": args.peds, "env_max_steps": args.max_steps}, device=net.device)
-    ro = StateRollout(net, args.envs, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None)
+                           "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status}, device=net.device)
+    ro = StateRollout(net, args.envs, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None,
+                      track_nav_status=args.nav_status)
 
     per_episode, per_1000 = random_policy_return(env, args.baseline_steps, args.seed + 1)
     out = {"tool": "train_device_nav_env", "N": args.envs, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
@@ -84,8 +91,15 @@ def main():
         out["curve"].append({"update": u, "env_steps": u * args.envs * args.horizon, "mean_return": mean_return,
                              "losses": {k: v for k, v in losses.items() if k != "PpoBackUpTime"}})
         if u % args.log_every == 0 or u == args.updates:
-            print("update %4d  steps %9d  mean return %8.3f  VLoss %.4f  EntLoss %.4f  %.0f s"
-                  % (u, u * args.envs * args.horizon, mean_return, losses["VLoss"], losses["EntLoss"], time.time() - t0), flush=True)
+            rates = ""
+            if ro.nav_status is not None:
+                status = ro.nav_status.summary()
+                out["curve"][-1]["nav_status"] = status
+                rates = "  reach %.3f  static %.3f  ped %.3f  trunc %.3f" % tuple(
+                    status[k] for k in ("ReducedReachRateLogger", "ReducedStaticObsCollisionRateLogger", "ReducedPedCollisionRateLogger",
+                                        "TruncationRate"))
+            print("update %4d  steps %9d  mean return %8.3f%s  VLoss %.4f  EntLoss %.4f  %.0f s"
+                  % (u, u * args.envs * args.horizon, mean_return, rates, losses["VLoss"], losses["EntLoss"], time.time() - t0), flush=True)
     out["seconds"] = round(time.time() - t0, 1)
     out["env_steps_per_s_end_to_end"] = round(args.updates * args.envs * args.horizon / max(out["seconds"], 1e-9))
     if args.out:
@@ -95,6 +109,8 @@ def main():
     brief = {k: v for k, v in out.items() if k != "curve"}
     brief["first_return"] = next((c["mean_return"] for c in out["curve"] if c["mean_return"] == c["mean_return"]), None)
     brief["last_return"] = out["curve"][-1]["mean_return"] if out["curve"] else None
+    if ro.nav_status is not None and out["curve"]:
+        brief["last_nav_status"] = out["curve"][-1].get("nav_status")
     print(json.dumps(brief))
 
 
