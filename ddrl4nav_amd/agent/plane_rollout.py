@@ -9,8 +9,10 @@ written C times.  Here the pool is
 a quarter of the bytes at C = 4 (0.47 GB against 1.86 GB at 256 envs x 256 steps), and a stack is assembled where it is read
 (ddrl_op_gather_frame_stacks): act(t) gathers slot t into one [N, C, 84, 84] scratch, the learner gathers its minibatches from
 batch().states[0], a data.FramePlanes.  Same life cycle and the same methods as DeviceRollout except the whole-stack puts; the same
-actions, log-probs, values and updates bit for bit (tests/test_plane_pool_gpu.py).  The ring-fed put needs no staging buffers and no
-per-parity events: the DMA lands in the pool's plane row itself.
+actions, log-probs, values and updates bit for bit (tests/test_plane_pool_gpu.py).  The constructor, record(), finish() and carry_over()
+ARE DeviceRollout's (agent/rollout.py _RolloutBase): this class supplies the observation pool (_alloc_observation), how it is carried
+over (_carry_observation), its puts, act() and the `states` of batch().  The ring-fed put needs no staging buffers and no per-parity
+events: the DMA lands in the pool's plane row itself; its copy stream is ordered by the one rule, _order_copy_stream.
 
 act_in_place (None: the net's config_nn.ACT_IN_PLACE, nn/minibatch.py; off by default): act(t) gathers nothing.  The put's age launch is
 ops.frame_slot, which also writes the slot's frame table (int32 [N, 4], 16 bytes per env instead of the N * C * 7056 of the scratch), and
@@ -19,9 +21,7 @@ gathered path (tests/test_act_in_place_gpu.py).  The scratch is then allocated o
 import torch
 
 from ddrl4nav_amd import ops
-from ddrl4nav_amd.agent.normalize import check_knobs
 from ddrl4nav_amd.agent.rollout import DeviceRollout
-from ddrl4nav_amd.agent.statistics import EpisodeReturns
 from ddrl4nav_amd.data import Experience, FramePlanes
 from ddrl4nav_amd.utils.staging import copy_into
 
@@ -29,45 +29,26 @@ from ddrl4nav_amd.utils.staging import copy_into
 class PlaneRollout(DeviceRollout):
     def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False,
                  act_in_place=None, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
-        # the pools of DeviceRollout.__init__ with `frames` replaced by planes + age (not called: it would allocate the stacked pool)
-        check_knobs(norm_eps, reward_clip)
-        self.hp = net.hot_path if hasattr(net, "hot_path") else net
-        self.with_old_values = bool(getattr(net, "wants_old_values", False))
-        self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
-        if not 1 <= self.C <= 4:
-            raise ValueError("1 to 4 stacked frames, got %d" % self.C)
-        if self.T < self.C:
-            raise ValueError("horizon %d < channels %d: carry_over() moves pool rows T..T+C-1 to rows 0..C-1, which would overlap"
-                             % (self.T, self.C))
-        self.H = self.C - 1
-        self.gamma, self.landa = gamma, landa
-        dev = torch.device(device if device is not None else self.hp.device)
-        self.device = dev
-        N, T = self.N, self.T
+        C, T = int(channels), int(horizon)
+        if not 1 <= C <= 4:                # both refused before anything is allocated
+            raise ValueError("1 to 4 stacked frames, got %d" % C)
+        if T < C:
+            raise ValueError("horizon %d < channels %d: carry_over() moves pool rows T..T+C-1 to rows 0..C-1, which would overlap" % (T, C))
+        self.H = C - 1
+        self.act_in_place = bool(getattr(net, "act_in_place", False) if act_in_place is None else act_in_place)
+        super().__init__(net, n_envs, horizon=T, channels=C, gamma=gamma, landa=landa, device=device, seed=seed,
+                         track_returns=track_returns, normalize_returns=normalize_returns, reward_clip=reward_clip, norm_eps=norm_eps)
+
+    def _alloc_observation(self):
+        """DeviceRollout's constructor with `frames` replaced by planes + age, and what acting on them needs."""
+        N, T, dev = self.N, self.T, self.device
         self.planes = torch.empty((self.H + T + 1, N, 84, 84), dtype=torch.uint8, device=dev)
         self.age = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
-        self.act_in_place = bool(getattr(net, "act_in_place", False) if act_in_place is None else act_in_place)
         # the slot act(t) reads: gathered into _stack, or in place through _slot_tab, the frame table of slot _slot_t (-1: of none)
         self._stack = None if self.act_in_place else torch.empty((N, self.C, 84, 84), dtype=torch.uint8, device=dev)
         self._slot_tab = torch.empty((N, 4), dtype=torch.int32, device=dev) if self.act_in_place else None
         self._slot_t = -1
-        self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self._rewards = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
-        self._actions = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self._logps = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self.rewards, self.dones = self._rewards[:T], self._dones[:T]
-        self.actions, self.logps = self._actions[:T], self._logps[:T]
-        self.adv = torch.empty((T, N), dtype=torch.float32, device=dev)
-        self.ret = torch.empty((T, N), dtype=torch.float32, device=dev)
-        self._probs = torch.empty((N, self.hp.n_actions), dtype=torch.float32, device=dev)
-        self.seed, self.rollouts, self.t = int(seed), 0, 0
-        self.t0 = 0
-        self.copy_stream = torch.cuda.Stream(device=dev)
-        self.returns = EpisodeReturns(N, dev) if track_returns else None
         self._reset_buf = torch.ones((2, N), dtype=torch.uint8, device=dev)   # _reset_flags: 0 a caller's flags, 1 all ones
-        self._ring_rollout = -1            # the rollout (self.rollouts) whose first ring put ordered the copy stream
-        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
 
     # ---- ingest ---------------------------------------------------------------------------------
     def put_frames(self, t, frames):
@@ -104,15 +85,12 @@ class PlaneRollout(DeviceRollout):
     def put_new_frames_from_ring(self, t, ring, reset=None):
         """put_new_frames with the frame taken from a pinned ring whose slots hold N * 7056 bytes: hipMemcpyAsync on the copy stream straight
         into pool row H + t, which nothing enqueued earlier in this rollout touches; the compute stream waits for it.  The FIRST such put
-        of a rollout, at whatever t, orders the copy stream behind the compute stream (the previous update and carry_over() still read
-        and write the pool); later puts do not wait again, so copy t + 1 runs under forward t."""
+        of a rollout, at whatever t, orders the copy stream behind the compute stream (_order_copy_stream: the previous update and
+        carry_over() still read and write the pool); later puts do not wait again, so copy t + 1 runs under forward t."""
         flags = self._reset_flags(t, reset)           # before the ring is touched: a refused call consumes no slot
-        cur = torch.cuda.current_stream()
-        if self._ring_rollout != self.rollouts:     # finish() counts the rollouts: one wait per rollout, none per slot
-            self.copy_stream.wait_stream(cur)
-            self._ring_rollout = self.rollouts
+        self._order_copy_stream()
         ring.pop_to(self.planes[self.H + t], stream=self.copy_stream)
-        cur.wait_stream(self.copy_stream)
+        torch.cuda.current_stream().wait_stream(self.copy_stream)
         self._age(t, flags)
 
     # ---- acting ---------------------------------------------------------------------------------
@@ -141,22 +119,13 @@ class PlaneRollout(DeviceRollout):
         return self._actions[t]
 
     # ---- carry-over + learner batch ---------------------------------------------------------------
-    def carry_over(self, keep_step=False):
-        """DeviceRollout.carry_over: the last stored step's frame WITH its history (pool rows T..T+H -> 0..H, age[T] -> age[0])."""
+    def _carry_observation(self):
+        """carry_over(): the last stored step's frame WITH its history (pool rows T..T+H -> 0..H, age[T] -> age[0])."""
         T, H = self.T, self.H
         self.planes[:H + 1].copy_(self.planes[T:T + H + 1])
         self.age[0].copy_(self.age[T])
         self._slot_t = -1          # slot 0 now holds another step's frames: whatever the table describes is stale
-        if keep_step:
-            self.values[0].copy_(self.values[T])
-            for pool in (self._rewards, self._dones, self._actions, self._logps):
-                pool[0].copy_(pool[T])
-            self.t0 = 1
-        else:
-            self.t0 = 0
 
     def batch(self):
         """DeviceRollout.batch with the states as FramePlanes over the pool (zero-copy)."""
-        B = self.N * self.T
-        return Experience(states=[FramePlanes(self.planes, self.age, self.T, self.N, self.C)], advs=self.adv.view(B),
-                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self._value_rows(B))
+        return Experience(states=[FramePlanes(self.planes, self.age, self.T, self.N, self.C)], **self._columns(self.N * self.T))

@@ -10,6 +10,11 @@ hipMemcpyAsync on a copy stream, overlapping the previous step's forward.  A slo
 (put_frames*) or from ONE new frame per env (put_new_frames*): csrc/fstack.hip then builds slot t from slot t-1 on the device,
 as the reference's FrameStackWrapper does on the host, and a quarter of the bytes cross PCIe at C = 4.
 
+One core: everything but the observation -- the step pools, the counters, record() / finish() / carry_over(), the learner columns of
+batch() and the ordering of the copy stream -- is _RolloutBase, shared by DeviceRollout, PlaneRollout (agent/plane_rollout.py) and
+StateRollout.  Every ring-fed put follows one rule (_RolloutBase._order_copy_stream): the first of them after construction or after a
+finish(), at whatever slot, makes the copy stream wait for the compute stream once; none waits after it.
+
 Carry-over between rollouts (reference agent.py:286-292: ``rewards_step[0] = rewards_step[T]; exps = [exps[-1]]``): the
 reference keeps the WHOLE (T+1)-th Experience -- state, the action already sent to the env, its old log-prob, its value
 under the weights of that moment, its reward and done -- as step 0 of the next rollout and acts from step 1 on.
@@ -37,17 +42,71 @@ def value_rows(ret, values, T, B, with_old_values):
     return torch.stack([ret.view(B), values[:T].reshape(B)])
 
 
-class _ReturnScaling:
-    """What DeviceRollout, PlaneRollout and StateRollout share of normalize_returns (agent/normalize.py ReturnNorm; DESIGN.md section
-    6.6): off (the default) nothing is allocated, nothing is launched and finish() runs GAE on the raw rewards as before."""
+class _RolloutBase:
+    """What DeviceRollout, PlaneRollout and StateRollout share, written once: the [T+1, N] step pools and their [:T] views, adv / ret, the
+    counters, the copy stream, record() / finish() / carry_over(), the learner columns of batch() and the ring-ordering rule.  A subclass
+    adds its observation pool, its puts, act() and the `states` of batch(), and two hooks: _before_gae() and _carry_observation().
+
+    normalize_returns (agent/normalize.py ReturnNorm): off (the default) nothing is allocated, nothing is launched
+    and finish() runs GAE on the raw rewards as before."""
     ret_norm = None
     rewards_norm = None
 
-    def _init_return_scaling(self, normalize_returns, reward_clip, norm_eps):
-        """After N, T, gamma and device are set."""
+    def __init__(self, net, n_envs, horizon, gamma, landa, device, action_shape=None, track_returns=False, track_nav_status=False,
+                 normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
+        """action_shape: (T+1, N) (the default), or (T+1, N, n_actions) for a continuous net."""
+        check_knobs(norm_eps, reward_clip)
+        self.with_old_values = bool(getattr(net, "wants_old_values", False))
+        self.N, self.T = N, T = int(n_envs), int(horizon)
+        self.gamma, self.landa = gamma, landa
+        self.device = dev = torch.device(device)
+        f = dict(dtype=torch.float32, device=dev)
+        self.values = torch.zeros((T + 1, N), **f)
+        # rows 0..T-1 are the rollout (contiguous [T, N] views: what GAE and the learner batch read); row T holds the (T+1)-th
+        # step's reward / done / action / log-prob for carry_over(keep_step=True)
+        self._rewards = torch.zeros((T + 1, N), **f)
+        self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
+        self._actions = torch.zeros((T + 1, N) if action_shape is None else action_shape, **f)
+        self._logps = torch.zeros((T + 1, N), **f)
+        self.rewards, self.dones = self._rewards[:T], self._dones[:T]
+        self.actions, self.logps = self._actions[:T], self._logps[:T]
+        self.adv = torch.empty((T, N), **f)
+        self.ret = torch.empty((T, N), **f)
+        self.t0 = 0        # first step the next rollout has to act on: 1 after carry_over(keep_step=True), else 0
+        self.rollouts = 0  # finish() counts them (runner/device_loop.py resets its env before the first)
+        self.copy_stream = torch.cuda.Stream(device=dev)
+        self._ring_rollout = -1   # the rollout (self.rollouts) whose first ring-fed put ordered the copy stream
+        self.returns = EpisodeReturns(N, dev) if track_returns else None
+        self.nav_status = NavStatus(N, dev) if track_nav_status else None
+        self._infos = torch.zeros((T + 1, N), dtype=torch.int32, device=dev) if track_nav_status else None
         if normalize_returns:
-            self.ret_norm = ReturnNorm(self.N, self.T, self.gamma, self.device, eps=norm_eps, clip=reward_clip)
+            self.ret_norm = ReturnNorm(N, T, gamma, dev, eps=norm_eps, clip=reward_clip)
             self.rewards_norm = self.ret_norm.rewards_norm
+
+    def _order_copy_stream(self):
+        """The one ring rule: the FIRST ring-fed put after construction or after a finish(), of whatever kind,
+        slot and component, makes the copy stream wait for the current stream once, before its DMA -- whatever was enqueued there on the
+        pools before this rollout (their zero fill, the previous update still reading them, carry_over(), an in-place normalisation)
+        is through before the first DMA overwrites a slot.  No later put of that rollout waits again, so copy t + 1 runs under
+        forward t (bench.py async_ingest_leg: waiting per slot cost 10 % of the overlapped ingest rate)."""
+        if self._ring_rollout != self.rollouts:     # finish() counts the rollouts: one wait per rollout, none per slot
+            self.copy_stream.wait_stream(torch.cuda.current_stream())
+            self._ring_rollout = self.rollouts
+
+    def record(self, t, rewards, dones, info=None):
+        """Reward / done of step t (0..T; T = the (T+1)-th step, only needed for keep_step); for a rollout that tracks the navigation
+        status also the env's info words."""
+        if t < self.t0:
+            raise ValueError("step %d was carried over from the previous rollout with its reward and done" % t)
+        if self._infos is not None:
+            if info is None:
+                raise ValueError("this rollout tracks the navigation status: record() needs the env's info words")
+            copy_into(self._infos[t], info)
+        copy_into(self._rewards[t], rewards)
+        copy_into(self._dones[t], dones)
+
+    def _before_gae(self):
+        """finish(): what a subclass commits in front of GAE (StateRollout: the observation statistics)."""
 
     def _gae(self):
         """finish(): GAE over rows 0..T-1, on the scaled rewards when normalize_returns is on.  Those rows are every step exactly once,
@@ -56,6 +115,39 @@ class _ReturnScaling:
         is then a synchronising collective that every rank has to call."""
         rewards = self.rewards if self.ret_norm is None else self.ret_norm.scale(self.rewards, self.dones)
         gae_device(self.values, rewards, self.dones, self.gamma, self.landa, adv=self.adv, ret=self.ret)
+
+    def finish(self):
+        """GAE over the rollout; with normalize_obs / normalize_returns first the commits of the statistics.  Under an initialised
+        process group every commit is one small all-reduce (through the host on gloo): finish() is then a synchronising collective that
+        EVERY rank has to call, once per normalised component and once for the returns, in this order."""
+        self._before_gae()
+        self._gae()
+        if self.returns is not None:  # Status.update_reward_status over rows 0..T-1: every step once, also with keep_step
+            self.returns.update(self.rewards, self.dones)
+        if self.nav_status is not None:    # Status.update_nav_status over the same rows
+            self.nav_status.update(self._infos[:self.T])
+        self.rollouts += 1
+
+    def carry_over(self, keep_step=False):
+        """The last stored step becomes step 0 of the next rollout (agent.py:286-292).  keep_step=True: the whole step, as the
+        reference keeps it (observation, action, old log-prob, value, reward, done of row T; the next rollout acts from t0 = 1);
+        False (default): the observation only, slot 0 is evaluated again by act(0) under the current weights.  The observation moves
+        as it is stored: a frame with its history (PlaneRollout), a slot normalised at its put (StateRollout)."""
+        T = self.T
+        self._carry_observation()
+        if keep_step:
+            for pool in (self.values, self._rewards, self._dones, self._actions, self._logps, self._infos):
+                if pool is not None:
+                    pool[0].copy_(pool[T])
+        self.t0 = 1 if keep_step else 0
+
+    def _value_rows(self, B):
+        return value_rows(self.ret, self.values, self.T, B, self.with_old_values)
+
+    def _columns(self, B):
+        """The learner's columns of batch() next to `states`: zero-copy views of rows 0..T-1."""
+        return dict(advs=self.adv.view(B), actions=self.actions.view((B,) + tuple(self.actions.shape[2:])),
+                    old_logps=self.logps.view(B), values=self._value_rows(B))
 
     def state_dict(self):
         """The running statistics a checkpoint has to carry next to the net's (host tensors): the return scaling's state and carry."""
@@ -68,40 +160,23 @@ class _ReturnScaling:
             self.ret_norm.load_state_dict(sd["ret_norm"])
 
 
-class DeviceRollout(_ReturnScaling):
+class DeviceRollout(_RolloutBase):
     def __init__(self, net, n_envs, horizon=256, channels=4, gamma=0.99, landa=0.95, device=None, seed=0, track_returns=False,
                  normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
-        check_knobs(norm_eps, reward_clip)
         self.hp = net.hot_path if hasattr(net, "hot_path") else net
-        self.with_old_values = bool(getattr(net, "wants_old_values", False))
-        self.N, self.T, self.C = int(n_envs), int(horizon), int(channels)
-        self.gamma, self.landa = gamma, landa
-        dev = torch.device(device if device is not None else self.hp.device)
-        self.device = dev
-        N, T = self.N, self.T
-        self.frames = torch.empty((T + 1, N, self.C, 84, 84), dtype=torch.uint8, device=dev)
-        self.values = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        # rows 0..T-1 are the rollout (contiguous [T, N] views: what GAE and the learner batch read); row T holds the (T+1)-th
-        # step's reward / done / action / log-prob for carry_over(keep_step=True)
-        self._rewards = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
-        self._actions = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self._logps = torch.zeros((T + 1, N), dtype=torch.float32, device=dev)
-        self.rewards, self.dones = self._rewards[:T], self._dones[:T]
-        self.actions, self.logps = self._actions[:T], self._logps[:T]
-        self.adv = torch.empty((T, N), dtype=torch.float32, device=dev)
-        self.ret = torch.empty((T, N), dtype=torch.float32, device=dev)
-        self._probs = torch.empty((N, self.hp.n_actions), dtype=torch.float32, device=dev)
-        self.seed, self.rollouts, self.t = int(seed), 0, 0
-        self.t0 = 0  # first step the next rollout has to act on: 1 after carry_over(keep_step=True), else 0
-        self.copy_stream = torch.cuda.Stream(device=dev)
-        self.returns = EpisodeReturns(N, dev) if track_returns else None
+        super().__init__(net, n_envs, horizon, gamma, landa, device if device is not None else self.hp.device,
+                         track_returns=track_returns, normalize_returns=normalize_returns, reward_clip=reward_clip, norm_eps=norm_eps)
+        self.C = int(channels)
+        self._probs = torch.empty((self.N, self.hp.n_actions), dtype=torch.float32, device=self.device)
+        self.seed, self.t = int(seed), 0
         # single-frame ingest (put_new_frames*): allocated at first use, a host that ships whole stacks pays nothing
         self._newest = None                # uint8 [3, N, 84, 84]: 0 / 1 the ring's DMA targets (step parity), 2 put_new_frames' copy
         self._reset_buf = None             # uint8 [2, N]: 0 a caller's reset flags brought to the device, 1 all ones (reset=True)
         self._pushed = [None, None]        # events: the push kernel that read _newest[parity] is through
-        self._ring_rollout = -1            # the rollout (self.rollouts) whose first single-frame ring put ordered the copy stream
-        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
+        self._alloc_observation()
+
+    def _alloc_observation(self):
+        self.frames = torch.empty((self.T + 1, self.N, self.C, 84, 84), dtype=torch.uint8, device=self.device)
 
     # ---- ingest ---------------------------------------------------------------------------------
     def put_frames(self, t, frames):
@@ -109,13 +184,10 @@ class DeviceRollout(_ReturnScaling):
         copy_into(self.frames[t], frames)
 
     def put_frames_from_ring(self, t, ring):
-        """hipMemcpyAsync from the pinned ring on the copy stream; the compute stream waits on it.  The FIRST slot a rollout fills
-        (t <= t0) also orders the copy stream behind the compute stream: whatever was enqueued there on the pool before this rollout
-        (its zero fill, the previous update still reading the frames) is through before the first DMA overwrites a slot.  Later slots
-        do not wait again -- copy t + 1 runs under forward t (bench.py async_ingest_leg: waiting per slot cost 10 % of the overlapped
-        ingest rate)."""
-        if t <= self.t0:
-            self.copy_stream.wait_stream(torch.cuda.current_stream())
+        """hipMemcpyAsync from the pinned ring on the copy stream; the compute stream waits on it.  The FIRST ring-fed put of a rollout,
+        at whatever t (slot 1 after the default carry_over(), which leaves t0 == 0), also orders the copy stream behind the compute
+        stream (_order_copy_stream); later slots do not wait again."""
+        self._order_copy_stream()
         ring.pop_to(self.frames[t], stream=self.copy_stream)
         torch.cuda.current_stream().wait_stream(self.copy_stream)
 
@@ -166,15 +238,13 @@ class DeviceRollout(_ReturnScaling):
         """put_new_frames with the frame taken from a pinned ring whose slots hold N * 7056 bytes: hipMemcpyAsync on the copy stream into
         one of two staging buffers (step parity), the compute stream waits for it and runs the push kernel.  Ordered with events only, so
         copy t + 1 still runs under forward t: the DMA of step t waits for the last push kernel that read the same staging
-        buffer (step t - 2's); and the FIRST such put of a rollout, at whatever t (slot 1 after the default carry_over()), orders the copy stream
-        behind everything the compute stream holds at that moment."""
+        buffer (step t - 2's); and the FIRST ring-fed put of a rollout, at whatever t (slot 1 after the default carry_over()), orders the
+        copy stream behind everything the compute stream holds at that moment (_order_copy_stream)."""
         buf = self._single_frame_buffers()
         flags = self._reset_flags(t, reset)           # before the ring is touched: a refused call consumes no slot
         cur = torch.cuda.current_stream()
         k = t & 1
-        if self._ring_rollout != self.rollouts:     # finish() counts the rollouts: one wait per rollout, none per slot
-            self.copy_stream.wait_stream(cur)
-            self._ring_rollout = self.rollouts
+        self._order_copy_stream()
         if self._pushed[k] is None:
             self._pushed[k] = torch.cuda.Event()
         else:
@@ -199,45 +269,17 @@ class DeviceRollout(_ReturnScaling):
         host that steps the env with them and keeps the step (carry_over(keep_step=True)).  Returns the action."""
         return self.act(self.T)
 
-    def record(self, t, rewards, dones):
-        """Reward / done of step t (0..T; T = the (T+1)-th step, only needed for keep_step)."""
-        if t < self.t0:
-            raise ValueError("step %d was carried over from the previous rollout with its reward and done" % t)
-        copy_into(self._rewards[t], rewards)
-        copy_into(self._dones[t], dones)
-
-    # ---- GAE + learner batch ----------------------------------------------------------------------
-    def finish(self):
-        self._gae()
-        if self.returns is not None:  # Status.update_reward_status over rows 0..T-1: every step once, also with keep_step
-            self.returns.update(self.rewards, self.dones)
-        self.rollouts += 1
-
-    def carry_over(self, keep_step=False):
-        """The last stored step becomes step 0 of the next rollout (agent.py:286-292).  keep_step=True: the whole step, as the
-        reference keeps it (frame, action, old log-prob, value, reward, done of row T; the next rollout acts from t0 = 1);
-        False (default): the frame only, slot 0 is evaluated again by act(0) under the current weights."""
-        T = self.T
-        self.frames[0].copy_(self.frames[T])
-        if keep_step:
-            self.values[0].copy_(self.values[T])
-            for pool in (self._rewards, self._dones, self._actions, self._logps):
-                pool[0].copy_(pool[T])
-            self.t0 = 1
-        else:
-            self.t0 = 0
-
-    def _value_rows(self, B):
-        return value_rows(self.ret, self.values, self.T, B, self.with_old_values)
+    # ---- carry-over + learner batch ---------------------------------------------------------------
+    def _carry_observation(self):
+        self.frames[0].copy_(self.frames[self.T])
 
     def batch(self):
         """Zero-copy views in the layout net.learn expects (sample order is irrelevant to the maths)."""
         B = self.N * self.T
-        return Experience(states=[self.frames[:self.T].view(B, self.C, 84, 84)], advs=self.adv.view(B),
-                          actions=self.actions.view(B), old_logps=self.logps.view(B), values=self._value_rows(B))
+        return Experience(states=[self.frames[:self.T].view(B, self.C, 84, 84)], **self._columns(B))
 
 
-class StateRollout(_ReturnScaling):
+class StateRollout(_RolloutBase):
     """DeviceRollout for the operator-composed nets (nn/generic.py): the observation is a LIST of
     float tensors per env (e.g. robot_nav: laser [1,960], vector [5], pedestrian image [3,48,48]) and
     the action may be continuous.  Same pool layout idea ([time][env] major, everything on the GPU),
@@ -249,7 +291,7 @@ class StateRollout(_ReturnScaling):
     ``obs_norm[k]`` with (update / commit / freeze, or load_state_dict).  act() and batch() therefore read the same numbers and stay
     zero-copy.  finish() commits and freezes.  carry_over() moves a slot that is normalised already: it is neither counted nor
     normalised again, so slot 0 of the next rollout carries the statistics of one finish() earlier than slots 1..T (DESIGN.md
-    section 6.6).  normalize_returns: see _ReturnScaling.
+    section 6.6).  normalize_returns: see _RolloutBase.
 
     track_nav_status: record() also takes the env's info words (DeviceNavEnv(emit_info=True).info) into an int32 [T + 1, N] pool and
     finish() feeds rows 0..T-1 to ``nav_status`` (agent.NavStatus), exactly where it feeds ``returns``."""
@@ -259,38 +301,18 @@ class StateRollout(_ReturnScaling):
         state_shapes = [tuple(int(d) for d in shape) for shape in state_shapes]
         flags = obs_norm_flags(normalize_obs, len(state_shapes))
         check_knobs(norm_eps, obs_clip)
-        check_knobs(norm_eps, reward_clip)
         self.net = net
-        self.with_old_values = bool(getattr(net, "wants_old_values", False))
-        self.N, self.T = int(n_envs), int(horizon)
-        self.gamma, self.landa = gamma, landa
-        dev = torch.device(device if device is not None else net.device)
-        self.device = dev
-        N, T = self.N, self.T
-        f = dict(dtype=torch.float32, device=dev)
-        self.states = [torch.empty((T + 1, N) + tuple(int(d) for d in shape), **f) for shape in state_shapes]
-        self.values = torch.zeros((T + 1, N), **f)
-        self._rewards = torch.zeros((T + 1, N), **f)
-        self._dones = torch.zeros((T + 1, N), dtype=torch.uint8, device=dev)
-        act_shape = (T + 1, N, net.n_actions) if getattr(net, "continuous", False) else (T + 1, N)
-        self._actions = torch.zeros(act_shape, **f)
-        self._logps = torch.zeros((T + 1, N), **f)
-        self.rewards, self.dones = self._rewards[:T], self._dones[:T]
-        self.actions, self.logps = self._actions[:T], self._logps[:T]
-        self.adv = torch.empty((T, N), **f)
-        self.ret = torch.empty((T, N), **f)
-        self.t0 = 0
-        self.rollouts = 0                  # finish() counts them (runner/device_loop.collect_states resets its env before the first)
-        self.copy_stream = torch.cuda.Stream(device=dev)
-        self.returns = EpisodeReturns(N, dev) if track_returns else None
-        self.nav_status = NavStatus(N, dev) if track_nav_status else None
-        self._infos = torch.zeros((T + 1, N), dtype=torch.int32, device=dev) if track_nav_status else None
+        N, T = int(n_envs), int(horizon)
+        super().__init__(net, N, T, gamma, landa, device if device is not None else net.device,
+                         action_shape=(T + 1, N, net.n_actions) if getattr(net, "continuous", False) else None,
+                         track_returns=track_returns, track_nav_status=track_nav_status, normalize_returns=normalize_returns,
+                         reward_clip=reward_clip, norm_eps=norm_eps)
+        dev = self.device
+        self.states = [torch.empty((T + 1, N) + shape, dtype=torch.float32, device=dev) for shape in state_shapes]
         self.obs_norm = None
-        self._ring_ordered = False         # normalize_obs: a ring put has ordered the copy stream since the last finish()
         if any(flags):
             self.obs_norm = [RunningNorm(shape, dev, eps=norm_eps, clip=obs_clip) if on else None
                              for on, shape in zip(flags, state_shapes)]
-        self._init_return_scaling(normalize_returns, reward_clip, norm_eps)
 
     def _normalize_slot(self, t, index):
         """Slot t of component `index` holds raw rows: count them, then normalise them in place with the frozen affine."""
@@ -318,13 +340,11 @@ class StateRollout(_ReturnScaling):
             self._normalize_slot(t, k)
 
     def put_state_from_ring(self, t, index, ring):
-        """Component `index` of slot t from a pinned ring (raw fp32 bytes), on the copy stream (the first slot of a rollout orders the
-        copy stream behind the compute stream, as put_frames_from_ring).  With normalize_obs the compute stream also WRITES the slots
-        (the in-place normalisation of the previous rollout's puts), so the first ring put behind a finish() orders the copy stream
-        as well, at whatever t: after carry_over() that put is t == 1."""
-        if t <= self.t0 or (self.obs_norm is not None and not self._ring_ordered):
-            self.copy_stream.wait_stream(torch.cuda.current_stream())
-            self._ring_ordered = True
+        """Component `index` of slot t from a pinned ring (raw fp32 bytes), on the copy stream.  The FIRST ring-fed put of a rollout, of
+        whatever component and at whatever t (slot 1 after carry_over()), orders the copy stream behind the compute stream
+        (_order_copy_stream), with or without normalize_obs: once per rollout, not once per component of the first slot.  Later puts
+        land in rows that nothing enqueued since then touches (the in-place normalisation writes the slot it just received)."""
+        self._order_copy_stream()
         ring.pop_to(self.states[index][t], stream=self.copy_stream)
         torch.cuda.current_stream().wait_stream(self.copy_stream)
         self._normalize_slot(t, index)
@@ -348,34 +368,15 @@ class StateRollout(_ReturnScaling):
         self.values[self.T].copy_(values[0][:, 0])
         return None
 
-    def record(self, t, rewards, dones, info=None):
-        if t < self.t0:
-            raise ValueError("step %d was carried over from the previous rollout with its reward and done" % t)
-        if self._infos is not None:
-            if info is None:
-                raise ValueError("this rollout tracks the navigation status: record() needs the env's info words")
-            copy_into(self._infos[t], info)
-        copy_into(self._rewards[t], rewards)
-        copy_into(self._dones[t], dones)
-
-    def finish(self):
-        """GAE over the rollout; with normalize_obs / normalize_returns first the commits of the statistics.  Under an initialised
-        process group every commit is one small all-reduce (through the host on gloo): finish() is then a synchronising collective that
-        EVERY rank has to call, once per normalised component and once for the returns, in this order."""
+    def _before_gae(self):
+        """finish() commits and freezes the observation statistics in component order, in front of the returns' commit."""
         for norm in self.obs_norm or ():
             if norm is not None:
                 norm.commit()
                 norm.freeze()
-        self._ring_ordered = False
-        self._gae()
-        if self.returns is not None:
-            self.returns.update(self.rewards, self.dones)
-        if self.nav_status is not None:    # Status.update_nav_status over the same rows
-            self.nav_status.update(self._infos[:self.T])
-        self.rollouts += 1
 
     def state_dict(self):
-        """_ReturnScaling.state_dict plus the observation statistics, one entry (or None) per component."""
+        """_RolloutBase.state_dict plus the observation statistics, one entry (or None) per component."""
         sd = super().state_dict()
         sd["obs_norm"] = None if self.obs_norm is None else [None if n is None else n.state_dict() for n in self.obs_norm]
         return sd
@@ -390,25 +391,11 @@ class StateRollout(_ReturnScaling):
             if n is not None:
                 n.load_state_dict(s)
 
-    def carry_over(self, keep_step=False):
-        """DeviceRollout.carry_over: keep_step=True keeps the whole (T+1)-th step as the reference does (agent.py:286-292).  A slot
-        normalised at its put moves as it is (class docstring)."""
-        T = self.T
+    def _carry_observation(self):
+        """Every component; a slot normalised at its put moves as it is (class docstring)."""
         for p in self.states:
-            p[0].copy_(p[T])
-        if keep_step:
-            self.values[0].copy_(self.values[T])
-            for pool in (self._rewards, self._dones, self._actions, self._logps) + (() if self._infos is None else (self._infos,)):
-                pool[0].copy_(pool[T])
-            self.t0 = 1
-        else:
-            self.t0 = 0
-
-    def _value_rows(self, B):
-        return value_rows(self.ret, self.values, self.T, B, self.with_old_values)
+            p[0].copy_(p[self.T])
 
     def batch(self):
         B = self.N * self.T
-        return Experience(states=[p[:self.T].reshape((B,) + tuple(p.shape[2:])) for p in self.states],
-                          advs=self.adv.view(B), actions=self.actions.view((B,) + tuple(self.actions.shape[2:])),
-                          old_logps=self.logps.view(B), values=self._value_rows(B))
+        return Experience(states=[p[:self.T].reshape((B,) + tuple(p.shape[2:])) for p in self.states], **self._columns(B))

@@ -7,41 +7,29 @@ a trajectory is reproducible bit for bit from (game, seed, global env index, act
 import torch
 
 from ddrl4nav_amd import ops
+from ddrl4nav_amd.env.device_env_base import DeviceEnvBase
 from ddrl4nav_amd.env.device_nav_env import NAV_ENV_NAME, make_device_nav_env
 
 ENV_NAMES = {"DevicePong-v0": "pong", "DeviceCatch-v0": "catch"}
-_PARAMS = ("game", "n_envs", "seed", "n_actions", "points", "max_steps", "env0")
 
 
-class DeviceEnv:
+class DeviceEnv(DeviceEnvBase):
+    _PARAMS = ("game", "n_envs", "seed", "n_actions", "points", "max_steps", "env0")
+    _state_ints = staticmethod(ops.env_state_ints)
+
     def __init__(self, game, n_envs, device=None, seed=0, n_actions=6, points=21, max_steps=10000, env0=0):
         """game: "pong" or "catch".  env0: the global index of local env 0 -- a rank that owns dist.shard_envs' range [a, b) builds
         DeviceEnv(game, b - a, env0=a) and plays exactly the games envs a..b-1 of a single process would.  Pong ends at `points` points
         of either side, every game at `max_steps` steps (a truncation counts as a done)."""
         if game not in ops.ENV_GAMES:
             raise ValueError("game must be one of %s, got %r" % (sorted(ops.ENV_GAMES), game))
-        self.game, self.N = game, int(n_envs)
-        self.seed, self.n_actions, self.points, self.max_steps, self.env0 = int(seed), int(n_actions), int(points), int(max_steps), int(env0)
-        if self.N < 1:
-            raise ValueError("n_envs must be at least 1, got %d" % self.N)
+        self.game, self.n_actions, self.points, self.max_steps = game, int(n_actions), int(points), int(max_steps)
         if not 2 <= self.n_actions <= 18:
             raise ValueError("n_actions must be in 2..18, got %d" % self.n_actions)
         if self.points < 1 or self.max_steps < 1:
             raise ValueError("points and max_steps must be at least 1, got %d and %d" % (self.points, self.max_steps))
-        if not 0 <= self.seed < 2 ** 32:
-            raise ValueError("seed must fit 32 bits, got %d" % self.seed)
-        if self.env0 < 0 or self.env0 + self.N > 2 ** 32:
-            raise ValueError("global env indices env0 .. env0 + n_envs - 1 must fit 32 bits")
-        dev = torch.device("cuda" if device is None else device)
-        self.device = dev
-        self.state = torch.zeros((self.N, ops.env_state_ints()), dtype=torch.int32, device=dev)
-        self.frame = torch.empty((self.N, 84, 84), dtype=torch.uint8, device=dev)
-        self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
-
-    @property
-    def n_envs(self):
-        return self.N
+        super().__init__(n_envs, device, seed, env0)
+        self.frame = torch.empty((self.N, 84, 84), dtype=torch.uint8, device=self.device)
 
     def _frame_out(self, frame_out):
         return self.frame if frame_out is None else frame_out
@@ -58,21 +46,6 @@ class DeviceEnv:
         episode: the frame is that episode's first and done is the reset flag the frame pools expect.  Asynchronous."""
         return ops.env_step(self.game, self.state, actions, self._frame_out(frame_out), self.reward, self.done, env0=self.env0,
                             n_actions=self.n_actions, points=self.points, max_steps=self.max_steps, seed=self.seed)
-
-    def state_dict(self):
-        """The state words (a host tensor) and the parameters: an env loaded from it continues bit-identically."""
-        sd = {k: getattr(self, k) for k in _PARAMS}
-        sd["state"] = self.state.cpu()
-        return sd
-
-    def load_state_dict(self, sd):
-        for k in _PARAMS:
-            if sd[k] != getattr(self, k):
-                raise ValueError("%s differs between the saved env (%r) and this one (%r)" % (k, sd[k], getattr(self, k)))
-        s = torch.as_tensor(sd["state"])
-        if s.dtype != torch.int32 or tuple(s.shape) != tuple(self.state.shape):
-            raise ValueError("state must be int32 %s, got %s %s" % (tuple(self.state.shape), s.dtype, tuple(s.shape)))
-        self.state.copy_(s)
 
 
 def make_device_env(config_env, device=None, env0=0):

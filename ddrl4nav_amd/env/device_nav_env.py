@@ -8,12 +8,14 @@ index, populations, actions)."""
 import torch
 
 from ddrl4nav_amd import ops
+from ddrl4nav_amd.env.device_env_base import DeviceEnvBase
 
 NAV_ENV_NAME = "DeviceNav-v0"
-_PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
 
 
-class DeviceNavEnv:
+class DeviceNavEnv(DeviceEnvBase):
+    _PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
+    _state_ints = staticmethod(ops.nav_env_state_ints)
     state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
     def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False):
@@ -21,32 +23,18 @@ class DeviceNavEnv:
         steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv.  emit_info: every step also
         fills ``info`` (int32 [N]: why the step ended or did not, ops.nav_info_fields; agent.NavStatus accumulates it); the trajectory is
         the same either way."""
-        self.N, self.seed, self.env0 = int(n_envs), int(seed), int(env0)
         self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
-        if self.N < 1:
-            raise ValueError("n_envs must be at least 1, got %d" % self.N)
         if not 0 <= self.n_obstacles <= 10:
             raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
         if not 0 <= self.n_peds <= 5:
             raise ValueError("n_peds must be in 0..5, got %d" % self.n_peds)
         if self.max_steps < 1:
             raise ValueError("max_steps must be at least 1, got %d" % self.max_steps)
-        if not 0 <= self.seed < 2 ** 32:
-            raise ValueError("seed must fit 32 bits, got %d" % self.seed)
-        if self.env0 < 0 or self.env0 + self.N > 2 ** 32:
-            raise ValueError("global env indices env0 .. env0 + n_envs - 1 must fit 32 bits")
-        dev = torch.device("cuda" if device is None else device)
-        self.device = dev
-        self.state = torch.zeros((self.N, ops.nav_env_state_ints()), dtype=torch.int32, device=dev)
+        super().__init__(n_envs, device, seed, env0)
+        dev = self.device
         self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
-        self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
         self.emit_info = bool(emit_info)
         self.info = torch.zeros(self.N, dtype=torch.int32, device=dev) if self.emit_info else None
-
-    @property
-    def n_envs(self):
-        return self.N
 
     def _obs_out(self, obs_out):
         return self.obs if obs_out is None else list(obs_out)
@@ -68,21 +56,6 @@ class DeviceNavEnv:
                                          seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
         return ops.nav_env_step(self.state, actions, self._obs_out(obs_out), self.reward, self.done, env0=self.env0, seed=self.seed,
                                 n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)
-
-    def state_dict(self):
-        """The state words (a host tensor) and the parameters: an env loaded from it continues bit-identically."""
-        sd = {k: getattr(self, k) for k in _PARAMS}
-        sd["state"] = self.state.cpu()
-        return sd
-
-    def load_state_dict(self, sd):
-        for k in _PARAMS:
-            if sd[k] != getattr(self, k):
-                raise ValueError("%s differs between the saved env (%r) and this one (%r)" % (k, sd[k], getattr(self, k)))
-        s = torch.as_tensor(sd["state"])
-        if s.dtype != torch.int32 or tuple(s.shape) != tuple(self.state.shape):
-            raise ValueError("state must be int32 %s, got %s %s" % (tuple(self.state.shape), s.dtype, tuple(s.shape)))
-        self.state.copy_(s)
 
 
 def make_device_nav_env(config_env, device=None, env0=0):

@@ -444,16 +444,22 @@ def nav_env_reset(state, obs, env0=0, seed=0, n_obstacles=10, n_peds=5, mask=Non
     return obs
 
 
-def nav_env_step(state, actions, obs, reward, done, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
-    """One step of every env (include/ddrl.h ddrl_op_nav_env_step; csrc/navenv.hip): actions fp32 [n, 2] -> state (in place), obs =
-    [laser, vector, image], reward fp32 [n], done uint8 [n].  Asynchronous on the current stream; returns (obs, reward, done)."""
+def _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps):
+    """The checks nav_env_step and nav_env_step_info share, and the arguments both C entry points take up to `done`."""
     n = _nav_env_args(state, obs)
     assert tuple(_f32(actions).shape) == (n, 2) and _f32(reward).numel() == n and actions.device == state.device \
         and reward.device == state.device, "actions fp32 [n, 2], reward fp32 [n] on the state's device"
     assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
         and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
-    check(_lib.load().ddrl_op_nav_env_step(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps),
-                                           _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward), _p(done), _st()))
+    return (_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps), _p(actions), _p(obs[0]),
+            _p(obs[1]), _p(obs[2]), _p(reward), _p(done))
+
+
+def nav_env_step(state, actions, obs, reward, done, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
+    """One step of every env (include/ddrl.h ddrl_op_nav_env_step; csrc/navenv.hip): actions fp32 [n, 2] -> state (in place), obs =
+    [laser, vector, image], reward fp32 [n], done uint8 [n].  Asynchronous on the current stream; returns (obs, reward, done)."""
+    args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
+    check(_lib.load().ddrl_op_nav_env_step(*args, _st()))
     return obs, reward, done
 
 
@@ -461,16 +467,10 @@ def nav_env_step_info(state, actions, obs, reward, done, info, env0=0, seed=0, n
     """nav_env_step plus the info word of every env, info int32 [n] (include/ddrl.h ddrl_op_nav_env_step_info): what the step just played
     did -- done, goal, collision kind, truncation, closeness to a pedestrian, the decoded action (nav_info_fields unpacks it).  The other
     outputs are bit-identical to nav_env_step's.  Asynchronous on the current stream; returns (obs, reward, done, info)."""
-    n = _nav_env_args(state, obs)
-    assert tuple(_f32(actions).shape) == (n, 2) and _f32(reward).numel() == n and actions.device == state.device \
-        and reward.device == state.device, "actions fp32 [n, 2], reward fp32 [n] on the state's device"
-    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
-        and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
-    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (n,) \
+    args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
+    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (args[1],) \
         and info.device == state.device, "info: contiguous int32 [n] on the state's device"
-    check(_lib.load().ddrl_op_nav_env_step_info(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds),
-                                                int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward), _p(done),
-                                                _p(info), _st()))
+    check(_lib.load().ddrl_op_nav_env_step_info(*args, _p(info), _st()))
     return obs, reward, done, info
 
 

@@ -154,6 +154,7 @@ def test_plane_rollout_argument_overrides_the_nets_value(monkeypatch):
     out (no device here): what is looked at is which buffers it asks for."""
     import torch
     from ddrl4nav_amd.agent import plane_rollout as P
+    from ddrl4nav_amd.agent import rollout as R
     asked = []
 
     class FakeTensor:
@@ -170,6 +171,7 @@ def test_plane_rollout_argument_overrides_the_nets_value(monkeypatch):
     fake_torch = types.SimpleNamespace(empty=alloc, zeros=alloc, ones=alloc, uint8=torch.uint8, float32=torch.float32, int32=torch.int32,
                                        device=lambda d: d, cuda=types.SimpleNamespace(Stream=lambda device=None: None))
     monkeypatch.setattr(P, "torch", fake_torch)
+    monkeypatch.setattr(R, "torch", fake_torch)     # the constructor's shared part lives in agent/rollout.py
     N, T, C = 5, 6, 4
 
     def build(net_value, arg):
