@@ -233,6 +233,11 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_nav_status_update": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_nav_status_reduce": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_fleet_env_state_ints": (c_int32, []),
+    "ddrl_op_fleet_env_reset": (c_int32, [c_void_p, c_int32, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_fleet_env_step": (c_int32, [c_void_p, c_int32, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -69,7 +69,8 @@ class NavStatus:
     """Status.update_nav_status for N device envs.  The per-env state carries the reference's attribute names (v_speeds_sum,
     w_speeds_episode_close_human, steps_episode_no_human, episode_num, arrive_num [100, N], ...): views of the three buffers the
     kernels own -- ``sums`` fp32 [18, N], ``episode_num`` int32 [N], ``rings`` fp32 [5, 100, N].  ``trunc_num`` is a fifth ring kept by the
-    ring rule of the other four: whether the episode ended by the time limit.  coll_robot_num stays zero (one robot per env)."""
+    ring rule of the other four: whether the episode ended by the time limit.  coll_robot_num counts collision kind 3, another robot: only
+    a FleetNavEnv (env/fleet_nav_env.py, one status row per robot) emits it; other_robot_collision_rate() is its rate."""
 
     def __init__(self, n_envs, device):
         self.N = int(n_envs)
@@ -121,6 +122,13 @@ class NavStatus:
         envs whose latest finished episode has steps of that kind; nan when there is none (EpisodeReturns.mean_return's convention)."""
         total = self.combine([self.partial().cpu()] if partials is None else partials)
         return {k: (total[2 * i] / total[2 * i + 1] if total[2 * i + 1] > 0 else float("nan")) for i, k in enumerate(NAV_SUMMARY_KEYS)}
+
+    def other_robot_collision_rate(self):
+        """ReducedOtherRobotCollisionRateLogger: the mean over the rows of sum(coll_robot_num, 0) / clip(episode_num + 1, 1, 100), the rule
+        of the other collision rates of partial(); float64 on the device, returned as a host float (one scalar copy, which synchronises).
+        Not one of summary()'s keys."""
+        window = torch.clamp(self.episode_num + 1, 1, ops.NAV_STATUS_WINDOW).to(torch.float64)
+        return float((self.coll_robot_num.to(torch.float64).sum(0) / window).mean().item())
 
     def state_dict(self):
         return {"sums": self.sums.cpu(), "episode_num": self.episode_num.cpu(), "rings": self.rings.cpu()}

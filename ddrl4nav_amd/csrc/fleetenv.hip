@@ -1,0 +1,416 @@
+// Multi-robot navigation env: R = 1..4 differential-drive robots share one arena with up to 10 static circular obstacles and up to 5
+// walking pedestrians, see each other in their lidar and dynamic-agent map and collide with each other (include/ddrl.h
+// ddrl_op_fleet_env_*).  tests/fleet_env_ref.py is the rule book, in integers only, so every state word, lidar
+// range, vector entry, map cell, reward, done and info word equals the model's.  Context-free, no allocation, no atomics; the same
+// arguments give the same bits.  The sizes, the trig table, the hash and the ray cast are section 6.8's (navcore.h).
+//
+// A world is one arena, a row is one robot: row i * R + r is robot r of world i.  One workgroup of 256 R threads per world, and nobody
+// else touches that world's state.  Threads 0..95 load one state word each, bring it into its range and park it in LDS `s`.  Behind
+// barrier 1 thread 0 plays the step on `s` -- pedestrians, every robot's move, every robot's outcome from the positions after all
+// moves -- and stores the rows' reward, done and info and the mask of finished robots.  Behind barrier 2 wave 0 respawns the finished
+// robots in index order: `s` is only read, one lane tests one cell of a scan and a ballot finds the first free one in scan order, the
+// positions earlier respawns left live in registers, and lane 0 writes the new episodes into `fresh`, not into `s`.  Behind barrier 3
+// threads 0..39 and 90 move `fresh` and the event counter into `s`; behind barrier 4 threads 0..23 store the 384 bytes of state
+// (16 bytes each) and the 256 threads of robot r render row i * R + r from `s`, as section 6.8's render does.  So no thread reads a word
+// of LDS or of global state that another thread writes in the same phase: the global words are read before barrier 1 and written
+// after barrier 4, `s` is written by thread 0 alone between barriers 1 and 2, read-only between 2 and 3, and final after 4.
+#include "navcore.h"
+
+namespace ddrl {
+
+constexpr int FL_STATE_INTS = 96, FL_MAX_ROBOTS = 4, FL_ROBOT_INTS = 10, FL_ROBOT_USED = 9;
+constexpr int FL_OBS0 = 40, FL_PED0 = 70, FL_EVENTS = 90;
+constexpr int FL_CELLS = 25, FL_GRID = 5, FL_CLEAR = 300;
+constexpr int FL_DISCS = NAV_MAX_PEDS + FL_MAX_ROBOTS - 1;  // what one robot's map can hold: the pedestrians, then the other robots
+constexpr int FL_MAX_THREADS = NAV_THREADS * FL_MAX_ROBOTS;
+static_assert(FL_MAX_ROBOTS * FL_ROBOT_INTS == FL_OBS0 && FL_OBS0 + 3 * NAV_MAX_OBS == FL_PED0 && FL_PED0 + 4 * NAV_MAX_PEDS == FL_EVENTS &&
+                  FL_EVENTS < FL_STATE_INTS && FL_STATE_INTS % 4 == 0,
+              "state layout");
+static_assert(FL_CELLS <= 64 && FL_DISCS <= NAV_THREADS && 2 * FL_CLEAR < NAV_CELL, "one cell a lane; one circle blocks one cell at most");
+
+// word k of a loaded state brought into its range (FleetEnvRef.sanitize): a no-op on every state the rules produce
+__device__ __forceinline__ int fleet_sanitize_word(int k, int v, int R, int n_obs, int n_peds) {
+  if (k < FL_OBS0) {
+    const int r = k / FL_ROBOT_INTS, f = k - FL_ROBOT_INTS * r;  // f < 9: X .. STEPS, the words of section 6.8's robot
+    return (r < R && f < FL_ROBOT_USED) ? nav_sanitize_word(f, v, 0, 0) : 0;
+  }
+  if (k < FL_PED0) return nav_sanitize_word(k - FL_OBS0 + NS_OBS0, v, n_obs, n_peds);
+  if (k < FL_EVENTS) return nav_sanitize_word(k - FL_PED0 + NS_PED0, v, n_obs, n_peds);
+  return k == FL_EVENTS ? v : 0;
+}
+
+__device__ __forceinline__ uint32_t fleet_draw(int* s, uint32_t seed, uint32_t gworld) {
+  const uint32_t h = nav_hash(seed, gworld, (uint32_t)s[FL_EVENTS]);
+  s[FL_EVENTS] = (int)((uint32_t)s[FL_EVENTS] + 1u);
+  return h;
+}
+
+__device__ __forceinline__ int fleet_cell_x(int cell) { return (cell % FL_GRID - 2) * NAV_CELL; }
+__device__ __forceinline__ int fleet_cell_y(int cell) { return (cell / FL_GRID - 2) * NAV_CELL; }
+__device__ __forceinline__ int fleet_jitter_x(uint32_t h) { return (int)((h >> 8) % 257u) - 128; }
+__device__ __forceinline__ int fleet_jitter_y(uint32_t h) { return (int)((h >> 17) % 257u) - 128; }
+
+__device__ __forceinline__ int fleet_distance(int gx, int gy, int x, int y) {
+  const int64_t dx = gx - x, dy = gy - y;
+  return (int)nav_isqrt(dx * dx + dy * dy);
+}
+
+// FleetEnvRef._new_world on the zeroed LDS copy, by one thread: 1 + n_obs + 2 R + n_peds draws, every slot in a cell of its own
+__device__ void fleet_new_world(int* s, int R, int n_obs, int n_peds, uint32_t seed, uint32_t gworld) {
+  uint32_t h = fleet_draw(s, seed, gworld);
+  const uint32_t m = h % 20u;
+  const int a = (int)(1u + m + m / 4u);  // the m-th of 1..24 that is no multiple of 5
+  const int b = (int)((h >> 8) % 25u);
+  int slot = 0;
+  auto next_cell = [&]() { return (a * slot++ + b) % FL_CELLS; };
+  for (int k = 0; k < n_obs; ++k) {
+    h = fleet_draw(s, seed, gworld);
+    const int cell = next_cell();
+    s[FL_OBS0 + 3 * k] = fleet_cell_x(cell) + fleet_jitter_x(h);
+    s[FL_OBS0 + 3 * k + 1] = fleet_cell_y(cell) + fleet_jitter_y(h);
+    s[FL_OBS0 + 3 * k + 2] = NAV_OBS_R_MIN + (int)(h % 52u);
+  }
+  for (int r = 0; r < R; ++r) {
+    int* p = s + FL_ROBOT_INTS * r;
+    h = fleet_draw(s, seed, gworld);
+    int cell = next_cell();
+    p[NS_X] = fleet_cell_x(cell);
+    p[NS_Y] = fleet_cell_y(cell);
+    p[NS_H] = (int)(h % (uint32_t)NAV_HEADINGS);
+    h = fleet_draw(s, seed, gworld);
+    cell = next_cell();
+    p[NS_GX] = fleet_cell_x(cell) + fleet_jitter_x(h);
+    p[NS_GY] = fleet_cell_y(cell) + fleet_jitter_y(h);
+    p[NS_V] = p[NS_W] = p[NS_STEPS] = 0;
+    p[NS_DPREV] = fleet_distance(p[NS_GX], p[NS_GY], p[NS_X], p[NS_Y]);
+  }
+  for (int j = 0; j < n_peds; ++j) {
+    h = fleet_draw(s, seed, gworld);
+    const int cell = next_cell();
+    s[FL_PED0 + 4 * j] = fleet_cell_x(cell);
+    s[FL_PED0 + 4 * j + 1] = fleet_cell_y(cell);
+    s[FL_PED0 + 4 * j + 2] = (int)(h % (uint32_t)NAV_HEADINGS);
+    s[FL_PED0 + 4 * j + 3] = NAV_SPEED_MIN + (int)((h >> 12) % 17u);
+  }
+}
+
+// Steps 1 to 5 of FleetEnvRef.step on the LDS copy, by one thread: the pedestrians, every robot's move, then every robot's outcome from
+// the positions after all moves (R (n_obs + n_peds + R) circle tests).  `act`, `reward`, `done`, `info` are the world's R rows; `units`
+// is LDS scratch [R].  Returns the mask of finished robots; their respawn is fleet_respawn's.  Every product fits 32 bits.
+__device__ int fleet_play(int* s, int* units, int R, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t gworld,
+                          const float* __restrict__ act, float* __restrict__ reward, uint8_t* __restrict__ done, int32_t* __restrict__ info) {
+  for (int j = 0; j < n_peds; ++j) {
+    int* p = s + FL_PED0 + 4 * j;
+    const int cx = p[0] + ((p[3] * nav_cos(p[2])) >> NAV_Q), cy = p[1] + ((p[3] * nav_sin(p[2])) >> NAV_Q);
+    bool refused = cx * cx + cy * cy > (NAV_ARENA_R - NAV_PED_R) * (NAV_ARENA_R - NAV_PED_R);
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1], rr = NAV_PED_R + s[FL_OBS0 + 3 * k + 2];
+      refused = refused || dx * dx + dy * dy < rr * rr;
+    }
+    if (refused) {
+      p[2] = (int)(fleet_draw(s, seed, gworld) % (uint32_t)NAV_HEADINGS);
+    } else {
+      p[0] = cx;
+      p[1] = cy;
+    }
+  }
+  for (int r = 0; r < R; ++r) {
+    int* p = s + FL_ROBOT_INTS * r;
+    int v, w;
+    nav_decode(act[2 * r], act[2 * r + 1], &v, &w);
+    const int h = nav_heading(p[NS_H] + w);
+    p[NS_X] += (v * nav_cos(h)) >> NAV_Q;
+    p[NS_Y] += (v * nav_sin(h)) >> NAV_Q;
+    p[NS_H] = h;
+    p[NS_V] = v;
+    p[NS_W] = w;
+    p[NS_STEPS] = (int)((uint32_t)p[NS_STEPS] + 1u);
+    const int d = fleet_distance(p[NS_GX], p[NS_GY], p[NS_X], p[NS_Y]);
+    units[r] = 2 * (p[NS_DPREV] - d);
+    p[NS_DPREV] = d;
+  }
+  int fin = 0;
+  for (int r = 0; r < R; ++r) {
+    const int* p = s + FL_ROBOT_INTS * r;
+    const int x = p[NS_X], y = p[NS_Y];
+    const bool wall = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
+    bool hit_o = false, hit_p = false, hit_r = false, close = false;
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = x - s[FL_OBS0 + 3 * k], dy = y - s[FL_OBS0 + 3 * k + 1], rr = NAV_ROBOT_R + s[FL_OBS0 + 3 * k + 2];
+      hit_o = hit_o || dx * dx + dy * dy < rr * rr;
+    }
+    for (int j = 0; j < n_peds; ++j) {
+      const int dx = x - s[FL_PED0 + 4 * j], dy = y - s[FL_PED0 + 4 * j + 1], dd = dx * dx + dy * dy;
+      hit_p = hit_p || dd < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
+      close = close || dd <= NAV_CLOSE * NAV_CLOSE;
+    }
+    for (int q = 0; q < R; ++q) {
+      const int dx = x - s[FL_ROBOT_INTS * q + NS_X], dy = y - s[FL_ROBOT_INTS * q + NS_Y];
+      hit_r = hit_r || (q != r && dx * dx + dy * dy < 4 * NAV_ROBOT_R * NAV_ROBOT_R);
+    }
+    const bool collision = wall || hit_o || hit_p || hit_r;
+    const bool goal = !collision && p[NS_DPREV] <= NAV_GOAL_TOL;
+    const bool trunc = !collision && !goal && p[NS_STEPS] >= max_steps;
+    const bool fini = collision || goal || trunc;
+    const int u = units[r] - (collision ? NAV_BONUS : 0) + (goal ? NAV_BONUS : 0);
+    reward[r] = (float)u * 0.00390625f;
+    done[r] = fini ? 1 : 0;
+    if (info != nullptr) {
+      const int kind = (wall || hit_o) ? 1 : (hit_p ? 2 : (hit_r ? 3 : 0));  // static wins, then the pedestrian
+      info[r] = (fini ? NI_DONE : 0) | (goal ? NI_GOAL : 0) | (kind << NI_KIND_SHIFT) | (trunc ? NI_TRUNC : 0) | (close ? NI_CLOSE : 0) |
+                (wall ? NI_WALL : 0) | (hit_o ? NI_OBSTACLE : 0) | (p[NS_V] << NI_V_SHIFT) | ((p[NS_W] + NAV_W_MAX) << NI_W_SHIFT);
+    }
+    fin |= (fini ? 1 : 0) << r;
+  }
+  return fin;
+}
+
+// the first lane in scan order whose cell holds; a free cell always exists in a sanitised state (the rule book asserts it), 0 otherwise
+__device__ __forceinline__ int fleet_first(bool ok) {
+  const unsigned long long vote = __ballot(ok);
+  return vote ? __ffsll((long long)vote) - 1 : 0;
+}
+
+// Step 6 of FleetEnvRef.step, by all 64 lanes of one wave in uniform control flow: the robots of `fin` respawn in index order, two draws
+// each.  Lane l < 25 tests cell (c0 + l) % 25 of a scan, so the first set bit of the ballot is the rule book's first free cell.  `s` is
+// only read; the positions earlier respawns left are kept in registers (px, py: the loop over r is unrolled, so no index is run-time);
+// lane 0 writes the new episodes to fresh[r] and the advanced event counter to *events.
+__device__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBOT_USED], int* events, int fin, int R, int n_obs, int n_peds, uint32_t seed,
+                              uint32_t gworld, int lane) {
+  uint32_t counter = (uint32_t)s[FL_EVENTS];
+  int px[FL_MAX_ROBOTS], py[FL_MAX_ROBOTS];
+#pragma unroll
+  for (int q = 0; q < FL_MAX_ROBOTS; ++q) {
+    px[q] = s[FL_ROBOT_INTS * q + NS_X];
+    py[q] = s[FL_ROBOT_INTS * q + NS_Y];
+  }
+  const bool scans = lane < FL_CELLS;
+#pragma unroll
+  for (int r = 0; r < FL_MAX_ROBOTS; ++r) {
+    if (r >= R || !((fin >> r) & 1)) continue;  // uniform over the wave
+    // the start: the first cell that is clear of every obstacle centre, every pedestrian and every other robot
+    const uint32_t h1 = nav_hash(seed, gworld, counter++);
+    int c0 = (int)(h1 % (uint32_t)FL_CELLS);
+    int cell = (c0 + lane) % FL_CELLS;
+    int cx = fleet_cell_x(cell), cy = fleet_cell_y(cell);
+    bool ok = scans;
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1];
+      ok = ok && dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR;
+    }
+    for (int j = 0; j < n_peds; ++j) {
+      const int dx = cx - s[FL_PED0 + 4 * j], dy = cy - s[FL_PED0 + 4 * j + 1];
+      ok = ok && dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR;
+    }
+#pragma unroll
+    for (int q = 0; q < FL_MAX_ROBOTS; ++q) {
+      const int dx = cx - px[q], dy = cy - py[q];
+      ok = ok && (q == r || q >= R || dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR);
+    }
+    const int start = (c0 + fleet_first(ok)) % FL_CELLS;
+    const int sx = fleet_cell_x(start), sy = fleet_cell_y(start);
+    px[r] = sx;
+    py[r] = sy;
+    // the goal: the first cell other than the start's whose jittered goal is clear of every obstacle centre
+    const uint32_t h2 = nav_hash(seed, gworld, counter++);
+    const int jx = fleet_jitter_x(h2), jy = fleet_jitter_y(h2);
+    c0 = (int)(h2 % (uint32_t)FL_CELLS);
+    cell = (c0 + lane) % FL_CELLS;
+    cx = fleet_cell_x(cell) + jx;
+    cy = fleet_cell_y(cell) + jy;
+    ok = scans && cell != start;
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1];
+      ok = ok && dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR;
+    }
+    const int gcell = (c0 + fleet_first(ok)) % FL_CELLS;
+    const int gx = fleet_cell_x(gcell) + jx, gy = fleet_cell_y(gcell) + jy;
+    if (lane == 0) {
+      int* f = fresh[r];
+      f[NS_X] = sx;
+      f[NS_Y] = sy;
+      f[NS_H] = (int)((h1 >> 8) % (uint32_t)NAV_HEADINGS);
+      f[NS_V] = f[NS_W] = f[NS_STEPS] = 0;
+      f[NS_GX] = gx;
+      f[NS_GY] = gy;
+      f[NS_DPREV] = fleet_distance(gx, gy, sx, sy);
+    }
+  }
+  if (lane == 0) *events = (int)counter;
+}
+
+// Everything behind the step: threads 0..23 store the world's state, then the 256 threads of robot r render row r of the world's
+// observation from the LDS copy `s`.  `disc` is LDS scratch [R][FL_DISCS][4]: what robot r's map holds in its frame, in the order that
+// wins -- the pedestrians, then the other robots, by index.  Called by every thread of the workgroup, behind a barrier that made `s` final.
+__device__ __forceinline__ void fleet_store_and_render(const int* s, int (*disc)[FL_DISCS][4], int R, int n_obs, int n_peds,
+                                                       int32_t* __restrict__ st, float* __restrict__ laser, float* __restrict__ vector,
+                                                       float* __restrict__ image) {
+  const int tid = threadIdx.x, r = tid / NAV_THREADS, t = tid - r * NAV_THREADS;
+  if (tid < FL_STATE_INTS / 4) reinterpret_cast<int4*>(st)[tid] = make_int4(s[4 * tid], s[4 * tid + 1], s[4 * tid + 2], s[4 * tid + 3]);
+  const int* me = s + FL_ROBOT_INTS * r;
+  const int x = me[NS_X], y = me[NS_Y], h = me[NS_H];
+  const int c = nav_cos(h), sn = nav_sin(h);
+  const int n_discs = n_peds + R - 1;
+  if (t < n_discs) {  // disc t in the robot's frame: position, velocity in ticks / step
+    int ax, ay, ah, av;
+    if (t < n_peds) {
+      const int* p = s + FL_PED0 + 4 * t;
+      ax = p[0], ay = p[1], ah = p[2], av = p[3];
+    } else {
+      const int o = t - n_peds, q = o < r ? o : o + 1;  // the o-th robot other than r
+      const int* p = s + FL_ROBOT_INTS * q;
+      ax = p[NS_X], ay = p[NS_Y], ah = p[NS_H], av = p[NS_V];
+    }
+    const int qx = ax - x, qy = ay - y, rel = nav_heading(ah - h);
+    disc[r][t][0] = (qx * c + qy * sn) >> NAV_Q;
+    disc[r][t][1] = (-qx * sn + qy * c) >> NAV_Q;
+    disc[r][t][2] = (av * nav_cos(rel)) >> NAV_Q;
+    disc[r][t][3] = (av * nav_sin(rel)) >> NAV_Q;
+  }
+  __syncthreads();
+  laser += (int64_t)r * NAV_BEAMS;
+  vector += (int64_t)r * NAV_VECTOR;
+  image += (int64_t)r * NAV_MAP_FLOATS;
+  // laser: beams 4 t .. 4 t + 3 over the wall, the obstacles, the pedestrians and the other robots
+  if (t < NAV_BEAMS / 4) {
+    int dx[4], dy[4], rng[4];
+    nav_beams(x, y, h, t, dx, dy, rng);
+    for (int k = 0; k < n_obs; ++k) nav_cast(s[FL_OBS0 + 3 * k] - x, s[FL_OBS0 + 3 * k + 1] - y, s[FL_OBS0 + 3 * k + 2], dx, dy, rng);
+    for (int j = 0; j < n_peds; ++j) nav_cast(s[FL_PED0 + 4 * j] - x, s[FL_PED0 + 4 * j + 1] - y, NAV_PED_R, dx, dy, rng);
+    for (int q = 0; q < R; ++q)
+      if (q != r) nav_cast(s[FL_ROBOT_INTS * q + NS_X] - x, s[FL_ROBOT_INTS * q + NS_Y] - y, NAV_ROBOT_R, dx, dy, rng);
+    nav_store_ranges(rng, reinterpret_cast<float4*>(laser) + t);
+  } else if (t == NAV_THREADS - 1) {  // vector: goal in the robot's frame, the last action, the distance
+    const int gx = me[NS_GX] - x, gy = me[NS_GY] - y;
+    vector[0] = (float)((gx * c + gy * sn) >> NAV_Q) * 0.00390625f;
+    vector[1] = (float)((-gx * sn + gy * c) >> NAV_Q) * 0.00390625f;
+    vector[2] = (float)me[NS_V] * 0.03125f;
+    vector[3] = (float)me[NS_W] * 0.015625f;
+    vector[4] = (float)me[NS_DPREV] * 0.00390625f;
+  }
+  // map: chunk = 4 consecutive cells of one row of one channel; the first disc of the winning order that covers a cell wins
+  for (int ck = t; ck < NAV_MAP_CHUNKS; ck += NAV_THREADS) {
+    const int ch = ck / (NAV_MAP * NAV_MAP / 4), rem = ck - ch * (NAV_MAP * NAV_MAP / 4);
+    const int row = rem / (NAV_MAP / 4), col0 = (rem - row * (NAV_MAP / 4)) * 4;
+    const int fwd = (NAV_MAP / 2 - row) * NAV_MAP_CELL - NAV_MAP_CELL / 2;
+    float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int j = n_discs - 1; j >= 0; --j) {
+      const int df = fwd - disc[r][j][0], rr = j < n_peds ? NAV_PED_R * NAV_PED_R : NAV_ROBOT_R * NAV_ROBOT_R;
+      const float pv = ch == 0 ? 1.0f : (float)disc[r][j][ch + 1] * 0.03125f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int dl = (NAV_MAP / 2 - (col0 + q)) * NAV_MAP_CELL - NAV_MAP_CELL / 2 - disc[r][j][1];
+        if (df * df + dl * dl <= rr) val[q] = pv;
+      }
+    }
+    reinterpret_cast<float4*>(image)[ck] = make_float4(val[0], val[1], val[2], val[3]);
+  }
+}
+
+__global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_step_kernel(int32_t* __restrict__ state, int R, int64_t world0, uint32_t seed,
+                                                                        int n_obs, int n_peds, int max_steps,
+                                                                        const float* __restrict__ actions, float* __restrict__ laser,
+                                                                        float* __restrict__ vector, float* __restrict__ image,
+                                                                        float* __restrict__ reward, uint8_t* __restrict__ done,
+                                                                        int32_t* __restrict__ info) {
+  __shared__ int s[FL_STATE_INTS];
+  __shared__ int fresh[FL_MAX_ROBOTS][FL_ROBOT_USED];
+  __shared__ int disc[FL_MAX_ROBOTS][FL_DISCS][4];
+  __shared__ int units[FL_MAX_ROBOTS];
+  __shared__ int ctl[2];  // the mask of finished robots, the event counter after their respawns
+  const int64_t i = blockIdx.x, row0 = i * R;
+  const int tid = threadIdx.x;
+  const uint32_t gworld = (uint32_t)(world0 + i);
+  int32_t* st = state + i * FL_STATE_INTS;
+  if (tid < FL_STATE_INTS) s[tid] = fleet_sanitize_word(tid, st[tid], R, n_obs, n_peds);
+  __syncthreads();  // 1: the old state is in LDS; nothing reads the world's global words after this
+  if (tid == 0)
+    ctl[0] = fleet_play(s, units, R, n_obs, n_peds, max_steps, seed, gworld, actions + 2 * row0, reward + row0, done + row0,
+                        info != nullptr ? info + row0 : nullptr);
+  __syncthreads();  // 2: every robot has moved and knows its outcome
+  const int fin = ctl[0];
+  if (fin != 0) {  // uniform over the workgroup
+    if (tid < 64) fleet_respawn(s, fresh, &ctl[1], fin, R, n_obs, n_peds, seed, gworld, tid);
+    __syncthreads();  // 3: the new episodes wait in `fresh`
+    if (tid < FL_OBS0) {
+      const int r = tid / FL_ROBOT_INTS, f = tid - FL_ROBOT_INTS * r;
+      if (f < FL_ROBOT_USED && ((fin >> r) & 1)) s[tid] = fresh[r][f];
+    } else if (tid == FL_EVENTS) {
+      s[tid] = ctl[1];
+    }
+    __syncthreads();  // 4: the new state is final
+  }
+  fleet_store_and_render(s, disc, R, n_obs, n_peds, st, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR, image + row0 * NAV_MAP_FLOATS);
+}
+
+__global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_reset_kernel(int32_t* __restrict__ state, int R, int64_t world0, uint32_t seed,
+                                                                         int n_obs, int n_peds, const uint8_t* __restrict__ mask,
+                                                                         float* __restrict__ laser, float* __restrict__ vector,
+                                                                         float* __restrict__ image) {
+  __shared__ int s[FL_STATE_INTS];
+  __shared__ int disc[FL_MAX_ROBOTS][FL_DISCS][4];
+  const int64_t i = blockIdx.x, row0 = i * R;
+  const int tid = threadIdx.x;
+  if (mask != nullptr && mask[i] == 0) return;  // uniform over the workgroup; the world's state and observations stay as they are
+  if (tid < FL_STATE_INTS) s[tid] = 0;
+  __syncthreads();
+  if (tid == 0) fleet_new_world(s, R, n_obs, n_peds, seed, (uint32_t)(world0 + i));
+  __syncthreads();
+  fleet_store_and_render(s, disc, R, n_obs, n_peds, state + i * FL_STATE_INTS, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR,
+                         image + row0 * NAV_MAP_FLOATS);
+}
+
+// what both operators check of the sizes: the worlds as section 6.8's envs, 1..4 robots, the rows inside int32
+inline bool fleet_range_ok(int32_t n_worlds, int32_t n_robots, int64_t world0, int32_t n_obs, int32_t n_peds) {
+  return nav_range_ok(n_worlds, world0, n_obs, n_peds) && n_robots >= 1 && n_robots <= FL_MAX_ROBOTS &&
+         (int64_t)n_worlds * n_robots <= INT32_MAX;
+}
+
+}  // namespace ddrl
+
+using namespace ddrl;
+
+extern "C" {
+
+// every check comes before the first HIP call: a host without a GPU gets the same answers
+
+int32_t ddrl_op_fleet_env_state_ints(void) { return FL_STATE_INTS; }
+
+int32_t ddrl_op_fleet_env_reset(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                int32_t n_peds, const uint8_t* mask, float* laser, float* vector, float* image, void* stream) {
+  if (!state || !laser || !vector || !image || !fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds)) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3)) return DDRL_ERR_INVALID_ARG;
+  const uint64_t rows = (uint64_t)n_worlds * n_robots;
+  const void* src[1] = {mask};
+  const uint64_t src_b[1] = {(uint64_t)n_worlds};
+  void* dst[4] = {state, laser, vector, image};
+  const uint64_t dst_b[4] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 4)) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(fleet_env_reset_kernel, dim3((unsigned)n_worlds), dim3(NAV_THREADS * n_robots), 0, (hipStream_t)stream, state,
+                     n_robots, world0, seed, n_obstacles, n_peds, mask, laser, vector, image);
+  return launch_status();
+}
+
+int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                               int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                               float* reward, uint8_t* done, int32_t* info, void* stream) {
+  if (!state || !actions || !laser || !vector || !image || !reward || !done ||
+      !fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds))
+    return DDRL_ERR_INVALID_ARG;
+  if (max_steps < 1) return DDRL_ERR_INVALID_ARG;
+  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
+      ((uintptr_t)reward & 3) || ((uintptr_t)info & 3))
+    return DDRL_ERR_INVALID_ARG;
+  const uint64_t rows = (uint64_t)n_worlds * n_robots;
+  const void* src[1] = {actions};
+  const uint64_t src_b[1] = {rows * 8};
+  void* dst[7] = {state, laser, vector, image, reward, done, info};
+  const uint64_t dst_b[7] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4,
+                             rows * 4, rows, rows * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 7)) return DDRL_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(fleet_env_step_kernel, dim3((unsigned)n_worlds), dim3(NAV_THREADS * n_robots), 0, (hipStream_t)stream, state, n_robots,
+                     world0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -12,79 +12,14 @@
 // has not been through nav_sanitize_word.
 #include <cstring>
 
-#include "rows.h"
+#include "navcore.h"
 
 namespace ddrl {
 
-constexpr int NAV_STATE_INTS = 64, NAV_THREADS = 256;
-constexpr int NAV_HEADINGS = 3840, NAV_BEAMS = 960, NAV_BEAM_STEP = 4, NAV_Q = 14;
-constexpr int NAV_MAX_OBS = 10, NAV_MAX_PEDS = 5;
-constexpr int NAV_ARENA_R = 2560, NAV_ROBOT_R = 64, NAV_PED_R = 77, NAV_OBS_R_MIN = 77, NAV_OBS_R_MAX = 128;
-constexpr int NAV_RANGE_MAX = 1536, NAV_GOAL_TOL = 77, NAV_CELL = 608;
-constexpr int NAV_V_MAX = 32, NAV_W_MAX = 64, NAV_SPEED_MIN = 8, NAV_SPEED_MAX = 24, NAV_DPREV_MAX = 8191;
-constexpr int NAV_BONUS = 15 * 256;
-constexpr int NAV_MAP = 48, NAV_MAP_CELL = 64, NAV_MAP_FLOATS = 3 * NAV_MAP * NAV_MAP, NAV_MAP_CHUNKS = NAV_MAP_FLOATS / 4;
-constexpr int NAV_VECTOR = 5;
-enum { NS_X = 0, NS_Y, NS_H, NS_V, NS_W, NS_GX, NS_GY, NS_DPREV, NS_STEPS, NS_EVENTS, NS_OBS0 = 10, NS_PED0 = 40, NS_USED = 60 };
-static_assert(NAV_BEAMS == 4 * 240 && NAV_BEAMS * NAV_BEAM_STEP == NAV_HEADINGS, "four beams a thread, one turn");
-static_assert(NS_OBS0 + 3 * NAV_MAX_OBS == NS_PED0 && NS_PED0 + 4 * NAV_MAX_PEDS == NS_USED, "state layout");
-
-// Q14 cos[3840] then sin[3840] (tools/gen_nav_trig.py): the copy the kernels index and the copy ddrl_op_nav_env_trig hands out
-__device__ const int32_t nav_trig_dev[2 * NAV_HEADINGS] = {
-#include "nav_trig.inc"
-};
+// the copy of the Q14 table ddrl_op_nav_env_trig hands out (the kernels index navcore.h's)
 static const int32_t nav_trig_host[2 * NAV_HEADINGS] = {
 #include "nav_trig.inc"
 };
-
-__device__ __forceinline__ int nav_cos(int h) { return nav_trig_dev[h]; }  // h in 0..3839: sanitised or reduced by the caller
-__device__ __forceinline__ int nav_sin(int h) { return nav_trig_dev[NAV_HEADINGS + h]; }
-__device__ __forceinline__ int nav_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int nav_heading(int v) {  // any int -> 0..3839
-  const int m = v % NAV_HEADINGS;
-  return m < 0 ? m + NAV_HEADINGS : m;
-}
-
-// section 6.7's counter-based hash (denv.hip env_hash, tests/device_env_ref.py hash32), word for word
-__device__ __forceinline__ uint32_t nav_hash(uint32_t seed, uint32_t env, uint32_t counter) {
-  uint32_t x = seed ^ (env * 0x9E3779B1u) ^ (counter * 0x85EBCA77u);
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 16;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// floor(sqrt(x)), 0 <= x < 2^62: the double estimate is within one of it, the loops settle the rest in either direction
-__device__ __forceinline__ int64_t nav_isqrt(int64_t x) {
-  int64_t r = (int64_t)sqrt((double)x);
-  while (r * r > x) --r;
-  while ((r + 1) * (r + 1) <= x) ++r;
-  return r;
-}
-
-// word k of a loaded state brought into its range (NavEnvRef.sanitize): a no-op on every state the rules produce
-__device__ __forceinline__ int nav_sanitize_word(int k, int v, int n_obs, int n_peds) {
-  if (k == NS_X || k == NS_Y || k == NS_GX || k == NS_GY) return nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R);
-  if (k == NS_H) return nav_heading(v);
-  if (k == NS_V) return nav_clamp(v, 0, NAV_V_MAX);
-  if (k == NS_W) return nav_clamp(v, -NAV_W_MAX, NAV_W_MAX);
-  if (k == NS_DPREV) return nav_clamp(v, 0, NAV_DPREV_MAX);
-  if (k == NS_STEPS || k == NS_EVENTS) return v;
-  if (k < NS_PED0) {
-    const int q = k - NS_OBS0, o = q / 3, f = q - 3 * o;
-    if (o >= n_obs) return 0;
-    return f < 2 ? nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R) : nav_clamp(v, NAV_OBS_R_MIN, NAV_OBS_R_MAX);
-  }
-  if (k < NS_USED) {
-    const int q = k - NS_PED0, p = q >> 2, f = q & 3;
-    if (p >= n_peds) return 0;
-    if (f < 2) return nav_clamp(v, -NAV_ARENA_R, NAV_ARENA_R);
-    return f == 2 ? nav_heading(v) : nav_clamp(v, NAV_SPEED_MIN, NAV_SPEED_MAX);
-  }
-  return 0;
-}
 
 __device__ __forceinline__ uint32_t nav_draw(int* s, uint32_t seed, uint32_t genv) {
   const uint32_t h = nav_hash(seed, genv, (uint32_t)s[NS_EVENTS]);
@@ -139,26 +74,13 @@ __device__ void nav_new_episode(int* s, int n_obs, int n_peds, uint32_t seed, ui
   s[NS_DPREV] = nav_distance(s);
 }
 
-__device__ __forceinline__ bool nav_finite(float a) { return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u; }
-
-// The info word of ddrl_op_nav_env_step_info (include/ddrl.h; tests/nav_status_ref.py spells it out): what the step just played did,
-// read off the moved robot and pedestrians before a finished env's new episode is drawn.
-constexpr int NAV_CLOSE = 512;  // "close to a pedestrian": centres within 2 m
-enum {
-  NI_DONE = 1 << 0, NI_GOAL = 1 << 1, NI_KIND_SHIFT = 2, NI_TRUNC = 1 << 4, NI_CLOSE = 1 << 5, NI_WALL = 1 << 6, NI_OBSTACLE = 1 << 7,
-  NI_V_SHIFT = 8, NI_W_SHIFT = 16
-};
-
 // one step of the rules on the LDS copy (NavEnvRef.step), the new episode of a finished env included; every product fits 32 bits.
 // INFO: *info_out receives the info word; the state, the units and the done are the same either way.
 template <bool INFO>
 __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t genv, int* units_out,
                             int* done_out, int* info_out) {
-  a0 = nav_finite(a0) ? a0 : 0.0f;
-  a1 = nav_finite(a1) ? a1 : 0.0f;
-  a0 = a0 < 0.0f ? 0.0f : (a0 > 1.0f ? 1.0f : a0);
-  a1 = a1 < -1.0f ? -1.0f : (a1 > 1.0f ? 1.0f : a1);
-  const int v = (int)floorf(a0 * 32.0f), w = (int)truncf(a1 * 64.0f);
+  int v, w;
+  nav_decode(a0, a1, &v, &w);
   // 1. the pedestrians, in index order
   for (int j = 0; j < n_peds; ++j) {
     int* p = s + NS_PED0 + 4 * j;
@@ -223,23 +145,6 @@ __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, i
   *done_out = done ? 1 : 0;
 }
 
-// the nearest hit of four beams on the circle at (mx, my) from the robot, radius rad (NavEnvRef.lidar; |d|^2 counts as 2^28)
-__device__ __forceinline__ void nav_cast(int mx, int my, int rad, const int* dx, const int* dy, int* rng) {
-  const int cc = mx * mx + my * my - rad * rad;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    int t = NAV_RANGE_MAX;
-    if (cc <= 0) {
-      t = 0;
-    } else {
-      const int64_t b = (int64_t)mx * dx[q] + (int64_t)my * dy[q];
-      const int64_t disc = b * b - (int64_t)cc * ((int64_t)1 << 28);
-      if (b > 0 && disc >= 0) t = (int)((b - nav_isqrt(disc)) >> NAV_Q);
-    }
-    rng[q] = min(rng[q], t);
-  }
-}
-
 // Everything behind the step: thread 0 stores the state, then all threads render the observation of the LDS copy `s`.  `ped` is LDS
 // scratch [NAV_MAX_PEDS][4].  Called by every thread of the workgroup, behind a barrier that made `s` final.
 __device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4], int n_obs, int n_peds, int32_t* __restrict__ st,
@@ -264,28 +169,10 @@ __device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4]
   // laser: beams 4 tid .. 4 tid + 3
   if (tid < NAV_BEAMS / 4) {
     int dx[4], dy[4], rng[4];
-    const int cw = x * x + y * y - NAV_ARENA_R * NAV_ARENA_R;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      int hb = h + NAV_BEAM_STEP * (4 * tid + q);  // below 2 * 3840
-      hb = hb >= NAV_HEADINGS ? hb - NAV_HEADINGS : hb;
-      dx[q] = nav_cos(hb);
-      dy[q] = nav_sin(hb);
-      int t = 0;
-      if (cw < 0) {  // the wall from inside
-        const int64_t b = -((int64_t)x * dx[q] + (int64_t)y * dy[q]);
-        t = (int)((b + nav_isqrt(b * b - (int64_t)cw * ((int64_t)1 << 28))) >> NAV_Q);
-      }
-      rng[q] = t;
-    }
+    nav_beams(x, y, h, tid, dx, dy, rng);
     for (int k = 0; k < n_obs; ++k) nav_cast(s[NS_OBS0 + 3 * k] - x, s[NS_OBS0 + 3 * k + 1] - y, s[NS_OBS0 + 3 * k + 2], dx, dy, rng);
     for (int j = 0; j < n_peds; ++j) nav_cast(s[NS_PED0 + 4 * j] - x, s[NS_PED0 + 4 * j + 1] - y, NAV_PED_R, dx, dy, rng);
-    float4 out;
-    out.x = (float)nav_clamp(rng[0], 0, NAV_RANGE_MAX) * 0.00390625f;
-    out.y = (float)nav_clamp(rng[1], 0, NAV_RANGE_MAX) * 0.00390625f;
-    out.z = (float)nav_clamp(rng[2], 0, NAV_RANGE_MAX) * 0.00390625f;
-    out.w = (float)nav_clamp(rng[3], 0, NAV_RANGE_MAX) * 0.00390625f;
-    reinterpret_cast<float4*>(laser)[tid] = out;
+    nav_store_ranges(rng, reinterpret_cast<float4*>(laser) + tid);
   } else if (tid == NAV_THREADS - 1) {  // vector: goal in the robot's frame, the last action, the distance
     const int gx = s[NS_GX] - x, gy = s[NS_GY] - y;
     vector[0] = (float)((gx * c + gy * sn) >> NAV_Q) * 0.00390625f;
@@ -353,12 +240,6 @@ __global__ __launch_bounds__(NAV_THREADS) void nav_env_reset_kernel(int32_t* __r
   __syncthreads();
   nav_store_and_render(s, ped, n_obs, n_peds, state + i * NAV_STATE_INTS, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR,
                        image + i * NAV_MAP_FLOATS);
-}
-
-// what both operators check of n, env0 and the populations: 1 <= n, global env indices inside 32 bits
-inline bool nav_range_ok(int32_t n, int64_t env0, int32_t n_obs, int32_t n_peds) {
-  return n >= 1 && env0 >= 0 && env0 + (int64_t)n <= ((int64_t)1 << 32) && n_obs >= 0 && n_obs <= NAV_MAX_OBS && n_peds >= 0 &&
-         n_peds <= NAV_MAX_PEDS;
 }
 
 }  // namespace ddrl

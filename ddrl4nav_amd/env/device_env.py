@@ -9,6 +9,7 @@ import torch
 from ddrl4nav_amd import ops
 from ddrl4nav_amd.env.device_env_base import DeviceEnvBase
 from ddrl4nav_amd.env.device_nav_env import NAV_ENV_NAME, make_device_nav_env
+from ddrl4nav_amd.env.fleet_nav_env import FLEET_ENV_NAME, make_fleet_nav_env
 
 ENV_NAMES = {"DevicePong-v0": "pong", "DeviceCatch-v0": "catch"}
 
@@ -51,12 +52,15 @@ class DeviceEnv(DeviceEnvBase):
 def make_device_env(config_env, device=None, env0=0):
     """The DeviceEnv of a config_env dict: env_name "DevicePong-v0" / "DeviceCatch-v0", env_num, and the optional knobs env_seed,
     discrete_actions (its length is n_actions), env_points, env_max_steps; or the DeviceNavEnv of env_name "DeviceNav-v0" with env_num,
-    env_seed, env_obstacles, env_peds, env_max_steps (env/device_nav_env.py)."""
+    env_seed, env_obstacles, env_peds, env_max_steps (env/device_nav_env.py); or the FleetNavEnv of env_name "DeviceNavFleet-v0", where
+    env_num counts the worlds and agent_num_per_env (required) the robots of each, with the same knobs (env/fleet_nav_env.py)."""
     name = config_env.get("env_name")
     if name == NAV_ENV_NAME:
         return make_device_nav_env(config_env, device=device, env0=env0)
+    if name == FLEET_ENV_NAME:
+        return make_fleet_nav_env(config_env, device=device, env0=env0)
     if name not in ENV_NAMES:
-        raise ValueError("env_name must be one of %s, got %r" % (sorted(ENV_NAMES) + [NAV_ENV_NAME], name))
+        raise ValueError("env_name must be one of %s, got %r" % (sorted(ENV_NAMES) + [NAV_ENV_NAME, FLEET_ENV_NAME], name))
     if "env_num" not in config_env:
         raise ValueError("config_env needs env_num")
     actions = config_env.get("discrete_actions")

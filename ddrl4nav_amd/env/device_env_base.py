@@ -1,5 +1,7 @@
 """What DeviceEnv (env/device_env.py) and DeviceNavEnv (env/device_nav_env.py) share: the checks of n_envs / seed / env0, the state,
-reward and done tensors, and the checkpoint of the state words next to the parameters a subclass names in _PARAMS."""
+reward and done tensors, and the checkpoint of the state words next to the parameters a subclass names in _PARAMS.  FleetNavEnv
+(env/fleet_nav_env.py), whose state has a row per world and whose outputs have a row per robot, allocates for itself and shares the
+checkpoint."""
 import torch
 
 

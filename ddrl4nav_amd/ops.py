@@ -525,6 +525,62 @@ def nav_status_reduce(sums, episode_num, rings, summary):
     return summary
 
 
+FLEET_ENV_MAX_ROBOTS = 4          # robots per world of ddrl_op_fleet_env_*; a row is one robot, with the shapes of NAV_ENV_SHAPES
+
+
+@functools.lru_cache(maxsize=None)
+def fleet_env_state_ints():
+    """The int32 words of one world's state of the multi-robot navigation env (include/ddrl.h ddrl_op_fleet_env_state_ints)."""
+    return int(_lib.load().ddrl_op_fleet_env_state_ints())
+
+
+def _fleet_env_args(state, n_robots, obs):
+    """(n_worlds, rows) of a fleet-env call after the checks both operators share: state int32 [n_worlds, fleet_env_state_ints()] and the
+    three observation components fp32 [rows, 1, 960], [rows, 5], [rows, 3, 48, 48] with rows = n_worlds * n_robots, contiguous, on one
+    device, laser and image 16-byte aligned."""
+    assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 \
+        and state.shape[1] == fleet_env_state_ints(), "state: contiguous int32 [n_worlds, fleet_env_state_ints()] on the device"
+    n_robots = int(n_robots)
+    assert 1 <= n_robots <= FLEET_ENV_MAX_ROBOTS, "n_robots: 1..%d" % FLEET_ENV_MAX_ROBOTS
+    rows = state.shape[0] * n_robots
+    assert len(obs) == 3, "obs: [laser, vector, image]"
+    for name, t, shape in zip(("laser", "vector", "image"), obs, NAV_ENV_SHAPES):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (rows,) + shape \
+            and t.device == state.device, "%s: contiguous fp32 %s on the state's device" % (name, ("n_worlds * n_robots",) + shape)
+    assert obs[0].data_ptr() % 16 == 0 and obs[2].data_ptr() % 16 == 0, "laser / image: the base must be 16-byte aligned"
+    return state.shape[0], rows
+
+
+def fleet_env_reset(state, n_robots, obs, world0=0, seed=0, n_obstacles=10, n_peds=5, mask=None):
+    """A new world for every world of `state`, or for those with a non-zero byte in mask (uint8 [n_worlds]), and the first observations
+    obs = [laser, vector, image] of their rows (include/ddrl.h ddrl_op_fleet_env_reset; csrc/fleetenv.hip).  Asynchronous on the current
+    stream; returns obs."""
+    n_worlds, _ = _fleet_env_args(state, n_robots, obs)
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == n_worlds
+                            and mask.device == state.device), "mask: contiguous uint8 [n_worlds] on the state's device"
+    check(_lib.load().ddrl_op_fleet_env_reset(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF, int(n_obstacles),
+                                              int(n_peds), _p(mask), _p(obs[0]), _p(obs[1]), _p(obs[2]), _st()))
+    return obs
+
+
+def fleet_env_step(state, n_robots, actions, obs, reward, done, info=None, world0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
+    """One step of every world (include/ddrl.h ddrl_op_fleet_env_step; csrc/fleetenv.hip): actions fp32 [rows, 2] -> state (in place),
+    obs = [laser, vector, image], reward fp32 [rows], done uint8 [rows] and, when given, info int32 [rows] (nav_info_fields unpacks it;
+    collision 3 is another robot); rows = n_worlds * n_robots, row i * n_robots + r is robot r of world i.  Asynchronous on the current
+    stream; returns (obs, reward, done)."""
+    n_worlds, rows = _fleet_env_args(state, n_robots, obs)
+    assert tuple(_f32(actions).shape) == (rows, 2) and _f32(reward).numel() == rows and actions.device == state.device \
+        and reward.device == state.device, "actions fp32 [rows, 2], reward fp32 [rows] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == rows \
+        and done.device == state.device, "done: contiguous uint8 [rows] on the state's device"
+    assert info is None or (info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (rows,)
+                            and info.device == state.device), "info: contiguous int32 [rows] on the state's device"
+    check(_lib.load().ddrl_op_fleet_env_step(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF, int(n_obstacles),
+                                             int(n_peds), int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward),
+                                             _p(done), _p(info), _st()))
+    return obs, reward, done
+
+
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off
 
 

@@ -1,5 +1,6 @@
 """The closed loop on one GPU: a DeviceRollout / PlaneRollout driven by a DeviceEnv (env/device_env.py), or a StateRollout driven by a
-DeviceNavEnv (env/device_nav_env.py; collect_states / train_states), then net.learn on its batch.
+DeviceNavEnv (env/device_nav_env.py) or a FleetNavEnv (env/fleet_nav_env.py; collect_states / train_states), then net.learn on its
+batch.
 
 Every tensor that moves between acting, the env and the pools is a device tensor and every call is asynchronous on the current stream:
 a rollout adds no host synchronisation to what act(), record() and the puts do already (none, for device arguments).  On a PlaneRollout
@@ -80,7 +81,8 @@ def train(net, env, ro, updates, keep_step=False):
 
 
 def collect_states(ro, env, keep_step=False, reset=None):
-    """collect() for a StateRollout `ro` and an env whose observation is a list of fp32 components (DeviceNavEnv): act(t) ->
+    """collect() for a StateRollout `ro` and an env whose observation is a list of fp32 components (DeviceNavEnv; or a FleetNavEnv, whose
+    rows are robots: build the rollout with n_envs = env.N = n_worlds * n_robots): act(t) ->
     env.step(obs_out=ro.state_rows(t + 1)) -> record(t, reward, done) -> put_states_in_place(t + 1) for t = t0 .. T - 1, then
     bootstrap() and finish().  The env renders into the pool rows, so no observation is copied.
 
@@ -97,5 +99,5 @@ def collect_states(ro, env, keep_step=False, reset=None):
 def train_states(net, env, ro, updates, keep_step=False):
     """train() for a StateRollout: collect_states(ro, env), net.learn(ro.batch()), carry_over(keep_step).  Yields, per update, (the last
     loss dict of net.learn, ro.returns.mean_return() -- None without track_returns).  The navigation status of a tracking rollout is read
-    from ro.nav_status (summary() is its one device-to-host copy)."""
+    from ro.nav_status (summary() is its one device-to-host copy; on a FleetNavEnv other_robot_collision_rate() is one more)."""
     return _train(collect_states, net, env, ro, updates, keep_step)

@@ -845,6 +845,39 @@ int32_t ddrl_op_nav_status_update(const int32_t* info, int32_t T, int32_t N, flo
 int32_t ddrl_op_nav_status_reduce(const float* sums, const int32_t* episode_num, const float* rings, int32_t N, double* summary,
                                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multi-robot navigation env (additive: ABI 3; the rules are tests/fleet_env_ref.py, in integers only, and the
+ * kernels reproduce them bit for bit): n_robots = 1..4 robots of the navigation env above share one arena (a world) with its obstacles
+ * and pedestrians, see each other in their lidar (circles of radius 64 ticks) and in their map (under the pedestrians) and collide with
+ * each other.  Context-free, no allocation, no atomics, asynchronous on `stream`; one launch serves all worlds.  A ROW is one robot: row
+ * i * n_robots + r is robot r of world i, and every per-row argument has n_worlds * n_robots rows of the navigation env's shapes:
+ *   laser   float32 [rows][1][960], 16-byte aligned     vector  float32 [rows][5]     image  float32 [rows][3][48][48], 16-byte aligned
+ *   state   int32 [n_worlds][ddrl_op_fleet_env_state_ints()], 16-byte aligned: robot r at words 10 r .. 10 r + 8 (X, Y, H, V, W, GX, GY,
+ *           DPREV, STEPS), obstacle k at 40 + 3 k, pedestrian j at 70 + 4 j, the world's event counter at 90, zeros elsewhere
+ *   world0  the global index of local world 0 (the draws hash (seed, world0 + i, event counter)): 0 <= world0, world0 + n_worlds <= 2^32
+ * A null pointer (mask and info excepted), n_worlds < 1, n_robots outside 1..4, n_worlds * n_robots beyond int32, n_obstacles outside
+ * 0..10, n_peds outside 0..5, max_steps < 1, a misaligned state, laser or image, an overlap of two arguments: DDRL_ERR_INVALID_ARG,
+ * decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+/* the int32 words of one world's state (96) */
+int32_t ddrl_op_fleet_env_state_ints(void);
+/* A new world (all counters zero; obstacles, robots with their goals and pedestrians in cells of their own) for every world, or for
+ * those with a non-zero byte in mask (uint8 [n_worlds], NULL = all); the first observations of their rows are rendered.  The state and
+ * the rows of a world whose mask byte is zero are not touched. */
+int32_t ddrl_op_fleet_env_reset(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                int32_t n_peds, const uint8_t* mask, float* laser, float* vector, float* image, void* stream);
+/* One step of every world: actions float32 [rows][2], decoded as ddrl_op_nav_env_step's -> the new state, every row's observation,
+ * reward float32 [rows] and done uint8 [rows].  The pedestrians move, then every robot; a robot's outcome is read off the positions
+ * after all moves: a collision with the wall, an obstacle, a pedestrian or another robot (centres closer than 128 ticks; both partners
+ * collide) costs 15, the goal pays 15, max_steps steps truncate.  Only a finished robot starts a new episode, in the same launch, at
+ * the centre of a grid cell at least 300 ticks from every obstacle centre, pedestrian and other robot, with a new goal; the world is
+ * never redrawn.  info int32 [rows] or NULL: the info word of ddrl_op_nav_env_step_info for the step just played, where collision kind
+ * 3 is another robot (static wins, then the pedestrian); the other outputs are the same with and without it.  actions, vector, reward
+ * and info 4-byte aligned. */
+int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                               int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                               float* reward, uint8_t* done, int32_t* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

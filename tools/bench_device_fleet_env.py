@@ -1,0 +1,80 @@
+#!/usr/bin/env python
+"""What the multi-robot navigation env costs (env/fleet_nav_env.py, csrc/fleetenv.hip), on one box in one
+process, the legs alternating: ddrl_op_fleet_env_step at --rows rows (robots) as (n_worlds, R) = (rows, 1), (rows / 2, 2), (rows / 4, 4),
+against two baselines -- ddrl_op_nav_env_step (env/device_nav_env.py) at N = rows, and a plain device-to-device copy of the same
+rows * 31,508 observation bytes.  `calls` launches between one pair of device events give one sample (time per call); every leg is warmed
+up first and reports the median, the p95 and the extremes of its samples.  The envs run under the same uniform-random actions, so robots
+finish and respawn at the rate a fresh policy meets.  Prints one JSON line.
+
+    python tools/bench_device_fleet_env.py [--rows 512] [--calls 200] [--samples 30] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tools.bench_device_env import summary, timed  # noqa: E402
+from tools.bench_device_nav_env import OBS_FLOATS  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=512, help="robots in all: a multiple of 4")
+    ap.add_argument("--calls", type=int, default=200, help="launches per sample")
+    ap.add_argument("--samples", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    if args.rows < 4 or args.rows % 4:
+        sys.exit("--rows must be a positive multiple of 4")
+    if not torch.cuda.is_available():
+        sys.exit("bench_device_fleet_env needs a GPU: there is nothing to measure without one")
+    from ddrl4nav_amd.env import DeviceNavEnv, FleetNavEnv
+    rows = args.rows
+    g = torch.Generator(device="cuda").manual_seed(0)
+    actions = torch.rand((rows, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
+    src = torch.rand((rows, OBS_FLOATS), device="cuda", generator=g)
+    dst = torch.empty_like(src)
+    envs = {"nav_env_step": DeviceNavEnv(rows, device="cuda", seed=1)}
+    for R in (1, 2, 4):
+        envs["fleet_env_step_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1)
+    for env in envs.values():
+        env.reset()
+
+    def stepping(env):
+        def run():
+            for _ in range(args.calls):
+                env.step(actions)
+        return run
+
+    def copies():
+        for _ in range(args.calls):
+            dst.copy_(src)
+
+    legs = {k: stepping(env) for k, env in envs.items()}
+    legs["d2d_copy"] = copies
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.samples):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    out = {"tool": "bench_device_fleet_env", "rows": rows, "calls": args.calls, "device": torch.cuda.get_device_name(0),
+           "bytes_per_call": rows * OBS_FLOATS * 4}
+    out.update({k: summary(v, per=args.calls) for k, v in ms.items()})
+    for R in (1, 2, 4):
+        k = "fleet_env_step_R%d" % R
+        out[k]["worlds"] = rows // R
+        out[k]["over_nav_env_step"] = round(out[k]["median_us"] / out["nav_env_step"]["median_us"], 3)
+        out[k]["over_d2d_copy"] = round(out[k]["median_us"] / out["d2d_copy"]["median_us"], 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -7,11 +7,15 @@ a1 ~ U(-1, 1)) on the same env, measured first on the device over --baseline-ste
 
     python tools/train_device_nav_env.py [--envs 256] [--horizon 64] [--updates 100] [--obstacles 10] [--peds 5] [--max-steps 500]
                                          [--iters 4] [--actor-lr R] [--critic-lr R] [--normalize-obs] [--seed 0] [--out curve.json]
-                                         [--nav-status]
+                                         [--nav-status] [--robots 1]
 
 --nav-status: the env emits its info words and the rollout keeps the reference's navigation statistics on the device (agent.NavStatus;
 DESIGN.md section 6.9); reach, collision and truncation rates over the envs' latest 100 episodes are printed next to the return and
 stored in the curve.  The loop gains no host synchronisation per step: the one copy is NavStatus.summary() at a logged update.
+
+--robots R (2..4): --envs counts WORLDS of R robots each (env/fleet_nav_env.py) and the rollout has envs * R rows,
+one per robot; with --nav-status the other-robot collision rate (NavStatus.other_robot_collision_rate, one more scalar copy at a logged
+update) is printed and stored too.  --robots 1 is the single-robot env above.
 """
 import argparse
 import json
@@ -57,6 +61,7 @@ def main():
     ap.add_argument("--critic-lr", type=float, default=None)
     ap.add_argument("--normalize-obs", action="store_true", help="StateRollout(normalize_obs=True)")
     ap.add_argument("--nav-status", action="store_true", help="track and print reach / collision / truncation rates (agent.NavStatus)")
+    ap.add_argument("--robots", type=int, default=1, help="robots per world; above 1 the env is a FleetNavEnv and --envs counts worlds")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--baseline-steps", type=int, default=1000)
     ap.add_argument("--log-every", type=int, default=10)
@@ -73,14 +78,20 @@ def main():
     for name, value in (("ACTOR_LEARNING_RATE", args.actor_lr), ("CRITIC_LEARNING_RATE", args.critic_lr)):
         if value is not None:
             knobs[name] = value
-    net = make_net(max(args.micro_batch, args.envs), seed=args.seed, **knobs)
-    env = make_device_env({"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
-                           "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status}, device=net.device)
-    ro = StateRollout(net, args.envs, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None,
+    if args.robots < 1:
+        sys.exit("--robots must be at least 1")
+    rows = args.envs * args.robots
+    net = make_net(max(args.micro_batch, rows), seed=args.seed, **knobs)
+    config_env = {"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
+                  "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status}
+    if args.robots > 1:
+        config_env.update(env_name="DeviceNavFleet-v0", agent_num_per_env=args.robots)
+    env = make_device_env(config_env, device=net.device)
+    ro = StateRollout(net, env.N, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None,
                       track_nav_status=args.nav_status)
 
     per_episode, per_1000 = random_policy_return(env, args.baseline_steps, args.seed + 1)
-    out = {"tool": "train_device_nav_env", "N": args.envs, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
+    out = {"tool": "train_device_nav_env", "N": rows, "robots": args.robots, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
            "max_steps": args.max_steps, "iters": args.iters, "normalize_obs": bool(args.normalize_obs),
            "device": torch.cuda.get_device_name(0),
            "random_policy": {"return_per_episode": per_episode, "reward_per_env_per_1000_steps": per_1000, "steps": args.baseline_steps},
@@ -88,7 +99,7 @@ def main():
     print("random policy: %.3f per episode, %.2f per env per 1,000 steps" % (per_episode, per_1000), flush=True)
     t0 = time.time()
     for u, (losses, mean_return) in enumerate(train_states(net, env, ro, args.updates), 1):
-        out["curve"].append({"update": u, "env_steps": u * args.envs * args.horizon, "mean_return": mean_return,
+        out["curve"].append({"update": u, "env_steps": u * rows * args.horizon, "mean_return": mean_return,
                              "losses": {k: v for k, v in losses.items() if k != "PpoBackUpTime"}})
         if u % args.log_every == 0 or u == args.updates:
             rates = ""
@@ -98,10 +109,13 @@ def main():
                 rates = "  reach %.3f  static %.3f  ped %.3f  trunc %.3f" % tuple(
                     status[k] for k in ("ReducedReachRateLogger", "ReducedStaticObsCollisionRateLogger", "ReducedPedCollisionRateLogger",
                                         "TruncationRate"))
+                if args.robots > 1:
+                    status["ReducedOtherRobotCollisionRateLogger"] = ro.nav_status.other_robot_collision_rate()
+                    rates += "  robot %.3f" % status["ReducedOtherRobotCollisionRateLogger"]
             print("update %4d  steps %9d  mean return %8.3f%s  VLoss %.4f  EntLoss %.4f  %.0f s"
-                  % (u, u * args.envs * args.horizon, mean_return, rates, losses["VLoss"], losses["EntLoss"], time.time() - t0), flush=True)
+                  % (u, u * rows * args.horizon, mean_return, rates, losses["VLoss"], losses["EntLoss"], time.time() - t0), flush=True)
     out["seconds"] = round(time.time() - t0, 1)
-    out["env_steps_per_s_end_to_end"] = round(args.updates * args.envs * args.horizon / max(out["seconds"], 1e-9))
+    out["env_steps_per_s_end_to_end"] = round(args.updates * rows * args.horizon / max(out["seconds"], 1e-9))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
