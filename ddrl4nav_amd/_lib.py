@@ -238,6 +238,15 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     "ddrl_op_fleet_env_step": (c_int32, [c_void_p, c_int32, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_nav_env_step_final": (c_int32, [c_void_p, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_fleet_env_step_final": (c_int32, [c_void_p, c_int32, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
+    "ddrl_op_file_flagged_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p), POINTER(c_void_p),
+                                            POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "ddrl_gae_bootstrap": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
+                                     c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -29,7 +29,7 @@ from ddrl4nav_amd.agent.agent import gae_device
 from ddrl4nav_amd.agent.normalize import ReturnNorm, RunningNorm, check_knobs, obs_norm_flags
 from ddrl4nav_amd.agent.statistics import EpisodeReturns, NavStatus
 from ddrl4nav_amd.data import Experience
-from ddrl4nav_amd.ops import frame_stack_push
+from ddrl4nav_amd.ops import file_flagged_rows, frame_stack_push, gae_bootstrap
 from ddrl4nav_amd.utils.staging import copy_into
 
 
@@ -51,6 +51,7 @@ class _RolloutBase:
     and finish() runs GAE on the raw rewards as before."""
     ret_norm = None
     rewards_norm = None
+    S = 0           # StateRollout(bootstrap_truncated=S): the depth of the pools of terminal observations; 0 = off
 
     def __init__(self, net, n_envs, horizon, gamma, landa, device, action_shape=None, track_returns=False, track_nav_status=False,
                  normalize_returns=False, reward_clip=10.0, norm_eps=1e-8):
@@ -93,17 +94,26 @@ class _RolloutBase:
             self.copy_stream.wait_stream(torch.cuda.current_stream())
             self._ring_rollout = self.rollouts
 
-    def record(self, t, rewards, dones, info=None):
+    def record(self, t, rewards, dones, info=None, final_obs=None):
         """Reward / done of step t (0..T; T = the (T+1)-th step, only needed for keep_step); for a rollout that tracks the navigation
-        status also the env's info words."""
+        status or bootstraps truncated episodes also the env's info words, and for the latter the env's terminal observations of the
+        step (final_obs: [N, ...] fp32 device tensors, one per component), whose truncated rows are filed (_file_final_obs)."""
         if t < self.t0:
             raise ValueError("step %d was carried over from the previous rollout with its reward and done" % t)
+        S = getattr(self, "S", 0)
+        if S == 0 and final_obs is not None:
+            raise ValueError("this rollout does not bootstrap truncated episodes: build it with bootstrap_truncated=S")
+        if S > 0 and (info is None or final_obs is None):
+            raise ValueError("this rollout bootstraps truncated episodes: record() needs the env's info words and its terminal "
+                             "observations (an env built with emit_final_obs=True)")
         if self._infos is not None:
             if info is None:
                 raise ValueError("this rollout tracks the navigation status: record() needs the env's info words")
             copy_into(self._infos[t], info)
         copy_into(self._rewards[t], rewards)
         copy_into(self._dones[t], dones)
+        if S > 0:
+            self._file_final_obs(t, final_obs)
 
     def _before_gae(self):
         """finish(): what a subclass commits in front of GAE (StateRollout: the observation statistics)."""
@@ -134,6 +144,9 @@ class _RolloutBase:
         False (default): the observation only, slot 0 is evaluated again by act(0) under the current weights.  The observation moves
         as it is stored: a frame with its history (PlaneRollout), a slot normalised at its put (StateRollout)."""
         T = self.T
+        if keep_step and self.S > 0:
+            raise ValueError("carry_over(keep_step=True) is not supported with bootstrap_truncated: the terminal observation of row T "
+                             "would have to move between rollouts")
         self._carry_observation()
         if keep_step:
             for pool in (self.values, self._rewards, self._dones, self._actions, self._logps, self._infos):
@@ -294,13 +307,28 @@ class StateRollout(_RolloutBase):
     section 6.6).  normalize_returns: see _RolloutBase.
 
     track_nav_status: record() also takes the env's info words (DeviceNavEnv(emit_info=True).info) into an int32 [T + 1, N] pool and
-    finish() feeds rows 0..T-1 to ``nav_status`` (agent.NavStatus), exactly where it feeds ``returns``."""
+    finish() feeds rows 0..T-1 to ``nav_status`` (agent.NavStatus), exactly where it feeds ``returns``.
+
+    bootstrap_truncated = S > 0 (off by default): a step that a time limit ended (info bit 4) is no outcome of
+    the task, so GAE goes on from the critic's value of the observation the episode ended in instead of from 0.  record() then also
+    takes the env's info words and its terminal observations (DeviceNavEnv(emit_final_obs=True).final_obs) and files the truncated
+    envs' rows, with one launch and no read-back, into ``final_pools`` ([S, N, *shape] per component: up to S truncations per env and
+    rollout; ``slots`` int32 [T + 1, N] names the pool slot of a step, -1 for none).  finish() normalises the pools like the rollout's
+    own slots (normalize_obs: the still-frozen affine, nothing is counted), evaluates them with ONE extra forward of the net into
+    ``boot`` [S, N] and runs ddrl_gae_bootstrap.  A truncation beyond the S-th of an env in one rollout keeps the terminal treatment
+    and is counted (truncations_dropped()); S = env.truncations_per_rollout(T) drops none.  The net must take a batch of S * N."""
 
     def __init__(self, net, n_envs, state_shapes, horizon=256, gamma=0.99, landa=0.95, device=None, track_returns=False,
-                 normalize_obs=None, obs_clip=10.0, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8, track_nav_status=False):
+                 normalize_obs=None, obs_clip=10.0, normalize_returns=False, reward_clip=10.0, norm_eps=1e-8, track_nav_status=False,
+                 bootstrap_truncated=0):
         state_shapes = [tuple(int(d) for d in shape) for shape in state_shapes]
         flags = obs_norm_flags(normalize_obs, len(state_shapes))
         check_knobs(norm_eps, obs_clip)
+        self.S = S = int(bootstrap_truncated)
+        if S < 0:
+            raise ValueError("bootstrap_truncated must be 0 (off) or the pool depth S >= 1, got %d" % S)
+        if S > 0 and len(state_shapes) > 4:
+            raise ValueError("bootstrap_truncated files at most four observation components, got %d" % len(state_shapes))
         self.net = net
         N, T = int(n_envs), int(horizon)
         super().__init__(net, N, T, gamma, landa, device if device is not None else net.device,
@@ -313,6 +341,47 @@ class StateRollout(_RolloutBase):
         if any(flags):
             self.obs_norm = [RunningNorm(shape, dev, eps=norm_eps, clip=obs_clip) if on else None
                              for on, shape in zip(flags, state_shapes)]
+        self.final_pools = self.trunc_count = self.slots = self.boot = None
+        if S > 0:
+            self.final_pools = [torch.zeros((S, N) + shape, dtype=torch.float32, device=dev) for shape in state_shapes]
+            self.trunc_count = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.slots = torch.full((T + 1, N), -1, dtype=torch.int32, device=dev)
+            self.boot = torch.zeros((S, N), dtype=torch.float32, device=dev)
+            if self._infos is None:     # the info pool exists when either this or track_nav_status is on
+                self._infos = torch.zeros((T + 1, N), dtype=torch.int32, device=dev)
+
+    def _file_final_obs(self, t, final_obs):
+        """record() of a rollout that bootstraps truncated episodes: the rows of the envs whose info word of step t has the truncation
+        bit go into slot trunc_count[n] of ``final_pools``, ``slots[t]`` saying which (-1: none, or no room left).  One launch, no
+        read-back."""
+        file_flagged_rows(self._infos[t], list(zip(final_obs, self.final_pools)), self.trunc_count, self.slots[t])
+
+    def truncations_dropped(self):
+        """How many truncations of this rollout found no room in the pools and kept the terminal treatment, clamp(count - S, 0).sum():
+        one device-to-host copy, for logs and tests."""
+        if self.S == 0:
+            return 0
+        return int((self.trunc_count - self.S).clamp_(min=0).sum().item())
+
+    def _evaluate_final_pools(self):
+        """finish(), in front of the commits: the filed terminal observations become what the net reads -- normalised in place with the
+        affine this rollout's own slots were normalised with (still frozen: nothing is counted) -- and one forward writes their values
+        into ``boot``.  Pool rows that no slot names are evaluated too and never read."""
+        SN = self.S * self.N
+        flat = [p.view((SN,) + tuple(p.shape[2:])) for p in self.final_pools]
+        for norm, rows in zip(self.obs_norm or (), flat):
+            if norm is not None:
+                norm.apply(rows, out=rows)
+        (_, _), values = self.net(flat, play_mode=True)
+        self.boot.view(SN).copy_(values[0][:, 0])
+
+    def _gae(self):
+        """_RolloutBase._gae; with bootstrap_truncated the scan is ddrl_gae_bootstrap on the same rewards (the scaled ones under
+        normalize_returns: the critic is trained in those units)."""
+        if self.S == 0:
+            return super()._gae()
+        rewards = self.rewards if self.ret_norm is None else self.ret_norm.scale(self.rewards, self.dones)
+        gae_bootstrap(self.values, rewards, self.dones, self.slots[:self.T], self.boot, self.gamma, self.landa, self.adv, self.ret)
 
     def _normalize_slot(self, t, index):
         """Slot t of component `index` holds raw rows: count them, then normalise them in place with the frozen affine."""
@@ -369,7 +438,10 @@ class StateRollout(_RolloutBase):
         return None
 
     def _before_gae(self):
-        """finish() commits and freezes the observation statistics in component order, in front of the returns' commit."""
+        """finish() commits and freezes the observation statistics in component order, in front of the returns' commit; before that,
+        while the affine this rollout's slots were normalised with is still frozen, the filed terminal observations are evaluated."""
+        if self.S > 0:
+            self._evaluate_final_pools()
         for norm in self.obs_norm or ():
             if norm is not None:
                 norm.commit()
@@ -392,9 +464,14 @@ class StateRollout(_RolloutBase):
                 n.load_state_dict(s)
 
     def _carry_observation(self):
-        """Every component; a slot normalised at its put moves as it is (class docstring)."""
+        """Every component; a slot normalised at its put moves as it is (class docstring).  The pools of terminal observations start
+        the next rollout empty."""
         for p in self.states:
             p[0].copy_(p[self.T])
+        if self.S > 0:
+            self.trunc_count.zero_()
+            for p in self.final_pools:
+                p.zero_()
 
     def batch(self):
         B = self.N * self.T

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "rows.h"
 
 using namespace ddrl;
 
@@ -287,6 +288,22 @@ int32_t ddrl_gae(const float* values, const float* rewards, const uint8_t* dones
   if (!values || !rewards || !dones || !adv || !ret || T < 0 || N < 1) return DDRL_ERR_INVALID_ARG;
   if (T == 0) return DDRL_OK;  // len(experiences) <= 1 -> nothing to do (agent.py:125-126)
   launch_gae(values, rewards, dones, T, N, gamma, landa, adv, ret, (hipStream_t)stream);
+  return launch_status();
+}
+
+int32_t ddrl_gae_bootstrap(const float* values, const float* rewards, const uint8_t* dones, const int32_t* slot, const float* boot,
+                           int32_t S, int32_t T, int32_t N, float gamma, float landa, float* adv, float* ret, void* stream) {
+  if (!values || !rewards || !dones || !slot || !boot || !adv || !ret || S < 1 || T < 0 || N < 1) return DDRL_ERR_INVALID_ARG;
+  if (((uintptr_t)values | (uintptr_t)rewards | (uintptr_t)slot | (uintptr_t)boot | (uintptr_t)adv | (uintptr_t)ret) & 3)
+    return DDRL_ERR_INVALID_ARG;
+  const uint64_t tn = (uint64_t)T * N;
+  const void* src[5] = {values, rewards, dones, slot, boot};
+  const uint64_t src_b[5] = {(tn + N) * 4, tn * 4, tn, tn * 4, (uint64_t)S * N * 4};
+  void* dst[2] = {adv, ret};
+  const uint64_t dst_b[2] = {tn * 4, tn * 4};
+  if (!reads_and_writes_apart(src, src_b, 5, dst, dst_b, 2)) return DDRL_ERR_INVALID_ARG;
+  if (T == 0) return DDRL_OK;  // as ddrl_gae
+  launch_gae_bootstrap(values, rewards, dones, slot, boot, S, T, N, gamma, landa, adv, ret, (hipStream_t)stream);
   return launch_status();
 }
 

@@ -14,6 +14,7 @@
 // (16 bytes each) and the 256 threads of robot r render row i * R + r from `s`, as section 6.8's render does.  So no thread reads a word
 // of LDS or of global state that another thread writes in the same phase: the global words are read before barrier 1 and written
 // after barrier 4, `s` is written by thread 0 alone between barriers 1 and 2, read-only between 2 and 3, and final after 4.
+// ddrl_op_fleet_env_step_final's instantiation renders the truncated robots' terminal observations in that read-only phase.
 #include "navcore.h"
 
 namespace ddrl {
@@ -97,6 +98,8 @@ __device__ void fleet_new_world(int* s, int R, int n_obs, int n_peds, uint32_t s
 // Steps 1 to 5 of FleetEnvRef.step on the LDS copy, by one thread: the pedestrians, every robot's move, then every robot's outcome from
 // the positions after all moves (R (n_obs + n_peds + R) circle tests).  `act`, `reward`, `done`, `info` are the world's R rows; `units`
 // is LDS scratch [R].  Returns the mask of finished robots; their respawn is fleet_respawn's.  Every product fits 32 bits.
+// FINAL: bits FL_MAX_ROBOTS.. of the result are the mask of truncated robots (a subset of the finished ones).
+template <bool FINAL>
 __device__ int fleet_play(int* s, int* units, int R, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t gworld,
                           const float* __restrict__ act, float* __restrict__ reward, uint8_t* __restrict__ done, int32_t* __restrict__ info) {
   for (int j = 0; j < n_peds; ++j) {
@@ -161,6 +164,7 @@ __device__ int fleet_play(int* s, int* units, int R, int n_obs, int n_peds, int 
                 (wall ? NI_WALL : 0) | (hit_o ? NI_OBSTACLE : 0) | (p[NS_V] << NI_V_SHIFT) | ((p[NS_W] + NAV_W_MAX) << NI_W_SHIFT);
     }
     fin |= (fini ? 1 : 0) << r;
+    if (FINAL) fin |= (trunc ? 1 : 0) << (FL_MAX_ROBOTS + r);
   }
   return fin;
 }
@@ -174,9 +178,10 @@ __device__ __forceinline__ int fleet_first(bool ok) {
 // Step 6 of FleetEnvRef.step, by all 64 lanes of one wave in uniform control flow: the robots of `fin` respawn in index order, two draws
 // each.  Lane l < 25 tests cell (c0 + l) % 25 of a scan, so the first set bit of the ballot is the rule book's first free cell.  `s` is
 // only read; the positions earlier respawns left are kept in registers (px, py: the loop over r is unrolled, so no index is run-time);
-// lane 0 writes the new episodes to fresh[r] and the advanced event counter to *events.
-__device__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBOT_USED], int* events, int fin, int R, int n_obs, int n_peds, uint32_t seed,
-                              uint32_t gworld, int lane) {
+// lane 0 writes the new episodes to fresh[r] and the advanced event counter to *events.  __forceinline__: with two step
+// kernels calling it the compiler would otherwise call it out of line, which costs the plain step 0.4 us at R = 2.
+__device__ __forceinline__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBOT_USED], int* events, int fin, int R, int n_obs, int n_peds,
+                                              uint32_t seed, uint32_t gworld, int lane) {
   uint32_t counter = (uint32_t)s[FL_EVENTS];
   int px[FL_MAX_ROBOTS], py[FL_MAX_ROBOTS];
 #pragma unroll
@@ -239,19 +244,27 @@ __device__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBOT_USED], int* ev
   if (lane == 0) *events = (int)counter;
 }
 
-// Everything behind the step: threads 0..23 store the world's state, then the 256 threads of robot r render row r of the world's
-// observation from the LDS copy `s`.  `disc` is LDS scratch [R][FL_DISCS][4]: what robot r's map holds in its frame, in the order that
-// wins -- the pedestrians, then the other robots, by index.  Called by every thread of the workgroup, behind a barrier that made `s` final.
-__device__ __forceinline__ void fleet_store_and_render(const int* s, int (*disc)[FL_DISCS][4], int R, int n_obs, int n_peds,
-                                                       int32_t* __restrict__ st, float* __restrict__ laser, float* __restrict__ vector,
-                                                       float* __restrict__ image) {
-  const int tid = threadIdx.x, r = tid / NAV_THREADS, t = tid - r * NAV_THREADS;
+// threads 0..23 store the world's state (16 bytes each) from the LDS copy `s`, behind a barrier that made it final
+__device__ __forceinline__ void fleet_store_state(const int* s, int32_t* __restrict__ st) {
+  const int tid = threadIdx.x;
   if (tid < FL_STATE_INTS / 4) reinterpret_cast<int4*>(st)[tid] = make_int4(s[4 * tid], s[4 * tid + 1], s[4 * tid + 2], s[4 * tid + 3]);
+}
+
+// The 256 threads of robot r render row r of the world's observation from the LDS copy `s`.  `disc` is LDS scratch [R][FL_DISCS][4]: what
+// robot r's map holds in its frame, in the order that wins -- the pedestrians, then the other robots, by index.  Called by every thread
+// of the workgroup, behind a barrier after which nobody writes `s` or reads `disc`; holds one barrier of its own.
+// MASKED: only the robots of the mask `rows` render (uniform over a robot's four waves; every thread still meets the barrier), the
+// rows of the others are not written.
+template <bool MASKED>
+__device__ __forceinline__ void fleet_render(const int* s, int (*disc)[FL_DISCS][4], int R, int n_obs, int n_peds, int rows,
+                                             float* __restrict__ laser, float* __restrict__ vector, float* __restrict__ image) {
+  const int tid = threadIdx.x, r = tid / NAV_THREADS, t = tid - r * NAV_THREADS;
+  const bool mine = !MASKED || ((rows >> r) & 1);
   const int* me = s + FL_ROBOT_INTS * r;
   const int x = me[NS_X], y = me[NS_Y], h = me[NS_H];
   const int c = nav_cos(h), sn = nav_sin(h);
   const int n_discs = n_peds + R - 1;
-  if (t < n_discs) {  // disc t in the robot's frame: position, velocity in ticks / step
+  if (mine && t < n_discs) {  // disc t in the robot's frame: position, velocity in ticks / step
     int ax, ay, ah, av;
     if (t < n_peds) {
       const int* p = s + FL_PED0 + 4 * t;
@@ -268,6 +281,7 @@ __device__ __forceinline__ void fleet_store_and_render(const int* s, int (*disc)
     disc[r][t][3] = (av * nav_sin(rel)) >> NAV_Q;
   }
   __syncthreads();
+  if (!mine) return;
   laser += (int64_t)r * NAV_BEAMS;
   vector += (int64_t)r * NAV_VECTOR;
   image += (int64_t)r * NAV_MAP_FLOATS;
@@ -307,17 +321,23 @@ __device__ __forceinline__ void fleet_store_and_render(const int* s, int (*disc)
   }
 }
 
+// FINAL: the instantiation behind ddrl_op_fleet_env_step_final -- between barrier 2 and the respawn the 256
+// threads of every truncated robot also render its row of final_* from `s`, which then holds every robot where it is after all moves
+// and before any respawn (FleetEnvRef.played); `s` stays read-only until barrier 3, and the last reader of that render's `disc` is
+// through before barrier 3, long before the render behind barrier 4 writes it again.  final_* are not touched otherwise.
+template <bool FINAL>
 __global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_step_kernel(int32_t* __restrict__ state, int R, int64_t world0, uint32_t seed,
                                                                         int n_obs, int n_peds, int max_steps,
                                                                         const float* __restrict__ actions, float* __restrict__ laser,
                                                                         float* __restrict__ vector, float* __restrict__ image,
                                                                         float* __restrict__ reward, uint8_t* __restrict__ done,
-                                                                        int32_t* __restrict__ info) {
+                                                                        int32_t* __restrict__ info, float* __restrict__ final_laser,
+                                                                        float* __restrict__ final_vector, float* __restrict__ final_image) {
   __shared__ int s[FL_STATE_INTS];
   __shared__ int fresh[FL_MAX_ROBOTS][FL_ROBOT_USED];
   __shared__ int disc[FL_MAX_ROBOTS][FL_DISCS][4];
   __shared__ int units[FL_MAX_ROBOTS];
-  __shared__ int ctl[2];  // the mask of finished robots, the event counter after their respawns
+  __shared__ int ctl[2];  // the mask of finished robots (FINAL: and of the truncated ones above it), the event counter after their respawns
   const int64_t i = blockIdx.x, row0 = i * R;
   const int tid = threadIdx.x;
   const uint32_t gworld = (uint32_t)(world0 + i);
@@ -325,10 +345,16 @@ __global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_step_kernel(int32_t*
   if (tid < FL_STATE_INTS) s[tid] = fleet_sanitize_word(tid, st[tid], R, n_obs, n_peds);
   __syncthreads();  // 1: the old state is in LDS; nothing reads the world's global words after this
   if (tid == 0)
-    ctl[0] = fleet_play(s, units, R, n_obs, n_peds, max_steps, seed, gworld, actions + 2 * row0, reward + row0, done + row0,
-                        info != nullptr ? info + row0 : nullptr);
+    ctl[0] = fleet_play<FINAL>(s, units, R, n_obs, n_peds, max_steps, seed, gworld, actions + 2 * row0, reward + row0, done + row0,
+                               info != nullptr ? info + row0 : nullptr);
   __syncthreads();  // 2: every robot has moved and knows its outcome
-  const int fin = ctl[0];
+  const int fin = FINAL ? (ctl[0] & ((1 << FL_MAX_ROBOTS) - 1)) : ctl[0];
+  if (FINAL) {
+    const int trunc = ctl[0] >> FL_MAX_ROBOTS;
+    if (trunc != 0)  // uniform over the workgroup
+      fleet_render<true>(s, disc, R, n_obs, n_peds, trunc, final_laser + row0 * NAV_BEAMS, final_vector + row0 * NAV_VECTOR,
+                         final_image + row0 * NAV_MAP_FLOATS);
+  }
   if (fin != 0) {  // uniform over the workgroup
     if (tid < 64) fleet_respawn(s, fresh, &ctl[1], fin, R, n_obs, n_peds, seed, gworld, tid);
     __syncthreads();  // 3: the new episodes wait in `fresh`
@@ -340,7 +366,8 @@ __global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_step_kernel(int32_t*
     }
     __syncthreads();  // 4: the new state is final
   }
-  fleet_store_and_render(s, disc, R, n_obs, n_peds, st, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR, image + row0 * NAV_MAP_FLOATS);
+  fleet_store_state(s, st);
+  fleet_render<false>(s, disc, R, n_obs, n_peds, 0, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR, image + row0 * NAV_MAP_FLOATS);
 }
 
 __global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_reset_kernel(int32_t* __restrict__ state, int R, int64_t world0, uint32_t seed,
@@ -356,8 +383,8 @@ __global__ __launch_bounds__(FL_MAX_THREADS) void fleet_env_reset_kernel(int32_t
   __syncthreads();
   if (tid == 0) fleet_new_world(s, R, n_obs, n_peds, seed, (uint32_t)(world0 + i));
   __syncthreads();
-  fleet_store_and_render(s, disc, R, n_obs, n_peds, state + i * FL_STATE_INTS, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR,
-                         image + row0 * NAV_MAP_FLOATS);
+  fleet_store_state(s, state + i * FL_STATE_INTS);
+  fleet_render<false>(s, disc, R, n_obs, n_peds, 0, laser + row0 * NAV_BEAMS, vector + row0 * NAV_VECTOR, image + row0 * NAV_MAP_FLOATS);
 }
 
 // what both operators check of the sizes: the worlds as section 6.8's envs, 1..4 robots, the rows inside int32
@@ -391,9 +418,10 @@ int32_t ddrl_op_fleet_env_reset(int32_t* state, int32_t n_worlds, int32_t n_robo
   return launch_status();
 }
 
-int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
-                               int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
-                               float* reward, uint8_t* done, int32_t* info, void* stream) {
+// both step entries: `final_obs` (laser, vector, image) is given by ddrl_op_fleet_env_step_final alone, which also requires `info`
+static int32_t fleet_env_step_launch(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                     int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                                     float* reward, uint8_t* done, int32_t* info, float* const* final_obs, void* stream) {
   if (!state || !actions || !laser || !vector || !image || !reward || !done ||
       !fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds))
     return DDRL_ERR_INVALID_ARG;
@@ -401,16 +429,42 @@ int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robot
   if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
       ((uintptr_t)reward & 3) || ((uintptr_t)info & 3))
     return DDRL_ERR_INVALID_ARG;
+  float* fl = final_obs ? final_obs[0] : nullptr;
+  float* fv = final_obs ? final_obs[1] : nullptr;
+  float* fi = final_obs ? final_obs[2] : nullptr;
+  if (final_obs && (!info || !fl || !fv || !fi || !aligned16(fl) || !aligned16(fi) || ((uintptr_t)fv & 3))) return DDRL_ERR_INVALID_ARG;
   const uint64_t rows = (uint64_t)n_worlds * n_robots;
   const void* src[1] = {actions};
   const uint64_t src_b[1] = {rows * 8};
-  void* dst[7] = {state, laser, vector, image, reward, done, info};
-  const uint64_t dst_b[7] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4,
-                             rows * 4, rows, rows * 4};
-  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 7)) return DDRL_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(fleet_env_step_kernel, dim3((unsigned)n_worlds), dim3(NAV_THREADS * n_robots), 0, (hipStream_t)stream, state, n_robots,
-                     world0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info);
+  void* dst[10] = {state, laser, vector, image, reward, done, info, fl, fv, fi};
+  const uint64_t dst_b[10] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4,
+                              rows * 4, rows, rows * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 10)) return DDRL_ERR_INVALID_ARG;
+  const dim3 grid((unsigned)n_worlds), block(NAV_THREADS * n_robots);
+  if (final_obs)
+    hipLaunchKernelGGL(fleet_env_step_kernel<true>, grid, block, 0, (hipStream_t)stream, state, n_robots, world0, seed, n_obstacles, n_peds,
+                       max_steps, actions, laser, vector, image, reward, done, info, fl, fv, fi);
+  else
+    hipLaunchKernelGGL(fleet_env_step_kernel<false>, grid, block, 0, (hipStream_t)stream, state, n_robots, world0, seed, n_obstacles,
+                       n_peds, max_steps, actions, laser, vector, image, reward, done, info, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr);
   return launch_status();
+}
+
+int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                               int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                               float* reward, uint8_t* done, int32_t* info, void* stream) {
+  return fleet_env_step_launch(state, n_worlds, n_robots, world0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image,
+                               reward, done, info, nullptr, stream);
+}
+
+int32_t ddrl_op_fleet_env_step_final(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                     int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                                     float* reward, uint8_t* done, int32_t* info, float* final_laser, float* final_vector,
+                                     float* final_image, void* stream) {
+  float* const final_obs[3] = {final_laser, final_vector, final_image};
+  return fleet_env_step_launch(state, n_worlds, n_robots, world0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image,
+                               reward, done, info, final_obs, stream);
 }
 
 }  // extern "C"

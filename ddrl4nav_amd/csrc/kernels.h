@@ -84,6 +84,8 @@ void launch_episode_returns(const float* rewards, const uint8_t* dones, int T, i
                             int* finished, hipStream_t st);
 void launch_gae(const float* values, const float* rewards, const uint8_t* dones, int T, int N,
                 float gamma, float landa, float* adv, float* ret, hipStream_t st);
+void launch_gae_bootstrap(const float* values, const float* rewards, const uint8_t* dones, const int32_t* slot, const float* boot, int S,
+                          int T, int N, float gamma, float landa, float* adv, float* ret, hipStream_t st);
 void launch_fill_lut(float* lut, hipStream_t st);
 
 // heads.hip: what one launch of the Categorical head kernels reads and writes.  The Atari context fills it from its workspace

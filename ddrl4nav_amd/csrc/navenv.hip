@@ -10,6 +10,11 @@
 // the LDS copy: a thread owns 4 consecutive beams (240 threads, one 16-byte store each) and 16-byte chunks of the 3 x 48 x 48 map (1,728
 // chunks).  Render is a gather: every address written is a function of the env index alone, and no table index depends on a word that
 // has not been through nav_sanitize_word.
+//
+// ddrl_op_nav_env_step_final is a third instantiation of the step kernel: a workgroup whose step truncated its
+// episode renders the state the episode ended in into final_* before thread 0 draws the next episode, so the rules are played in two
+// halves -- nav_advance (rules 1 to 6) and nav_new_episode -- with that render and one barrier between them.  The other two
+// instantiations play both halves back to back in thread 0.
 #include <cstring>
 
 #include "navcore.h"
@@ -74,7 +79,8 @@ __device__ void nav_new_episode(int* s, int n_obs, int n_peds, uint32_t seed, ui
   s[NS_DPREV] = nav_distance(s);
 }
 
-// one step of the rules on the LDS copy (NavEnvRef.step), the new episode of a finished env included; every product fits 32 bits.
+// rules 1 to 6 of one step on the LDS copy (NavEnvRef.step): everything but the new episode of a finished env, which the caller draws
+// (nav_new_episode) when *done_out is set; every product fits 32 bits.
 // INFO: *info_out receives the info word; the state, the units and the done are the same either way.
 template <bool INFO>
 __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t genv, int* units_out,
@@ -140,21 +146,24 @@ __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, i
                 (close ? NI_CLOSE : 0) | (wall ? NI_WALL : 0) | (hit_o ? NI_OBSTACLE : 0) | (v << NI_V_SHIFT) |
                 ((w + NAV_W_MAX) << NI_W_SHIFT);
   }
-  if (done) nav_new_episode(s, n_obs, n_peds, seed, genv);
   *units_out = units;
   *done_out = done ? 1 : 0;
 }
 
-// Everything behind the step: thread 0 stores the state, then all threads render the observation of the LDS copy `s`.  `ped` is LDS
-// scratch [NAV_MAX_PEDS][4].  Called by every thread of the workgroup, behind a barrier that made `s` final.
-__device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4], int n_obs, int n_peds, int32_t* __restrict__ st,
-                                                     float* __restrict__ laser, float* __restrict__ vector, float* __restrict__ image) {
-  const int tid = threadIdx.x;
-  if (tid == 0) {
+// thread 0 stores the 256 bytes of the LDS copy `s`, behind a barrier that made it final
+__device__ __forceinline__ void nav_store_state(const int* s, int32_t* __restrict__ st) {
+  if (threadIdx.x == 0) {
     int4* o = reinterpret_cast<int4*>(st);
 #pragma unroll
     for (int k = 0; k < NAV_STATE_INTS / 4; ++k) o[k] = make_int4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
   }
+}
+
+// All threads render the observation of the LDS copy `s`.  `ped` is LDS scratch [NAV_MAX_PEDS][4].  Called by every thread of the
+// workgroup, behind a barrier after which nobody writes `s` or reads `ped`; holds one barrier of its own.
+__device__ __forceinline__ void nav_render(const int* s, int (*ped)[4], int n_obs, int n_peds, float* __restrict__ laser,
+                                           float* __restrict__ vector, float* __restrict__ image) {
+  const int tid = threadIdx.x;
   const int x = s[NS_X], y = s[NS_Y], h = s[NS_H];
   const int c = nav_cos(h), sn = nav_sin(h);
   if (tid < n_peds) {  // pedestrian tid in the robot's frame: position, velocity in ticks / step
@@ -200,29 +209,46 @@ __device__ __forceinline__ void nav_store_and_render(const int* s, int (*ped)[4]
   }
 }
 
-// INFO: the instantiation behind ddrl_op_nav_env_step_info; `info` is not touched otherwise
-template <bool INFO>
+// INFO: the instantiation behind ddrl_op_nav_env_step_info; `info` is not touched otherwise.  FINAL (with INFO): the one behind
+// ddrl_op_nav_env_step_final -- a truncated env (uniform over its workgroup) also renders the state rule 6 left into final_*, and only
+// behind a further barrier does thread 0 draw the next episode; final_* are not touched otherwise.
+template <bool INFO, bool FINAL>
 __global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
                                                                    int n_peds, int max_steps, const float* __restrict__ actions,
                                                                    float* __restrict__ laser, float* __restrict__ vector,
                                                                    float* __restrict__ image, float* __restrict__ reward,
-                                                                   uint8_t* __restrict__ done, int32_t* __restrict__ info) {
+                                                                   uint8_t* __restrict__ done, int32_t* __restrict__ info,
+                                                                   float* __restrict__ final_laser, float* __restrict__ final_vector,
+                                                                   float* __restrict__ final_image) {
+  static_assert(INFO || !FINAL, "the terminal render is chosen by the info word");
   __shared__ int s[NAV_STATE_INTS];
   __shared__ int ped[NAV_MAX_PEDS][4];
+  __shared__ int truncated;  // FINAL: rule 6 ended the episode, for every thread
   const int64_t i = blockIdx.x;
   const int tid = threadIdx.x;
+  const uint32_t genv = (uint32_t)(env0 + i);
   int32_t* st = state + i * NAV_STATE_INTS;
   if (tid < NAV_STATE_INTS) s[tid] = nav_sanitize_word(tid, st[tid], n_obs, n_peds);
   __syncthreads();  // the old state is in LDS: nothing reads the env's global words after this, thread 0 alone writes them
   if (tid == 0) {
     int units, d, word = 0;
-    nav_advance<INFO>(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, (uint32_t)(env0 + i), &units, &d, &word);
+    nav_advance<INFO>(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, genv, &units, &d, &word);
+    const bool held = FINAL && (word & NI_TRUNC);  // the state the episode ended in is rendered before the next one is drawn
+    if (d && !held) nav_new_episode(s, n_obs, n_peds, seed, genv);
     reward[i] = (float)units * 0.00390625f;
     done[i] = (uint8_t)d;
     if (INFO) info[i] = word;
+    if (FINAL) truncated = held ? 1 : 0;
   }
-  __syncthreads();  // the new state is final
-  nav_store_and_render(s, ped, n_obs, n_peds, st, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
+  __syncthreads();  // the new state is final (FINAL, truncated: the state the episode ended in)
+  if (FINAL && truncated) {  // uniform over the workgroup
+    nav_render(s, ped, n_obs, n_peds, final_laser + i * NAV_BEAMS, final_vector + i * NAV_VECTOR, final_image + i * NAV_MAP_FLOATS);
+    __syncthreads();  // every thread has read `s` and `ped` for the terminal render
+    if (tid == 0) nav_new_episode(s, n_obs, n_peds, seed, genv);
+    __syncthreads();  // the new state is final
+  }
+  nav_store_state(s, st);
+  nav_render(s, ped, n_obs, n_peds, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
 }
 
 __global__ __launch_bounds__(NAV_THREADS) void nav_env_reset_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
@@ -238,8 +264,8 @@ __global__ __launch_bounds__(NAV_THREADS) void nav_env_reset_kernel(int32_t* __r
   __syncthreads();
   if (tid == 0) nav_new_episode(s, n_obs, n_peds, seed, (uint32_t)(env0 + i));
   __syncthreads();
-  nav_store_and_render(s, ped, n_obs, n_peds, state + i * NAV_STATE_INTS, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR,
-                       image + i * NAV_MAP_FLOATS);
+  nav_store_state(s, state + i * NAV_STATE_INTS);
+  nav_render(s, ped, n_obs, n_peds, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
 }
 
 }  // namespace ddrl
@@ -273,10 +299,11 @@ int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t 
   return launch_status();
 }
 
-// both step entries: `info` is given (and checked like the other outputs) by ddrl_op_nav_env_step_info alone
+// the three step entries: `info` is given (and checked like the other outputs) by ddrl_op_nav_env_step_info and _final, `final_obs`
+// (laser, vector, image) by ddrl_op_nav_env_step_final alone
 static int32_t nav_env_step_launch(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
                                    int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
-                                   uint8_t* done, int32_t* info, bool with_info, void* stream) {
+                                   uint8_t* done, int32_t* info, bool with_info, float* const* final_obs, void* stream) {
   if (!state || !actions || !laser || !vector || !image || !reward || !done || !nav_range_ok(n, env0, n_obstacles, n_peds))
     return DDRL_ERR_INVALID_ARG;
   if (with_info && (!info || ((uintptr_t)info & 3))) return DDRL_ERR_INVALID_ARG;
@@ -284,32 +311,50 @@ static int32_t nav_env_step_launch(int32_t* state, int32_t n, int64_t env0, uint
   if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
       ((uintptr_t)reward & 3))
     return DDRL_ERR_INVALID_ARG;
+  float* fl = final_obs ? final_obs[0] : nullptr;
+  float* fv = final_obs ? final_obs[1] : nullptr;
+  float* fi = final_obs ? final_obs[2] : nullptr;
+  if (final_obs && (!fl || !fv || !fi || !aligned16(fl) || !aligned16(fi) || ((uintptr_t)fv & 3))) return DDRL_ERR_INVALID_ARG;
   const void* src[1] = {actions};
   const uint64_t src_b[1] = {(uint64_t)n * 8};
-  void* dst[7] = {state, laser, vector, image, reward, done, with_info ? info : nullptr};
-  const uint64_t dst_b[7] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
-                             (uint64_t)n * NAV_MAP_FLOATS * 4, (uint64_t)n * 4, (uint64_t)n, (uint64_t)n * 4};
-  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 7)) return DDRL_ERR_INVALID_ARG;
-  if (with_info)
-    hipLaunchKernelGGL(nav_env_step_kernel<true>, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed,
-                       n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info);
+  void* dst[10] = {state, laser, vector, image, reward, done, with_info ? info : nullptr, fl, fv, fi};
+  const uint64_t dst_b[10] = {(uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4,
+                              (uint64_t)n * NAV_MAP_FLOATS * 4, (uint64_t)n * 4, (uint64_t)n, (uint64_t)n * 4,
+                              (uint64_t)n * NAV_BEAMS * 4, (uint64_t)n * NAV_VECTOR * 4, (uint64_t)n * NAV_MAP_FLOATS * 4};
+  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 10)) return DDRL_ERR_INVALID_ARG;
+  const dim3 grid((unsigned)n), block(NAV_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+  if (final_obs)
+    hipLaunchKernelGGL((nav_env_step_kernel<true, true>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
+                       laser, vector, image, reward, done, info, fl, fv, fi);
+  else if (with_info)
+    hipLaunchKernelGGL((nav_env_step_kernel<true, false>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
+                       laser, vector, image, reward, done, info, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   else
-    hipLaunchKernelGGL(nav_env_step_kernel<false>, dim3((unsigned)n), dim3(NAV_THREADS), 0, (hipStream_t)stream, state, env0, seed,
-                       n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, (int32_t*)nullptr);
+    hipLaunchKernelGGL((nav_env_step_kernel<false, false>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
+                       laser, vector, image, reward, done, (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   return launch_status();
 }
 
 int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
                              const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream) {
   return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, nullptr,
-                             false, stream);
+                             false, nullptr, stream);
 }
 
 int32_t ddrl_op_nav_env_step_info(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
                                   uint8_t* done, int32_t* info, void* stream) {
   return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info, true,
-                             stream);
+                             nullptr, stream);
+}
+
+int32_t ddrl_op_nav_env_step_final(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
+                                   uint8_t* done, int32_t* info, float* final_laser, float* final_vector, float* final_image, void* stream) {
+  float* const final_obs[3] = {final_laser, final_vector, final_image};
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info, true,
+                             final_obs, stream);
 }
 
 }  // extern "C"

@@ -347,9 +347,13 @@ void launch_clip_adam(const ddrl_config& cfg, const ParamLayout& L, double* npar
 
 // --------------------------------------------------------------------------------------------
 // GAE reverse scan, one lane per env column, reference operation order (no fma contraction)
+// BOOT (ddrl_gae_bootstrap): where slot[t][n] is in [0, S) the successor term (gamma * V_next) * (1 - d) is
+// gamma * boot[slot][n] instead -- a select, so a boot entry no slot names is never loaded; the sum is still zeroed behind every done.
 // --------------------------------------------------------------------------------------------
+template <bool BOOT>
 __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ values, const float* __restrict__ rewards,
-                                                 const uint8_t* __restrict__ dones, int T, int N, float gamma, float landa,
+                                                 const uint8_t* __restrict__ dones, const int32_t* __restrict__ slot,
+                                                 const float* __restrict__ boot, int S, int T, int N, float gamma, float landa,
                                                  float* __restrict__ adv, float* __restrict__ ret) {
   const int n = blockIdx.x * 64 + threadIdx.x;
   if (n >= N) return;
@@ -364,7 +368,11 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ value
     const float r = rewards[i];
     g = __fmul_rn(g, d);                                        // rewards_sum *= (1 - dones)
     const float t1 = __fmul_rn(gl, g);                          // discounts*landa*rewards_sum
-    const float t2 = __fmul_rn(__fmul_rn(gamma, nv), d);        // discounts*next_v*(1-dones)
+    float t2 = __fmul_rn(__fmul_rn(gamma, nv), d);              // discounts*next_v*(1-dones)
+    if (BOOT) {
+      const int k = slot[i];
+      if (k >= 0 && k < S) t2 = __fmul_rn(gamma, boot[(int64_t)k * N + n]);  // discounts*V(terminal observation)
+    }
     const float t3 = __fadd_rn(__fsub_rn(t2, v), r);            // ... - values + rewards
     g = __fadd_rn(t1, t3);
     nv = v;
@@ -374,8 +382,13 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ value
 }
 void launch_gae(const float* values, const float* rewards, const uint8_t* dones, int T, int N, float gamma, float landa,
                 float* adv, float* ret, hipStream_t st) {
-  hipLaunchKernelGGL(gae_kernel, dim3((N + 63) / 64), dim3(64), 0, st, values, rewards, dones, T, N, gamma, landa, adv,
-                     ret);
+  hipLaunchKernelGGL(gae_kernel<false>, dim3((N + 63) / 64), dim3(64), 0, st, values, rewards, dones, (const int32_t*)nullptr,
+                     (const float*)nullptr, 0, T, N, gamma, landa, adv, ret);
+}
+void launch_gae_bootstrap(const float* values, const float* rewards, const uint8_t* dones, const int32_t* slot, const float* boot, int S,
+                          int T, int N, float gamma, float landa, float* adv, float* ret, hipStream_t st) {
+  hipLaunchKernelGGL(gae_kernel<true>, dim3((N + 63) / 64), dim3(64), 0, st, values, rewards, dones, slot, boot, S, T, N, gamma, landa,
+                     adv, ret);
 }
 
 // --------------------------------------------------------------------------------------------

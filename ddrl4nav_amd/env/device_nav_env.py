@@ -18,11 +18,14 @@ class DeviceNavEnv(DeviceEnvBase):
     _state_ints = staticmethod(ops.nav_env_state_ints)
     state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
-    def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False):
+    def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False,
+                 emit_final_obs=False):
         """n_obstacles 0..10 static circles, n_peds 0..5 pedestrians; an episode ends at a collision, at the goal or after max_steps
         steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv.  emit_info: every step also
         fills ``info`` (int32 [N]: why the step ended or did not, ops.nav_info_fields; agent.NavStatus accumulates it); the trajectory is
-        the same either way."""
+        the same either way.  emit_final_obs (implies emit_info): a step that truncates an env's episode also
+        renders the observation that episode ended in into row i of ``final_obs`` ([laser, vector, image], [N, ...] each; the rows of
+        the other envs keep what they held), for a rollout that bootstraps truncated episodes."""
         self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
         if not 0 <= self.n_obstacles <= 10:
             raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
@@ -33,8 +36,10 @@ class DeviceNavEnv(DeviceEnvBase):
         super().__init__(n_envs, device, seed, env0)
         dev = self.device
         self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
-        self.emit_info = bool(emit_info)
+        self.emit_final_obs = bool(emit_final_obs)
+        self.emit_info = bool(emit_info) or self.emit_final_obs
         self.info = torch.zeros(self.N, dtype=torch.int32, device=dev) if self.emit_info else None
+        self.final_obs = [torch.zeros_like(o) for o in self.obs] if self.emit_final_obs else None
 
     def _obs_out(self, obs_out):
         return self.obs if obs_out is None else list(obs_out)
@@ -46,11 +51,23 @@ class DeviceNavEnv(DeviceEnvBase):
         return ops.nav_env_reset(self.state, self._obs_out(obs_out), env0=self.env0, seed=self.seed, n_obstacles=self.n_obstacles,
                                  n_peds=self.n_peds, mask=mask)
 
-    def step(self, actions, obs_out=None):
+    def truncations_per_rollout(self, horizon):
+        """The most truncations one env can have in `horizon` steps, ceil(horizon / max_steps): the pool depth with which a
+        StateRollout(bootstrap_truncated=...) drops none."""
+        return truncations_per_rollout(horizon, self.max_steps)
+
+    def step(self, actions, obs_out=None, final_out=None):
         """actions fp32 [N, 2] on the device (what a Gaussian actor's act() returns) -> ([laser, vector, image], reward fp32 [N], done
         uint8 [N]): device tensors the env owns, valid until the next step (obs_out: render there instead).  A finished env has already
         begun its next episode: the observation is that episode's first and done is the reset flag.  With emit_info, ``info`` describes the
-        step just played (the finished episode's last, not the new one's first).  Asynchronous."""
+        step just played (the finished episode's last, not the new one's first).  With emit_final_obs the truncated envs' rows of
+        ``final_obs`` (final_out: of those tensors instead) receive the observation their episode ended in.  Asynchronous."""
+        if final_out is not None and not self.emit_final_obs:
+            raise ValueError("final_out needs an env built with emit_final_obs=True")
+        if self.emit_final_obs:
+            return ops.nav_env_step_final(self.state, actions, self._obs_out(obs_out), self.reward, self.done, self.info,
+                                          self.final_obs if final_out is None else list(final_out), env0=self.env0, seed=self.seed,
+                                          n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
         if self.emit_info:
             return ops.nav_env_step_info(self.state, actions, self._obs_out(obs_out), self.reward, self.done, self.info, env0=self.env0,
                                          seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
@@ -58,13 +75,22 @@ class DeviceNavEnv(DeviceEnvBase):
                                 n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)
 
 
+def truncations_per_rollout(horizon, max_steps):
+    """ceil(horizon / max_steps): an episode lasts max_steps steps at the most, so no env truncates more often in `horizon` steps."""
+    horizon, max_steps = int(horizon), int(max_steps)
+    if horizon < 1 or max_steps < 1:
+        raise ValueError("horizon and max_steps must be at least 1, got %d and %d" % (horizon, max_steps))
+    return -(-horizon // max_steps)
+
+
 def make_device_nav_env(config_env, device=None, env0=0):
     """The DeviceNavEnv of a config_env dict: env_name "DeviceNav-v0", env_num, and the optional knobs env_obstacles, env_peds,
-    env_max_steps, env_seed, env_info (emit_info)."""
+    env_max_steps, env_seed, env_info (emit_info), env_final_obs (emit_final_obs)."""
     if config_env.get("env_name") != NAV_ENV_NAME:
         raise ValueError("env_name must be %r, got %r" % (NAV_ENV_NAME, config_env.get("env_name")))
     if "env_num" not in config_env:
         raise ValueError("config_env needs env_num")
     return DeviceNavEnv(int(config_env["env_num"]), device=device, seed=int(config_env.get("env_seed", 0)),
                         n_obstacles=int(config_env.get("env_obstacles", 10)), n_peds=int(config_env.get("env_peds", 5)),
-                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0, emit_info=bool(config_env.get("env_info", False)))
+                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0, emit_info=bool(config_env.get("env_info", False)),
+                        emit_final_obs=bool(config_env.get("env_final_obs", False)))

@@ -474,6 +474,29 @@ def nav_env_step_info(state, actions, obs, reward, done, info, env0=0, seed=0, n
     return obs, reward, done, info
 
 
+def _nav_final_args(final_obs, obs, rows):
+    """The pointers of the terminal-observation buffers of a *_step_final call: three contiguous fp32 tensors of the observation's
+    shapes on its device, laser and image 16-byte aligned."""
+    assert len(final_obs) == 3, "final_obs: [laser, vector, image]"
+    for name, t, o, shape in zip(("laser", "vector", "image"), final_obs, obs, NAV_ENV_SHAPES):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (rows,) + shape \
+            and t.device == o.device, "final %s: contiguous fp32 %s on the state's device" % (name, ("rows",) + shape)
+    assert final_obs[0].data_ptr() % 16 == 0 and final_obs[2].data_ptr() % 16 == 0, "final laser / image: the base must be 16-byte aligned"
+    return _p(final_obs[0]), _p(final_obs[1]), _p(final_obs[2])
+
+
+def nav_env_step_final(state, actions, obs, reward, done, info, final_obs, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
+    """nav_env_step_info plus the terminal observation (include/ddrl.h ddrl_op_nav_env_step_final): for an env
+    whose info word has the truncation bit, row i of final_obs = [laser, vector, image] (the observation's shapes) receives the
+    observation of the state the episode ended in; no other row of final_obs is written.  The other outputs are bit-identical to
+    nav_env_step_info's.  Asynchronous on the current stream; returns (obs, reward, done, info, final_obs)."""
+    args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
+    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (args[1],) \
+        and info.device == state.device, "info: contiguous int32 [n] on the state's device"
+    check(_lib.load().ddrl_op_nav_env_step_final(*args, _p(info), *_nav_final_args(final_obs, obs, args[1]), _st()))
+    return obs, reward, done, info, final_obs
+
+
 NAV_INFO_FIELDS = ("done", "goal", "collision", "truncated", "close", "wall_hit", "obstacle_hit", "v", "w")
 NAV_COLLISION_STATIC, NAV_COLLISION_PED = 1, 2    # the reference's coding of info["collision"]
 
@@ -579,6 +602,77 @@ def fleet_env_step(state, n_robots, actions, obs, reward, done, info=None, world
                                              int(n_peds), int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward),
                                              _p(done), _p(info), _st()))
     return obs, reward, done
+
+
+def fleet_env_step_final(state, n_robots, actions, obs, reward, done, info, final_obs, world0=0, seed=0, n_obstacles=10, n_peds=5,
+                         max_steps=500):
+    """fleet_env_step with info required, plus the terminal observation of every truncated row (include/ddrl.h
+    ddrl_op_fleet_env_step_final): what the robot sees with every robot where it is after all moves of the step
+    and before any respawn.  Rows without the truncation bit are not written; the other outputs are bit-identical to fleet_env_step's.
+    Asynchronous on the current stream; returns (obs, reward, done)."""
+    n_worlds, rows = _fleet_env_args(state, n_robots, obs)
+    assert tuple(_f32(actions).shape) == (rows, 2) and _f32(reward).numel() == rows and actions.device == state.device \
+        and reward.device == state.device, "actions fp32 [rows, 2], reward fp32 [rows] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == rows \
+        and done.device == state.device, "done: contiguous uint8 [rows] on the state's device"
+    assert info is not None and info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (rows,) \
+        and info.device == state.device, "info: contiguous int32 [rows] on the state's device"
+    check(_lib.load().ddrl_op_fleet_env_step_final(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF,
+                                                   int(n_obstacles), int(n_peds), int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]),
+                                                   _p(obs[2]), _p(reward), _p(done), _p(info), *_nav_final_args(final_obs, obs, rows),
+                                                   _st()))
+    return obs, reward, done
+
+
+NAV_INFO_TRUNCATED = 1 << 4        # the truncation bit of an info word (include/ddrl.h ddrl_op_nav_env_step_info)
+FILE_ROWS_MAX_PARTS = 4
+
+
+def file_flagged_rows(info, parts, count, slot_out, mask=NAV_INFO_TRUNCATED):
+    """Files the rows of the envs whose info word has a bit of `mask` into per-env pools (include/ddrl.h ddrl_op_file_flagged_rows;
+    csrc/truncate.hip): info int32 [N]; parts = up to four (src fp32 [N, ...], dst fp32 [S, N, ...]) pairs; count int32 [N] (in/out) and
+    slot_out int32 [N].  A flagged env n with count[n] < S gets its rows copied to dst[count[n]][n] and slot_out[n] = count[n]; every
+    other env slot_out[n] = -1 and no copy; count[n] goes up for every flagged env.  Asynchronous on the current stream, no read-back;
+    returns slot_out."""
+    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and info.dim() == 1, "info: contiguous int32 [N] on the device"
+    N = info.shape[0]
+    for name, t in (("count", count), ("slot_out", slot_out)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (N,) and t.device == info.device, \
+            "%s: contiguous int32 [N] on info's device" % name
+    parts = list(parts)
+    assert 1 <= len(parts) <= FILE_ROWS_MAX_PARTS, "parts: one to four (src, dst) pairs"
+    S = parts[0][1].shape[0]
+    widths = []
+    for src, dst in parts:
+        assert _f32(src).shape[0] == N and src.dim() >= 2 and src.device == info.device, "src: contiguous fp32 [N, ...] on info's device"
+        assert _f32(dst).dim() == src.dim() + 1 and tuple(dst.shape) == (S,) + tuple(src.shape) and dst.device == info.device, \
+            "dst: contiguous fp32 [S, N, ...] on info's device"
+        widths.append(src[0].numel())
+    k = len(parts)
+    srcs = (c_void_p * k)(*[src.data_ptr() for src, _ in parts])
+    dsts = (c_void_p * k)(*[dst.data_ptr() for _, dst in parts])
+    check(_lib.load().ddrl_op_file_flagged_rows(_p(info), int(mask), N, int(S), k, srcs, dsts, (c_int32 * k)(*widths), _p(count),
+                                                _p(slot_out), _st()))
+    return slot_out
+
+
+def gae_bootstrap(values, rewards, dones, slots, boot, gamma, landa, adv, ret):
+    """ddrl_gae with the successor value of flagged steps taken from `boot` (include/ddrl.h ddrl_gae_bootstrap):
+    values fp32 [T + 1, N], rewards fp32 [T, N], dones uint8 [T, N], slots int32 [T, N], boot fp32 [S, N]; where slots[t, n] is in
+    [0, S) the term (gamma * V_next) * (1 - done) is gamma * boot[slots[t, n], n].  Asynchronous on the current stream; returns
+    (adv, ret)."""
+    T, N = rewards.shape
+    assert tuple(_f32(values).shape) == (T + 1, N) and _f32(rewards).device == values.device, "values fp32 [T + 1, N], rewards fp32 [T, N]"
+    assert dones.dtype == torch.uint8 and dones.is_contiguous() and tuple(dones.shape) == (T, N) and dones.device == values.device, \
+        "dones: contiguous uint8 [T, N] on the values' device"
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and tuple(slots.shape) == (T, N) and slots.device == values.device, \
+        "slots: contiguous int32 [T, N] on the values' device"
+    assert _f32(boot).dim() == 2 and boot.shape[1] == N and boot.shape[0] >= 1 and boot.device == values.device, "boot: fp32 [S, N]"
+    assert tuple(_f32(adv).shape) == (T, N) and tuple(_f32(ret).shape) == (T, N) and adv.device == values.device \
+        and ret.device == values.device, "adv / ret: fp32 [T, N] on the values' device"
+    check(_lib.load().ddrl_gae_bootstrap(_p(values), _p(rewards), _p(dones), _p(slots), _p(boot), int(boot.shape[0]), int(T), int(N),
+                                         float(gamma), float(landa), _p(adv), _p(ret), _st()))
+    return adv, ret
 
 
 NO_LOSS_OPTIONS = (0.0, False)   # (value_clip, entropy_split): both off

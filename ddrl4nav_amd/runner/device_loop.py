@@ -21,10 +21,19 @@ def _frame_io(ro, env, keep_step):
 def _state_io(ro, env, keep_step):
     """The same of a StateRollout on a DeviceNavEnv: the env renders into the pool rows, so the put copies nothing."""
     tracks = getattr(ro, "nav_status", None) is not None
+    boots = getattr(ro, "S", 0) > 0
     if tracks and getattr(env, "info", None) is None:
         raise ValueError("the rollout tracks the navigation status but the env was built without emit_info")
+    if boots and getattr(env, "final_obs", None) is None:
+        raise ValueError("the rollout bootstraps truncated episodes but the env was built without emit_final_obs")
+    if boots and keep_step:
+        raise ValueError("keep_step is not supported with bootstrap_truncated: the terminal observation of row T would have to move "
+                         "between rollouts")
+    info = {"info": env.info} if tracks or boots else {}
+    if boots:
+        info["final_obs"] = env.final_obs
     return (lambda t: {"obs_out": ro.state_rows(t)}, lambda t, obs, reset=None: ro.put_states_in_place(t),
-            lambda t: ro.put_states(t, env.obs), lambda: ro.bootstrap(sample=keep_step), {"info": env.info} if tracks else {})
+            lambda t: ro.put_states(t, env.obs), lambda: ro.bootstrap(sample=keep_step), info)
 
 
 def _collect(ro, env, keep_step, reset, io):
@@ -92,7 +101,9 @@ def collect_states(ro, env, keep_step=False, reset=None):
     reward and done are recorded in row T; the next rollout starts at ro.t0 == 1 and copies that observation into slot 1.
 
     A rollout built with track_nav_status=True also records env.info, the info words of every step: the env must have been built with
-    emit_info=True (ValueError otherwise)."""
+    emit_info=True (ValueError otherwise).  A rollout built with bootstrap_truncated=S also records env.info and env.final_obs, the
+    terminal observations of truncated episodes: the env must have been built with emit_final_obs=True, and keep_step is refused
+    (ValueError either way)."""
     _collect(ro, env, keep_step, reset, _state_io)
 
 

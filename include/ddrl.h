@@ -878,6 +878,46 @@ int32_t ddrl_op_fleet_env_step(int32_t* state, int32_t n_worlds, int32_t n_robot
                                int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
                                float* reward, uint8_t* done, int32_t* info, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Bootstrapping truncated episodes (additive: ABI 3).  A time limit is not an outcome of the task: at a step
+ * that max_steps ended (info bit 4) GAE should go on from the critic's value of the observation the episode ended in, not from 0.  The
+ * step kernels draw the next episode in the same launch, so that observation is rendered by these two entry points, filed per env by
+ * ddrl_op_file_flagged_rows and its value used by ddrl_gae_bootstrap.  Context-free, no allocation, no atomics, asynchronous on
+ * `stream`; every check is decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+/* ddrl_op_nav_env_step_info plus the terminal observation: final_laser float32 [n][1][960], final_vector [n][5], final_image
+ * [n][3][48][48], aligned like laser, vector and image and apart from every other argument.  For an env whose info word has bit 4 set,
+ * row i of final_* receives the observation of the state the episode ended in (after the move and the outcome, before the new episode
+ * is drawn: in the vector, v and w are the action just played and the distance is the one after the move); the rows of every other env
+ * are not written.  State, observation, reward, done and info are bit-identical to ddrl_op_nav_env_step_info. */
+int32_t ddrl_op_nav_env_step_final(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
+                                   uint8_t* done, int32_t* info, float* final_laser, float* final_vector, float* final_image,
+                                   void* stream);
+/* ddrl_op_fleet_env_step with info required, plus the terminal observation of every truncated row (final_* [rows], as above): what the
+ * robot sees with every robot where it is after all moves of the step and before any respawn.  Rows without bit 4 are not written; the
+ * other outputs are bit-identical to ddrl_op_fleet_env_step. */
+int32_t ddrl_op_fleet_env_step_final(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                     int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                                     float* reward, uint8_t* done, int32_t* info, float* final_laser, float* final_vector,
+                                     float* final_image, void* stream);
+/* Files the rows of flagged envs into a pool of S slots per env: for env n with (info[n] & mask) != 0 and 0 <= count[n] < S, row n of
+ * every part's src (float32 [N][widths[k]]) is copied to dst[k] (float32 [S][N][widths[k]]) at [count[n]][n] and slot_out[n] = count[n];
+ * a flagged env without room gets slot_out[n] = -1 and nothing is copied; either way count[n] (int32 [N], in/out) goes up by one, so an
+ * overflow stays visible.  An env that is not flagged gets slot_out[n] = -1 and keeps its count.  src, dst and widths are HOST arrays of
+ * n_parts = 1..4 entries.  One workgroup per env; a part whose width is a multiple of 4 floats on 16-byte aligned bases moves in 16-byte
+ * units, any other in 4-byte units.  A null or misaligned (4 bytes) pointer, mask == 0, N < 1, S < 1, n_parts outside 1..4, a width
+ * < 1, an overlap of two arguments: DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_file_flagged_rows(const int32_t* info, int32_t mask, int32_t N, int32_t S, int32_t n_parts, const float* const* src,
+                                  float* const* dst, const int32_t* widths, int32_t* count, int32_t* slot_out, void* stream);
+/* ddrl_gae with one change: where slot[t][n] (int32 [T][N]) is in [0, S), the successor term (gamma * V_next) * (1 - done) is
+ * gamma * boot[slot[t][n]][n] (boot float32 [S][N]) -- a select, not a blend; any other slot value counts as -1, the plain term.  The
+ * accumulated sum is still zeroed behind every done.  A boot entry that no slot names is never read.  With every slot -1 the results
+ * equal ddrl_gae's bit for bit.  A null or misaligned pointer, S < 1, T < 0, N < 1, adv or ret overlapping an input:
+ * DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_gae_bootstrap(const float* values, const float* rewards, const uint8_t* dones, const int32_t* slot, const float* boot,
+                           int32_t S, int32_t T, int32_t N, float gamma, float landa, float* adv, float* ret, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,10 @@ process, the legs alternating: ddrl_op_fleet_env_step at --rows rows (robots) as
 against two baselines -- ddrl_op_nav_env_step (env/device_nav_env.py) at N = rows, and a plain device-to-device copy of the same
 rows * 31,508 observation bytes.  `calls` launches between one pair of device events give one sample (time per call); every leg is warmed
 up first and reports the median, the p95 and the extremes of its samples.  The envs run under the same uniform-random actions, so robots
-finish and respawn at the rate a fresh policy meets.  Prints one JSON line.
+finish and respawn at the rate a fresh policy meets.  A second set of legs runs ddrl_op_fleet_env_step_final
+against ddrl_op_fleet_env_step with the info word at R = 1, 2, 4, at the default max_steps and at max_steps = 1 (every robot that does
+not collide truncates in every step), and the filing launch ddrl_op_file_flagged_rows of the terminal rows into pools of depth 1.  Prints
+one JSON line.
 
     python tools/bench_device_fleet_env.py [--rows 512] [--calls 200] [--samples 30] [--warmup 2]
 """
@@ -19,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tools.bench_device_env import summary, timed  # noqa: E402
-from tools.bench_device_nav_env import OBS_FLOATS  # noqa: E402
+from tools.bench_device_nav_env import OBS_FLOATS, halves_spread  # noqa: E402
 
 
 def main():
@@ -73,7 +76,60 @@ def main():
         out[k]["worlds"] = rows // R
         out[k]["over_nav_env_step"] = round(out[k]["median_us"] / out["nav_env_step"]["median_us"], 3)
         out[k]["over_d2d_copy"] = round(out[k]["median_us"] / out["d2d_copy"]["median_us"], 3)
+    out["final"] = final_legs(args, actions)
     print(json.dumps(out))
+
+
+def final_legs(args, actions):
+    from ddrl4nav_amd import ops
+    from ddrl4nav_amd.env import FleetNavEnv
+    rows, out = args.rows, {}
+    for name, max_steps in (("default_max_steps", 500), ("max_steps_1", 1)):
+        envs = {}
+        for R in (1, 2, 4):
+            envs["fleet_env_step_info_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_info=True)
+            envs["fleet_env_step_final_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_final_obs=True)
+        for env in envs.values():
+            env.reset()
+        last = envs["fleet_env_step_final_R4"]
+        pools = [torch.zeros((1,) + tuple(f.shape), device="cuda") for f in last.final_obs]
+        count = torch.zeros(rows, dtype=torch.int32, device="cuda")
+        slot = torch.zeros(rows, dtype=torch.int32, device="cuda")
+
+        def stepping(env):
+            def run():
+                for _ in range(args.calls):
+                    env.step(actions)
+            return run
+
+        def filing():                   # the info words and terminal rows the R = 4 env's last step left; an empty pool every time
+            for _ in range(args.calls):
+                count.zero_()
+                ops.file_flagged_rows(last.info, list(zip(last.final_obs, pools)), count, slot)
+
+        def zeroing():
+            for _ in range(args.calls):
+                count.zero_()
+
+        legs = {k: stepping(env) for k, env in envs.items()}
+        legs["file_flagged_rows_and_zero"], legs["zero_count"] = filing, zeroing
+        for _ in range(args.warmup):
+            for fn in legs.values():
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in legs}
+        for _ in range(args.samples):
+            for k, fn in legs.items():
+                ms[k].append(timed(fn))
+        res = {k: summary(v, per=args.calls) for k, v in ms.items()}
+        for R in (1, 2, 4):
+            a, b = "fleet_env_step_info_R%d" % R, "fleet_env_step_final_R%d" % R
+            res[a]["spread_us"] = halves_spread(ms[a], per=args.calls)
+            res[b]["minus_info_us"] = round(res[b]["median_us"] - res[a]["median_us"], 3)
+            res[b]["same_state"] = bool(torch.equal(envs[a].state, envs[b].state))
+        res["filing_us"] = round(res["file_flagged_rows_and_zero"]["median_us"] - res["zero_count"]["median_us"], 3)
+        out[name] = res
+    return out
 
 
 if __name__ == "__main__":

@@ -14,6 +14,13 @@ legs of each measurement alternating:
                section 6.9), samples alternating as in (a).  The plain leg's samples are also split into its even and its odd ones: the
                gap between the two halves' medians is the session's own run-to-run spread, which the info leg is held against.
   (d) status   ddrl_op_nav_status_update over T x N info words and ddrl_op_nav_status_reduce, `calls` launches per sample.
+  (e) final    ddrl_op_nav_env_step_final against ddrl_op_nav_env_step_info on envs of the same seed under the same actions (DESIGN.md
+               section 6.12), at the env's default max_steps (truncations as rare as a fresh policy meets them) and at max_steps = 1
+               (every env that does not collide truncates in every step: the terminal render at its most expensive), and the filing
+               launch ddrl_op_file_flagged_rows of the terminal observations into pools of depth 1 under both.  The info leg's even and
+               odd samples give the session's spread, as in (c).
+  (f) bootstrap  the acting phase of (b) with the option on -- DeviceNavEnv(emit_final_obs=True), StateRollout(bootstrap_truncated=S),
+               record() filing the rows -- against the same phase with it off, and finish() (with the extra forward) against finish().
 
 Every leg is warmed up first; a leg reports the median, the p95 and the extremes of its samples.  Prints one JSON line.
 
@@ -33,6 +40,14 @@ sys.path.insert(0, ROOT)
 from tools.bench_device_env import summary, timed  # noqa: E402
 
 OBS_FLOATS = 960 + 5 + 3 * 48 * 48
+
+
+def halves_spread(samples, **kw):
+    """|median of the even samples - median of the odd ones| of one leg: the session's own run-to-run spread (None below two samples)."""
+    if len(samples) < 2:
+        return None
+    a, b = (list(summary(samples[h::2], **kw).values())[0] for h in (0, 1))
+    return round(abs(a - b), 4)
 
 
 def make_net(max_batch, seed=0, **config_nn):
@@ -113,6 +128,103 @@ def info_legs(args):
     out["env_step_spread_us"] = round(abs(halves[0] - halves[1]), 3)
     out["info_minus_plain_us"] = round(out["env_step_info"]["median_us"] - out["env_step"]["median_us"], 3)
     out["same_state"] = bool(torch.equal(plain.state, told.state))
+    return out
+
+
+def final_legs(args):
+    from ddrl4nav_amd import ops
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N = args.envs
+    g = torch.Generator(device="cuda").manual_seed(0)
+    actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
+    out = {}
+    for name, max_steps in (("default_max_steps", 500), ("max_steps_1", 1)):
+        told = DeviceNavEnv(N, device="cuda", seed=1, max_steps=max_steps, emit_info=True)
+        final = DeviceNavEnv(N, device="cuda", seed=1, max_steps=max_steps, emit_final_obs=True)
+        told.reset()
+        final.reset()
+        pools = [torch.zeros((1,) + tuple(f.shape), device="cuda") for f in final.final_obs]
+        count = torch.zeros(N, dtype=torch.int32, device="cuda")
+        slot = torch.zeros(N, dtype=torch.int32, device="cuda")
+        truncated = torch.zeros((), dtype=torch.int64, device="cuda")
+
+        def leg(env):
+            def run():
+                for _ in range(args.calls):
+                    env.step(actions)
+            return run
+
+        def filing():                   # the info words and terminal rows the last step left; an empty pool every time
+            for _ in range(args.calls):
+                count.zero_()
+                ops.file_flagged_rows(final.info, list(zip(final.final_obs, pools)), count, slot)
+
+        def zeroing():                  # what the filing leg spends on emptying the pool
+            for _ in range(args.calls):
+                count.zero_()
+
+        legs = {"env_step_info": leg(told), "env_step_final": leg(final), "file_flagged_rows_and_zero": filing, "zero_count": zeroing}
+        for _ in range(args.warmup):
+            for fn in legs.values():
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in legs}
+        for _ in range(args.samples):
+            for k, fn in legs.items():
+                ms[k].append(timed(fn))
+            truncated += ((final.info >> 4) & 1).sum()
+        res = {k: summary(v, per=args.calls) for k, v in ms.items()}
+        res["env_step_info_spread_us"] = halves_spread(ms["env_step_info"], per=args.calls)
+        res["final_minus_info_us"] = round(res["env_step_final"]["median_us"] - res["env_step_info"]["median_us"], 3)
+        res["filing_us"] = round(res["file_flagged_rows_and_zero"]["median_us"] - res["zero_count"]["median_us"], 3)
+        res["truncated_share_of_last_steps"] = round(float(truncated) / (args.samples * N), 4)
+        res["same_state"] = bool(torch.equal(told.state, final.state))
+        out[name] = res
+    return out
+
+
+def bootstrap_legs(args):
+    from ddrl4nav_amd.agent import StateRollout
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N, T = args.envs, args.steps
+    net = make_net(N)
+    plain = DeviceNavEnv(N, device="cuda", seed=1)
+    final = DeviceNavEnv(N, device="cuda", seed=1, emit_final_obs=True)
+    S = final.truncations_per_rollout(T)
+    off = StateRollout(net, N, plain.state_shapes, horizon=T)
+    on = StateRollout(net, N, final.state_shapes, horizon=T, bootstrap_truncated=S)
+    for env, ro in ((plain, off), (final, on)):
+        env.reset(obs_out=ro.state_rows(0))
+        ro.put_states_in_place(0)
+
+    def acting_off():
+        for t in range(T):
+            _, r, d = plain.step(off.act(t), obs_out=off.state_rows(t + 1))
+            off.record(t, r, d)
+            off.put_states_in_place(t + 1)
+
+    def acting_on():
+        on.trunc_count.zero_()
+        for t in range(T):
+            _, r, d = final.step(on.act(t), obs_out=on.state_rows(t + 1))
+            on.record(t, r, d, info=final.info, final_obs=final.final_obs)
+            on.put_states_in_place(t + 1)
+
+    legs = {"acting_off": acting_off, "acting_on": acting_on, "finish_off": off.finish, "finish_on": on.finish}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.runs):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    out = {k: summary(v, unit="ms") for k, v in ms.items()}
+    out["acting_off_spread_ms"] = halves_spread(ms["acting_off"], unit="ms")
+    out["acting_on_over_off"] = round(out["acting_on"]["median_ms"] / out["acting_off"]["median_ms"], 4)
+    out["finish_on_minus_off_ms"] = round(out["finish_on"]["median_ms"] - out["finish_off"]["median_ms"], 4)
+    out["S"] = S
+    out["truncations_dropped"] = on.truncations_dropped()
     return out
 
 
@@ -204,7 +316,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_device_nav_env needs a GPU: there is nothing to measure without one")
     out = {"tool": "bench_device_nav_env", "N": args.envs, "T": args.steps, "device": torch.cuda.get_device_name(0),
-           "kernel": kernel_legs(args), "info": info_legs(args), "status": status_legs(args), "acting": acting_legs(args)}
+           "kernel": kernel_legs(args), "info": info_legs(args), "status": status_legs(args), "final": final_legs(args),
+           "acting": acting_legs(args), "bootstrap": bootstrap_legs(args)}
     print(json.dumps(out))
 
 

@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--critic-lr", type=float, default=None)
     ap.add_argument("--normalize-obs", action="store_true", help="StateRollout(normalize_obs=True)")
     ap.add_argument("--nav-status", action="store_true", help="track and print reach / collision / truncation rates (agent.NavStatus)")
+    ap.add_argument("--bootstrap-truncated", action="store_true",
+                    help="GAE goes on from the critic's value of a truncated episode's last observation (DESIGN.md section 6.12): the "
+                         "env renders it, StateRollout(bootstrap_truncated=env.truncations_per_rollout(horizon)) files and evaluates it")
     ap.add_argument("--robots", type=int, default=1, help="robots per world; above 1 the env is a FleetNavEnv and --envs counts worlds")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--baseline-steps", type=int, default=1000)
@@ -83,16 +86,19 @@ def main():
     rows = args.envs * args.robots
     net = make_net(max(args.micro_batch, rows), seed=args.seed, **knobs)
     config_env = {"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
-                  "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status}
+                  "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status,
+                  "env_final_obs": args.bootstrap_truncated}
     if args.robots > 1:
         config_env.update(env_name="DeviceNavFleet-v0", agent_num_per_env=args.robots)
     env = make_device_env(config_env, device=net.device)
     ro = StateRollout(net, env.N, env.state_shapes, horizon=args.horizon, track_returns=True, normalize_obs=args.normalize_obs or None,
-                      track_nav_status=args.nav_status)
+                      track_nav_status=args.nav_status,
+                      bootstrap_truncated=env.truncations_per_rollout(args.horizon) if args.bootstrap_truncated else 0)
 
     per_episode, per_1000 = random_policy_return(env, args.baseline_steps, args.seed + 1)
     out = {"tool": "train_device_nav_env", "N": rows, "robots": args.robots, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
            "max_steps": args.max_steps, "iters": args.iters, "normalize_obs": bool(args.normalize_obs),
+           "bootstrap_truncated": ro.S,
            "device": torch.cuda.get_device_name(0),
            "random_policy": {"return_per_episode": per_episode, "reward_per_env_per_1000_steps": per_1000, "steps": args.baseline_steps},
            "curve": []}
