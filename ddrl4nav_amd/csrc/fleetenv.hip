@@ -2,7 +2,9 @@
 // walking pedestrians, see each other in their lidar and dynamic-agent map and collide with each other (include/ddrl.h
 // ddrl_op_fleet_env_*).  tests/fleet_env_ref.py is the rule book, in integers only, so every state word, lidar
 // range, vector entry, map cell, reward, done and info word equals the model's.  Context-free, no allocation, no atomics; the same
-// arguments give the same bits.  The sizes, the trig table, the hash and the ray cast are section 6.8's (navcore.h).
+// arguments give the same bits.  The arena is section 6.8's: the sizes, the tables, every rule of a step, the placement of a new world and
+// the render of a row come from navcore.h (section 6.13).  What is written here is what a fleet adds -- the 96-word layout, the order of a
+// step (all moves, then all outcomes), the robot-robot test, the respawn of a finished robot alone -- and the kernels.
 //
 // A world is one arena, a row is one robot: row i * R + r is robot r of world i.  One workgroup of 256 R threads per world, and nobody
 // else touches that world's state.  Threads 0..95 load one state word each, bring it into its range and park it in LDS `s`.  Behind
@@ -21,13 +23,13 @@ namespace ddrl {
 
 constexpr int FL_STATE_INTS = 96, FL_MAX_ROBOTS = 4, FL_ROBOT_INTS = 10, FL_ROBOT_USED = 9;
 constexpr int FL_OBS0 = 40, FL_PED0 = 70, FL_EVENTS = 90;
-constexpr int FL_CELLS = 25, FL_GRID = 5, FL_CLEAR = 300;
+constexpr int FL_CLEAR = 300;
 constexpr int FL_DISCS = NAV_MAX_PEDS + FL_MAX_ROBOTS - 1;  // what one robot's map can hold: the pedestrians, then the other robots
 constexpr int FL_MAX_THREADS = NAV_THREADS * FL_MAX_ROBOTS;
 static_assert(FL_MAX_ROBOTS * FL_ROBOT_INTS == FL_OBS0 && FL_OBS0 + 3 * NAV_MAX_OBS == FL_PED0 && FL_PED0 + 4 * NAV_MAX_PEDS == FL_EVENTS &&
                   FL_EVENTS < FL_STATE_INTS && FL_STATE_INTS % 4 == 0,
               "state layout");
-static_assert(FL_CELLS <= 64 && FL_DISCS <= NAV_THREADS && 2 * FL_CLEAR < NAV_CELL, "one cell a lane; one circle blocks one cell at most");
+static_assert(NAV_CELLS <= 64 && FL_DISCS <= NAV_THREADS && 2 * FL_CLEAR < NAV_CELL, "one cell a lane; one circle blocks one cell at most");
 
 // word k of a loaded state brought into its range (FleetEnvRef.sanitize): a no-op on every state the rules produce
 __device__ __forceinline__ int fleet_sanitize_word(int k, int v, int R, int n_obs, int n_peds) {
@@ -40,59 +42,16 @@ __device__ __forceinline__ int fleet_sanitize_word(int k, int v, int R, int n_ob
   return k == FL_EVENTS ? v : 0;
 }
 
-__device__ __forceinline__ uint32_t fleet_draw(int* s, uint32_t seed, uint32_t gworld) {
-  const uint32_t h = nav_hash(seed, gworld, (uint32_t)s[FL_EVENTS]);
-  s[FL_EVENTS] = (int)((uint32_t)s[FL_EVENTS] + 1u);
-  return h;
-}
-
-__device__ __forceinline__ int fleet_cell_x(int cell) { return (cell % FL_GRID - 2) * NAV_CELL; }
-__device__ __forceinline__ int fleet_cell_y(int cell) { return (cell / FL_GRID - 2) * NAV_CELL; }
-__device__ __forceinline__ int fleet_jitter_x(uint32_t h) { return (int)((h >> 8) % 257u) - 128; }
-__device__ __forceinline__ int fleet_jitter_y(uint32_t h) { return (int)((h >> 17) % 257u) - 128; }
-
-__device__ __forceinline__ int fleet_distance(int gx, int gy, int x, int y) {
-  const int64_t dx = gx - x, dy = gy - y;
-  return (int)nav_isqrt(dx * dx + dy * dy);
-}
-
-// FleetEnvRef._new_world on the zeroed LDS copy, by one thread: 1 + n_obs + 2 R + n_peds draws, every slot in a cell of its own
+// FleetEnvRef._new_world on the zeroed LDS copy, by one thread: 1 + n_obs + 2 R + n_peds draws -- the cells, the obstacles, every robot
+// and its goal, the pedestrians -- every slot in a cell of its own
 __device__ void fleet_new_world(int* s, int R, int n_obs, int n_peds, uint32_t seed, uint32_t gworld) {
-  uint32_t h = fleet_draw(s, seed, gworld);
-  const uint32_t m = h % 20u;
-  const int a = (int)(1u + m + m / 4u);  // the m-th of 1..24 that is no multiple of 5
-  const int b = (int)((h >> 8) % 25u);
-  int slot = 0;
-  auto next_cell = [&]() { return (a * slot++ + b) % FL_CELLS; };
-  for (int k = 0; k < n_obs; ++k) {
-    h = fleet_draw(s, seed, gworld);
-    const int cell = next_cell();
-    s[FL_OBS0 + 3 * k] = fleet_cell_x(cell) + fleet_jitter_x(h);
-    s[FL_OBS0 + 3 * k + 1] = fleet_cell_y(cell) + fleet_jitter_y(h);
-    s[FL_OBS0 + 3 * k + 2] = NAV_OBS_R_MIN + (int)(h % 52u);
-  }
+  NavCells cells = nav_cells(nav_draw(s + FL_EVENTS, seed, gworld));
+  nav_place_obstacles(s + FL_OBS0, n_obs, &cells, s + FL_EVENTS, seed, gworld);
   for (int r = 0; r < R; ++r) {
-    int* p = s + FL_ROBOT_INTS * r;
-    h = fleet_draw(s, seed, gworld);
-    int cell = next_cell();
-    p[NS_X] = fleet_cell_x(cell);
-    p[NS_Y] = fleet_cell_y(cell);
-    p[NS_H] = (int)(h % (uint32_t)NAV_HEADINGS);
-    h = fleet_draw(s, seed, gworld);
-    cell = next_cell();
-    p[NS_GX] = fleet_cell_x(cell) + fleet_jitter_x(h);
-    p[NS_GY] = fleet_cell_y(cell) + fleet_jitter_y(h);
-    p[NS_V] = p[NS_W] = p[NS_STEPS] = 0;
-    p[NS_DPREV] = fleet_distance(p[NS_GX], p[NS_GY], p[NS_X], p[NS_Y]);
+    nav_place_robot(s + FL_ROBOT_INTS * r, &cells, s + FL_EVENTS, seed, gworld);
+    nav_begin_episode(s + FL_ROBOT_INTS * r);
   }
-  for (int j = 0; j < n_peds; ++j) {
-    h = fleet_draw(s, seed, gworld);
-    const int cell = next_cell();
-    s[FL_PED0 + 4 * j] = fleet_cell_x(cell);
-    s[FL_PED0 + 4 * j + 1] = fleet_cell_y(cell);
-    s[FL_PED0 + 4 * j + 2] = (int)(h % (uint32_t)NAV_HEADINGS);
-    s[FL_PED0 + 4 * j + 3] = NAV_SPEED_MIN + (int)((h >> 12) % 17u);
-  }
+  nav_place_peds(s + FL_PED0, n_peds, &cells, s + FL_EVENTS, seed, gworld);
 }
 
 // Steps 1 to 5 of FleetEnvRef.step on the LDS copy, by one thread: the pedestrians, every robot's move, then every robot's outcome from
@@ -102,67 +61,33 @@ __device__ void fleet_new_world(int* s, int R, int n_obs, int n_peds, uint32_t s
 template <bool FINAL>
 __device__ int fleet_play(int* s, int* units, int R, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t gworld,
                           const float* __restrict__ act, float* __restrict__ reward, uint8_t* __restrict__ done, int32_t* __restrict__ info) {
-  for (int j = 0; j < n_peds; ++j) {
-    int* p = s + FL_PED0 + 4 * j;
-    const int cx = p[0] + ((p[3] * nav_cos(p[2])) >> NAV_Q), cy = p[1] + ((p[3] * nav_sin(p[2])) >> NAV_Q);
-    bool refused = cx * cx + cy * cy > (NAV_ARENA_R - NAV_PED_R) * (NAV_ARENA_R - NAV_PED_R);
-    for (int k = 0; k < n_obs; ++k) {
-      const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1], rr = NAV_PED_R + s[FL_OBS0 + 3 * k + 2];
-      refused = refused || dx * dx + dy * dy < rr * rr;
-    }
-    if (refused) {
-      p[2] = (int)(fleet_draw(s, seed, gworld) % (uint32_t)NAV_HEADINGS);
-    } else {
-      p[0] = cx;
-      p[1] = cy;
-    }
-  }
+  nav_walk_peds(s + FL_OBS0, s + FL_PED0, s + FL_EVENTS, n_obs, n_peds, seed, gworld);
   for (int r = 0; r < R; ++r) {
-    int* p = s + FL_ROBOT_INTS * r;
     int v, w;
     nav_decode(act[2 * r], act[2 * r + 1], &v, &w);
-    const int h = nav_heading(p[NS_H] + w);
-    p[NS_X] += (v * nav_cos(h)) >> NAV_Q;
-    p[NS_Y] += (v * nav_sin(h)) >> NAV_Q;
-    p[NS_H] = h;
-    p[NS_V] = v;
-    p[NS_W] = w;
-    p[NS_STEPS] = (int)((uint32_t)p[NS_STEPS] + 1u);
-    const int d = fleet_distance(p[NS_GX], p[NS_GY], p[NS_X], p[NS_Y]);
-    units[r] = 2 * (p[NS_DPREV] - d);
-    p[NS_DPREV] = d;
+    units[r] = nav_move_robot(s + FL_ROBOT_INTS * r, v, w);
   }
   int fin = 0;
   for (int r = 0; r < R; ++r) {
     const int* p = s + FL_ROBOT_INTS * r;
     const int x = p[NS_X], y = p[NS_Y];
-    const bool wall = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
-    bool hit_o = false, hit_p = false, hit_r = false, close = false;
-    for (int k = 0; k < n_obs; ++k) {
-      const int dx = x - s[FL_OBS0 + 3 * k], dy = y - s[FL_OBS0 + 3 * k + 1], rr = NAV_ROBOT_R + s[FL_OBS0 + 3 * k + 2];
-      hit_o = hit_o || dx * dx + dy * dy < rr * rr;
-    }
-    for (int j = 0; j < n_peds; ++j) {
-      const int dx = x - s[FL_PED0 + 4 * j], dy = y - s[FL_PED0 + 4 * j + 1], dd = dx * dx + dy * dy;
-      hit_p = hit_p || dd < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
-      close = close || dd <= NAV_CLOSE * NAV_CLOSE;
-    }
+    NavHits hit;
+    nav_hits(x, y, s + FL_OBS0, s + FL_PED0, n_obs, n_peds, &hit);
+    bool hit_r = false;  // what the fleet adds: another robot
     for (int q = 0; q < R; ++q) {
       const int dx = x - s[FL_ROBOT_INTS * q + NS_X], dy = y - s[FL_ROBOT_INTS * q + NS_Y];
       hit_r = hit_r || (q != r && dx * dx + dy * dy < 4 * NAV_ROBOT_R * NAV_ROBOT_R);
     }
-    const bool collision = wall || hit_o || hit_p || hit_r;
+    // this env's spelling of rules 4 to 6 (navcore.h says why the decision is not shared)
+    const bool collision = hit.wall || hit.obstacle || hit.ped || hit_r;
     const bool goal = !collision && p[NS_DPREV] <= NAV_GOAL_TOL;
     const bool trunc = !collision && !goal && p[NS_STEPS] >= max_steps;
     const bool fini = collision || goal || trunc;
     const int u = units[r] - (collision ? NAV_BONUS : 0) + (goal ? NAV_BONUS : 0);
     reward[r] = (float)u * 0.00390625f;
     done[r] = fini ? 1 : 0;
-    if (info != nullptr) {
-      const int kind = (wall || hit_o) ? 1 : (hit_p ? 2 : (hit_r ? 3 : 0));  // static wins, then the pedestrian
-      info[r] = (fini ? NI_DONE : 0) | (goal ? NI_GOAL : 0) | (kind << NI_KIND_SHIFT) | (trunc ? NI_TRUNC : 0) | (close ? NI_CLOSE : 0) |
-                (wall ? NI_WALL : 0) | (hit_o ? NI_OBSTACLE : 0) | (p[NS_V] << NI_V_SHIFT) | ((p[NS_W] + NAV_W_MAX) << NI_W_SHIFT);
-    }
+    if (info != nullptr)
+      info[r] = nav_info_word(fini, goal, nav_hit_kind(hit, hit_r), trunc, hit.close, hit.wall, hit.obstacle, p[NS_V], p[NS_W]);
     fin |= (fini ? 1 : 0) << r;
     if (FINAL) fin |= (trunc ? 1 : 0) << (FL_MAX_ROBOTS + r);
   }
@@ -189,15 +114,15 @@ __device__ __forceinline__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBO
     px[q] = s[FL_ROBOT_INTS * q + NS_X];
     py[q] = s[FL_ROBOT_INTS * q + NS_Y];
   }
-  const bool scans = lane < FL_CELLS;
+  const bool scans = lane < NAV_CELLS;
 #pragma unroll
   for (int r = 0; r < FL_MAX_ROBOTS; ++r) {
     if (r >= R || !((fin >> r) & 1)) continue;  // uniform over the wave
     // the start: the first cell that is clear of every obstacle centre, every pedestrian and every other robot
     const uint32_t h1 = nav_hash(seed, gworld, counter++);
-    int c0 = (int)(h1 % (uint32_t)FL_CELLS);
-    int cell = (c0 + lane) % FL_CELLS;
-    int cx = fleet_cell_x(cell), cy = fleet_cell_y(cell);
+    int c0 = (int)(h1 % (uint32_t)NAV_CELLS);
+    int cell = (c0 + lane) % NAV_CELLS;
+    int cx = nav_cell_x(cell), cy = nav_cell_y(cell);
     bool ok = scans;
     for (int k = 0; k < n_obs; ++k) {
       const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1];
@@ -212,24 +137,24 @@ __device__ __forceinline__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBO
       const int dx = cx - px[q], dy = cy - py[q];
       ok = ok && (q == r || q >= R || dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR);
     }
-    const int start = (c0 + fleet_first(ok)) % FL_CELLS;
-    const int sx = fleet_cell_x(start), sy = fleet_cell_y(start);
+    const int start = (c0 + fleet_first(ok)) % NAV_CELLS;
+    const int sx = nav_cell_x(start), sy = nav_cell_y(start);
     px[r] = sx;
     py[r] = sy;
     // the goal: the first cell other than the start's whose jittered goal is clear of every obstacle centre
     const uint32_t h2 = nav_hash(seed, gworld, counter++);
-    const int jx = fleet_jitter_x(h2), jy = fleet_jitter_y(h2);
-    c0 = (int)(h2 % (uint32_t)FL_CELLS);
-    cell = (c0 + lane) % FL_CELLS;
-    cx = fleet_cell_x(cell) + jx;
-    cy = fleet_cell_y(cell) + jy;
+    const int jx = nav_jitter_x(h2), jy = nav_jitter_y(h2);
+    c0 = (int)(h2 % (uint32_t)NAV_CELLS);
+    cell = (c0 + lane) % NAV_CELLS;
+    cx = nav_cell_x(cell) + jx;
+    cy = nav_cell_y(cell) + jy;
     ok = scans && cell != start;
     for (int k = 0; k < n_obs; ++k) {
       const int dx = cx - s[FL_OBS0 + 3 * k], dy = cy - s[FL_OBS0 + 3 * k + 1];
       ok = ok && dx * dx + dy * dy >= FL_CLEAR * FL_CLEAR;
     }
-    const int gcell = (c0 + fleet_first(ok)) % FL_CELLS;
-    const int gx = fleet_cell_x(gcell) + jx, gy = fleet_cell_y(gcell) + jy;
+    const int gcell = (c0 + fleet_first(ok)) % NAV_CELLS;
+    const int gx = nav_cell_x(gcell) + jx, gy = nav_cell_y(gcell) + jy;
     if (lane == 0) {
       int* f = fresh[r];
       f[NS_X] = sx;
@@ -238,7 +163,7 @@ __device__ __forceinline__ void fleet_respawn(const int* s, int (*fresh)[FL_ROBO
       f[NS_V] = f[NS_W] = f[NS_STEPS] = 0;
       f[NS_GX] = gx;
       f[NS_GY] = gy;
-      f[NS_DPREV] = fleet_distance(gx, gy, sx, sy);
+      f[NS_DPREV] = nav_distance(gx, gy, sx, sy);
     }
   }
   if (lane == 0) *events = (int)counter;
@@ -250,75 +175,18 @@ __device__ __forceinline__ void fleet_store_state(const int* s, int32_t* __restr
   if (tid < FL_STATE_INTS / 4) reinterpret_cast<int4*>(st)[tid] = make_int4(s[4 * tid], s[4 * tid + 1], s[4 * tid + 2], s[4 * tid + 3]);
 }
 
-// The 256 threads of robot r render row r of the world's observation from the LDS copy `s`.  `disc` is LDS scratch [R][FL_DISCS][4]: what
-// robot r's map holds in its frame, in the order that wins -- the pedestrians, then the other robots, by index.  Called by every thread
-// of the workgroup, behind a barrier after which nobody writes `s` or reads `disc`; holds one barrier of its own.
+// The 256 threads of robot r render row r of the world's observation from the LDS copy `s`: navcore.h's row render, the other R - 1
+// robots in sight.  `disc` is LDS scratch [R][FL_DISCS][4], a robot's map discs each.  Called by every thread of the workgroup, behind a
+// barrier after which nobody writes `s` or reads `disc`; holds one barrier of its own.
 // MASKED: only the robots of the mask `rows` render (uniform over a robot's four waves; every thread still meets the barrier), the
 // rows of the others are not written.
 template <bool MASKED>
 __device__ __forceinline__ void fleet_render(const int* s, int (*disc)[FL_DISCS][4], int R, int n_obs, int n_peds, int rows,
                                              float* __restrict__ laser, float* __restrict__ vector, float* __restrict__ image) {
   const int tid = threadIdx.x, r = tid / NAV_THREADS, t = tid - r * NAV_THREADS;
-  const bool mine = !MASKED || ((rows >> r) & 1);
-  const int* me = s + FL_ROBOT_INTS * r;
-  const int x = me[NS_X], y = me[NS_Y], h = me[NS_H];
-  const int c = nav_cos(h), sn = nav_sin(h);
-  const int n_discs = n_peds + R - 1;
-  if (mine && t < n_discs) {  // disc t in the robot's frame: position, velocity in ticks / step
-    int ax, ay, ah, av;
-    if (t < n_peds) {
-      const int* p = s + FL_PED0 + 4 * t;
-      ax = p[0], ay = p[1], ah = p[2], av = p[3];
-    } else {
-      const int o = t - n_peds, q = o < r ? o : o + 1;  // the o-th robot other than r
-      const int* p = s + FL_ROBOT_INTS * q;
-      ax = p[NS_X], ay = p[NS_Y], ah = p[NS_H], av = p[NS_V];
-    }
-    const int qx = ax - x, qy = ay - y, rel = nav_heading(ah - h);
-    disc[r][t][0] = (qx * c + qy * sn) >> NAV_Q;
-    disc[r][t][1] = (-qx * sn + qy * c) >> NAV_Q;
-    disc[r][t][2] = (av * nav_cos(rel)) >> NAV_Q;
-    disc[r][t][3] = (av * nav_sin(rel)) >> NAV_Q;
-  }
-  __syncthreads();
-  if (!mine) return;
-  laser += (int64_t)r * NAV_BEAMS;
-  vector += (int64_t)r * NAV_VECTOR;
-  image += (int64_t)r * NAV_MAP_FLOATS;
-  // laser: beams 4 t .. 4 t + 3 over the wall, the obstacles, the pedestrians and the other robots
-  if (t < NAV_BEAMS / 4) {
-    int dx[4], dy[4], rng[4];
-    nav_beams(x, y, h, t, dx, dy, rng);
-    for (int k = 0; k < n_obs; ++k) nav_cast(s[FL_OBS0 + 3 * k] - x, s[FL_OBS0 + 3 * k + 1] - y, s[FL_OBS0 + 3 * k + 2], dx, dy, rng);
-    for (int j = 0; j < n_peds; ++j) nav_cast(s[FL_PED0 + 4 * j] - x, s[FL_PED0 + 4 * j + 1] - y, NAV_PED_R, dx, dy, rng);
-    for (int q = 0; q < R; ++q)
-      if (q != r) nav_cast(s[FL_ROBOT_INTS * q + NS_X] - x, s[FL_ROBOT_INTS * q + NS_Y] - y, NAV_ROBOT_R, dx, dy, rng);
-    nav_store_ranges(rng, reinterpret_cast<float4*>(laser) + t);
-  } else if (t == NAV_THREADS - 1) {  // vector: goal in the robot's frame, the last action, the distance
-    const int gx = me[NS_GX] - x, gy = me[NS_GY] - y;
-    vector[0] = (float)((gx * c + gy * sn) >> NAV_Q) * 0.00390625f;
-    vector[1] = (float)((-gx * sn + gy * c) >> NAV_Q) * 0.00390625f;
-    vector[2] = (float)me[NS_V] * 0.03125f;
-    vector[3] = (float)me[NS_W] * 0.015625f;
-    vector[4] = (float)me[NS_DPREV] * 0.00390625f;
-  }
-  // map: chunk = 4 consecutive cells of one row of one channel; the first disc of the winning order that covers a cell wins
-  for (int ck = t; ck < NAV_MAP_CHUNKS; ck += NAV_THREADS) {
-    const int ch = ck / (NAV_MAP * NAV_MAP / 4), rem = ck - ch * (NAV_MAP * NAV_MAP / 4);
-    const int row = rem / (NAV_MAP / 4), col0 = (rem - row * (NAV_MAP / 4)) * 4;
-    const int fwd = (NAV_MAP / 2 - row) * NAV_MAP_CELL - NAV_MAP_CELL / 2;
-    float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int j = n_discs - 1; j >= 0; --j) {
-      const int df = fwd - disc[r][j][0], rr = j < n_peds ? NAV_PED_R * NAV_PED_R : NAV_ROBOT_R * NAV_ROBOT_R;
-      const float pv = ch == 0 ? 1.0f : (float)disc[r][j][ch + 1] * 0.03125f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int dl = (NAV_MAP / 2 - (col0 + q)) * NAV_MAP_CELL - NAV_MAP_CELL / 2 - disc[r][j][1];
-        if (df * df + dl * dl <= rr) val[q] = pv;
-      }
-    }
-    reinterpret_cast<float4*>(image)[ck] = make_float4(val[0], val[1], val[2], val[3]);
-  }
+  nav_render_row<true>(s + FL_ROBOT_INTS * r, s + FL_OBS0, s + FL_PED0, s, FL_ROBOT_INTS, R, r, disc[r], n_obs, n_peds, t,
+                       !MASKED || ((rows >> r) & 1), laser + (int64_t)r * NAV_BEAMS, vector + (int64_t)r * NAV_VECTOR,
+                       image + (int64_t)r * NAV_MAP_FLOATS);
 }
 
 // FINAL: the instantiation behind ddrl_op_fleet_env_step_final -- between barrier 2 and the respawn the 256
@@ -405,14 +273,10 @@ int32_t ddrl_op_fleet_env_state_ints(void) { return FL_STATE_INTS; }
 
 int32_t ddrl_op_fleet_env_reset(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
                                 int32_t n_peds, const uint8_t* mask, float* laser, float* vector, float* image, void* stream) {
-  if (!state || !laser || !vector || !image || !fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds)) return DDRL_ERR_INVALID_ARG;
-  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3)) return DDRL_ERR_INVALID_ARG;
-  const uint64_t rows = (uint64_t)n_worlds * n_robots;
-  const void* src[1] = {mask};
-  const uint64_t src_b[1] = {(uint64_t)n_worlds};
-  void* dst[4] = {state, laser, vector, image};
-  const uint64_t dst_b[4] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4};
-  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 4)) return DDRL_ERR_INVALID_ARG;
+  if (!fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds) ||
+      !nav_reset_args_ok(state, (uint64_t)n_worlds * FL_STATE_INTS * 4, (uint64_t)n_worlds * n_robots, mask, (uint64_t)n_worlds, laser,
+                         vector, image))
+    return DDRL_ERR_INVALID_ARG;
   hipLaunchKernelGGL(fleet_env_reset_kernel, dim3((unsigned)n_worlds), dim3(NAV_THREADS * n_robots), 0, (hipStream_t)stream, state,
                      n_robots, world0, seed, n_obstacles, n_peds, mask, laser, vector, image);
   return launch_status();
@@ -422,28 +286,14 @@ int32_t ddrl_op_fleet_env_reset(int32_t* state, int32_t n_worlds, int32_t n_robo
 static int32_t fleet_env_step_launch(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
                                      int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
                                      float* reward, uint8_t* done, int32_t* info, float* const* final_obs, void* stream) {
-  if (!state || !actions || !laser || !vector || !image || !reward || !done ||
-      !fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds))
+  if (!fleet_range_ok(n_worlds, n_robots, world0, n_obstacles, n_peds) || max_steps < 1 ||
+      !nav_step_args_ok(state, (uint64_t)n_worlds * FL_STATE_INTS * 4, (uint64_t)n_worlds * n_robots, actions, laser, vector, image, reward,
+                        done, info, final_obs != nullptr, final_obs))
     return DDRL_ERR_INVALID_ARG;
-  if (max_steps < 1) return DDRL_ERR_INVALID_ARG;
-  if (!aligned16(state) || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3) || ((uintptr_t)actions & 3) ||
-      ((uintptr_t)reward & 3) || ((uintptr_t)info & 3))
-    return DDRL_ERR_INVALID_ARG;
-  float* fl = final_obs ? final_obs[0] : nullptr;
-  float* fv = final_obs ? final_obs[1] : nullptr;
-  float* fi = final_obs ? final_obs[2] : nullptr;
-  if (final_obs && (!info || !fl || !fv || !fi || !aligned16(fl) || !aligned16(fi) || ((uintptr_t)fv & 3))) return DDRL_ERR_INVALID_ARG;
-  const uint64_t rows = (uint64_t)n_worlds * n_robots;
-  const void* src[1] = {actions};
-  const uint64_t src_b[1] = {rows * 8};
-  void* dst[10] = {state, laser, vector, image, reward, done, info, fl, fv, fi};
-  const uint64_t dst_b[10] = {(uint64_t)n_worlds * FL_STATE_INTS * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4,
-                              rows * 4, rows, rows * 4, rows * NAV_BEAMS * 4, rows * NAV_VECTOR * 4, rows * NAV_MAP_FLOATS * 4};
-  if (!reads_and_writes_apart(src, src_b, 1, dst, dst_b, 10)) return DDRL_ERR_INVALID_ARG;
   const dim3 grid((unsigned)n_worlds), block(NAV_THREADS * n_robots);
   if (final_obs)
     hipLaunchKernelGGL(fleet_env_step_kernel<true>, grid, block, 0, (hipStream_t)stream, state, n_robots, world0, seed, n_obstacles, n_peds,
-                       max_steps, actions, laser, vector, image, reward, done, info, fl, fv, fi);
+                       max_steps, actions, laser, vector, image, reward, done, info, final_obs[0], final_obs[1], final_obs[2]);
   else
     hipLaunchKernelGGL(fleet_env_step_kernel<false>, grid, block, 0, (hipStream_t)stream, state, n_robots, world0, seed, n_obstacles,
                        n_peds, max_steps, actions, laser, vector, image, reward, done, info, (float*)nullptr, (float*)nullptr,

@@ -1,6 +1,15 @@
-// What the navigation env (navenv.hip) and the multi-robot one (fleetenv.hip, section 6.11) share: the sizes of
-// the rule books (tests/nav_env_ref.py), the Q14 trig table, the counter-based hash, the exact integer square root, the ranges of a loaded
-// state word, the action decoding, the info word's layout and the cast of four beams on a circle.  Integer arithmetic only.
+// The arena core of the navigation env (navenv.hip) and the multi-robot one (fleetenv.hip, section 6.11): the sizes
+// of the rule books (tests/nav_env_ref.py, tests/fleet_env_ref.py), the Q14 trig table, the counter-based hash, the exact integer square
+// root, the ranges of a loaded state word, the action decoding -- and every rule and every piece of the render the two envs share
+// (section 6.13), written against pointers to an arena's parts, not against one state layout:
+//   a robot block   words NS_X .. NS_STEPS of one robot (both layouts lay a robot out this way)
+//   obs             3 words an obstacle: x, y, radius
+//   peds            4 words a pedestrian: x, y, heading, speed
+//   events          the counter of the draws
+// The draw, the pedestrian walk (rule 1), the robot's move (rules 2 and 3), the outcome tests, the info word, the placement of an
+// episode and the render of one row, then the argument checks of the host entry points.  The units / done decision (rules 4 to 6) is
+// the one piece each env keeps for itself.  Integer
+// arithmetic only; every device function is __forceinline__ (section 6.12 has the price of one that was not).
 #pragma once
 #include "rows.h"
 
@@ -85,6 +94,55 @@ __device__ __forceinline__ void nav_decode(float a0, float a1, int* v, int* w) {
   *w = (int)truncf(a1 * 64.0f);
 }
 
+// ---- the rules of a step --------------------------------------------------------------------------------------------------------------
+// one draw of the arena's counter-based stream: the hash of (seed, global index, events), and the counter goes up
+__device__ __forceinline__ uint32_t nav_draw(int* events, uint32_t seed, uint32_t gidx) {
+  const uint32_t h = nav_hash(seed, gidx, (uint32_t)*events);
+  *events = (int)((uint32_t)*events + 1u);
+  return h;
+}
+
+__device__ __forceinline__ int nav_distance(int gx, int gy, int x, int y) {
+  const int64_t dx = gx - x, dy = gy - y;
+  return (int)nav_isqrt(dx * dx + dy * dy);
+}
+
+// rule 1: the pedestrians walk in index order; one whose step would leave the arena or enter an obstacle draws a new heading instead
+__device__ __forceinline__ void nav_walk_peds(const int* obs, int* peds, int* events, int n_obs, int n_peds, uint32_t seed, uint32_t gidx) {
+  for (int j = 0; j < n_peds; ++j) {
+    int* p = peds + 4 * j;
+    const int cx = p[0] + ((p[3] * nav_cos(p[2])) >> NAV_Q), cy = p[1] + ((p[3] * nav_sin(p[2])) >> NAV_Q);
+    bool refused = cx * cx + cy * cy > (NAV_ARENA_R - NAV_PED_R) * (NAV_ARENA_R - NAV_PED_R);
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - obs[3 * k], dy = cy - obs[3 * k + 1], rr = NAV_PED_R + obs[3 * k + 2];
+      refused = refused || dx * dx + dy * dy < rr * rr;
+    }
+    if (refused) {
+      p[2] = (int)(nav_draw(events, seed, gidx) % (uint32_t)NAV_HEADINGS);
+    } else {
+      p[0] = cx;
+      p[1] = cy;
+    }
+  }
+}
+
+// rules 2 and 3 on the robot block `rb`: the action (v, w) as nav_decode gives it turns and moves it; -> the reward units of its progress
+// towards the goal
+__device__ __forceinline__ int nav_move_robot(int* rb, int v, int w) {
+  const int h = nav_heading(rb[NS_H] + w);
+  const int x = rb[NS_X] + ((v * nav_cos(h)) >> NAV_Q), y = rb[NS_Y] + ((v * nav_sin(h)) >> NAV_Q);
+  rb[NS_X] = x;
+  rb[NS_Y] = y;
+  rb[NS_H] = h;
+  rb[NS_V] = v;
+  rb[NS_W] = w;
+  rb[NS_STEPS] = (int)((uint32_t)rb[NS_STEPS] + 1u);
+  const int d = nav_distance(rb[NS_GX], rb[NS_GY], x, y);
+  const int units = 2 * (rb[NS_DPREV] - d);
+  rb[NS_DPREV] = d;
+  return units;
+}
+
 // The info word of a step (include/ddrl.h; tests/nav_status_ref.py spells it out): what the step just played did, read off the moved
 // robot and pedestrians before a finished robot's new episode is drawn.
 constexpr int NAV_CLOSE = 512;  // "close to a pedestrian": centres within 2 m
@@ -92,6 +150,107 @@ enum {
   NI_DONE = 1 << 0, NI_GOAL = 1 << 1, NI_KIND_SHIFT = 2, NI_TRUNC = 1 << 4, NI_CLOSE = 1 << 5, NI_WALL = 1 << 6, NI_OBSTACLE = 1 << 7,
   NI_V_SHIFT = 8, NI_W_SHIFT = 16
 };
+
+// what a robot at (x, y) touches: one flag per cause (the info word names them) and `close`; every product fits 32 bits.  The flags are
+// gathered in locals and handed out through `hit`: returned by value the four bools are packed and unpacked, which costs the nav kernels
+// 3 to 9 instructions and changes the fleet kernels' register allocation.
+struct NavHits {
+  bool wall, obstacle, ped, close;
+};
+__device__ __forceinline__ void nav_hits(int x, int y, const int* obs, const int* peds, int n_obs, int n_peds, NavHits* hit) {
+  const bool wall = x * x + y * y > (NAV_ARENA_R - NAV_ROBOT_R) * (NAV_ARENA_R - NAV_ROBOT_R);
+  bool hit_o = false, hit_p = false, close = false;
+  for (int k = 0; k < n_obs; ++k) {
+    const int dx = x - obs[3 * k], dy = y - obs[3 * k + 1], rr = NAV_ROBOT_R + obs[3 * k + 2];
+    hit_o = hit_o || dx * dx + dy * dy < rr * rr;
+  }
+  for (int j = 0; j < n_peds; ++j) {
+    const int dx = x - peds[4 * j], dy = y - peds[4 * j + 1], dd = dx * dx + dy * dy;
+    hit_p = hit_p || dd < (NAV_ROBOT_R + NAV_PED_R) * (NAV_ROBOT_R + NAV_PED_R);
+    close = close || dd <= NAV_CLOSE * NAV_CLOSE;
+  }
+  hit->wall = wall;
+  hit->obstacle = hit_o;
+  hit->ped = hit_p;
+  hit->close = close;
+}
+
+// the collision kind of the info word: static wins, then the pedestrian, then (the fleet's) another robot
+__device__ __forceinline__ int nav_hit_kind(const NavHits& hit, bool other_robot) {
+  return (hit.wall || hit.obstacle) ? 1 : (hit.ped ? 2 : (other_robot ? 3 : 0));
+}
+
+// Rules 4 to 6 -- the collision costs the bonus, else the goal earns it, else max_steps truncates -- are NOT here: nav_advance
+// (navenv.hip) keeps them as an if-chain and fleet_play (fleetenv.hip) as four expressions, as before.  One shared spelling of either
+// form made the kernels of the other env slower than the parent's, so this piece stays unshared.
+
+// the one place the NI_* fields are combined
+__device__ __forceinline__ int nav_info_word(bool fini, bool goal, int kind, bool trunc, bool close, bool wall, bool obstacle, int v, int w) {
+  return (fini ? NI_DONE : 0) | (goal ? NI_GOAL : 0) | (kind << NI_KIND_SHIFT) | (trunc ? NI_TRUNC : 0) | (close ? NI_CLOSE : 0) |
+         (wall ? NI_WALL : 0) | (obstacle ? NI_OBSTACLE : 0) | (v << NI_V_SHIFT) | ((w + NAV_W_MAX) << NI_W_SHIFT);
+}
+
+// ---- the placement of an episode ---------------------------------------------------------------------------------------------------------
+// The 5 x 5 grid of cells an episode is laid out on.  Slot k of a new world stands in cell (a k + b) % 25 with a no multiple of 5, so
+// every slot has a cell of its own.
+constexpr int NAV_GRID = 5, NAV_CELLS = NAV_GRID * NAV_GRID;
+struct NavCells {
+  int a, b, slot;
+};
+__device__ __forceinline__ NavCells nav_cells(uint32_t h) {
+  const uint32_t m = h % 20u;
+  return {(int)(1u + m + m / 4u), (int)((h >> 8) % 25u), 0};  // a: the m-th of 1..24 that is no multiple of 5
+}
+__device__ __forceinline__ int nav_next_cell(NavCells* c) { return (c->a * c->slot++ + c->b) % NAV_CELLS; }
+
+__device__ __forceinline__ int nav_cell_x(int cell) { return (cell % NAV_GRID - 2) * NAV_CELL; }
+__device__ __forceinline__ int nav_cell_y(int cell) { return (cell / NAV_GRID - 2) * NAV_CELL; }
+__device__ __forceinline__ int nav_jitter_x(uint32_t h) { return (int)((h >> 8) % 257u) - 128; }
+__device__ __forceinline__ int nav_jitter_y(uint32_t h) { return (int)((h >> 17) % 257u) - 128; }
+
+// n_obs obstacles, a draw and a cell each: jittered off the cell's centre, radius 77..128
+__device__ __forceinline__ void nav_place_obstacles(int* obs, int n_obs, NavCells* cells, int* events, uint32_t seed, uint32_t gidx) {
+  for (int k = 0; k < n_obs; ++k) {
+    const uint32_t h = nav_draw(events, seed, gidx);
+    const int cell = nav_next_cell(cells);
+    obs[3 * k] = nav_cell_x(cell) + nav_jitter_x(h);
+    obs[3 * k + 1] = nav_cell_y(cell) + nav_jitter_y(h);
+    obs[3 * k + 2] = NAV_OBS_R_MIN + (int)(h % 52u);
+  }
+}
+
+// the first episode of the robot block `rb` in a new world, two draws and two cells: the start and the heading, then the jittered goal
+__device__ __forceinline__ void nav_place_robot(int* rb, NavCells* cells, int* events, uint32_t seed, uint32_t gidx) {
+  uint32_t h = nav_draw(events, seed, gidx);
+  int cell = nav_next_cell(cells);
+  rb[NS_X] = nav_cell_x(cell);
+  rb[NS_Y] = nav_cell_y(cell);
+  rb[NS_H] = (int)(h % (uint32_t)NAV_HEADINGS);
+  h = nav_draw(events, seed, gidx);
+  cell = nav_next_cell(cells);
+  rb[NS_GX] = nav_cell_x(cell) + nav_jitter_x(h);
+  rb[NS_GY] = nav_cell_y(cell) + nav_jitter_y(h);
+}
+
+// a placed robot stands still at step 0, its distance to the goal taken
+__device__ __forceinline__ void nav_begin_episode(int* rb) {
+  rb[NS_V] = rb[NS_W] = rb[NS_STEPS] = 0;
+  rb[NS_DPREV] = nav_distance(rb[NS_GX], rb[NS_GY], rb[NS_X], rb[NS_Y]);
+}
+
+// n_peds pedestrians, a draw and a cell each: on the cell's centre, any heading, 8..24 ticks a step
+__device__ __forceinline__ void nav_place_peds(int* peds, int n_peds, NavCells* cells, int* events, uint32_t seed, uint32_t gidx) {
+  for (int j = 0; j < n_peds; ++j) {
+    const uint32_t h = nav_draw(events, seed, gidx);
+    const int cell = nav_next_cell(cells);
+    peds[4 * j] = nav_cell_x(cell);
+    peds[4 * j + 1] = nav_cell_y(cell);
+    peds[4 * j + 2] = (int)(h % (uint32_t)NAV_HEADINGS);
+    peds[4 * j + 3] = NAV_SPEED_MIN + (int)((h >> 12) % 17u);
+  }
+}
+
+// ---- the render --------------------------------------------------------------------------------------------------------------------------
 
 // the nearest hit of four beams on the circle at (mx, my) from the robot, radius rad (NavEnvRef.lidar; |d|^2 counts as 2^28)
 __device__ __forceinline__ void nav_cast(int mx, int my, int rad, const int* dx, const int* dy, int* rng) {
@@ -138,10 +297,129 @@ __device__ __forceinline__ void nav_store_ranges(const int* rng, float4* out) {
   *out = o;
 }
 
+// One row of the observation -- laser, vector, map -- as the robot block `me` sees the arena, by the 256 threads t = 0..255 of that row.
+// OTHERS: `me` is block r of the R blocks `robots`, `stride` words apart; the others are cast in the lidar and drawn into the map behind
+// the pedestrians, by index.  Without it there is no other robot and robots, stride, R and r are not looked at.  `disc` is LDS scratch
+// [n_peds + R - 1][4]: what the map holds, in the robot's frame, in the order that wins.  Called by every thread of the workgroup, behind
+// a barrier after which nobody writes the arena or reads `disc`; holds one barrier of its own, which a thread whose row is not `mine`
+// (uniform over the row's four waves) meets too before it leaves with nothing written.
+template <bool OTHERS>
+__device__ __forceinline__ void nav_render_row(const int* me, const int* obs, const int* peds, const int* robots, int stride, int R, int r,
+                                               int (*disc)[4], int n_obs, int n_peds, int t, bool mine, float* __restrict__ laser,
+                                               float* __restrict__ vector, float* __restrict__ image) {
+  const int x = me[NS_X], y = me[NS_Y], h = me[NS_H];
+  const int c = nav_cos(h), sn = nav_sin(h);
+  const int n_discs = OTHERS ? n_peds + R - 1 : n_peds;
+  if (mine && t < n_discs) {  // disc t in the robot's frame: position, velocity in ticks / step
+    int ax, ay, ah, av;
+    if (!OTHERS || t < n_peds) {
+      const int* p = peds + 4 * t;
+      ax = p[0], ay = p[1], ah = p[2], av = p[3];
+    } else {
+      const int o = t - n_peds, q = o < r ? o : o + 1;  // the o-th robot other than r
+      const int* p = robots + stride * q;
+      ax = p[NS_X], ay = p[NS_Y], ah = p[NS_H], av = p[NS_V];
+    }
+    const int qx = ax - x, qy = ay - y, rel = nav_heading(ah - h);
+    disc[t][0] = (qx * c + qy * sn) >> NAV_Q;
+    disc[t][1] = (-qx * sn + qy * c) >> NAV_Q;
+    disc[t][2] = (av * nav_cos(rel)) >> NAV_Q;
+    disc[t][3] = (av * nav_sin(rel)) >> NAV_Q;
+  }
+  __syncthreads();
+  if (!mine) return;
+  // laser: beams 4 t .. 4 t + 3 over the wall, the obstacles, the pedestrians and the other robots
+  if (t < NAV_BEAMS / 4) {
+    int dx[4], dy[4], rng[4];
+    nav_beams(x, y, h, t, dx, dy, rng);
+    for (int k = 0; k < n_obs; ++k) nav_cast(obs[3 * k] - x, obs[3 * k + 1] - y, obs[3 * k + 2], dx, dy, rng);
+    for (int j = 0; j < n_peds; ++j) nav_cast(peds[4 * j] - x, peds[4 * j + 1] - y, NAV_PED_R, dx, dy, rng);
+    if (OTHERS)
+      for (int q = 0; q < R; ++q)
+        if (q != r) nav_cast(robots[stride * q + NS_X] - x, robots[stride * q + NS_Y] - y, NAV_ROBOT_R, dx, dy, rng);
+    nav_store_ranges(rng, reinterpret_cast<float4*>(laser) + t);
+  } else if (t == NAV_THREADS - 1) {  // vector: goal in the robot's frame, the last action, the distance
+    const int gx = me[NS_GX] - x, gy = me[NS_GY] - y;
+    vector[0] = (float)((gx * c + gy * sn) >> NAV_Q) * 0.00390625f;
+    vector[1] = (float)((-gx * sn + gy * c) >> NAV_Q) * 0.00390625f;
+    vector[2] = (float)me[NS_V] * 0.03125f;
+    vector[3] = (float)me[NS_W] * 0.015625f;
+    vector[4] = (float)me[NS_DPREV] * 0.00390625f;
+  }
+  // map: chunk = 4 consecutive cells of one row of one channel; the lowest disc index that covers a cell wins
+  for (int ck = t; ck < NAV_MAP_CHUNKS; ck += NAV_THREADS) {
+    const int ch = ck / (NAV_MAP * NAV_MAP / 4), rem = ck - ch * (NAV_MAP * NAV_MAP / 4);
+    const int row = rem / (NAV_MAP / 4), col0 = (rem - row * (NAV_MAP / 4)) * 4;
+    const int fwd = (NAV_MAP / 2 - row) * NAV_MAP_CELL - NAV_MAP_CELL / 2;
+    float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int j = n_discs - 1; j >= 0; --j) {
+      const int df = fwd - disc[j][0], rr = (OTHERS && j >= n_peds) ? NAV_ROBOT_R * NAV_ROBOT_R : NAV_PED_R * NAV_PED_R;
+      const float pv = ch == 0 ? 1.0f : (float)disc[j][ch + 1] * 0.03125f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int dl = (NAV_MAP / 2 - (col0 + q)) * NAV_MAP_CELL - NAV_MAP_CELL / 2 - disc[j][1];
+        if (df * df + dl * dl <= rr) val[q] = pv;
+      }
+    }
+    reinterpret_cast<float4*>(image)[ck] = make_float4(val[0], val[1], val[2], val[3]);
+  }
+}
+
+// ---- the host's argument checks: all of them ahead of the first HIP call ------------------------------------------------------------------
 // what the operators check of n, env0 and the populations: 1 <= n, global env indices inside 32 bits
 inline bool nav_range_ok(int32_t n, int64_t env0, int32_t n_obs, int32_t n_peds) {
   return n >= 1 && env0 >= 0 && env0 + (int64_t)n <= ((int64_t)1 << 32) && n_obs >= 0 && n_obs <= NAV_MAX_OBS && n_peds >= 0 &&
          n_peds <= NAV_MAX_PEDS;
+}
+
+// what a call writes, for reads_and_writes_apart: the state, an observation triple, the step's scalars, the terminal triple
+struct NavWrites {
+  void* ptr[10];
+  uint64_t bytes[10];
+  int n;
+};
+inline void nav_writes(NavWrites* w, void* p, uint64_t bytes) {
+  w->ptr[w->n] = p;
+  w->bytes[w->n++] = bytes;
+}
+
+// an observation triple of `rows` rows: all three given, laser and image 16-byte aligned, the vector a float's; noted in `w`
+inline bool nav_obs_ok(float* laser, float* vector, float* image, uint64_t rows, NavWrites* w) {
+  if (!laser || !vector || !image || !aligned16(laser) || !aligned16(image) || ((uintptr_t)vector & 3)) return false;
+  nav_writes(w, laser, rows * NAV_BEAMS * 4);
+  nav_writes(w, vector, rows * NAV_VECTOR * 4);
+  nav_writes(w, image, rows * NAV_MAP_FLOATS * 4);
+  return true;
+}
+
+// a reset's pointers: the state of state_bytes, the observation of `rows` rows, the optional mask of mask_bytes; nothing written
+// overlaps anything else
+inline bool nav_reset_args_ok(int32_t* state, uint64_t state_bytes, uint64_t rows, const uint8_t* mask, uint64_t mask_bytes, float* laser,
+                              float* vector, float* image) {
+  NavWrites w = {};
+  if (!state || !aligned16(state)) return false;
+  nav_writes(&w, state, state_bytes);
+  if (!nav_obs_ok(laser, vector, image, rows, &w)) return false;
+  const void* src[1] = {mask};
+  return reads_and_writes_apart(src, &mask_bytes, 1, w.ptr, w.bytes, w.n);
+}
+
+// a step's pointers: a reset's without the mask, then actions [rows][2], reward and done [rows], `info` [rows] (may be null unless
+// info_required) and `final_obs` (null, or a second observation triple)
+inline bool nav_step_args_ok(int32_t* state, uint64_t state_bytes, uint64_t rows, const float* actions, float* laser, float* vector,
+                             float* image, float* reward, uint8_t* done, int32_t* info, bool info_required, float* const* final_obs) {
+  NavWrites w = {};
+  if (!state || !aligned16(state) || !actions || !reward || !done || (info_required && !info)) return false;
+  if (((uintptr_t)actions & 3) || ((uintptr_t)reward & 3) || ((uintptr_t)info & 3)) return false;
+  nav_writes(&w, state, state_bytes);
+  nav_writes(&w, reward, rows * 4);
+  nav_writes(&w, done, rows);
+  nav_writes(&w, info, rows * 4);
+  if (!nav_obs_ok(laser, vector, image, rows, &w)) return false;
+  if (final_obs && !nav_obs_ok(final_obs[0], final_obs[1], final_obs[2], rows, &w)) return false;
+  const void* src[1] = {actions};
+  const uint64_t src_b[1] = {rows * 8};
+  return reads_and_writes_apart(src, src_b, 1, w.ptr, w.bytes, w.n);
 }
 
 }  // namespace ddrl

@@ -1,25 +1,27 @@
-"""What DeviceEnv (env/device_env.py) and DeviceNavEnv (env/device_nav_env.py) share: the checks of n_envs / seed / env0, the state,
-reward and done tensors, and the checkpoint of the state words next to the parameters a subclass names in _PARAMS.  FleetNavEnv
-(env/fleet_nav_env.py), whose state has a row per world and whose outputs have a row per robot, allocates for itself and shares the
-checkpoint."""
+"""What DeviceEnv (env/device_env.py), DeviceNavEnv (env/device_nav_env.py) and FleetNavEnv (env/fleet_nav_env.py) share: the checks of the
+population / seed / first global index, the state, reward and done tensors, and the checkpoint of the state words next to the parameters
+a subclass names in _PARAMS.  A state row may own several output rows (rows_per_state: FleetNavEnv's world and its robots); ``N`` counts
+the output rows, which is what everything downstream of an env works on."""
 import torch
 
 
 class DeviceEnvBase:
     _PARAMS = ()              # the constructor arguments (attributes of the same name) a saved env has to agree on
-    _state_ints = None        # the int32 words of one env's state: a callable of the library
+    _state_ints = None        # the int32 words of one state row: a callable of the library
 
-    def __init__(self, n_envs, device, seed, env0):
-        """After the subclass's own checks: nothing is allocated for a refused argument."""
-        self.N, self.seed, self.env0 = int(n_envs), int(seed), int(env0)
-        if self.N < 1:
-            raise ValueError("n_envs must be at least 1, got %d" % self.N)
+    def __init__(self, n_envs, device, seed, env0, rows_per_state=1):
+        """After the subclass's own checks: nothing is allocated for a refused argument.  n_envs counts the state rows and env0 is the
+        global index of the first (FleetNavEnv: its worlds and world0, which it checks under those names first)."""
+        n, self.seed, self.env0 = int(n_envs), int(seed), int(env0)
+        if n < 1:
+            raise ValueError("n_envs must be at least 1, got %d" % n)
         if not 0 <= self.seed < 2 ** 32:
             raise ValueError("seed must fit 32 bits, got %d" % self.seed)
-        if self.env0 < 0 or self.env0 + self.N > 2 ** 32:
+        if self.env0 < 0 or self.env0 + n > 2 ** 32:
             raise ValueError("global env indices env0 .. env0 + n_envs - 1 must fit 32 bits")
+        self.N = n * int(rows_per_state)
         self.device = dev = torch.device("cuda" if device is None else device)
-        self.state = torch.zeros((self.N, self._state_ints()), dtype=torch.int32, device=dev)
+        self.state = torch.zeros((n, self._state_ints()), dtype=torch.int32, device=dev)
         self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
         self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
 

@@ -13,10 +13,64 @@ from ddrl4nav_amd.env.device_env_base import DeviceEnvBase
 NAV_ENV_NAME = "DeviceNav-v0"
 
 
-class DeviceNavEnv(DeviceEnvBase):
+def truncations_per_rollout(horizon, max_steps):
+    """ceil(horizon / max_steps): an episode lasts max_steps steps at the most, so no env truncates more often in `horizon` steps."""
+    horizon, max_steps = int(horizon), int(max_steps)
+    if horizon < 1 or max_steps < 1:
+        raise ValueError("horizon and max_steps must be at least 1, got %d and %d" % (horizon, max_steps))
+    return -(-horizon // max_steps)
+
+
+class NavArenaEnv(DeviceEnvBase):
+    """What DeviceNavEnv and FleetNavEnv (env/fleet_nav_env.py) share: the arena's populations and max_steps with their checks, the
+    observation, info and terminal-observation tensors (a row per robot), where a call renders to, and the knobs of a config_env."""
+    state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
+
+    def __init__(self, n_states, rows_per_state, device, seed, n_obstacles, n_peds, max_steps, index0, emit_info, emit_final_obs):
+        """After the subclass's own checks.  emit_final_obs implies emit_info."""
+        self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
+        if not 0 <= self.n_obstacles <= 10:
+            raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
+        if not 0 <= self.n_peds <= 5:
+            raise ValueError("n_peds must be in 0..5, got %d" % self.n_peds)
+        if self.max_steps < 1:
+            raise ValueError("max_steps must be at least 1, got %d" % self.max_steps)
+        super().__init__(n_states, device, seed, index0, rows_per_state)
+        self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=self.device) for shape in self.state_shapes]
+        self.emit_final_obs = bool(emit_final_obs)
+        self.emit_info = bool(emit_info) or self.emit_final_obs
+        self.info = torch.zeros(self.N, dtype=torch.int32, device=self.device) if self.emit_info else None
+        self.final_obs = [torch.zeros_like(o) for o in self.obs] if self.emit_final_obs else None
+
+    def _arena_kw(self):
+        return dict(seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds)
+
+    def _obs_out(self, obs_out):
+        return self.obs if obs_out is None else list(obs_out)
+
+    def _final_out(self, final_out):
+        """Where a step renders the terminal observations: the env's own tensors or the caller's; None for an env without them."""
+        if final_out is not None and not self.emit_final_obs:
+            raise ValueError("final_out needs an env built with emit_final_obs=True")
+        return self.final_obs if final_out is None else list(final_out)
+
+    def truncations_per_rollout(self, horizon):
+        """The most truncations one row can have in `horizon` steps, ceil(horizon / max_steps): the pool depth with which a
+        StateRollout(bootstrap_truncated=...) drops none."""
+        return truncations_per_rollout(horizon, self.max_steps)
+
+
+def arena_config_kw(config_env):
+    """The optional knobs of a config_env both nav envs read: env_seed, env_obstacles, env_peds, env_max_steps, env_info (emit_info),
+    env_final_obs (emit_final_obs)."""
+    return dict(seed=int(config_env.get("env_seed", 0)), n_obstacles=int(config_env.get("env_obstacles", 10)),
+                n_peds=int(config_env.get("env_peds", 5)), max_steps=int(config_env.get("env_max_steps", 500)),
+                emit_info=bool(config_env.get("env_info", False)), emit_final_obs=bool(config_env.get("env_final_obs", False)))
+
+
+class DeviceNavEnv(NavArenaEnv):
     _PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
     _state_ints = staticmethod(ops.nav_env_state_ints)
-    state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
     def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False,
                  emit_final_obs=False):
@@ -26,35 +80,13 @@ class DeviceNavEnv(DeviceEnvBase):
         the same either way.  emit_final_obs (implies emit_info): a step that truncates an env's episode also
         renders the observation that episode ended in into row i of ``final_obs`` ([laser, vector, image], [N, ...] each; the rows of
         the other envs keep what they held), for a rollout that bootstraps truncated episodes."""
-        self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
-        if not 0 <= self.n_obstacles <= 10:
-            raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
-        if not 0 <= self.n_peds <= 5:
-            raise ValueError("n_peds must be in 0..5, got %d" % self.n_peds)
-        if self.max_steps < 1:
-            raise ValueError("max_steps must be at least 1, got %d" % self.max_steps)
-        super().__init__(n_envs, device, seed, env0)
-        dev = self.device
-        self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
-        self.emit_final_obs = bool(emit_final_obs)
-        self.emit_info = bool(emit_info) or self.emit_final_obs
-        self.info = torch.zeros(self.N, dtype=torch.int32, device=dev) if self.emit_info else None
-        self.final_obs = [torch.zeros_like(o) for o in self.obs] if self.emit_final_obs else None
-
-    def _obs_out(self, obs_out):
-        return self.obs if obs_out is None else list(obs_out)
+        super().__init__(n_envs, 1, device, seed, n_obstacles, n_peds, max_steps, env0, emit_info, emit_final_obs)
 
     def reset(self, mask=None, obs_out=None):
         """A new first episode for every env, or for those with a non-zero entry in mask (uint8 [N] on the device); returns the
         observation [laser, vector, image] (the env's own tensors, or obs_out: contiguous fp32 device tensors of those shapes, laser and
         image 16-byte aligned -- the rows of a StateRollout's pools are).  A masked-out env's rows are not written."""
-        return ops.nav_env_reset(self.state, self._obs_out(obs_out), env0=self.env0, seed=self.seed, n_obstacles=self.n_obstacles,
-                                 n_peds=self.n_peds, mask=mask)
-
-    def truncations_per_rollout(self, horizon):
-        """The most truncations one env can have in `horizon` steps, ceil(horizon / max_steps): the pool depth with which a
-        StateRollout(bootstrap_truncated=...) drops none."""
-        return truncations_per_rollout(horizon, self.max_steps)
+        return ops.nav_env_reset(self.state, self._obs_out(obs_out), env0=self.env0, mask=mask, **self._arena_kw())
 
     def step(self, actions, obs_out=None, final_out=None):
         """actions fp32 [N, 2] on the device (what a Gaussian actor's act() returns) -> ([laser, vector, image], reward fp32 [N], done
@@ -62,35 +94,20 @@ class DeviceNavEnv(DeviceEnvBase):
         begun its next episode: the observation is that episode's first and done is the reset flag.  With emit_info, ``info`` describes the
         step just played (the finished episode's last, not the new one's first).  With emit_final_obs the truncated envs' rows of
         ``final_obs`` (final_out: of those tensors instead) receive the observation their episode ended in.  Asynchronous."""
-        if final_out is not None and not self.emit_final_obs:
-            raise ValueError("final_out needs an env built with emit_final_obs=True")
+        final = self._final_out(final_out)
+        args = (self.state, actions, self._obs_out(obs_out), self.reward, self.done)
+        kw = dict(env0=self.env0, max_steps=self.max_steps, **self._arena_kw())
         if self.emit_final_obs:
-            return ops.nav_env_step_final(self.state, actions, self._obs_out(obs_out), self.reward, self.done, self.info,
-                                          self.final_obs if final_out is None else list(final_out), env0=self.env0, seed=self.seed,
-                                          n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
+            return ops.nav_env_step_final(*args, self.info, final, **kw)[:3]
         if self.emit_info:
-            return ops.nav_env_step_info(self.state, actions, self._obs_out(obs_out), self.reward, self.done, self.info, env0=self.env0,
-                                         seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)[:3]
-        return ops.nav_env_step(self.state, actions, self._obs_out(obs_out), self.reward, self.done, env0=self.env0, seed=self.seed,
-                                n_obstacles=self.n_obstacles, n_peds=self.n_peds, max_steps=self.max_steps)
-
-
-def truncations_per_rollout(horizon, max_steps):
-    """ceil(horizon / max_steps): an episode lasts max_steps steps at the most, so no env truncates more often in `horizon` steps."""
-    horizon, max_steps = int(horizon), int(max_steps)
-    if horizon < 1 or max_steps < 1:
-        raise ValueError("horizon and max_steps must be at least 1, got %d and %d" % (horizon, max_steps))
-    return -(-horizon // max_steps)
+            return ops.nav_env_step_info(*args, self.info, **kw)[:3]
+        return ops.nav_env_step(*args, **kw)
 
 
 def make_device_nav_env(config_env, device=None, env0=0):
-    """The DeviceNavEnv of a config_env dict: env_name "DeviceNav-v0", env_num, and the optional knobs env_obstacles, env_peds,
-    env_max_steps, env_seed, env_info (emit_info), env_final_obs (emit_final_obs)."""
+    """The DeviceNavEnv of a config_env dict: env_name "DeviceNav-v0", env_num, and the optional knobs of arena_config_kw."""
     if config_env.get("env_name") != NAV_ENV_NAME:
         raise ValueError("env_name must be %r, got %r" % (NAV_ENV_NAME, config_env.get("env_name")))
     if "env_num" not in config_env:
         raise ValueError("config_env needs env_num")
-    return DeviceNavEnv(int(config_env["env_num"]), device=device, seed=int(config_env.get("env_seed", 0)),
-                        n_obstacles=int(config_env.get("env_obstacles", 10)), n_peds=int(config_env.get("env_peds", 5)),
-                        max_steps=int(config_env.get("env_max_steps", 500)), env0=env0, emit_info=bool(config_env.get("env_info", False)),
-                        emit_final_obs=bool(config_env.get("env_final_obs", False)))
+    return DeviceNavEnv(int(config_env["env_num"]), device=device, env0=env0, **arena_config_kw(config_env))

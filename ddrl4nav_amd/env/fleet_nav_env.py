@@ -5,19 +5,15 @@ The reference's agent runs ``agent_num_per_env`` robots in every env, all_num = 
 dynamic-agent map and collide with each other (info collision kind 3, the reference's coll_robot_num).  A ROW is one robot -- row
 i * R + r is robot r of world i -- and everything downstream of the env (StateRollout, GenericPPO, NavStatus, device_loop) works on rows:
 ``N`` is the number of rows.  One launch per step for all worlds; the rules are integer-only (tests/fleet_env_ref.py is the rule book)."""
-import torch
-
 from ddrl4nav_amd import ops
-from ddrl4nav_amd.env.device_env_base import DeviceEnvBase
-from ddrl4nav_amd.env.device_nav_env import truncations_per_rollout
+from ddrl4nav_amd.env.device_nav_env import NavArenaEnv, arena_config_kw
 
 FLEET_ENV_NAME = "DeviceNavFleet-v0"
 
 
-class FleetNavEnv(DeviceEnvBase):
+class FleetNavEnv(NavArenaEnv):
     _PARAMS = ("n_worlds", "n_robots", "seed", "n_obstacles", "n_peds", "max_steps", "world0")
     _state_ints = staticmethod(ops.fleet_env_state_ints)
-    state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
     def __init__(self, n_worlds, n_robots, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, world0=0, emit_info=False,
                  emit_final_obs=False):
@@ -28,50 +24,23 @@ class FleetNavEnv(DeviceEnvBase):
         way.  emit_final_obs (implies emit_info): a step that truncates a robot's episode also renders what that
         robot saw at its end -- every robot where it is after all moves and before any respawn -- into its row of ``final_obs``
         ([laser, vector, image], [N, ...] each; the other rows keep what they held)."""
-        self.n_worlds, self.n_robots, self.seed, self.world0 = int(n_worlds), int(n_robots), int(seed), int(world0)
-        self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
+        self.n_worlds, self.n_robots, self.world0 = int(n_worlds), int(n_robots), int(world0)
         if self.n_worlds < 1:
             raise ValueError("n_worlds must be at least 1, got %d" % self.n_worlds)
+        if self.world0 < 0 or self.world0 + self.n_worlds > 2 ** 32:
+            raise ValueError("global world indices world0 .. world0 + n_worlds - 1 must fit 32 bits")
         if not 1 <= self.n_robots <= ops.FLEET_ENV_MAX_ROBOTS:
             raise ValueError("n_robots must be in 1..%d, got %d" % (ops.FLEET_ENV_MAX_ROBOTS, self.n_robots))
         if self.n_worlds * self.n_robots >= 2 ** 31:
             raise ValueError("n_worlds * n_robots must fit int32")
-        if not 0 <= self.n_obstacles <= 10:
-            raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
-        if not 0 <= self.n_peds <= 5:
-            raise ValueError("n_peds must be in 0..5, got %d" % self.n_peds)
-        if self.max_steps < 1:
-            raise ValueError("max_steps must be at least 1, got %d" % self.max_steps)
-        if not 0 <= self.seed < 2 ** 32:
-            raise ValueError("seed must fit 32 bits, got %d" % self.seed)
-        if self.world0 < 0 or self.world0 + self.n_worlds > 2 ** 32:
-            raise ValueError("global world indices world0 .. world0 + n_worlds - 1 must fit 32 bits")
-        self.N = self.n_worlds * self.n_robots                           # rows: what device_loop compares with a rollout's N
-        self.device = dev = torch.device("cuda" if device is None else device)
-        self.state = torch.zeros((self.n_worlds, self._state_ints()), dtype=torch.int32, device=dev)
-        self.reward = torch.zeros(self.N, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
-        self.obs = [torch.empty((self.N,) + shape, dtype=torch.float32, device=dev) for shape in self.state_shapes]
-        self.emit_final_obs = bool(emit_final_obs)
-        self.emit_info = bool(emit_info) or self.emit_final_obs
-        self.info = torch.zeros(self.N, dtype=torch.int32, device=dev) if self.emit_info else None
-        self.final_obs = [torch.zeros_like(o) for o in self.obs] if self.emit_final_obs else None
-
-    def _obs_out(self, obs_out):
-        return self.obs if obs_out is None else list(obs_out)
-
-    def _world_kw(self):
-        return dict(world0=self.world0, seed=self.seed, n_obstacles=self.n_obstacles, n_peds=self.n_peds)
+        super().__init__(self.n_worlds, self.n_robots, device, seed, n_obstacles, n_peds, max_steps, self.world0, emit_info,
+                         emit_final_obs)                                 # N = the rows: what device_loop compares with a rollout's N
 
     def reset(self, mask=None, obs_out=None):
         """A new world for every world, or for those with a non-zero entry in mask (uint8 [n_worlds] on the device: one byte per WORLD);
         returns the observation [laser, vector, image] of all N rows (the env's own tensors, or obs_out: contiguous fp32 device tensors of
         those shapes, laser and image 16-byte aligned).  The rows of a masked-out world are not written."""
-        return ops.fleet_env_reset(self.state, self.n_robots, self._obs_out(obs_out), mask=mask, **self._world_kw())
-
-    def truncations_per_rollout(self, horizon):
-        """The most truncations one row can have in `horizon` steps, ceil(horizon / max_steps) (DeviceNavEnv.truncations_per_rollout)."""
-        return truncations_per_rollout(horizon, self.max_steps)
+        return ops.fleet_env_reset(self.state, self.n_robots, self._obs_out(obs_out), world0=self.world0, mask=mask, **self._arena_kw())
 
     def step(self, actions, obs_out=None, final_out=None):
         """actions fp32 [N, 2] on the device -> ([laser, vector, image], reward fp32 [N], done uint8 [N]): device tensors the env owns,
@@ -79,26 +48,21 @@ class FleetNavEnv(DeviceEnvBase):
         is that episode's first and done is its reset flag.  With emit_info, ``info`` describes the step just played.  With
         emit_final_obs the truncated rows of ``final_obs`` (final_out: of those tensors instead) receive the observation their episode
         ended in.  Asynchronous."""
-        if final_out is not None and not self.emit_final_obs:
-            raise ValueError("final_out needs an env built with emit_final_obs=True")
+        final = self._final_out(final_out)
+        args = (self.state, self.n_robots, actions, self._obs_out(obs_out), self.reward, self.done, self.info)
+        kw = dict(world0=self.world0, max_steps=self.max_steps, **self._arena_kw())
         if self.emit_final_obs:
-            return ops.fleet_env_step_final(self.state, self.n_robots, actions, self._obs_out(obs_out), self.reward, self.done, self.info,
-                                            self.final_obs if final_out is None else list(final_out), max_steps=self.max_steps,
-                                            **self._world_kw())
-        return ops.fleet_env_step(self.state, self.n_robots, actions, self._obs_out(obs_out), self.reward, self.done, info=self.info,
-                                  max_steps=self.max_steps, **self._world_kw())
+            return ops.fleet_env_step_final(*args, final, **kw)
+        return ops.fleet_env_step(*args, **kw)
 
 
 def make_fleet_nav_env(config_env, device=None, env0=0):
     """The FleetNavEnv of a config_env dict: env_name "DeviceNavFleet-v0", env_num (the worlds), agent_num_per_env (the robots of a
-    world; required), and the optional knobs env_obstacles, env_peds, env_max_steps, env_seed, env_info (emit_info), env_final_obs
-    (emit_final_obs).  env0: world0."""
+    world; required), and the optional knobs of arena_config_kw.  env0: world0."""
     if config_env.get("env_name") != FLEET_ENV_NAME:
         raise ValueError("env_name must be %r, got %r" % (FLEET_ENV_NAME, config_env.get("env_name")))
     for key in ("env_num", "agent_num_per_env"):
         if key not in config_env:
             raise ValueError("config_env needs %s" % key)
-    return FleetNavEnv(int(config_env["env_num"]), int(config_env["agent_num_per_env"]), device=device,
-                       seed=int(config_env.get("env_seed", 0)), n_obstacles=int(config_env.get("env_obstacles", 10)),
-                       n_peds=int(config_env.get("env_peds", 5)), max_steps=int(config_env.get("env_max_steps", 500)), world0=env0,
-                       emit_info=bool(config_env.get("env_info", False)), emit_final_obs=bool(config_env.get("env_final_obs", False)))
+    return FleetNavEnv(int(config_env["env_num"]), int(config_env["agent_num_per_env"]), device=device, world0=env0,
+                       **arena_config_kw(config_env))

@@ -418,41 +418,59 @@ def nav_env_trig():
     return out
 
 
-def _nav_env_args(state, obs):
-    """n of a navigation-env call after the checks both operators share: state int32 [n, nav_env_state_ints()] and the three observation
-    components fp32 [n, 1, 960], [n, 5], [n, 3, 48, 48], contiguous, on one device, laser and image 16-byte aligned."""
+def _arena_args(state, state_ints, rows_per_state, obs, what="obs"):
+    """(n_states, rows) of a navigation-arena call after the checks the nav and the fleet operators share: state int32 [n_states,
+    state_ints] and the three components of `obs` fp32 [rows, 1, 960], [rows, 5], [rows, 3, 48, 48] with rows = n_states *
+    rows_per_state, contiguous, on one device, laser and image 16-byte aligned."""
     assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 \
-        and state.shape[1] == nav_env_state_ints(), "state: contiguous int32 [n, nav_env_state_ints()] on the device"
-    n = state.shape[0]
-    assert len(obs) == 3, "obs: [laser, vector, image]"
+        and state.shape[1] == state_ints, "state: contiguous int32 [n, %d] on the device" % state_ints
+    rows = state.shape[0] * rows_per_state
+    assert len(obs) == 3, "%s: [laser, vector, image]" % what
     for name, t, shape in zip(("laser", "vector", "image"), obs, NAV_ENV_SHAPES):
-        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (n,) + shape \
-            and t.device == state.device, "%s: contiguous fp32 %s on the state's device" % (name, ("n",) + shape)
-    assert obs[0].data_ptr() % 16 == 0 and obs[2].data_ptr() % 16 == 0, "laser / image: the base must be 16-byte aligned"
-    return n
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (rows,) + shape \
+            and t.device == state.device, "%s %s: contiguous fp32 %s on the state's device" % (what, name, ("rows",) + shape)
+    assert obs[0].data_ptr() % 16 == 0 and obs[2].data_ptr() % 16 == 0, "%s laser / image: the base must be 16-byte aligned" % what
+    return state.shape[0], rows
+
+
+def _arena_mask_ok(mask, state):
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == state.shape[0]
+                            and mask.device == state.device), "mask: contiguous uint8 [n], a byte a state row, on the state's device"
+
+
+def _arena_step_ok(state, rows, actions, reward, done):
+    assert tuple(_f32(actions).shape) == (rows, 2) and _f32(reward).numel() == rows and actions.device == state.device \
+        and reward.device == state.device, "actions fp32 [rows, 2], reward fp32 [rows] on the state's device"
+    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == rows \
+        and done.device == state.device, "done: contiguous uint8 [rows] on the state's device"
+
+
+def _arena_info_ok(state, rows, info):
+    assert info is not None and info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (rows,) \
+        and info.device == state.device, "info: contiguous int32 [rows] on the state's device"
+
+
+def _p3(obs):
+    return _p(obs[0]), _p(obs[1]), _p(obs[2])
 
 
 def nav_env_reset(state, obs, env0=0, seed=0, n_obstacles=10, n_peds=5, mask=None):
     """A new first episode for every env of `state`, or for those with a non-zero byte in mask (uint8 [n]), and their first observations
     obs = [laser, vector, image] (include/ddrl.h ddrl_op_nav_env_reset; csrc/navenv.hip).  Asynchronous on the current stream; returns
     obs."""
-    n = _nav_env_args(state, obs)
-    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == n
-                            and mask.device == state.device), "mask: contiguous uint8 [n] on the state's device"
+    n, _ = _arena_args(state, nav_env_state_ints(), 1, obs)
+    _arena_mask_ok(mask, state)
     check(_lib.load().ddrl_op_nav_env_reset(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), _p(mask),
-                                            _p(obs[0]), _p(obs[1]), _p(obs[2]), _st()))
+                                            *_p3(obs), _st()))
     return obs
 
 
 def _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps):
-    """The checks nav_env_step and nav_env_step_info share, and the arguments both C entry points take up to `done`."""
-    n = _nav_env_args(state, obs)
-    assert tuple(_f32(actions).shape) == (n, 2) and _f32(reward).numel() == n and actions.device == state.device \
-        and reward.device == state.device, "actions fp32 [n, 2], reward fp32 [n] on the state's device"
-    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == n \
-        and done.device == state.device, "done: contiguous uint8 [n] on the state's device"
-    return (_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps), _p(actions), _p(obs[0]),
-            _p(obs[1]), _p(obs[2]), _p(reward), _p(done))
+    """The checks the three nav_env_step* share, and the arguments all three C entry points take up to `done`."""
+    n, _ = _arena_args(state, nav_env_state_ints(), 1, obs)
+    _arena_step_ok(state, n, actions, reward, done)
+    return (_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps), _p(actions), *_p3(obs),
+            _p(reward), _p(done))
 
 
 def nav_env_step(state, actions, obs, reward, done, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
@@ -468,21 +486,9 @@ def nav_env_step_info(state, actions, obs, reward, done, info, env0=0, seed=0, n
     did -- done, goal, collision kind, truncation, closeness to a pedestrian, the decoded action (nav_info_fields unpacks it).  The other
     outputs are bit-identical to nav_env_step's.  Asynchronous on the current stream; returns (obs, reward, done, info)."""
     args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
-    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (args[1],) \
-        and info.device == state.device, "info: contiguous int32 [n] on the state's device"
+    _arena_info_ok(state, args[1], info)
     check(_lib.load().ddrl_op_nav_env_step_info(*args, _p(info), _st()))
     return obs, reward, done, info
-
-
-def _nav_final_args(final_obs, obs, rows):
-    """The pointers of the terminal-observation buffers of a *_step_final call: three contiguous fp32 tensors of the observation's
-    shapes on its device, laser and image 16-byte aligned."""
-    assert len(final_obs) == 3, "final_obs: [laser, vector, image]"
-    for name, t, o, shape in zip(("laser", "vector", "image"), final_obs, obs, NAV_ENV_SHAPES):
-        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (rows,) + shape \
-            and t.device == o.device, "final %s: contiguous fp32 %s on the state's device" % (name, ("rows",) + shape)
-    assert final_obs[0].data_ptr() % 16 == 0 and final_obs[2].data_ptr() % 16 == 0, "final laser / image: the base must be 16-byte aligned"
-    return _p(final_obs[0]), _p(final_obs[1]), _p(final_obs[2])
 
 
 def nav_env_step_final(state, actions, obs, reward, done, info, final_obs, env0=0, seed=0, n_obstacles=10, n_peds=5, max_steps=500):
@@ -491,9 +497,9 @@ def nav_env_step_final(state, actions, obs, reward, done, info, final_obs, env0=
     observation of the state the episode ended in; no other row of final_obs is written.  The other outputs are bit-identical to
     nav_env_step_info's.  Asynchronous on the current stream; returns (obs, reward, done, info, final_obs)."""
     args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
-    assert info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (args[1],) \
-        and info.device == state.device, "info: contiguous int32 [n] on the state's device"
-    check(_lib.load().ddrl_op_nav_env_step_final(*args, _p(info), *_nav_final_args(final_obs, obs, args[1]), _st()))
+    _arena_info_ok(state, args[1], info)
+    _arena_args(state, nav_env_state_ints(), 1, final_obs, what="final_obs")
+    check(_lib.load().ddrl_op_nav_env_step_final(*args, _p(info), *_p3(final_obs), _st()))
     return obs, reward, done, info, final_obs
 
 
@@ -557,32 +563,26 @@ def fleet_env_state_ints():
     return int(_lib.load().ddrl_op_fleet_env_state_ints())
 
 
-def _fleet_env_args(state, n_robots, obs):
-    """(n_worlds, rows) of a fleet-env call after the checks both operators share: state int32 [n_worlds, fleet_env_state_ints()] and the
-    three observation components fp32 [rows, 1, 960], [rows, 5], [rows, 3, 48, 48] with rows = n_worlds * n_robots, contiguous, on one
-    device, laser and image 16-byte aligned."""
-    assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 \
-        and state.shape[1] == fleet_env_state_ints(), "state: contiguous int32 [n_worlds, fleet_env_state_ints()] on the device"
-    n_robots = int(n_robots)
-    assert 1 <= n_robots <= FLEET_ENV_MAX_ROBOTS, "n_robots: 1..%d" % FLEET_ENV_MAX_ROBOTS
-    rows = state.shape[0] * n_robots
-    assert len(obs) == 3, "obs: [laser, vector, image]"
-    for name, t, shape in zip(("laser", "vector", "image"), obs, NAV_ENV_SHAPES):
-        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (rows,) + shape \
-            and t.device == state.device, "%s: contiguous fp32 %s on the state's device" % (name, ("n_worlds * n_robots",) + shape)
-    assert obs[0].data_ptr() % 16 == 0 and obs[2].data_ptr() % 16 == 0, "laser / image: the base must be 16-byte aligned"
-    return state.shape[0], rows
+def _fleet_env_step_args(state, n_robots, actions, obs, reward, done, info, info_required, world0, seed, n_obstacles, n_peds, max_steps):
+    """The arguments both fleet C step entry points take up to `info`, after the checks they share."""
+    assert 1 <= int(n_robots) <= FLEET_ENV_MAX_ROBOTS, "n_robots: 1..%d" % FLEET_ENV_MAX_ROBOTS
+    n_worlds, rows = _arena_args(state, fleet_env_state_ints(), int(n_robots), obs)
+    _arena_step_ok(state, rows, actions, reward, done)
+    if info_required or info is not None:
+        _arena_info_ok(state, rows, info)
+    return (_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), int(max_steps),
+            _p(actions), *_p3(obs), _p(reward), _p(done), _p(info))
 
 
 def fleet_env_reset(state, n_robots, obs, world0=0, seed=0, n_obstacles=10, n_peds=5, mask=None):
     """A new world for every world of `state`, or for those with a non-zero byte in mask (uint8 [n_worlds]), and the first observations
     obs = [laser, vector, image] of their rows (include/ddrl.h ddrl_op_fleet_env_reset; csrc/fleetenv.hip).  Asynchronous on the current
     stream; returns obs."""
-    n_worlds, _ = _fleet_env_args(state, n_robots, obs)
-    assert mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() == n_worlds
-                            and mask.device == state.device), "mask: contiguous uint8 [n_worlds] on the state's device"
+    assert 1 <= int(n_robots) <= FLEET_ENV_MAX_ROBOTS, "n_robots: 1..%d" % FLEET_ENV_MAX_ROBOTS
+    n_worlds, _ = _arena_args(state, fleet_env_state_ints(), int(n_robots), obs)
+    _arena_mask_ok(mask, state)
     check(_lib.load().ddrl_op_fleet_env_reset(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF, int(n_obstacles),
-                                              int(n_peds), _p(mask), _p(obs[0]), _p(obs[1]), _p(obs[2]), _st()))
+                                              int(n_peds), _p(mask), *_p3(obs), _st()))
     return obs
 
 
@@ -591,16 +591,8 @@ def fleet_env_step(state, n_robots, actions, obs, reward, done, info=None, world
     obs = [laser, vector, image], reward fp32 [rows], done uint8 [rows] and, when given, info int32 [rows] (nav_info_fields unpacks it;
     collision 3 is another robot); rows = n_worlds * n_robots, row i * n_robots + r is robot r of world i.  Asynchronous on the current
     stream; returns (obs, reward, done)."""
-    n_worlds, rows = _fleet_env_args(state, n_robots, obs)
-    assert tuple(_f32(actions).shape) == (rows, 2) and _f32(reward).numel() == rows and actions.device == state.device \
-        and reward.device == state.device, "actions fp32 [rows, 2], reward fp32 [rows] on the state's device"
-    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == rows \
-        and done.device == state.device, "done: contiguous uint8 [rows] on the state's device"
-    assert info is None or (info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (rows,)
-                            and info.device == state.device), "info: contiguous int32 [rows] on the state's device"
-    check(_lib.load().ddrl_op_fleet_env_step(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF, int(n_obstacles),
-                                             int(n_peds), int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]), _p(obs[2]), _p(reward),
-                                             _p(done), _p(info), _st()))
+    args = _fleet_env_step_args(state, n_robots, actions, obs, reward, done, info, False, world0, seed, n_obstacles, n_peds, max_steps)
+    check(_lib.load().ddrl_op_fleet_env_step(*args, _st()))
     return obs, reward, done
 
 
@@ -610,17 +602,9 @@ def fleet_env_step_final(state, n_robots, actions, obs, reward, done, info, fina
     ddrl_op_fleet_env_step_final): what the robot sees with every robot where it is after all moves of the step
     and before any respawn.  Rows without the truncation bit are not written; the other outputs are bit-identical to fleet_env_step's.
     Asynchronous on the current stream; returns (obs, reward, done)."""
-    n_worlds, rows = _fleet_env_args(state, n_robots, obs)
-    assert tuple(_f32(actions).shape) == (rows, 2) and _f32(reward).numel() == rows and actions.device == state.device \
-        and reward.device == state.device, "actions fp32 [rows, 2], reward fp32 [rows] on the state's device"
-    assert done.dtype == torch.uint8 and done.is_cuda and done.is_contiguous() and done.numel() == rows \
-        and done.device == state.device, "done: contiguous uint8 [rows] on the state's device"
-    assert info is not None and info.dtype == torch.int32 and info.is_cuda and info.is_contiguous() and tuple(info.shape) == (rows,) \
-        and info.device == state.device, "info: contiguous int32 [rows] on the state's device"
-    check(_lib.load().ddrl_op_fleet_env_step_final(_p(state), n_worlds, int(n_robots), int(world0), int(seed) & 0xFFFFFFFF,
-                                                   int(n_obstacles), int(n_peds), int(max_steps), _p(actions), _p(obs[0]), _p(obs[1]),
-                                                   _p(obs[2]), _p(reward), _p(done), _p(info), *_nav_final_args(final_obs, obs, rows),
-                                                   _st()))
+    args = _fleet_env_step_args(state, n_robots, actions, obs, reward, done, info, True, world0, seed, n_obstacles, n_peds, max_steps)
+    _arena_args(state, fleet_env_state_ints(), int(n_robots), final_obs, what="final_obs")
+    check(_lib.load().ddrl_op_fleet_env_step_final(*args, *_p3(final_obs), _st()))
     return obs, reward, done
 
 

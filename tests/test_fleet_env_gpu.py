@@ -141,6 +141,47 @@ def test_sweep_equals_the_model(case):
     assert want_d.any()
 
 
+def test_one_robot_per_world_is_the_nav_kernel():
+    """The device twin of test_fleet_env_cpu.py::test_one_robot_per_world_is_the_nav_rule_book: 4 worlds of one robot against 4 envs, same
+    seed, same actions from [0, 1] x [-1, 1] -- the two kernels' shared pieces (csrc/navcore.h) against each other, not each against its
+    own model.  After the reset and after each of 6 steps the laser, vector, image, reward, done, info word and every mapped state word
+    are equal bit for bit.  No episode can end in 6 steps (so the two envs' different new-episode rules stay out of it): every obstacle
+    centre and goal starts >= 608 - 128 sqrt(2) = 427 ticks from the robot, which moves <= 32 a step against a collision distance
+    <= 192 and a goal tolerance of 77; a pedestrian starts >= 608 away and closes <= 56 a step against 141; the wall is >= 2,496 - 1,720
+    away; max_steps is 500.  Populations (10, 5), (0, 0) and (3, 2)."""
+    for n_obs, n_peds in ((10, 5), (0, 0), (3, 2)):
+        _one_robot_against_nav(n_obs, n_peds)
+
+
+def _one_robot_against_nav(n_obs, n_peds):
+    from ddrl4nav_amd import ops
+    n, steps = 4, 6
+    kw = dict(seed=11, n_obstacles=n_obs, n_peds=n_peds)
+    make = lambda: ([torch.empty((n,) + s, dtype=torch.float32, device="cuda") for s in SHAPES],
+                    torch.empty(n, dtype=torch.float32, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda"),
+                    torch.empty(n, dtype=torch.int32, device="cuda"))
+    (fo, fr, fd, fw), (no, nr, nd, nw) = make(), make()
+    fs = torch.full((n, 96), -12345, dtype=torch.int32, device="cuda")
+    ns = torch.full((n, 64), -12345, dtype=torch.int32, device="cuda")
+    ops.fleet_env_reset(fs, 1, fo, world0=5, **kw)
+    ops.nav_env_reset(ns, no, env0=5, **kw)
+
+    def compare(t):
+        assert np.array_equal(F.nav_state(host(fs)), host(ns)), (t, np.nonzero(F.nav_state(host(fs)) != host(ns)))
+        for name, a, b in zip(("laser", "vector", "image"), fo, no):
+            assert same(host(a), host(b)), (t, name)
+
+    compare("reset")
+    actions = np.random.RandomState(n_obs + 7).uniform([0.0, -1.0], [1.0, 1.0], (steps, n, 2)).astype(np.float32)
+    for t in range(steps):
+        a = dev(actions[t])
+        ops.fleet_env_step(fs, 1, a, fo, fr, fd, info=fw, world0=5, max_steps=500, **kw)
+        ops.nav_env_step_info(ns, a, no, nr, nd, nw, env0=5, max_steps=500, **kw)
+        compare(t)
+        assert same(host(fr), host(nr)) and np.array_equal(host(fd), host(nd)) and np.array_equal(host(fw), host(nw)), t
+        assert not host(fd).any() and not host(nd).any(), t
+
+
 def test_repeats_are_bit_identical_and_the_info_word_changes_nothing():
     kw, actions, _, _, _ = reference(SWEEP[3])
     a, b, c = (play_on_device(kw, actions, emit_info=e) for e in (True, True, False))
