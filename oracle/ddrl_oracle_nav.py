@@ -11,6 +11,10 @@ Reference sites restated (under /root/reference/USTC_lab):
   * nn/utils.py:10-20          mlp            * nn/actor.py:43-70         GaussionActor
   * nn/actor.py:73-101         CategoricalActor   * nn/critic.py:8-21     Critic
   * nn/ppo.py:72-129           PPO.forward / learn (shared and non-shared branch)
+
+losses() / learn() take the configuration knobs (hyper-parameters, SMOOTH_L1_LOSS, CLIP_GRID) and the project's update options
+(VALUE_CLIP, ENTROPY_BONUS_SPLIT; DESIGN.md section 6.5, stated in tests/loss_options_ref.py) as keyword-only arguments; with the
+defaults they evaluate what they always did, bit for bit (tests/test_generic_cross_cpu.py).
 """
 import math
 import time
@@ -167,28 +171,71 @@ class OracleNet(nn.Module):
         return (torch.optim.Adam(self.actor.parameters(), ACTOR_LR), torch.optim.Adam(self.critic.parameters(), CRITIC_LR))
 
 
-def losses(net, states, actions, old_logps, advs, rets):
-    _, log_p, ent_el, v = net(states, actions)
+DEFAULT_HYPER = dict(ppo_clip=PPO_CLIP, dual_clip=DUEL_PPO_CLIP, v_loss_theta=V_LOSS_THETA, ent_loss_theta=ENT_LOSS_THETA)
+
+
+def value_element(x, smooth_l1):
+    """The value-loss element of an error x: x^2 / 2 (MSE, ppo.py's default), or F.smooth_l1_loss with beta 1 written out."""
+    if smooth_l1:
+        ax = x.abs()
+        return torch.where(ax < 1.0, 0.5 * x ** 2, ax - 0.5)
+    return x ** 2 / 2
+
+
+def losses(net, states, actions, old_logps, advs, rets, *, hyper=None, smooth_l1=False, value_clip=0.0, old_values=None):
+    """(total, actor_loss, v_loss, entropy).  The keyword arguments default to the reference's constants and its MSE value loss, and
+    then every expression below is the one this function has always evaluated.  hyper: ppo_clip / dual_clip / v_loss_theta /
+    ent_loss_theta (missing keys: the defaults); smooth_l1: SMOOTH_L1_LOSS; value_clip c > 0 with old_values (VALUE_CLIP): the value
+    element becomes max(e(ret - v), e(ret - v_c)), v_c = v_old + clamp(v - v_old, +-c)."""
+    h = dict(DEFAULT_HYPER, **(hyper or {}))
+    dist_out, log_p, ent_el, v = net(states, actions)
+    if not net.gaussian and dist_out.dtype != torch.float32:
+        # the clamp of log(clamp(p_hat, eps, 1 - eps)) is float32's eps whatever the dtype (include/ddrl.h; OracleNet.forward takes
+        # the eps of its own dtype, torch.distributions' rule): inside the interval these are the same numbers, bit for bit
+        from oracle.ddrl_oracle import EPS
+        p_hat = dist_out / dist_out.sum(-1, keepdim=True)
+        logits = torch.log(torch.clamp(p_hat, EPS, 1.0 - EPS))
+        log_p, ent_el = categorical_log_prob(logits, actions), categorical_entropy(p_hat, logits)
     ratio = torch.exp(log_p - old_logps)
-    m = torch.min(ratio * advs, torch.clamp(ratio, 1.0 - PPO_CLIP, 1.0 + PPO_CLIP) * advs)
-    actor_loss = -torch.mean(torch.where(advs > 0, m, torch.max(m, DUEL_PPO_CLIP * advs)))
-    v_loss = torch.mean((rets - v.squeeze()) ** 2) / 2
+    m = torch.min(ratio * advs, torch.clamp(ratio, 1.0 - h["ppo_clip"], 1.0 + h["ppo_clip"]) * advs)
+    actor_loss = -torch.mean(torch.where(advs > 0, m, torch.max(m, h["dual_clip"] * advs)))
+    if not smooth_l1 and not value_clip > 0:
+        v_loss = torch.mean((rets - v.squeeze()) ** 2) / 2
+    else:
+        v = v.squeeze(-1)
+        v_el = value_element(rets - v, smooth_l1)
+        if value_clip > 0:
+            v_c = old_values + torch.clamp(v - old_values, -value_clip, value_clip)
+            v_el = torch.max(v_el, value_element(rets - v_c, smooth_l1))
+        v_loss = torch.mean(v_el)
     ent = torch.mean(ent_el)
-    return actor_loss + v_loss * V_LOSS_THETA - ent * ENT_LOSS_THETA, actor_loss, v_loss, ent
+    return actor_loss + v_loss * h["v_loss_theta"] - ent * h["ent_loss_theta"], actor_loss, v_loss, ent
 
 
-def learn(net, optims, states, actions, old_logps, advs, rets, iters=TRAINING_ITER_TIME):
+def backward(net, total, actor_loss, v_loss, ent, *, hyper=None, entropy_split=False):
+    """The backward of ppo.py:110-129: a shared net differentiates the total; a non-shared one actor_loss and v_loss, the actor's
+    with its entropy bonus under entropy_split (ENTROPY_BONUS_SPLIT)."""
+    if net.shared:
+        total.backward()
+    elif entropy_split:
+        (actor_loss - dict(DEFAULT_HYPER, **(hyper or {}))["ent_loss_theta"] * ent).backward()
+        v_loss.backward()
+    else:
+        actor_loss.backward()
+        v_loss.backward()
+
+
+def learn(net, optims, states, actions, old_logps, advs, rets, iters=TRAINING_ITER_TIME, *, hyper=None, smooth_l1=False,
+          value_clip=0.0, old_values=None, entropy_split=False, clip_grad=(True, CLIP_GRAD_NUM)):
+    """clip_grad: (CLIP_GRID on / off, the max norm); off, the norm is still measured and reported."""
     for _ in range(iters):
         t0 = time.time()
-        total, actor_loss, v_loss, ent = losses(net, states, actions, old_logps, advs, rets)
+        total, actor_loss, v_loss, ent = losses(net, states, actions, old_logps, advs, rets, hyper=hyper, smooth_l1=smooth_l1,
+                                                value_clip=value_clip, old_values=old_values)
         for o in optims:
             o.zero_grad()
-        if net.shared:
-            total.backward()
-        else:
-            actor_loss.backward()
-            v_loss.backward()
-        gnorm = torch.nn.utils.clip_grad_norm_(net.parameters(), CLIP_GRAD_NUM)
+        backward(net, total, actor_loss, v_loss, ent, hyper=hyper, entropy_split=entropy_split)
+        gnorm = torch.nn.utils.clip_grad_norm_(net.parameters(), clip_grad[1] if clip_grad[0] else math.inf)
         for o in optims:
             o.step()
         net.update_time += 1

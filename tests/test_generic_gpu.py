@@ -231,16 +231,14 @@ def test_generic_net_learn_sequence_golden(golden, name):
 
 
 @pytest.mark.parametrize("name", ["f15_mlp_classical", "f13_nav1d_gauss"])
-def test_generic_deferred_loss_readback_yields_the_same_values(golden, name):
-    """config_nn.DEFERRED_LOSS_READBACK on the operator-composed PPO (nn/generic.py:learn): all iterations enqueued, every iteration's
-    loss terms copied to its own pinned row, ONE synchronisation, then the same items -- keys, values, update_time -- and the same
-    parameters as the per-iteration protocol of the reference (ppo.py:131-146), bit for bit."""
+def test_two_runs_of_the_two_micro_batch_learn_are_bit_identical(golden, name):
+    """Two runs of learn() on two micro-batches (one of them ragged) from the same weights: the same items -- keys, values, update_time --
+    and the same parameters, bit for bit.  (GenericPPO has no deferred read-back path; nn/generic.py reads no `deferred_stats`.)"""
     from ddrl4nav_amd.data import Experience
     g = golden(name)
     runs = []
-    for deferred in (False, True):
+    for run in range(2):
         net, _ = _make(name, max_batch=48)      # two micro-batches (one of them ragged) per iteration
-        net.deferred_stats = deferred
         exp = Experience(states=_states(g), advs=g["advs"], actions=g["actions"], old_logps=g["old_logps"], values=g["rets"].reshape(1, -1))
         items = [(dict(l), ut, last) for l, ut, last in net.learn(exp)]
         runs.append((items, net.params.clone()))
