@@ -114,22 +114,25 @@ class HotPath:
         return s.value
 
     # ---- forward ----------------------------------------------------------------------------
-    def forward(self, frames, act=None, seed=0, stream_id=0, probs=None, value=None, action=None, logp=None):
-        """frames uint8 [n,4,84,84] on device.  Returns (probs [n,A], value [n], action [n], logp [n])."""
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        n = frames.shape[0]
-        dev = frames.device
+    def _act_outputs(self, n, dev, act, probs, value, action, logp):
+        """(probs, value, action, logp, pointer for the drawn actions) of an acting forward over n samples: what the caller did not
+        hand in is allocated; a given `act` [n] is evaluated, returned as the action, and nothing is drawn (NULL pointer)."""
         probs = torch.empty((n, self.n_actions), dtype=torch.float32, device=dev) if probs is None else probs
         value = torch.empty(n, dtype=torch.float32, device=dev) if value is None else value
         logp = torch.empty(n, dtype=torch.float32, device=dev) if logp is None else logp
         if act is None:
             action = torch.empty(n, dtype=torch.float32, device=dev) if action is None else action
-        else:
-            assert act.dtype == torch.float32 and act.is_contiguous() and act.numel() == n
-            action = act
+            return probs, value, action, logp, _p(action)
+        assert act.dtype == torch.float32 and act.is_contiguous() and act.numel() == n
+        return probs, value, act, logp, c_void_p(0)
+
+    def forward(self, frames, act=None, seed=0, stream_id=0, probs=None, value=None, action=None, logp=None):
+        """frames uint8 [n,4,84,84] on device.  Returns (probs [n,A], value [n], action [n], logp [n])."""
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        n = frames.shape[0]
+        probs, value, action, logp, drawn = self._act_outputs(n, frames.device, act, probs, value, action, logp)
         check(self.lib.ddrl_forward(self.ctx, _p(frames), n, _p(act), int(seed) & (2 ** 64 - 1),
-                                    int(stream_id) & (2 ** 64 - 1), _p(probs), _p(value),
-                                    _p(action) if act is None else c_void_p(0), _p(logp), _st()))
+                                    int(stream_id) & (2 ** 64 - 1), _p(probs), _p(value), drawn, _p(logp), _st()))
         return probs, value, action, logp
 
     def forward_indexed(self, planes, tab, n, act=None, seed=0, stream_id=0, probs=None, value=None, action=None, logp=None):
@@ -139,18 +142,10 @@ class HotPath:
         n = int(n)
         assert planes.dtype == torch.uint8 and planes.is_cuda and planes.is_contiguous() and planes.numel() % (84 * 84) == 0
         assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * n
-        dev = planes.device
-        probs = torch.empty((n, self.n_actions), dtype=torch.float32, device=dev) if probs is None else probs
-        value = torch.empty(n, dtype=torch.float32, device=dev) if value is None else value
-        logp = torch.empty(n, dtype=torch.float32, device=dev) if logp is None else logp
-        if act is None:
-            action = torch.empty(n, dtype=torch.float32, device=dev) if action is None else action
-        else:
-            assert act.dtype == torch.float32 and act.is_contiguous() and act.numel() == n
-            action = act
+        probs, value, action, logp, drawn = self._act_outputs(n, planes.device, act, probs, value, action, logp)
         check(self.lib.ddrl_forward_indexed(self.ctx, _p(planes), planes.numel() // (84 * 84), _p(tab), n, _p(act),
                                             int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), _p(probs), _p(value),
-                                            _p(action) if act is None else c_void_p(0), _p(logp), _st()))
+                                            drawn, _p(logp), _st()))
         return probs, value, action, logp
 
     def categorical_stats(self, probs):
@@ -191,6 +186,20 @@ class HotPath:
         opt = ops.loss_options(clip, split)
         check(self.lib.ddrl_ppo_iter_opt(self.ctx, byref(batch), byref(opt), B, int(b_global if b_global is not None else B), _st()))
 
+    def _ppo_launch(self, frames_or_planes, n_planes, tab, actions, old_logps, advs, rets, B, b_global, old_values):
+        """ppo_iter (tab None) and ppo_iter_indexed behind their own frame checks: the column checks, then the entry point -- the
+        option form when self.loss_options is set, else the plain one of the frame source."""
+        for t in (actions, old_logps, advs, rets):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
+        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
+            return self._ppo_iter_opt(frames_or_planes, n_planes, tab, actions, old_logps, advs, rets, old_values, B, b_global)
+        b_global = int(b_global if b_global is not None else B)
+        if tab is None:
+            check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames_or_planes), _p(actions), _p(old_logps), _p(advs), _p(rets), B, b_global, _st()))
+        else:
+            check(self.lib.ddrl_ppo_iter_indexed(self.ctx, _p(frames_or_planes), n_planes, _p(tab), _p(actions), _p(old_logps),
+                                                 _p(advs), _p(rets), B, b_global, _st()))
+
     def set_rates(self, actor_lr, critic_lr, learning_rate, ppo_clip):
         """Overwrite the two Adam groups' learning rates, the shared mode's and PPO_CLIP in the context (include/ddrl.h ddrl_set_rates):
         the next ppo_iter / ppo_diag / clip_adam_step read them.  Host only."""
@@ -199,14 +208,8 @@ class HotPath:
         self.cfg.learning_rate, self.cfg.ppo_clip = float(learning_rate), float(ppo_clip)
 
     def ppo_iter(self, frames, actions, old_logps, advs, rets, b_global=None, old_values=None):
-        B = frames.shape[0]
-        for t in (actions, old_logps, advs, rets):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
         assert frames.dtype == torch.uint8 and frames.is_contiguous()
-        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
-            return self._ppo_iter_opt(frames, 0, None, actions, old_logps, advs, rets, old_values, B, b_global)
-        check(self.lib.ddrl_ppo_iter(self.ctx, _p(frames), _p(actions), _p(old_logps), _p(advs), _p(rets),
-                                     B, int(b_global if b_global is not None else B), _st()))
+        self._ppo_launch(frames, 0, None, actions, old_logps, advs, rets, frames.shape[0], b_global, old_values)
 
     def ppo_iter_indexed(self, planes, tab, actions, old_logps, advs, rets, b_global=None, old_values=None):
         """ppo_iter on frames read where they lie (include/ddrl.h ddrl_ppo_iter_indexed): `planes` is any contiguous uint8 device tensor
@@ -214,14 +217,9 @@ class HotPath:
         frame_table_stacks) names the plane of every channel of the B = actions.numel() samples.  Bit-identical to ppo_iter on the
         materialised frames."""
         B = actions.numel()
-        for t in (actions, old_logps, advs, rets):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
         assert planes.dtype == torch.uint8 and planes.is_cuda and planes.is_contiguous() and planes.numel() % (84 * 84) == 0
         assert tab.dtype == torch.int32 and tab.is_cuda and tab.is_contiguous() and tab.numel() >= 4 * B
-        if tuple(self.loss_options) != ops.NO_LOSS_OPTIONS:
-            return self._ppo_iter_opt(planes, planes.numel() // (84 * 84), tab, actions, old_logps, advs, rets, old_values, B, b_global)
-        check(self.lib.ddrl_ppo_iter_indexed(self.ctx, _p(planes), planes.numel() // (84 * 84), _p(tab), _p(actions), _p(old_logps),
-                                             _p(advs), _p(rets), B, int(b_global if b_global is not None else B), _st()))
+        self._ppo_launch(planes, planes.numel() // (84 * 84), tab, actions, old_logps, advs, rets, B, b_global, old_values)
 
     def ppo_diag(self, actions, old_logps, rets, out=None):
         """The eight diagnostics sums (ops.diag_dict) of THIS rank's batch on the features the last ppo_iter left behind, i.e. for the

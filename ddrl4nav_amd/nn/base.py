@@ -17,6 +17,28 @@ def _prod(shape):
     return n
 
 
+def bind_arena(named_params, params, grad_arena=None, offset_of=None):
+    """Make every parameter of named_params [(name, p)] a view of the flat tensor `params`, in the order given: its values are copied
+    into its slice (cast to the arena's dtype and device), p.data becomes the view, requires_grad goes off, and with a gradient arena
+    p.grad_view is the same slice of that one (where the operators write gradients).  A parameter starts where the one before it ended,
+    or at offset_of[name] when that names it (the discriminator's pad).  Returns {name: offset}.  The one place the module trees of
+    PPO, GenericPPO and the Discriminator are tied to their arenas."""
+    offsets, off = {}, 0
+    with torch.no_grad():
+        for name, p in named_params:
+            off = off if offset_of is None else offset_of.get(name, off)
+            n = p.numel()
+            view = params[off:off + n].view(p.shape)
+            view.copy_(p.detach().to(params.device, params.dtype))
+            p.data = view            # the module now aliases the flat arena
+            p.requires_grad_(False)
+            if grad_arena is not None:
+                p.grad_view = grad_arena[off:off + n].view(p.shape)
+            offsets[name] = off
+            off += n
+    return offsets
+
+
 class PreNet(torch.nn.Module):
     def __init__(self):
         super().__init__()

@@ -21,17 +21,20 @@ from ctypes import byref, c_int64
 
 import numpy as np
 import torch
+import torch.distributed as tdist
 
 from ddrl4nav_amd import _lib, ops
-from ddrl4nav_amd._lib import STATS_FLOATS, check
+from ddrl4nav_amd._lib import check
 from ddrl4nav_amd.data import Experience
-from ddrl4nav_amd.nn.base import Basenn
-from ddrl4nav_amd.nn.generic import FEAT, _pad4, dense_layer, mlp
+from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
+from ddrl4nav_amd.dist import allreduce_flat, global_batch
+from ddrl4nav_amd.nn.base import Basenn, bind_arena
+from ddrl4nav_amd.nn.generic import FEAT, OperatorNet, _pad4, dense_layer, mlp
+from ddrl4nav_amd.nn.minibatch import learner_options
 from ddrl4nav_amd.ops import _p, _st
-from ddrl4nav_amd.utils.staging import to_device
 
 
-class Discriminator(Basenn):
+class Discriminator(OperatorNet, Basenn):
     def __init__(self, **kwargs):
         config, config_nn = kwargs['config'], kwargs['config_nn']
         super().__init__(config, config_nn)
@@ -76,26 +79,10 @@ class Discriminator(Basenn):
         params = list(self.named_parameters())
         n_mlp = sum(p.numel() for k, p in params if k.startswith("mlp_layer."))
         pad = (-n_mlp) % 16
-        total = sum(p.numel() for _, p in params) + pad
-        f = dict(dtype=torch.float32, device=self.device)
-        self.n_params = total
-        self.params = torch.zeros(total, **f)
-        self.grads = torch.zeros(total + STATS_FLOATS, **f)
-        self.gtmp = torch.zeros(total + STATS_FLOATS, **f)
-        self.square_avg = torch.zeros(total, **f)
-        off, seen_pre = 0, False
-        with torch.no_grad():
-            for name, p in params:
-                if name.startswith("pre.") and not seen_pre:
-                    off, seen_pre = off + pad, True
-                n = p.numel()
-                view = self.params[off:off + n].view(p.shape)
-                view.copy_(p.detach().to(self.device, torch.float32))
-                p.data = view
-                p.requires_grad_(False)
-                p.grad_view = self.gtmp[off:off + n].view(p.shape)
-                off += n
-        assert off == total or not seen_pre
+        self._alloc_arenas(sum(p.numel() for _, p in params) + pad)
+        self.square_avg = torch.zeros_like(self.params)
+        first_pre = next((k for k, _ in params if k.startswith("pre.")), None)      # mlp_layer.* all come before it
+        bind_arena(params, self.params, self.gtmp, {first_pre: n_mlp + pad})
 
     def _build(self):
         f = dict(dtype=torch.float32, device=self.device)
@@ -121,33 +108,11 @@ class Discriminator(Basenn):
         check(self.lib.ddrl_op_clip_adam_ws_bytes(byref(cb)))
         self._opt_ws = torch.empty(cb.value, dtype=torch.uint8, device=self.device)
         self._raw_u8 = bool(getattr(self.pre, "raw_u8", False))
-        self._dirty = True
 
-    def params_changed(self):
-        self._dirty = True
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        out = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._dirty = True
-        return out
-
-    def to(self, *args, **kwargs):
-        return self
-
-    def _ensure_packed(self):
-        if self._dirty:
-            self.pre.pack()
-            for l in self._layers:
-                l.pack()
-            self._dirty = False
+    def _packables(self):
+        return [self.pre] + self._layers
 
     # ---- D(s, a) (GAIL.py:63-71) -----------------------------------------------------------------------------------------
-    def _stage(self, states, lo, hi):
-        states = states if isinstance(states, (list, tuple)) else [states]
-        if self._raw_u8:
-            return [torch.as_tensor(s)[lo:hi] for s in states]
-        return [to_device(torch.as_tensor(s)[lo:hi], self.device, torch.float32) for s in states]
-
     def _forward_chunk(self, st, action, n):
         """scores of one micro-batch -> self._act[-1][:n, 0]; activations stay in place for the backward."""
         h = self.pre.forward_dev(st, n)
@@ -178,8 +143,7 @@ class Discriminator(Basenn):
         self._ensure_packed()
         action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(n, self.action_dim)
         out = torch.empty((n, 1), dtype=torch.float32, device=self.device)
-        for lo in range(0, n, self.cap):
-            hi = min(n, lo + self.cap)
+        for lo, hi in self.chunks(n):
             score = self._forward_chunk(self._stage(states, lo, hi), action[lo:hi], hi - lo)
             out[lo:hi, 0].copy_(score[:hi - lo, 0])
         return out
@@ -188,23 +152,17 @@ class Discriminator(Basenn):
     def _pass(self, states, action, sign, first, n_total=None):
         """forward + backward of one term  sign * mean(D(states, action)); gradients are accumulated into self.grads.
         n_total: the size of the whole batch the mean runs over (default: the sum of the ranks' shard sizes)."""
-        from ddrl4nav_amd.dist import global_batch
         states = states if isinstance(states, (list, tuple)) else [states]
         n = int(torch.as_tensor(states[0]).shape[0])
         if n_total is None:
             n_total = global_batch(n, self._process_group)   # one collective per term: every rank runs the same two terms per step
         action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(n, self.action_dim)
-        total = self.n_params + STATS_FLOATS
-        for lo in range(0, n, self.cap):
-            hi = min(n, lo + self.cap)
+        for lo, hi in self.chunks(n):
             score = self._forward_chunk(self._stage(states, lo, hi), action[lo:hi], hi - lo)
             check(self.lib.ddrl_op_wgan_terms(_p(score), self._ld[-1], hi - lo, n_total, float(sign), _p(self._dact[-1]), self._ld[-1],
                                               self._ld[-1], _p(self._loss), 0 if first else 1, _st()))
             self._backward_chunk(hi - lo)
-            if first:
-                self.grads.copy_(self.gtmp)
-            else:
-                check(self.lib.ddrl_op_accumulate(_p(self.grads), _p(self.gtmp), total, _st()))
+            self.fold_gradient(first)
             first = False
 
     @staticmethod
@@ -224,9 +182,7 @@ class Discriminator(Basenn):
                 # g_loss = mean(D(data.states, data.actions)); expert_loss = -mean(D(expert)) (GAIL.py:78-80)
                 self._pass(data.states, torch.as_tensor(data.actions), +1.0, True)
                 self._pass(self._expert_states(expert_batch[0]), expert_batch[1], -1.0, False)
-                import torch.distributed as tdist
                 if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size(self._process_group) > 1:
-                    from ddrl4nav_amd.dist import allreduce_flat
                     allreduce_flat(self.grads, self._process_group)     # SUM of shard gradients pre-scaled by 1 / n_total
                     allreduce_flat(self._loss, self._process_group)
                 check(self.lib.ddrl_op_clip_rmsprop(_p(self.params), _p(self.grads), _p(self.square_avg), self.n_params, self.lr,
@@ -243,26 +199,10 @@ class Discriminator(Basenn):
         return {"GradNorm": float(s[0]), "ClipCoef": float(s[1]), "lr": self.lr}
 
 
-def refuse_diag_options(config_nn):
-    """PPO_DIAGNOSTICS / TARGET_KL (nn/ppo.py) are not built for a generator that carries the extra GAIL critic."""
-    if bool(getattr(config_nn, "PPO_DIAGNOSTICS", False)) or getattr(config_nn, "TARGET_KL", None) is not None:
-        raise NotImplementedError("PPO_DIAGNOSTICS / TARGET_KL are not built for NETWORK_TYPE='gail': the diagnostics head evaluates one "
-                                  "critic, the generator's value loss here is the sum over two (ppo.py:95-107), so ExplainedVariance would "
-                                  "describe half of what VLoss reports; unset both")
-
-
 class GAIL(Basenn):
     def __init__(self, generator, discriminator: Discriminator, gail_critic):
         super().__init__(discriminator.config, discriminator.config_nn)
-        refuse_diag_options(discriminator.config_nn)
-        from ddrl4nav_amd.nn.minibatch import refuse_minibatch_options
-        refuse_minibatch_options(discriminator.config_nn, "NETWORK_TYPE='gail'")
-        from ddrl4nav_amd.nn.minibatch import refuse_frames_in_place
-        refuse_frames_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
-        from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
-        refuse_act_in_place(discriminator.config_nn, "NETWORK_TYPE='gail'")
-        from ddrl4nav_amd.nn.minibatch import refuse_loss_options
-        refuse_loss_options(discriminator.config_nn, "NETWORK_TYPE='gail'")
+        learner_options(discriminator.config_nn, "NETWORK_TYPE='gail'", two_critics=True)     # refuses what is not built for it
         if tuple(getattr(generator, "loss_options", ops.NO_LOSS_OPTIONS)) != ops.NO_LOSS_OPTIONS:
             raise ValueError("the generator was built with VALUE_CLIP / ENTROPY_BONUS_SPLIT, which GAIL does not support (its value loss "
                              "sums two critics)")
@@ -305,7 +245,6 @@ class GAIL(Basenn):
             return self.discriminator(x)
 
     def learn(self, data: Experience):
-        from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
         refuse_frame_planes(data.states, "NETWORK_TYPE='gail'")
         for loss_item, update_time, last in self._train_discriminator(data):
             yield loss_item, update_time, False

@@ -8,17 +8,26 @@ ddrl_op_* launches (csrc/gconv.hip, glinear.hip, gheads.hip, heads.hip, optim.hi
 owns.  torch supplies memory, streams and input staging (dtype casts, channel concat) only.
 
 The Atari encoder does not go through this file: it has its own fused kernels (nn/ppo.py).
+
+OperatorNet is the shell every net composed here wears (GenericPPO, nn/gail.py Discriminator): input staging, lazy weight packing,
+micro-batch chunks and the gradient fold over them.  GenericPPO.learn parses the batch (update_loop.learn_columns), stages it once and
+hands nn/update_loop.py run() ONE Step; GenericPPO is that loop's update backend itself (set_rates ... stats below), so the protocol
+after the launch is spelled once for this learner and the Atari one.
 """
-import time
 from ctypes import byref, c_int64, c_void_p
 
 import torch
+import torch.distributed as tdist
 from torch import nn
 
 from ddrl4nav_amd import _lib, ops
 from ddrl4nav_amd._lib import STATS_FLOATS, HeadsDesc, check
 from ddrl4nav_amd.data import Experience
-from ddrl4nav_amd.nn.base import Basenn, PreNet
+from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
+from ddrl4nav_amd.dist import allgather_diag_sums, allreduce_flat, global_batch
+from ddrl4nav_amd.nn import minibatch, update_loop
+from ddrl4nav_amd.nn.atari_encoder import frames_u8
+from ddrl4nav_amd.nn.base import Basenn, PreNet, bind_arena
 from ddrl4nav_amd.ops import Conv, Linear, maxpool2_idx, maxpool2_backward_idx, sample_amax, _p, _st
 from ddrl4nav_amd.utils.staging import to_device
 
@@ -476,7 +485,59 @@ class HipNormal:
         return (0.5 + 0.9189385332046727 + self._log_std).expand_as(self.mean)
 
 
-class GenericPPO(Basenn):
+class OperatorNet:
+    """The shell of a net composed from the operators (mixed in before Basenn): it owns `params`, the gradient arena `grads` the
+    optimiser reads and `gtmp` a micro-batch's backward overwrites (both n_params + STATS_FLOATS long), works on micro-batches of at
+    most `cap` samples, and names in _packables() what keeps a packed copy of its weights."""
+    _dirty = True      # the packed weight layouts are behind the parameter views
+    _raw_u8 = False    # AtariPreNet: uint8 frames go to the kernels as they are
+
+    def _packables(self):
+        raise NotImplementedError
+
+    def _ensure_packed(self):
+        if self._dirty:
+            for x in self._packables():
+                x.pack()
+            self._dirty = False
+
+    def params_changed(self):
+        self._dirty = True
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        self._dirty = True
+        return out
+
+    def to(self, *args, **kwargs):  # the arena already lives on the GPU
+        return self
+
+    def _stage(self, states, lo, hi):
+        states = states if isinstance(states, (list, tuple)) else [states]
+        if self._raw_u8:
+            return [torch.as_tensor(s)[lo:hi] for s in states]
+        return [to_device(torch.as_tensor(s)[lo:hi], self.device, torch.float32) for s in states]
+
+    def chunks(self, n):
+        """(lo, hi) of the micro-batches of n samples."""
+        for lo in range(0, n, self.cap):
+            yield lo, min(n, lo + self.cap)
+
+    def _alloc_arenas(self, total):
+        f = dict(dtype=torch.float32, device=self.device)
+        self.n_params = total
+        self.params = torch.zeros(total, **f)
+        self.grads, self.gtmp = torch.zeros(total + STATS_FLOATS, **f), torch.zeros(total + STATS_FLOATS, **f)
+
+    def fold_gradient(self, first):
+        """grads <- gtmp (the first micro-batch of a step) or grads += gtmp: gradients and statistics tail alike."""
+        if first:
+            self.grads.copy_(self.gtmp)
+        else:
+            check(self.lib.ddrl_op_accumulate(_p(self.grads), _p(self.gtmp), self.n_params + STATS_FLOATS, _st()))
+
+
+class GenericPPO(OperatorNet, Basenn):
     """PPO over operator-composed encoders (any PreNet above) with a Categorical or Gaussian actor.
     Same constructor and protocol as the reference's PPO (ppo.py:17-146); see nn/ppo.py for the
     Atari fast path."""
@@ -484,21 +545,10 @@ class GenericPPO(Basenn):
     def __init__(self, actor, critic, prenet=None, rnd=None, config=None, config_nn=None, max_batch=None,
                  process_group=None):
         super().__init__(config, config_nn)
-        # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional; nn/ppo.py): the four diagnostics in every loss dict, KL early stopping
-        self.diagnostics, self.target_kl = ops.diag_options(config_nn)
-        from ddrl4nav_amd.nn.minibatch import refuse_minibatch_options
-        refuse_minibatch_options(config_nn, "the operator-composed GenericPPO")
-        from ddrl4nav_amd.nn.minibatch import refuse_frames_in_place
-        refuse_frames_in_place(config_nn, "the operator-composed GenericPPO")
-        from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
-        refuse_act_in_place(config_nn, "the operator-composed GenericPPO")
-        # config_nn.VALUE_CLIP / ENTROPY_BONUS_SPLIT / LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL (optional; nn/minibatch.py)
-        from ddrl4nav_amd.nn import minibatch
-        self.loss_options = minibatch.loss_options(config_nn)
-        self.lr_anneal = minibatch.anneal_options(config_nn)
+        # the optional knobs (nn/minibatch.py learner_options; nn/ppo.py says what each does); the Atari-only ones are refused
+        (self.diagnostics, self.target_kl, _, _, _, self.loss_options, self.lr_anneal,
+         self._base_rates) = minibatch.learner_options(config_nn, "the operator-composed GenericPPO")
         self.anneal_step = 0       # optimiser steps this net has applied: the schedule's u
-        self._base_rates = (float(config_nn.ACTOR_LEARNING_RATE), float(config_nn.CRITIC_LEARNING_RATE), float(config_nn.LEARNING_RATE),
-                            float(config_nn.PPO_CLIP))
         if rnd is not None:
             raise NotImplementedError("RND is disabled in the reference defaults (USE_RND=False) and out of scope")
         if bool(config_nn.SHARE_CNN_NET) != (prenet is not None):
@@ -526,7 +576,7 @@ class GenericPPO(Basenn):
             if not all(hasattr(e, k) for k in ("build", "forward_dev", "backward_dev", "pack")):
                 raise TypeError("GenericPPO needs operator-composed encoders (MLPPreNet, NavPreNet, AtariPreNet, ...), "
                                 "got %r" % type(e))
-        self._raw_u8 = bool(getattr(self._encs[0], "raw_u8", False))  # AtariPreNet: uint8 frames go to the kernels as they are
+        self._raw_u8 = bool(getattr(self._encs[0], "raw_u8", False))
         self._extra = []   # [(critic module, value-loss scratch)]: PPO.add_critic (ppo.py:61-62)
         self._bind_arena()
         for e in self._encs:
@@ -535,7 +585,6 @@ class GenericPPO(Basenn):
                 raise NotImplementedError("the head kernels take %d-wide features (AC_INPUT_DIM, config_nn.py:23); "
                                           "this encoder emits %d" % (FEAT, e.h.shape[1]))
         self._build_heads()
-        self._dirty = True
         self._step = 0
         self.encoder_streams = True     # actor and critic encoders on two HIP streams (_side)
 
@@ -543,24 +592,9 @@ class GenericPPO(Basenn):
     def _bind_arena(self):
         params = list(self.named_parameters())
         total = sum(p.numel() for _, p in params)
-        f = dict(dtype=torch.float32, device=self.device)
-        self.n_params = total
-        self.params = torch.zeros(total, **f)
-        self.grads = torch.zeros(total + STATS_FLOATS, **f)
-        self.gtmp = torch.zeros(total + STATS_FLOATS, **f)
-        self.adam_m = torch.zeros(total, **f)
-        self.adam_v = torch.zeros(total, **f)
-        self._offsets, off = {}, 0
-        with torch.no_grad():
-            for name, p in params:
-                n = p.numel()
-                view = self.params[off:off + n].view(p.shape)
-                view.copy_(p.detach().to(self.device, torch.float32))
-                p.data = view
-                p.requires_grad_(False)
-                p.grad_view = self.gtmp[off:off + n].view(p.shape)  # operators write gradients here
-                self._offsets[name] = off
-                off += n
+        self._alloc_arenas(total)
+        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self._offsets = bind_arena(params, self.params, self.gtmp)   # operators write gradients to the gtmp views
         # actor group = the leading run of actor.* parameters (ppo.py:40-42); everything when shared
         self.n_actor = total if self.share_cnn_net else sum(p.numel() for k, p in params if k.startswith("actor."))
         if not self.share_cnn_net:
@@ -594,22 +628,8 @@ class GenericPPO(Basenn):
             critic_lr=float(c.CRITIC_LEARNING_RATE), ppo_clip=float(c.PPO_CLIP), dual_clip=float(c.DUEL_PPO_CLIP),
             v_loss_theta=float(c.V_LOSS_THETA), ent_loss_theta=float(c.ENTROPY_LOSS_THETA))
 
-    def _ensure_packed(self):
-        if self._dirty:
-            for e in self._encs:
-                e.pack()
-            self._dirty = False
-
-    def params_changed(self):
-        self._dirty = True
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        out = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._dirty = True
-        return out
-
-    def to(self, *args, **kwargs):
-        return self
+    def _packables(self):
+        return self._encs
 
     def reset_optimizer(self):
         self.adam_m.zero_()
@@ -617,11 +637,6 @@ class GenericPPO(Basenn):
         self._step = 0
 
     # ---- forward -----------------------------------------------------------------------------------
-    def _stage(self, states, lo, hi):
-        if self._raw_u8:
-            return [torch.as_tensor(s)[lo:hi] for s in states]
-        return [to_device(torch.as_tensor(s)[lo:hi], self.device, torch.float32) for s in states]
-
     def _side(self):
         """The second encoder's stream: actor and critic encoders are independent networks with their own buffers and their own slices
         of the gradient arena, so the critic's runs beside the actor's (its small, latency-bound launches -- dense layers, the laser
@@ -671,8 +686,7 @@ class GenericPPO(Basenn):
         a_in = None if act is None else torch.as_tensor(act, **f).contiguous()
         action = a_in if a_in is not None else torch.empty((n, A) if self.continuous else (n,), **f)
         extra_values = [torch.empty(n, **f) for _ in self._extra]
-        for lo in range(0, n, self.cap):
-            hi = min(n, lo + self.cap)
+        for lo, hi in self.chunks(n):
             ha, hc = self._features(self._stage(states, lo, hi), hi - lo)
             for (crit, _), xv in zip(self._extra, extra_values):   # [critic(states) for critic in self._critics] (ppo.py:75)
                 check(self.lib.ddrl_op_value_head_forward(_p(crit.critic_linear.weight.data), _p(crit.critic_linear.bias.data),
@@ -775,71 +789,56 @@ class GenericPPO(Basenn):
         self._backward_both(dha, dhc, n)
 
     def learn(self, data: Experience):
-        from ddrl4nav_amd.data.frame_planes import refuse_frame_planes
+        """Parse the batch, stage it once, and hand nn/update_loop.py run() ONE Step TRAINING_ITER_TIME times: its launch runs the
+        micro-batches and folds their gradients into self.grads.  No deferred read-back here: a deferred_stats set from outside is not read."""
         refuse_frame_planes(data.states, "the operator-composed GenericPPO")
         states = data.states if isinstance(data.states, (list, tuple)) else [data.states]
         B = int(torch.as_tensor(states[0]).shape[0])
-        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
-        actions, old_logps, advs = f32(data.actions), f32(data.old_logps), f32(data.advs)
-        vals = f32(data.values)
-        rets = vals[0].contiguous()
-        assert rets.shape == (B,)
-        # ppo.py:97-104: the GAIL critic's targets are the LAST row of data.values (with RND unbuilt there is one extra head)
-        assert len(self._extra) <= 1 and (not self._extra or vals.shape[0] >= 2), "data.values needs one row per critic"
-        extra_rets = [vals[-1].contiguous()] if self._extra else []
-        old_values = None
-        if self.wants_old_values:
-            if self._extra:
-                raise ValueError("VALUE_CLIP is not built for a net with an extra critic (GAIL): its value loss sums two critics")
-            if vals.dim() != 2 or vals.shape[0] < 2:
-                raise ValueError("VALUE_CLIP needs the collecting policy's values as row 1 of data.values (row 0: the returns); this "
-                                 "batch has %d row(s)" % (vals.shape[0] if vals.dim() == 2 else 1))
-            old_values = vals[1].contiguous()
-        import torch.distributed as dist
-        from ddrl4nav_amd.dist import global_batch
-        world = dist.get_world_size(self._process_group) if dist.is_available() and dist.is_initialized() else 1
-        b_global = global_batch(B, self._process_group)  # shards may be uneven
-        total = self.n_params + STATS_FLOATS
+        if self.wants_old_values and self._extra:
+            raise ValueError("VALUE_CLIP is not built for a net with an extra critic (GAIL): its value loss sums two critics")
+        assert len(self._extra) <= 1    # with RND unbuilt there is one extra head at the most (the GAIL critic)
+        (*columns, old_values), extra_rets = update_loop.learn_columns(data, self.device, self.wants_old_values, len(self._extra))
+        assert columns[3].shape == (B,)
         # the batch is read by every one of the TRAINING_ITER_TIME iterations: stage it on the device once
         if self._raw_u8:
-            from ddrl4nav_amd.nn.atari_encoder import frames_u8
             dstates = [frames_u8(states, self.device)]
         else:
             dstates = [to_device(s, self.device, torch.float32) for s in states]
-        for _ in range(self.training_iter_time):
-            t0 = time.time()
+
+        def launch(actions, old_logps, advs, rets, b_global, old_values):
             self._ensure_packed()
-            if self.lr_anneal is not None:   # the rates of optimiser step number anneal_step, on this net's own configuration
-                from ddrl4nav_amd.nn.minibatch import annealed_rates
-                c = self._cfg
-                c.actor_lr, c.critic_lr, c.learning_rate, c.ppo_clip = annealed_rates(self._base_rates, self.anneal_step, *self.lr_anneal)
-            for ci, lo in enumerate(range(0, B, self.cap)):
-                hi = min(B, lo + self.cap)
-                self._iter_chunk([s[lo:hi] for s in dstates], hi - lo, actions[lo:hi], old_logps[lo:hi], advs[lo:hi],
-                                 rets[lo:hi], b_global, [x[lo:hi] for x in extra_rets], diag_first=(ci == 0) if self.diagnostics else None,
+            for lo, hi in self.chunks(B):
+                self._iter_chunk([s[lo:hi] for s in dstates], hi - lo, actions[lo:hi], old_logps[lo:hi], advs[lo:hi], rets[lo:hi],
+                                 b_global, [x[lo:hi] for x in extra_rets], diag_first=(lo == 0) if self.diagnostics else None,
                                  old_values=None if old_values is None else old_values[lo:hi])
-                if ci == 0:
-                    self.grads.copy_(self.gtmp)
-                else:
-                    check(self.lib.ddrl_op_accumulate(_p(self.grads), _p(self.gtmp), total, _st()))
-            d = None
-            if self.diagnostics:
-                # before anything is applied, combined over the ranks so that all of them decide alike (nn/ppo.py)
-                from ddrl4nav_amd.dist import allgather_diag_sums
-                d = ops.diag_dict(allgather_diag_sums(self._diag_sums.cpu().tolist(), self._process_group))
-                if ops.kl_stop(d, self.target_kl):
-                    return   # this iteration's step is not applied: no all-reduce, no Adam, no yield, update_time as it was
-            if world > 1:
-                from ddrl4nav_amd.dist import allreduce_flat
-                allreduce_flat(self.grads, self._process_group)
-            self._step += 1
-            self.anneal_step += 1   # a step the KL stop skipped does not count
-            check(self.lib.ddrl_op_clip_adam(byref(self._cfg), _p(self.params), _p(self.grads), _p(self.adam_m),
-                                             _p(self.adam_v), self.n_params, self.n_actor, 1 if self.share_cnn_net else 0,
-                                             self._step, _p(self._adam_ws), _st()))
-            self._dirty = True
-            self.update_time += 1
-            yield ops.loss_dict(self.stats(), time.time() - t0, d), self.update_time, True
+                self.fold_gradient(lo == 0)
+
+        step = update_loop.Step(launch, *columns, global_batch(B, self._process_group), old_values)   # shards may be uneven
+        n_steps = self.training_iter_time
+        yield from update_loop.run(self, (step for _ in range(n_steps)), n_steps)
+
+    # ---- the update backend of nn/update_loop.py run(): what engine.HotPath is to the Atari PPO ---------------------------------------
+    update_backend = property(lambda self: self)
+
+    def set_rates(self, actor_lr, critic_lr, learning_rate, ppo_clip):
+        c = self._cfg     # this net's own configuration: the loss and the Adam operators read it at their next launch
+        c.actor_lr, c.critic_lr, c.learning_rate, c.ppo_clip = actor_lr, critic_lr, learning_rate, ppo_clip
+
+    def ppo_diag(self, actions, old_logps, rets):
+        return self._diag_sums     # the launch's micro-batches have filled it (_iter_chunk: the first writes, the others add)
+
+    def diag_global(self, sums):
+        return allgather_diag_sums(sums.cpu().tolist(), self._process_group)
+
+    def allreduce_grads(self):
+        if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size(self._process_group) > 1:
+            allreduce_flat(self.grads, self._process_group)
+
+    def clip_adam_step(self):
+        self._step += 1
+        check(self.lib.ddrl_op_clip_adam(byref(self._cfg), _p(self.params), _p(self.grads), _p(self.adam_m), _p(self.adam_v),
+                                         self.n_params, self.n_actor, 1 if self.share_cnn_net else 0, self._step, _p(self._adam_ws), _st()))
+        self._dirty = True
 
     def stats(self):
         return ops.stats_dict(self.grads[self.n_params:self.n_params + 6].cpu())

@@ -2,7 +2,8 @@
 contiguous minibatches, with optional advantage normalisation -- what the reference does not have (USTC_lab/nn/ppo.py:77-146 runs
 TRAINING_ITER_TIME full-batch steps on raw advantages).
 
-The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the ConfigNN contract does not carry them):
+The knobs are read from config_nn with getattr (like PPO_DIAGNOSTICS; the ConfigNN contract does not carry them), by every learner's
+constructor through one reader, learner_options() below, which also refuses the Atari-only ones for the operator-composed learners:
 
   PPO_MINIBATCHES      1       K optimiser steps per epoch; a count, so every rank of a group does the same number of collectives
   PPO_SHUFFLE          False   True: a fresh permutation of this rank's samples every epoch
@@ -34,6 +35,8 @@ and columns into ONE staging buffer (or, in place, one frame table); off, contig
 asked for; then the launch and what run() does after it.  split() and epoch_order() are plain CPU functions: a test recomputes
 every minibatch from them.
 """
+import collections
+
 import torch
 
 from ddrl4nav_amd import ops
@@ -152,11 +155,35 @@ def refuse_loss_options(config_nn, who):
         raise ValueError("VALUE_CLIP / ENTROPY_BONUS_SPLIT are not built for %s (its value loss sums two critics): unset them" % who)
 
 
-def refuse_minibatch_options(config_nn, who):
-    """GenericPPO and GAIL keep their states as float lists per encoder input: the frame-row collation does not serve them."""
-    if minibatch_options(config_nn) != DEFAULTS:
+LearnerOptions = collections.namedtuple("LearnerOptions", "diagnostics target_kl minibatch frames_in_place act_in_place loss_options "
+                                                          "lr_anneal base_rates")
+
+
+def learner_options(config_nn, who=None, two_critics=False):
+    """Every optional knob a learner's constructor reads, validated, as a LearnerOptions: PPO_DIAGNOSTICS / TARGET_KL (ops.diag_options;
+    ValueError when TARGET_KL meets DEFERRED_LOSS_READBACK), the four minibatch knobs, FRAMES_IN_PLACE, ACT_IN_PLACE, VALUE_CLIP /
+    ENTROPY_BONUS_SPLIT, the annealing schedule, and the four base rates the schedule scales.  who (the Atari PPO passes none): a learner
+    over operator-composed encoders, named as its messages name it -- it keeps its states as float lists per encoder input, so the
+    frame-row collation and the frame tables are refused.  two_critics (NETWORK_TYPE='gail'): the generator's value loss sums two critics
+    (ppo.py:95-107), so the diagnostics and the loss options are refused as well."""
+    if two_critics and (bool(getattr(config_nn, "PPO_DIAGNOSTICS", False)) or getattr(config_nn, "TARGET_KL", None) is not None):
+        raise NotImplementedError("PPO_DIAGNOSTICS / TARGET_KL are not built for %s: the diagnostics head evaluates one critic, the "
+                                  "generator's value loss here is the sum over two (ppo.py:95-107), so ExplainedVariance would describe "
+                                  "half of what VLoss reports; unset both" % who)
+    diagnostics, target_kl = ops.diag_options(config_nn)
+    mb = minibatch_options(config_nn)
+    if who is not None and mb != DEFAULTS:
         raise ValueError("%s are built for the Atari fast path alone (nn/ppo.py PPO over AtariPreNet), not for %s: unset them"
                          % (" / ".join(KNOBS), who))
+    if who is not None:
+        refuse_frames_in_place(config_nn, who)
+        refuse_act_in_place(config_nn, who)
+    if two_critics:
+        refuse_loss_options(config_nn, who)
+    in_place, loss, anneal = (frames_in_place_option(config_nn), act_in_place_option(config_nn)), loss_options(config_nn), anneal_options(config_nn)
+    base_rates = (float(config_nn.ACTOR_LEARNING_RATE), float(config_nn.CRITIC_LEARNING_RATE), float(config_nn.LEARNING_RATE),
+                  float(config_nn.PPO_CLIP))
+    return LearnerOptions(diagnostics, target_kl, mb, *in_place, loss, anneal, base_rates)
 
 
 def split(B, K):

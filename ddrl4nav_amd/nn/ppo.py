@@ -9,15 +9,14 @@ step sources, and one frame source decides where a step's frames are read (nn/up
 """
 import torch
 
-from ddrl4nav_amd import ops
 from ddrl4nav_amd.nn import minibatch
 from ddrl4nav_amd.data import Experience
 from ddrl4nav_amd.data.frame_planes import FramePlanes, planes_of
 from ddrl4nav_amd.dist import global_batch
 from ddrl4nav_amd.engine import HotPath
-from ddrl4nav_amd.nn.base import Basenn
+from ddrl4nav_amd.nn.base import Basenn, bind_arena
 from ddrl4nav_amd.nn.distribution import HipCategorical
-from ddrl4nav_amd.nn.update_loop import Step, frame_source, run
+from ddrl4nav_amd.nn.update_loop import Step, frame_source, learn_columns, run
 
 
 from ddrl4nav_amd.nn.atari_encoder import frames_u8 as _frames_u8  # noqa: E402
@@ -37,23 +36,15 @@ class PPO(Basenn):
     def __init__(self, actor, critic, prenet=None, rnd=None, config=None, config_nn=None, max_batch=None,
                  process_group=None):
         super().__init__(config, config_nn)
-        # config_nn.PPO_DIAGNOSTICS / TARGET_KL (optional, like DEFERRED_LOSS_READBACK): ApproxKL, ClipFraction, ExplainedVariance and
-        # RatioMax in every loss dict, and KL early stopping (ValueError when TARGET_KL meets the deferred read-back)
-        self.diagnostics, self.target_kl = ops.diag_options(config_nn)
-        # config_nn.PPO_MINIBATCHES / PPO_SHUFFLE / NORMALIZE_ADVANTAGE / ADV_NORM_EPS (optional, nn/minibatch.py): epochs of minibatch steps
-        self.minibatch = minibatch.minibatch_options(config_nn)
-        # config_nn.FRAMES_IN_PLACE (optional, nn/minibatch.py): no batch or minibatch of frames is materialised; the conv1 kernels read
-        # them where they lie through a frame table (ddrl_ppo_iter_indexed).  Same bits; off by default
-        self.frames_in_place = minibatch.frames_in_place_option(config_nn)
-        # config_nn.ACT_IN_PLACE (optional, nn/minibatch.py): a PlaneRollout over this net acts on its pool in place (agent/plane_rollout.py)
-        self.act_in_place = minibatch.act_in_place_option(config_nn)
-        # config_nn.VALUE_CLIP / ENTROPY_BONUS_SPLIT (optional, nn/minibatch.py): the loss block's option form (ddrl_ppo_iter_opt);
-        # LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL: linear schedules of the learning rates and PPO_CLIP (ddrl_set_rates)
-        self.loss_options = minibatch.loss_options(config_nn)
-        self.lr_anneal = minibatch.anneal_options(config_nn)
+        # the optional knobs of config_nn, all read in nn/minibatch.py learner_options.  PPO_DIAGNOSTICS / TARGET_KL: ApproxKL,
+        # ClipFraction, ExplainedVariance and RatioMax in every loss dict, and KL early stopping.  PPO_MINIBATCHES / PPO_SHUFFLE /
+        # NORMALIZE_ADVANTAGE / ADV_NORM_EPS: epochs of minibatch steps.  FRAMES_IN_PLACE: no batch or minibatch of frames is
+        # materialised, the conv1 kernels read them where they lie through a frame table (ddrl_ppo_iter_indexed).  ACT_IN_PLACE: a
+        # PlaneRollout over this net acts on its pool in place.  VALUE_CLIP / ENTROPY_BONUS_SPLIT: the loss block's option form
+        # (ddrl_ppo_iter_opt).  LR_ANNEAL_UPDATES / LR_ANNEAL_FLOOR / CLIP_ANNEAL: linear schedules of the rates (ddrl_set_rates)
+        (self.diagnostics, self.target_kl, self.minibatch, self.frames_in_place, self.act_in_place, self.loss_options, self.lr_anneal,
+         self._base_rates) = minibatch.learner_options(config_nn)
         self.anneal_step = 0       # optimiser steps this net has applied: the schedule's u
-        self._base_rates = (float(config_nn.ACTOR_LEARNING_RATE), float(config_nn.CRITIC_LEARNING_RATE), float(config_nn.LEARNING_RATE),
-                            float(config_nn.PPO_CLIP))
         self._frame_tab = None      # FramePlanes states, full-batch step, in place: int32 [B, 4]
         self._mb_stage = None
         self._plane_batch = None   # FramePlanes states, full-batch step, staged: the batch materialised once per learn call
@@ -108,15 +99,7 @@ class PPO(Basenn):
         total = sum(p.numel() for _, p in params)
         if total != hp.n_params:
             raise ValueError("module tree has %d parameters, the HIP path expects %d" % (total, hp.n_params))
-        off = 0
-        with torch.no_grad():
-            for _, p in params:
-                n = p.numel()
-                view = hp.params[off:off + n].view(p.shape)
-                view.copy_(p.detach().to(self.device, torch.float32))
-                p.data = view            # the module now aliases the flat arena
-                p.requires_grad_(False)
-                off += n
+        bind_arena(params, hp.params)
         if old is not None:
             hp.adam_m.copy_(old.adam_m)
             hp.adam_v.copy_(old.adam_v)
@@ -133,6 +116,8 @@ class PPO(Basenn):
     @property
     def hot_path(self):
         return self._hp
+
+    update_backend = hot_path   # what nn/update_loop.py run() drives
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -201,22 +186,12 @@ class PPO(Basenn):
     def learn(self, data: Experience):
         """One loop (nn/update_loop.py run()) over one of two step sources: the single full-batch step above, or, with a minibatch knob
         set, TRAINING_ITER_TIME epochs of K steps (nn/minibatch.py steps())."""
-        f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
-        values = f32(data.values)
-        old_values = None
-        if self.wants_old_values:
-            # row 0 stays the return target; row 1 = what the collecting policy predicted (not derivable: ret = fl(v_old + adv) is rounded)
-            if values.dim() != 2 or values.shape[0] < 2:
-                raise ValueError("VALUE_CLIP needs the collecting policy's values as row 1 of data.values (row 0: the returns); this "
-                                 "batch has %d row(s) -- the rollouts emit it for a net with VALUE_CLIP, the Redis learner path cannot "
-                                 "(its workers overwrite their values with the returns)" % (values.shape[0] if values.dim() == 2 else 1))
-            old_values = values[1].contiguous()
+        (*columns, old_values), _ = learn_columns(data, self.device, self.wants_old_values)
         fp = planes_of(data.states)
         frames = fp if fp is not None else _frames_u8(data.states, self.device)
-        columns = f32(data.actions), f32(data.old_logps), f32(data.advs), values[0].contiguous()
         assert columns[3].shape == (len(frames),)
         if self.minibatch != minibatch.DEFAULTS:
             steps, n_steps = minibatch.steps(self, frames, columns, old_values), self.training_iter_time * self.minibatch[0]
         else:
             steps, n_steps = self._full_batch_steps(frames, columns, old_values), self.training_iter_time
-        yield from run(self, steps, n_steps)
+        yield from run(self, steps, n_steps, self.deferred_stats)

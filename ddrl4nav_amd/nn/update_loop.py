@@ -1,10 +1,14 @@
-"""The one update loop of the Atari fast path (nn/ppo.py PPO.learn): where a step's frames come from, and what follows its launch.
+"""The one update loop of every PPO learner (nn/ppo.py PPO.learn, nn/generic.py GenericPPO.learn): what a step reads, where an Atari
+step's frames come from, and what follows a step's launch.
 
-A Step is one optimiser step that a step source has prepared: its launcher and columns.  The sources are PPO._full_batch_steps (all
-knobs at their defaults: ONE step, handed out TRAINING_ITER_TIME times) and minibatch.steps (epochs of K minibatches).  Both take
-their launchers from a frame source -- StackedFrames over uint8 [B, C, 84, 84], PlaneFrames over data.FramePlanes -- which alone
-decides between the staged and the in-place form (config_nn.FRAMES_IN_PLACE) and alone calls HotPath.ppo_iter / ppo_iter_indexed.
-run() owns everything after the launch: diagnostics, KL stop, gradient all-reduce, Adam step, statistics read-back, loss dict.
+A Step is one optimiser step that a step source has prepared: its launcher and columns.  learn_columns() reads the columns out of a
+batch.  The Atari sources are PPO._full_batch_steps (all knobs at their defaults: ONE step, handed out TRAINING_ITER_TIME times) and
+minibatch.steps (epochs of K minibatches).  Both take their launchers from a frame source -- StackedFrames over uint8 [B, C, 84, 84],
+PlaneFrames over data.FramePlanes -- which alone decides between the staged and the in-place form (config_nn.FRAMES_IN_PLACE) and
+alone calls HotPath.ppo_iter / ppo_iter_indexed.  GenericPPO's source is one Step whose launcher runs its micro-batches.
+run() owns everything after the launch: diagnostics, KL stop, gradient all-reduce, Adam step, statistics read-back, loss dict.  It
+talks to the net's update backend (net.update_backend: engine.HotPath for PPO, GenericPPO itself) through set_rates, loss_options,
+ppo_diag, diag_global, allreduce_grads, clip_adam_step, stats and, deferred only, stats_async.
 """
 import collections
 import time
@@ -19,6 +23,25 @@ from ddrl4nav_amd.nn import minibatch
 # launch(actions, old_logps, advs, rets, b_global=, old_values=) enqueues the step's ppo_iter on its frames; ppo_diag reads actions,
 # old_logps, rets.  old_values: the collecting policy's values, the fifth column of a net with VALUE_CLIP (None otherwise)
 Step = collections.namedtuple("Step", "launch actions old_logps advs rets b_global old_values", defaults=(None,))
+
+
+def learn_columns(data, device, wants_old_values, n_extra_critics=0):
+    """((actions, old_logps, advs, rets, old_values), extra_rets) of a batch: fp32, contiguous, on `device`.  Row 0 of data.values is the
+    return target; with wants_old_values (VALUE_CLIP) row 1 is what the collecting policy predicted (not derivable: ret = fl(v_old + adv)
+    is rounded), else old_values is None; with an extra critic (reference ppo.py:97-104) its targets are the LAST row, else extra_rets
+    is empty."""
+    f32 = lambda t: torch.as_tensor(t, dtype=torch.float32, device=device).contiguous()
+    values = f32(data.values)
+    old_values = None
+    if wants_old_values:
+        if values.dim() != 2 or values.shape[0] < 2:
+            raise ValueError("VALUE_CLIP needs the collecting policy's values as row 1 of data.values (row 0: the returns); this "
+                             "batch has %d row(s) -- the rollouts emit it for a net with VALUE_CLIP, the Redis learner path cannot "
+                             "(its workers overwrite their values with the returns)" % (values.shape[0] if values.dim() == 2 else 1))
+        old_values = values[1].contiguous()
+    assert n_extra_critics == 0 or values.shape[0] >= 1 + n_extra_critics, "data.values needs one row per critic"
+    extra_rets = [values[-1].contiguous()] if n_extra_critics else []
+    return (f32(data.actions), f32(data.old_logps), f32(data.advs), values[0].contiguous(), old_values), extra_rets
 
 
 class StackedFrames:
@@ -61,14 +84,15 @@ def frame_source(hp, frames, in_place, stage=None, tab=None):
     return (PlaneFrames if isinstance(frames, FramePlanes) else StackedFrames)(hp, frames, in_place, stage, tab)
 
 
-def run(net, steps, n_steps):
+def run(net, steps, n_steps, deferred=False):
     """learn()'s protocol over the n_steps Steps of `steps`.  Eager: one host synchronisation per step, the weights match update_time at
-    every yield (the reference's protocol).  net.deferred_stats (config_nn.DEFERRED_LOSS_READBACK): every step is enqueued back to back,
+    every yield (the reference's protocol).  deferred (PPO passes its deferred_stats, config_nn.DEFERRED_LOSS_READBACK; GenericPPO has no
+    such path and passes nothing): every step is enqueued back to back,
     its statistics tail and diagnostics sums go to pinned host rows of their own by asynchronous copies, and ONE synchronisation
     precedes the yields -- same keys, values and update_time per yield, but the weights are already the last step's at the first yield
     (the reference's consumer, backward.py:189-209, publishes after the last one either way), and with N > 1 ranks a slow host does not
     stall the others' collectives once per step."""
-    diag, deferred = net.diagnostics, net.deferred_stats
+    diag = net.diagnostics
     if net.target_kl is not None and deferred:   # net.deferred_stats switched on after construction
         raise ValueError("TARGET_KL needs the host after every step: not with DEFERRED_LOSS_READBACK (net.deferred_stats)")
     if deferred and (net._stats_rows is None or net._stats_rows.shape[0] < n_steps):
@@ -79,7 +103,7 @@ def run(net, steps, n_steps):
         net._diag_dev = torch.zeros((n_steps, ops.DIAG_SLOTS), dtype=torch.float64, device=net.device)
     t_all = t0 = time.time()
     for i, s in enumerate(steps):
-        hp = net._hp   # read per step: the step source ensures the capacity, which may rebuild the hot path
+        hp = net.update_backend   # read per step: the Atari step sources ensure the capacity, which may rebuild the hot path
         hp.loss_options = net.loss_options
         if net.lr_anneal is not None:
             # the rates of optimiser step number net.anneal_step (counted at enqueue: the deferred read-back sees the same numbers);
@@ -111,5 +135,5 @@ def run(net, steps, n_steps):
     for i in range(n_steps):
         net.update_time += 1
         # the ranks' diagnostics rows are combined after the synchronisation (a collective per step, on the host)
-        d = ops.diag_dict(net._hp.diag_global(net._diag_rows[i])) if diag else None
+        d = ops.diag_dict(net.update_backend.diag_global(net._diag_rows[i])) if diag else None
         yield ops.loss_dict(ops.stats_dict(net._stats_rows[i]), dt, d), net.update_time, True

@@ -78,16 +78,8 @@ def _create_gail_net(config, config_nn, config_env, max_batch, process_group, ex
     if not config_nn.SHARE_CNN_NET:
         raise NotImplementedError("NETWORK_TYPE='gail' needs SHARE_CNN_NET=True: the reference builds the discriminator's "
                                   "encoder as deepcopy(prenet) (runner/utils.py:164)")
-    from ddrl4nav_amd.nn.gail import refuse_diag_options
-    refuse_diag_options(config_nn)     # before any network is built
-    from ddrl4nav_amd.nn.minibatch import refuse_minibatch_options
-    refuse_minibatch_options(config_nn, "NETWORK_TYPE='gail'")
-    from ddrl4nav_amd.nn.minibatch import refuse_frames_in_place
-    refuse_frames_in_place(config_nn, "NETWORK_TYPE='gail'")
-    from ddrl4nav_amd.nn.minibatch import refuse_act_in_place
-    refuse_act_in_place(config_nn, "NETWORK_TYPE='gail'")
-    from ddrl4nav_amd.nn.minibatch import refuse_loss_options
-    refuse_loss_options(config_nn, "NETWORK_TYPE='gail'")
+    from ddrl4nav_amd.nn.minibatch import learner_options
+    learner_options(config_nn, "NETWORK_TYPE='gail'", two_critics=True)     # refused before any network is built
     dim = config_nn.AC_INPUT_DIM
     actor = config_nn.ACTOR_CLASS(action_output_dim=config_nn.ACTION_OUTPUT_DIM, device=config_nn.DEVICE, last_input_dim=dim,
                                   soft_max_grid=config_nn.SOFT_MAX_GRID, nn_dtype=config_nn.MODULE_TENSOR_DTYPE)

@@ -89,9 +89,6 @@ def _run(B, CAP, ITERS, T_loop, encoder, loop_iters=None, encoder_streams=True):
     cfg_nn.SHARE_CNN_NET = encoder == "navped"
     net = create_net({"config": cfg, "config_nn": cfg_nn, "config_env": env}, max_batch=CAP)
     net.encoder_streams = bool(encoder_streams)   # False: one stream, so that the per-operator events do not overlap
-    # GenericPPO has no deferred read-back path: learn() reads the loss terms back after every iteration, and nothing in
-    # nn/generic.py reads this attribute -- it is set for symmetry with bench.py's Atari net only and changes no number measured here
-    net.deferred_stats = os.environ.get("NAV_SYNC_EVERY_ITER") != "1"
     g = torch.Generator(device="cuda")
     g.manual_seed(4)
     if encoder == "navped":
