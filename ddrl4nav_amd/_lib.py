@@ -247,6 +247,12 @@ SIGNATURES = {
                                             POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "ddrl_gae_bootstrap": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
                                      c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_nav_expert": (c_int32, [c_void_p, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_void_p, ctypes.c_uint32,
+                                     ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_heads_bc_mse_ws_floats": (c_int32, [c_int32, c_int32, POINTER(c_int64)]),
+    "ddrl_op_heads_bc_mse": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ddrl_op_gather_rows_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

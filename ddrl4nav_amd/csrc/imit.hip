@@ -5,6 +5,8 @@
 //   Basenn._imitation_learning_classifier   USTC_lab/nn/base.py:120-150 (CrossEntropyLoss on the actor's logits + its autograd backward
 //                                           through actor_linear; the reference's own expression cannot run on a PPO net)
 //   DataLoader(dataset, batch, shuffle)     USTC_lab/nn/base.py:128,140-141 (the per-batch collation of the shuffled samples)
+#include <type_traits>
+
 #include "heads_common.h"
 #include "rows.h"
 
@@ -27,7 +29,9 @@ inline int bc_workgroups(int n) {
 }
 inline int64_t bc_stride(int A) { return ((int64_t)A * FEAT + A + 2 + 3) & ~(int64_t)3; }
 
-template <int MAXA, bool GREG>
+// MSE (ddrl_op_heads_bc_mse, the Gaussian actor's mean): `labels` holds A targets per sample, d(mu) = (mu - y) / (n_total A) takes the
+// place of d(logits), the loss sum is sum (mu - y)^2 and the second statistic sum |mu - y| (in double: it is no count).
+template <int MAXA, bool GREG, bool MSE = false>
 __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __restrict__ h, int64_t ld_h, const float* __restrict__ w,
                                                                  const float* __restrict__ bias, int A, int n,
                                                                  const float* __restrict__ labels, float inv_n, float* __restrict__ dh,
@@ -52,14 +56,14 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
     for (int k = 0; k < 8; ++k) gwa[j][k] = 0.0f;
   }
   double s_loss = 0.0;
-  float s_cnt = 0.0f;  // a count below 2^24: exact
+  std::conditional_t<MSE, double, float> s_cnt = 0;  // a count below 2^24: exact
   const int ls = lane & (NS - 1);  // the sample of the turn this lane works on in the scalar phase
   for (int b0 = gw * NS; b0 < n; b0 += nw * NS) {
     float ha[NS][8];
 #pragma unroll
     for (int i = 0; i < NS; ++i) load8(h + (int64_t)min(b0 + i, n - 1) * ld_h + lane * 8, ha[i]);  // past the end: the last sample again, masked below
     const int bl = min(b0 + ls, n - 1);
-    const float lab = labels[bl];
+    const float lab = MSE ? 0.0f : labels[bl];
     // ---- logits: a lane keeps those of ITS sample
     float zl[MAXA];
 #pragma unroll
@@ -76,28 +80,46 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
         zl[j] = (ls == i) ? zj : zl[j];
       }
     }
-    // ---- this lane's sample: log_softmax = z - max - log sum exp(z - max); d(logits) = (softmax - onehot) / n_total
-    const bool valid = lab >= 0.0f && lab < (float)A;  // a label outside [0, A) (NaN included): no loss, no gradient
-    const int a = valid ? (int)lab : -1;
-    float m = zl[0];
-    int am = 0;
+    float gzl[MAXA], nll = 0.0f;
+    bool valid = true;
+    int a = -1, am = 0;
+    if constexpr (MSE) {
+      // ---- this lane's sample: d = mu - y per dimension; d(mu) = d / (n_total A)
+      float se = 0.0f;
+      double sq = 0.0;
 #pragma unroll
-    for (int j = 1; j < MAXA; ++j)
-      if (j < A && zl[j] > m) {  // the first maximum, as torch.argmax
-        m = zl[j];
-        am = j;
+      for (int j = 0; j < MAXA; ++j) {
+        const float d = (j < A) ? zl[j] - labels[(int64_t)bl * A + min(j, A - 1)] : 0.0f;
+        gzl[j] = d * inv_n;
+        sq += (double)d * (double)d;
+        se += fabsf(d);
       }
-    float e[MAXA], se = 0.0f;
+      if (lane < NS && b0 + ls < n) {
+        s_loss += sq;
+        s_cnt += (double)se;
+      }
+    } else {
+      // ---- this lane's sample: log_softmax = z - max - log sum exp(z - max); d(logits) = (softmax - onehot) / n_total
+      valid = lab >= 0.0f && lab < (float)A;  // a label outside [0, A) (NaN included): no loss, no gradient
+      a = valid ? (int)lab : -1;
+      float m = zl[0];
 #pragma unroll
-    for (int j = 0; j < MAXA; ++j) {
-      e[j] = (j < A) ? expf(zl[j] - m) : 0.0f;
-      se += e[j];
+      for (int j = 1; j < MAXA; ++j)
+        if (j < A && zl[j] > m) {  // the first maximum, as torch.argmax
+          m = zl[j];
+          am = j;
+        }
+      float e[MAXA], se = 0.0f;
+#pragma unroll
+      for (int j = 0; j < MAXA; ++j) {
+        e[j] = (j < A) ? expf(zl[j] - m) : 0.0f;
+        se += e[j];
+      }
+      nll = valid ? -((pick(zl, a) - m) - logf(se)) : 0.0f;
+#pragma unroll
+      for (int j = 0; j < MAXA; ++j) gzl[j] = (valid && j < A) ? (e[j] / se - ((j == a) ? 1.0f : 0.0f)) * inv_n : 0.0f;
     }
-    const float nll = valid ? -((pick(zl, a) - m) - logf(se)) : 0.0f;
-    float gzl[MAXA];
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j) gzl[j] = (valid && j < A) ? (e[j] / se - ((j == a) ? 1.0f : 0.0f)) * inv_n : 0.0f;
-    if (lane < NS && b0 + ls < n) {
+    if (!MSE && lane < NS && b0 + ls < n) {
       s_loss += (double)nll;
       s_cnt += (valid && am == a) ? 1.0f : 0.0f;
       if constexpr (!GREG) {
@@ -137,7 +159,7 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
   // the loss sums live in lanes 0 .. NS-1 (one sample each per turn): added in sample order
   {
     double tl = 0.0;
-    float tc = 0.0f;
+    decltype(s_cnt) tc = 0;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       tl += __shfl(s_loss, i, 64);
@@ -160,7 +182,7 @@ __global__ __launch_bounds__(BC_WAVES * 64) void bc_loss_kernel(const float* __r
           for (int j = 0; j < MAXA; ++j) turn_add(first, red[j], gba[j]);
         }
         turn_add(first, red[MAXA], (float)s_loss);
-        turn_add(first, red[MAXA + 1], s_cnt);
+        turn_add(first, red[MAXA + 1], (float)s_cnt);
       }
     }
     __syncthreads();
@@ -194,6 +216,34 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_rows_kernel(const uint4
   const bool ok = r >= 0 && r < n_rows;
   gather_row_chunk(src, r, ok, row_vecs, c, i, dst);
   if (labels_dst != nullptr && c == 0 && threadIdx.x == 0) labels_dst[i] = ok ? labels_src[r] : -1.0f;
+}
+
+// dst[i][:] = src[clamp(idx[i])][:] for fp32 rows of any width (ddrl_op_gather_rows_f32): VEC moves the row mover's 16-byte units, the
+// other instantiation the same chunk of a row in floats (a 5-float vector row is 20 bytes)
+constexpr int GATHER_F32_CHUNK = GATHER_CHUNK * 4;  // floats of a row one workgroup moves
+template <bool VEC>
+__global__ __launch_bounds__(GATHER_THREADS) void gather_rows_f32_kernel(const float* __restrict__ src, int64_t n_rows, int64_t row_floats,
+                                                                          int chunks, const int32_t* __restrict__ idx,
+                                                                          float* __restrict__ dst) {
+  const int i = blockIdx.x / chunks, c = blockIdx.x % chunks;
+  int64_t r = idx[i];
+  r = r < 0 ? 0 : (r >= n_rows ? n_rows - 1 : r);
+  if constexpr (VEC) {
+    gather_row_chunk(reinterpret_cast<const uint4*>(src), r, true, row_floats / 4, c, i, reinterpret_cast<uint4*>(dst));
+  } else {
+    const int64_t u0 = (int64_t)c * GATHER_F32_CHUNK + threadIdx.x;
+    float v[GATHER_F32_CHUNK / GATHER_THREADS];
+#pragma unroll
+    for (int t = 0; t < GATHER_F32_CHUNK / GATHER_THREADS; ++t) {
+      const int64_t u = u0 + t * GATHER_THREADS;
+      v[t] = u < row_floats ? src[r * row_floats + u] : 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < GATHER_F32_CHUNK / GATHER_THREADS; ++t) {
+      const int64_t u = u0 + t * GATHER_THREADS;
+      if (u < row_floats) dst[(int64_t)i * row_floats + u] = v[t];
+    }
+  }
 }
 
 }  // namespace ddrl
@@ -230,6 +280,50 @@ int32_t ddrl_op_heads_bc_loss(const float* w, const float* b, int32_t n_actions,
     hipLaunchKernelGGL(head_wgrad_kernel<BC_A_LARGE>, dim3(nwg), dim3(256), 0, st, h, ld_h, (const float*)dlogits, n, A, ws, ps, A * FEAT);
   }
   launch_head_reduce(ws, ps, nwg, BcReduce{A, inv_n, dw, db, stats}, st);
+  return launch_status();
+}
+
+int32_t ddrl_op_heads_bc_mse_ws_floats(int32_t n_actions, int32_t max_n, int64_t* floats) {
+  if (!floats || max_n < 1) return DDRL_ERR_INVALID_ARG;
+  if (n_actions < 1 || n_actions > BC_A_SMALL) return DDRL_ERR_UNSUPPORTED;
+  *floats = (int64_t)BC_MAX_WG * bc_stride(n_actions);
+  return DDRL_OK;
+}
+
+int32_t ddrl_op_heads_bc_mse(const float* w, const float* b, int32_t n_actions, const float* h, int64_t ld_h, int32_t n,
+                             const float* targets, int64_t n_total, float* dh, int64_t ld_dh, float* dw, float* db, float* stats,
+                             float* ws, void* stream) {
+  // every check comes before the first HIP call: a host without a GPU gets the same answers
+  if (!w || !b || !h || !targets || !dh || !dw || !db || !stats || !ws || n < 1 || n_total < n) return DDRL_ERR_INVALID_ARG;
+  if (n_actions < 1 || n_actions > BC_A_SMALL) return DDRL_ERR_UNSUPPORTED;
+  if (ld_h < FEAT || ld_dh < FEAT || (ld_h & 3) || (ld_dh & 3) || !aligned16(h) || !aligned16(dh)) return DDRL_ERR_INVALID_ARG;
+  if (((uintptr_t)w & 3) || ((uintptr_t)b & 3) || ((uintptr_t)targets & 3) || ((uintptr_t)dw & 3) || ((uintptr_t)db & 3) ||
+      ((uintptr_t)stats & 3) || ((uintptr_t)ws & 3) || n_total > INT64_MAX / BC_A_SMALL)
+    return DDRL_ERR_INVALID_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const int A = n_actions, nwg = bc_workgroups(n);
+  const int64_t ps = bc_stride(A);
+  const double inv_e = 1.0 / ((double)n_total * (double)A);  // one over the elements of the mean
+  hipLaunchKernelGGL((bc_loss_kernel<BC_A_SMALL, true, true>), dim3(nwg), dim3(BC_WAVES * 64), 0, st, h, ld_h, w, b, A, n, targets,
+                     (float)inv_e, dh, ld_dh, (float*)nullptr, ws, ps);
+  launch_head_reduce(ws, ps, nwg, BcReduce{A, 0.5 * inv_e, dw, db, stats}, st);  // loss share = sum d^2 / (2 n_total A)
+  return launch_status();
+}
+
+int32_t ddrl_op_gather_rows_f32(const float* src, int64_t n_rows, int64_t row_floats, const int32_t* idx, int32_t n, float* dst,
+                                void* stream) {
+  if (!src || !idx || !dst || n < 1 || n_rows < 1 || row_floats < 1) return DDRL_ERR_INVALID_ARG;
+  if (((uintptr_t)src & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)idx & 3)) return DDRL_ERR_INVALID_ARG;
+  if (row_floats > INT64_MAX / 4 / n_rows || row_floats > INT64_MAX / 4 / n) return DDRL_ERR_INVALID_ARG;
+  const uint64_t dst_b = (uint64_t)n * row_floats * 4;
+  if (overlap(src, dst, (uint64_t)n_rows * row_floats * 4, dst_b) || overlap(idx, dst, (uint64_t)n * 4, dst_b)) return DDRL_ERR_INVALID_ARG;
+  const int64_t c = (row_floats + GATHER_F32_CHUNK - 1) / GATHER_F32_CHUNK;
+  if (c > INT32_MAX / n) return DDRL_ERR_INVALID_ARG;
+  const dim3 grid((unsigned)(n * c)), block(GATHER_THREADS);
+  if ((row_floats & 3) == 0 && aligned16(src) && aligned16(dst))
+    hipLaunchKernelGGL(gather_rows_f32_kernel<true>, grid, block, 0, (hipStream_t)stream, src, n_rows, row_floats, (int)c, idx, dst);
+  else
+    hipLaunchKernelGGL(gather_rows_f32_kernel<false>, grid, block, 0, (hipStream_t)stream, src, n_rows, row_floats, (int)c, idx, dst);
   return launch_status();
 }
 

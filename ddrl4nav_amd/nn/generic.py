@@ -752,6 +752,13 @@ class GenericPPO(OperatorNet, Basenn):
         self._critics.append(critic)
         self._extra.append((critic, torch.empty(wf.value, dtype=torch.float32, device=self.device)))
 
+    def clone_actor(self, pool, lr, batch, epochs, seed, trainer=None):
+        """Behaviour cloning of the actor side from a data.DemoPool (nn/dagger.py): `epochs` passes in
+        minibatches of `batch` with a private Adam at `lr`; the critic side, log_std and the PPO optimiser's state stay bit-unchanged.
+        -> [(epoch, batch index, loss, metric per sample)], also left in ``clone_log``."""
+        from ddrl4nav_amd.nn.dagger import clone_actor
+        return clone_actor(self, pool, lr, batch, epochs, seed, trainer)
+
     def get_rnd(self, states):
         raise NotImplementedError("RND is out of scope on this path")
 

@@ -186,6 +186,34 @@ def gather_rows_u8(src, idx, dst, labels_src=None, labels_dst=None, n=None):
     return dst
 
 
+def heads_bc_mse_ws_floats(n_actions, max_n):
+    """Floats of scratch ddrl_op_heads_bc_mse needs for launches of up to max_n samples."""
+    f = c_int64()
+    check(_lib.load().ddrl_op_heads_bc_mse_ws_floats(int(n_actions), int(max_n), byref(f)))
+    return f.value
+
+
+def heads_bc_mse(w, b, n_actions, h, ld_h, n, targets, n_total, dh, ld_dh, dw, db, stats, ws):
+    """mean((mu - y)^2) / 2 of a Gaussian actor's mean mu = w h + b against targets fp32 [n][A], over the n_total * A elements of the
+    whole batch, and its backward through the head layer (include/ddrl.h ddrl_op_heads_bc_mse; csrc/imit.hip): writes dh [n][ld_dh], dw,
+    db and stats = (loss share, sum |mu - y|).  Asynchronous on the current stream."""
+    check(_lib.load().ddrl_op_heads_bc_mse(_p(w), _p(b), int(n_actions), _p(h), int(ld_h), int(n), _p(targets), int(n_total), _p(dh),
+                                           int(ld_dh), _p(dw), _p(db), _p(stats), _p(ws), _st()))
+
+
+def gather_rows_f32(src, idx, dst, n=None):
+    """dst[i] = src[clamp(idx[i])] for the first n entries of idx (int32, on the device), rows being everything behind the leading axis
+    of the contiguous fp32 tensors `src` / `dst`, of any width (include/ddrl.h ddrl_op_gather_rows_f32).  Asynchronous on the current
+    stream; returns dst."""
+    n = int(idx.numel() if n is None else n)
+    _f32(src), _f32(dst)
+    assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() >= n, "idx: contiguous int32 on the device"
+    row = src[0].numel()
+    assert dst[0].numel() == row and dst.shape[0] >= n, "dst rows must match src rows"
+    check(_lib.load().ddrl_op_gather_rows_f32(_p(src), src.shape[0], row, _p(idx), n, _p(dst), _st()))
+    return dst
+
+
 def moments_ws_floats(n):
     """Floats of scratch ddrl_op_moments needs for a column of n floats."""
     f = c_int64()
@@ -501,6 +529,32 @@ def nav_env_step_final(state, actions, obs, reward, done, info, final_obs, env0=
     _arena_args(state, nav_env_state_ints(), 1, final_obs, what="final_obs")
     check(_lib.load().ddrl_op_nav_env_step_final(*args, _p(info), *_p3(final_obs), _st()))
     return obs, reward, done, info, final_obs
+
+
+def beta_threshold(beta):
+    """The uint32 threshold of DAgger's mixing rate: min(2^32 - 1, floor(beta 2^32)); an env plays the expert where its draw is below."""
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError("beta must be in [0, 1], got %r" % (beta,))
+    return min(2 ** 32 - 1, int(math.floor(beta * 2.0 ** 32)))
+
+
+def nav_expert(state, label=None, played=None, policy=None, step=0, threshold=2 ** 32 - 1, env0=0, seed=0, n_obstacles=10, n_peds=5):
+    """The scripted expert's action for every env of `state` (include/ddrl.h ddrl_op_nav_expert; csrc/navexpert.hip; the rules are
+    tests/nav_expert_ref.py): label fp32 [n, 2] = (v / 32, w / 64) of the arc it prefers; played fp32 [n, 2] = the label where the env's
+    draw of `step` is below `threshold` (beta_threshold), policy fp32 [n, 2] elsewhere.  The state is only read.  Asynchronous on the
+    current stream; returns (label, played)."""
+    ints = nav_env_state_ints()
+    assert state.dtype == torch.int32 and state.is_cuda and state.is_contiguous() and state.dim() == 2 and state.shape[1] == ints, \
+        "state: contiguous int32 [n, %d] on the device" % ints
+    n = state.shape[0]
+    for name, t in (("label", label), ("played", played), ("policy", policy)):
+        assert t is None or (tuple(_f32(t).shape) == (n, 2) and t.device == state.device), "%s: fp32 [n, 2] on the state's device" % name
+    if not 0 <= int(step) < 2 ** 32 or not 0 <= int(threshold) < 2 ** 32:
+        raise ValueError("step and threshold must fit 32 bits, got %r and %r" % (step, threshold))
+    check(_lib.load().ddrl_op_nav_expert(_p(state), n, int(env0), int(seed) & 0xFFFFFFFF, int(n_obstacles), int(n_peds), _p(policy),
+                                         int(step), int(threshold), _p(label), _p(played), _st()))
+    return label, played
 
 
 NAV_INFO_FIELDS = ("done", "goal", "collision", "truncated", "close", "wall_hit", "obstacle_hit", "v", "w")

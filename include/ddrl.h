@@ -918,6 +918,39 @@ int32_t ddrl_op_file_flagged_rows(const int32_t* info, int32_t mask, int32_t N, 
 int32_t ddrl_gae_bootstrap(const float* values, const float* rewards, const uint8_t* dones, const int32_t* slot, const float* boot,
                            int32_t S, int32_t T, int32_t N, float gamma, float landa, float* adv, float* ret, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DAgger on the device (additive: ABI 3): a scripted expert for the navigation env and the cloning loss of a
+ * Gaussian actor.  Context-free, no allocation, no atomics, asynchronous on `stream`; the same arguments and data give the same bits;
+ * every check is decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+/* The expert's action for every env of ddrl_op_nav_env_*'s `state` (read, never written; words are brought into their ranges as the
+ * step kernel does): the best of 51 constant-(v, w) arcs rolled 10 steps ahead against the wall, the obstacles and the pedestrians'
+ * straight-line predictions (the rules are tests/nav_expert_ref.py, in integers only, and the kernel reproduces them bit for bit).
+ *   label   float32 [n][2] or NULL: (v / 32, w / 64) of the winning arc, what ddrl_op_nav_env_step decodes back to (v, w)
+ *   played  float32 [n][2] or NULL: label[i] where hash(seed, env0 + i, step) < threshold (the hash of the envs' draws; the env's event
+ *           counter is not touched), policy[i] elsewhere; with policy NULL the label everywhere
+ *   policy  float32 [n][2] or NULL: the learner's actions, copied bit for bit where they are played
+ * threshold = min(2^32 - 1, floor(beta 2^32)) for DAgger's mixing rate beta.  All three of policy, played and label NULL, n < 1,
+ * env0 + n beyond 2^32, n_obstacles outside 0..10, n_peds outside 0..5, a state that is not 16-byte aligned, a float pointer that is
+ * not 4-byte aligned, an overlap of two arguments: DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_nav_expert(const int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                           const float* policy, uint32_t step, uint32_t threshold, float* label, float* played, void* stream);
+/* ddrl_op_heads_bc_loss for a Gaussian actor's mean: mu = w h + b with w [n_actions][512], 1 <= n_actions <= 8, against targets
+ * float32 [n][n_actions]; loss = mean((mu - y)^2) / 2 over the n_total * n_actions elements of the whole batch (n_total >= n: the n
+ * samples are a micro-batch of it).  Writes dh [n][ld_dh], dw, db and stats = (this call's share of the loss, sum |mu - y|); log_std
+ * takes no part.  One wave per sample, per-workgroup partial rows summed in a fixed order by a second launch: deterministic.
+ * h and dh 16-byte aligned with ld >= 512 a multiple of 4; ws = ddrl_op_heads_bc_mse_ws_floats floats. */
+int32_t ddrl_op_heads_bc_mse_ws_floats(int32_t n_actions, int32_t max_n, int64_t* floats);
+int32_t ddrl_op_heads_bc_mse(const float* w, const float* b, int32_t n_actions, const float* h, int64_t ld_h, int32_t n,
+                             const float* targets, int64_t n_total, float* dh, int64_t ld_dh, float* dw, float* db, float* stats,
+                             float* ws, void* stream);
+/* dst[i][:] = src[clamp(idx[i], 0, n_rows - 1)][:] for i < n, rows of row_floats floats (any width: the 5-float vector rows of the
+ * navigation env are 20 bytes).  16-byte accesses when row_floats % 4 == 0 and both bases are 16-byte aligned, 4-byte ones otherwise;
+ * the result is the same.  A null or misaligned (4 bytes) pointer, n < 1, n_rows < 1, row_floats < 1, dst overlapping src or idx:
+ * DDRL_ERR_INVALID_ARG. */
+int32_t ddrl_op_gather_rows_f32(const float* src, int64_t n_rows, int64_t row_floats, const int32_t* idx, int32_t n, float* dst,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ a1 ~ U(-1, 1)) on the same env, measured first on the device over --baseline-ste
 
     python tools/train_device_nav_env.py [--envs 256] [--horizon 64] [--updates 100] [--obstacles 10] [--peds 5] [--max-steps 500]
                                          [--iters 4] [--actor-lr R] [--critic-lr R] [--normalize-obs] [--seed 0] [--out curve.json]
-                                         [--nav-status] [--robots 1]
+                                         [--nav-status] [--robots 1] [--dagger ITERS]
 
 --nav-status: the env emits its info words and the rollout keeps the reference's navigation statistics on the device (agent.NavStatus;
 DESIGN.md section 6.9); reach, collision and truncation rates over the envs' latest 100 episodes are printed next to the return and
@@ -16,6 +16,11 @@ stored in the curve.  The loop gains no host synchronisation per step: the one c
 --robots R (2..4): --envs counts WORLDS of R robots each (env/fleet_nav_env.py) and the rollout has envs * R rows,
 one per robot; with --nav-status the other-robot collision rate (NavStatus.other_robot_collision_rate, one more scalar copy at a logged
 update) is printed and stored too.  --robots 1 is the single-robot env above.
+
+--dagger ITERS (default 0: off, and nothing below runs): ahead of the PPO updates, ITERS rounds of DAgger (runner/dagger_loop.py; DESIGN.md
+section 6.15) -- the net acts, the scripted expert (env.NavExpert) labels every visited state, GenericPPO.clone_actor fits the actor;
+beta goes from 1 to 0.  With --nav-status the net's mean action is played for --baseline-steps steps before and after, from the same
+reset, and the two reach rates are printed and stored: whether cloning helped is a measurement, not a claim.
 """
 import argparse
 import json
@@ -47,6 +52,47 @@ def random_policy_return(env, steps, seed):
     return (total / episodes if episodes else float("nan")), 1000.0 * total / (env.N * steps)
 
 
+def policy_outcomes(net, env, steps):
+    """The outcomes of the net's mean action over `steps` steps from a reset, read off the info words (the env needs emit_info):
+    {episodes, reach_rate, collision_rate, truncation_rate}; leaves the env reset."""
+    obs = env.reset()
+    counts = torch.zeros(4, dtype=torch.int64, device=env.device)
+    for _ in range(steps):
+        with torch.no_grad():
+            (mu, _), _ = net.forward(obs, None, True)
+        obs = env.step(mu)[0]
+        w = env.info
+        counts += torch.stack([(w & 1).sum(), ((w >> 1) & 1).sum(), (((w >> 2) & 3) != 0).sum(), ((w >> 4) & 1).sum()])
+    env.reset()
+    done, goal, hit, trunc = (int(c) for c in counts.tolist())
+    rate = lambda k: k / done if done else float("nan")
+    return {"episodes": done, "reach_rate": rate(goal), "collision_rate": rate(hit), "truncation_rate": rate(trunc)}
+
+
+def run_dagger(args, net, env, out):
+    from ddrl4nav_amd.data import DemoPool
+    from ddrl4nav_amd.env import NavExpert
+    from ddrl4nav_amd.runner import dagger_loop
+    if args.robots > 1:
+        sys.exit("--dagger is built for the single-robot env: a FleetNavEnv has no expert")
+    log = out["dagger"] = {"iterations": args.dagger, "steps": args.dagger_steps, "lr": args.dagger_lr, "batch": args.dagger_batch,
+                           "epochs": args.dagger_epochs, "rounds": []}
+    if args.nav_status:
+        log["before"] = policy_outcomes(net, env, args.baseline_steps)
+        print("before cloning: %s" % log["before"], flush=True)
+    pool = DemoPool(env.state_shapes, 2, env.N * max(2, args.dagger_pool), device=net.device, n_envs=env.N)
+    t0 = time.time()
+    rounds = dagger_loop.run(net, env, NavExpert(env), pool, args.dagger, args.dagger_steps, lr=args.dagger_lr, batch=args.dagger_batch,
+                             epochs=args.dagger_epochs, seed=args.seed)
+    for i, (loss, beta) in enumerate(rounds, 1):
+        log["rounds"].append({"round": i, "beta": beta, "mean_clone_loss": loss, "rows": len(pool)})
+        print("dagger %3d  beta %.2f  rows %7d  mean clone loss %.5f  %.0f s" % (i, beta, len(pool), loss, time.time() - t0), flush=True)
+    if args.nav_status:
+        log["after"] = policy_outcomes(net, env, args.baseline_steps)
+        print("after cloning:  %s" % log["after"], flush=True)
+    env.reset()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -65,6 +111,12 @@ def main():
                     help="GAE goes on from the critic's value of a truncated episode's last observation (DESIGN.md section 6.12): the "
                          "env renders it, StateRollout(bootstrap_truncated=env.truncations_per_rollout(horizon)) files and evaluates it")
     ap.add_argument("--robots", type=int, default=1, help="robots per world; above 1 the env is a FleetNavEnv and --envs counts worlds")
+    ap.add_argument("--dagger", type=int, default=0, help="rounds of DAgger ahead of the PPO updates (0: off)")
+    ap.add_argument("--dagger-steps", type=int, default=64, help="env steps collected per round")
+    ap.add_argument("--dagger-pool", type=int, default=256, help="the demonstration pool's depth in steps (rows = envs x this)")
+    ap.add_argument("--dagger-lr", type=float, default=3e-4)
+    ap.add_argument("--dagger-batch", type=int, default=1024)
+    ap.add_argument("--dagger-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--baseline-steps", type=int, default=1000)
     ap.add_argument("--log-every", type=int, default=10)
@@ -103,6 +155,8 @@ def main():
            "random_policy": {"return_per_episode": per_episode, "reward_per_env_per_1000_steps": per_1000, "steps": args.baseline_steps},
            "curve": []}
     print("random policy: %.3f per episode, %.2f per env per 1,000 steps" % (per_episode, per_1000), flush=True)
+    if args.dagger > 0:
+        run_dagger(args, net, env, out)
     t0 = time.time()
     for u, (losses, mean_return) in enumerate(train_states(net, env, ro, args.updates), 1):
         out["curve"].append({"update": u, "env_steps": u * rows * args.horizon, "mean_return": mean_return,
