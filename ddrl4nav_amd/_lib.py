@@ -253,6 +253,12 @@ SIGNATURES = {
     "ddrl_op_heads_bc_mse": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddrl_op_gather_rows_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ddrl_op_nav_env_step_model": (c_int32, [c_void_p, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "ddrl_op_fleet_env_step_model": (c_int32, [c_void_p, c_int32, c_int32, c_int64, ctypes.c_uint32, c_int32, c_int32, c_int32, c_int32,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
 }
 
 _lib = None

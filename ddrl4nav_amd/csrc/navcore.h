@@ -126,6 +126,86 @@ __device__ __forceinline__ void nav_walk_peds(const int* obs, int* peds, int* ev
   }
 }
 
+// Rule 1 under the pedestrian model "avoid" (tests/ped_avoid_ref.py is the rule book): a pedestrian gives way to
+// the other pedestrians and to the robots.  Its candidates are its step under the heading offsets 0, +D, -D, +2D, -2D, +3D, -3D, ranks
+// 0..6 in preference order.  A candidate is statically refused by nav_walk_peds' test, and agent-blocked when it is within NAV_KEEP of
+// another pedestrian or a robot and nearer to it than the pedestrian stands now.  Rank 0 statically refused: the pedestrian stays and
+// draws a heading, as in nav_walk_peds.  Else the lowest rank that is neither refused nor blocked moves it and its turn persists; no
+// such rank: it stays and draws a heading.
+constexpr int NAV_KEEP = 192, NAV_AVOID_D = 320, NAV_AVOID_RANKS = 7;
+static_assert(3 * NAV_AVOID_D < NAV_HEADINGS, "one wrap brings a candidate's heading into range");
+
+// By all 64 lanes of one wave in uniform control flow, as fleet_respawn: lane r < 7 tests the candidate of rank r, lanes 7..63 vote
+// "not free", and the first set bit of the ballot is the winning rank.  Every lane reads the pedestrians and the robots (MAXR blocks,
+// `stride` words apart at `robots`, R of them in use; where they stand before this step's moves) from LDS once, before anything is
+// written, and keeps them in registers (the loops over j, k and q are unrolled, so no register index is run-time); every lane applies
+// the winner's move to its own copy, the event counter advances uniformly in a register, and lane 0 alone writes the pedestrians'
+// words and the counter back when the walk is over.  Every product fits 32 bits (|coordinate| <= 2560 + 24).
+template <int MAXR>
+__device__ __forceinline__ void nav_walk_peds_avoid(const int* obs, int* peds, const int* robots, int stride, int R, int* events, int n_obs,
+                                                    int n_peds, uint32_t seed, uint32_t gidx, int lane) {
+  int px[NAV_MAX_PEDS], py[NAV_MAX_PEDS], ph[NAV_MAX_PEDS], ps[NAV_MAX_PEDS], rx[MAXR], ry[MAXR];
+#pragma unroll
+  for (int j = 0; j < NAV_MAX_PEDS; ++j) {
+    px[j] = peds[4 * j];
+    py[j] = peds[4 * j + 1];
+    ph[j] = peds[4 * j + 2];
+    ps[j] = peds[4 * j + 3];
+  }
+#pragma unroll
+  for (int q = 0; q < MAXR; ++q) {
+    rx[q] = robots[stride * q + NS_X];
+    ry[q] = robots[stride * q + NS_Y];
+  }
+  uint32_t counter = (uint32_t)*events;
+  const bool ranks = lane < NAV_AVOID_RANKS;
+  const int turn = ranks ? ((lane + 1) >> 1) * ((lane & 1) ? NAV_AVOID_D : -NAV_AVOID_D) : 0;  // 0, +D, -D, +2D, -2D, +3D, -3D
+#pragma unroll
+  for (int j = 0; j < NAV_MAX_PEDS; ++j) {
+    if (j >= n_peds) continue;  // uniform over the wave
+    int h = ph[j] + turn;       // -960 .. 3839 + 960
+    h = h < 0 ? h + NAV_HEADINGS : (h >= NAV_HEADINGS ? h - NAV_HEADINGS : h);
+    const int cx = px[j] + ((ps[j] * nav_cos(h)) >> NAV_Q), cy = py[j] + ((ps[j] * nav_sin(h)) >> NAV_Q);
+    bool refused = cx * cx + cy * cy > (NAV_ARENA_R - NAV_PED_R) * (NAV_ARENA_R - NAV_PED_R);
+    for (int k = 0; k < n_obs; ++k) {
+      const int dx = cx - obs[3 * k], dy = cy - obs[3 * k + 1], rr = NAV_PED_R + obs[3 * k + 2];
+      refused = refused || dx * dx + dy * dy < rr * rr;
+    }
+    bool blocked = false;
+#pragma unroll
+    for (int k = 0; k < NAV_MAX_PEDS; ++k) {
+      if (k == j || k >= n_peds) continue;  // uniform over the wave
+      const int dx = cx - px[k], dy = cy - py[k], ex = px[j] - px[k], ey = py[j] - py[k], dd = dx * dx + dy * dy;
+      blocked = blocked || (dd < NAV_KEEP * NAV_KEEP && dd < ex * ex + ey * ey);
+    }
+#pragma unroll
+    for (int q = 0; q < MAXR; ++q) {
+      if (q >= R) continue;  // uniform over the wave
+      const int dx = cx - rx[q], dy = cy - ry[q], ex = px[j] - rx[q], ey = py[j] - ry[q], dd = dx * dx + dy * dy;
+      blocked = blocked || (dd < NAV_KEEP * NAV_KEEP && dd < ex * ex + ey * ey);
+    }
+    const unsigned long long stat = __ballot(refused), vote = __ballot(ranks && !refused && !blocked);
+    if (!(stat & 1ull) && vote != 0ull) {  // uniform over the wave: the lowest free rank moves the pedestrian, and its turn persists
+      const int win = __ffsll((long long)vote) - 1;
+      px[j] = __shfl(cx, win);
+      py[j] = __shfl(cy, win);
+      ph[j] = __shfl(h, win);
+    } else {  // the way ahead is refused, or every rank is taken: the pedestrian stays and draws a heading
+      ph[j] = (int)(nav_hash(seed, gidx, counter++) % (uint32_t)NAV_HEADINGS);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < NAV_MAX_PEDS; ++j) {
+      if (j >= n_peds) continue;
+      peds[4 * j] = px[j];
+      peds[4 * j + 1] = py[j];
+      peds[4 * j + 2] = ph[j];
+    }
+    *events = (int)counter;
+  }
+}
+
 // rules 2 and 3 on the robot block `rb`: the action (v, w) as nav_decode gives it turns and moves it; -> the reward units of its progress
 // towards the goal
 __device__ __forceinline__ int nav_move_robot(int* rb, int v, int w) {
@@ -370,6 +450,15 @@ __device__ __forceinline__ void nav_render_row(const int* me, const int* obs, co
 inline bool nav_range_ok(int32_t n, int64_t env0, int32_t n_obs, int32_t n_peds) {
   return n >= 1 && env0 >= 0 && env0 + (int64_t)n <= ((int64_t)1 << 32) && n_obs >= 0 && n_obs <= NAV_MAX_OBS && n_peds >= 0 &&
          n_peds <= NAV_MAX_PEDS;
+}
+
+// the pedestrian model of a ddrl_op_*_env_step_model call: DDRL_PED_WALK or DDRL_PED_AVOID
+inline bool nav_ped_model_ok(int32_t ped_model) { return ped_model == DDRL_PED_WALK || ped_model == DDRL_PED_AVOID; }
+
+// the optional terminal triple of a ddrl_op_*_env_step_model call: 1 all three given, 0 all three null, -1 given in part
+inline int nav_final_given(float* const* final_obs) {
+  const int given = (final_obs[0] != nullptr) + (final_obs[1] != nullptr) + (final_obs[2] != nullptr);
+  return given == 3 ? 1 : (given == 0 ? 0 : -1);
 }
 
 // what a call writes, for reads_and_writes_apart: the state, an observation triple, the step's scalars, the terminal triple

@@ -40,12 +40,13 @@ __device__ void nav_new_episode(int* s, int n_obs, int n_peds, uint32_t seed, ui
 // rules 1 to 6 of one step on the LDS copy (NavEnvRef.step): everything but the new episode of a finished env, which the caller draws
 // (nav_new_episode) when *done_out is set.
 // INFO: *info_out receives the info word; the state, the units and the done are the same either way.
-template <bool INFO>
+// AVOID: rule 1 is not played here -- wave 0 has played it (nav_walk_peds_avoid) before this thread goes on with rules 2 to 6.
+template <bool INFO, bool AVOID>
 __device__ void nav_advance(int* s, float a0, float a1, int n_obs, int n_peds, int max_steps, uint32_t seed, uint32_t genv, int* units_out,
                             int* done_out, int* info_out) {
   int v, w;
   nav_decode(a0, a1, &v, &w);
-  nav_walk_peds(s + NS_OBS0, s + NS_PED0, s + NS_EVENTS, n_obs, n_peds, seed, genv);
+  if (!AVOID) nav_walk_peds(s + NS_OBS0, s + NS_PED0, s + NS_EVENTS, n_obs, n_peds, seed, genv);
   int units = nav_move_robot(s, v, w);
   NavHits hit;
   nav_hits(s[NS_X], s[NS_Y], s + NS_OBS0, s + NS_PED0, n_obs, n_peds, &hit);
@@ -87,8 +88,10 @@ __device__ __forceinline__ void nav_render(const int* s, int (*ped)[4], int n_ob
 
 // INFO: the instantiation behind ddrl_op_nav_env_step_info; `info` is not touched otherwise.  FINAL (with INFO): the one behind
 // ddrl_op_nav_env_step_final -- a truncated env (uniform over its workgroup) also renders the state rule 6 left into final_*, and only
-// behind a further barrier does thread 0 draw the next episode; final_* are not touched otherwise.
-template <bool INFO, bool FINAL>
+// behind a further barrier does thread 0 draw the next episode; final_* are not touched otherwise.  AVOID: the pedestrian model "avoid"
+//  -- wave 0 walks the pedestrians before thread 0, one of its lanes, plays the rest of the step: lane 0 wrote the
+// words it then reads, and nobody else reads them before the barrier.
+template <bool INFO, bool FINAL, bool AVOID>
 __global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __restrict__ state, int64_t env0, uint32_t seed, int n_obs,
                                                                    int n_peds, int max_steps, const float* __restrict__ actions,
                                                                    float* __restrict__ laser, float* __restrict__ vector,
@@ -106,9 +109,11 @@ __global__ __launch_bounds__(NAV_THREADS) void nav_env_step_kernel(int32_t* __re
   int32_t* st = state + i * NAV_STATE_INTS;
   if (tid < NAV_STATE_INTS) s[tid] = nav_sanitize_word(tid, st[tid], n_obs, n_peds);
   __syncthreads();  // the old state is in LDS: nothing reads the env's global words after this, thread 0 alone writes them
+  if (AVOID && tid < 64)  // wave 0, uniform
+    nav_walk_peds_avoid<1>(s + NS_OBS0, s + NS_PED0, s, 0, 1, s + NS_EVENTS, n_obs, n_peds, seed, genv, tid);
   if (tid == 0) {
     int units, d, word = 0;
-    nav_advance<INFO>(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, genv, &units, &d, &word);
+    nav_advance<INFO, AVOID>(s, actions[2 * i], actions[2 * i + 1], n_obs, n_peds, max_steps, seed, genv, &units, &d, &word);
     const bool held = FINAL && (word & NI_TRUNC);  // the state the episode ended in is rendered before the next one is drawn
     if (d && !held) nav_new_episode(s, n_obs, n_peds, seed, genv);
     reward[i] = (float)units * 0.00390625f;
@@ -144,6 +149,22 @@ __global__ __launch_bounds__(NAV_THREADS) void nav_env_reset_kernel(int32_t* __r
   nav_render(s, ped, n_obs, n_peds, laser + i * NAV_BEAMS, vector + i * NAV_VECTOR, image + i * NAV_MAP_FLOATS);
 }
 
+// the launches of one pedestrian model: the step kernel behind each set of outputs
+template <bool AVOID>
+static void nav_env_step_forms(dim3 grid, dim3 block, hipStream_t st, int32_t* state, int64_t env0, uint32_t seed, int32_t n_obstacles,
+                               int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
+                               float* reward, uint8_t* done, int32_t* info, bool with_info, float* const* final_obs) {
+  if (final_obs)
+    hipLaunchKernelGGL((nav_env_step_kernel<true, true, AVOID>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps,
+                       actions, laser, vector, image, reward, done, info, final_obs[0], final_obs[1], final_obs[2]);
+  else if (with_info)
+    hipLaunchKernelGGL((nav_env_step_kernel<true, false, AVOID>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps,
+                       actions, laser, vector, image, reward, done, info, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  else
+    hipLaunchKernelGGL((nav_env_step_kernel<false, false, AVOID>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps,
+                       actions, laser, vector, image, reward, done, (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+}
+
 }  // namespace ddrl
 
 using namespace ddrl;
@@ -170,48 +191,56 @@ int32_t ddrl_op_nav_env_reset(int32_t* state, int32_t n, int64_t env0, uint32_t 
   return launch_status();
 }
 
-// the three step entries: `info` is given (and checked like the other outputs) by ddrl_op_nav_env_step_info and _final, `final_obs`
-// (laser, vector, image) by ddrl_op_nav_env_step_final alone
+// the step entries: `info` is given (and checked like the other outputs) by ddrl_op_nav_env_step_info and _final, `final_obs` (laser,
+// vector, image) by ddrl_op_nav_env_step_final alone; ddrl_op_nav_env_step_model chooses among the three forms by what it is given, and
+// the pedestrian model
 static int32_t nav_env_step_launch(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
-                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
-                                   uint8_t* done, int32_t* info, bool with_info, float* const* final_obs, void* stream) {
-  if (!nav_range_ok(n, env0, n_obstacles, n_peds) || max_steps < 1 ||
+                                   int32_t max_steps, int32_t ped_model, const float* actions, float* laser, float* vector, float* image,
+                                   float* reward, uint8_t* done, int32_t* info, bool with_info, float* const* final_obs, void* stream) {
+  if (!nav_range_ok(n, env0, n_obstacles, n_peds) || max_steps < 1 || !nav_ped_model_ok(ped_model) ||
       !nav_step_args_ok(state, (uint64_t)n * NAV_STATE_INTS * 4, (uint64_t)n, actions, laser, vector, image, reward, done, info,
                         with_info, final_obs))
     return DDRL_ERR_INVALID_ARG;
   const dim3 grid((unsigned)n), block(NAV_THREADS);
-  hipStream_t st = (hipStream_t)stream;
-  if (final_obs)
-    hipLaunchKernelGGL((nav_env_step_kernel<true, true>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
-                       laser, vector, image, reward, done, info, final_obs[0], final_obs[1], final_obs[2]);
-  else if (with_info)
-    hipLaunchKernelGGL((nav_env_step_kernel<true, false>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
-                       laser, vector, image, reward, done, info, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  if (ped_model == DDRL_PED_WALK)
+    nav_env_step_forms<false>(grid, block, (hipStream_t)stream, state, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector,
+                              image, reward, done, info, with_info, final_obs);
   else
-    hipLaunchKernelGGL((nav_env_step_kernel<false, false>), grid, block, 0, st, state, env0, seed, n_obstacles, n_peds, max_steps, actions,
-                       laser, vector, image, reward, done, (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+    nav_env_step_forms<true>(grid, block, (hipStream_t)stream, state, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector,
+                             image, reward, done, info, with_info, final_obs);
   return launch_status();
 }
 
 int32_t ddrl_op_nav_env_step(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds, int32_t max_steps,
                              const float* actions, float* laser, float* vector, float* image, float* reward, uint8_t* done, void* stream) {
-  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, nullptr,
-                             false, nullptr, stream);
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, DDRL_PED_WALK, actions, laser, vector, image, reward,
+                             done, nullptr, false, nullptr, stream);
 }
 
 int32_t ddrl_op_nav_env_step_info(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
                                   int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
                                   uint8_t* done, int32_t* info, void* stream) {
-  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info, true,
-                             nullptr, stream);
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, DDRL_PED_WALK, actions, laser, vector, image, reward,
+                             done, info, true, nullptr, stream);
 }
 
 int32_t ddrl_op_nav_env_step_final(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
                                    int32_t max_steps, const float* actions, float* laser, float* vector, float* image, float* reward,
                                    uint8_t* done, int32_t* info, float* final_laser, float* final_vector, float* final_image, void* stream) {
   float* const final_obs[3] = {final_laser, final_vector, final_image};
-  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, actions, laser, vector, image, reward, done, info, true,
-                             final_obs, stream);
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, DDRL_PED_WALK, actions, laser, vector, image, reward,
+                             done, info, true, final_obs, stream);
+}
+
+int32_t ddrl_op_nav_env_step_model(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                   int32_t max_steps, int32_t ped_model, const float* actions, float* laser, float* vector, float* image,
+                                   float* reward, uint8_t* done, int32_t* info, float* final_laser, float* final_vector,
+                                   float* final_image, void* stream) {
+  float* const final_obs[3] = {final_laser, final_vector, final_image};
+  const int given = nav_final_given(final_obs);
+  if (given < 0 || (given && !info)) return DDRL_ERR_INVALID_ARG;
+  return nav_env_step_launch(state, n, env0, seed, n_obstacles, n_peds, max_steps, ped_model, actions, laser, vector, image, reward, done,
+                             info, info != nullptr, given ? final_obs : nullptr, stream);
 }
 
 }  // extern "C"

@@ -23,12 +23,17 @@ def truncations_per_rollout(horizon, max_steps):
 
 class NavArenaEnv(DeviceEnvBase):
     """What DeviceNavEnv and FleetNavEnv (env/fleet_nav_env.py) share: the arena's populations and max_steps with their checks, the
-    observation, info and terminal-observation tensors (a row per robot), where a call renders to, and the knobs of a config_env."""
+    observation, info and terminal-observation tensors (a row per robot), where a call renders to, the pedestrian model, and the knobs
+    of a config_env."""
     state_shapes = [tuple(s) for s in ops.NAV_ENV_SHAPES]
 
-    def __init__(self, n_states, rows_per_state, device, seed, n_obstacles, n_peds, max_steps, index0, emit_info, emit_final_obs):
-        """After the subclass's own checks.  emit_final_obs implies emit_info."""
+    def __init__(self, n_states, rows_per_state, device, seed, n_obstacles, n_peds, max_steps, index0, emit_info, emit_final_obs,
+                 ped_model="walk"):
+        """After the subclass's own checks.  emit_final_obs implies emit_info.  ped_model: "walk" or "avoid" (DESIGN.md section 6.16)."""
         self.n_obstacles, self.n_peds, self.max_steps = int(n_obstacles), int(n_peds), int(max_steps)
+        if not isinstance(ped_model, str) or ped_model not in ops.NAV_PED_MODELS:
+            raise ValueError("ped_model must be one of %r, got %r" % (ops.NAV_PED_MODELS, ped_model))
+        self.ped_model = ped_model
         if not 0 <= self.n_obstacles <= 10:
             raise ValueError("n_obstacles must be in 0..10, got %d" % self.n_obstacles)
         if not 0 <= self.n_peds <= 5:
@@ -59,28 +64,35 @@ class NavArenaEnv(DeviceEnvBase):
         StateRollout(bootstrap_truncated=...) drops none."""
         return truncations_per_rollout(horizon, self.max_steps)
 
+    def load_state_dict(self, sd):
+        """A state_dict saved before there was a choice of pedestrian model is one of "walk"."""
+        super().load_state_dict(sd if "ped_model" in sd else dict(sd, ped_model="walk"))
+
 
 def arena_config_kw(config_env):
     """The optional knobs of a config_env both nav envs read: env_seed, env_obstacles, env_peds, env_max_steps, env_info (emit_info),
-    env_final_obs (emit_final_obs)."""
+    env_final_obs (emit_final_obs), env_ped_model ("walk", the default, or "avoid")."""
     return dict(seed=int(config_env.get("env_seed", 0)), n_obstacles=int(config_env.get("env_obstacles", 10)),
                 n_peds=int(config_env.get("env_peds", 5)), max_steps=int(config_env.get("env_max_steps", 500)),
-                emit_info=bool(config_env.get("env_info", False)), emit_final_obs=bool(config_env.get("env_final_obs", False)))
+                emit_info=bool(config_env.get("env_info", False)), emit_final_obs=bool(config_env.get("env_final_obs", False)),
+                ped_model=config_env.get("env_ped_model", "walk"))
 
 
 class DeviceNavEnv(NavArenaEnv):
-    _PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0")
+    _PARAMS = ("n_envs", "seed", "n_obstacles", "n_peds", "max_steps", "env0", "ped_model")
     _state_ints = staticmethod(ops.nav_env_state_ints)
 
     def __init__(self, n_envs, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, env0=0, emit_info=False,
-                 emit_final_obs=False):
+                 emit_final_obs=False, ped_model="walk"):
         """n_obstacles 0..10 static circles, n_peds 0..5 pedestrians; an episode ends at a collision, at the goal or after max_steps
         steps (a truncation counts as a done).  env0: the global index of local env 0, as for DeviceEnv.  emit_info: every step also
         fills ``info`` (int32 [N]: why the step ended or did not, ops.nav_info_fields; agent.NavStatus accumulates it); the trajectory is
         the same either way.  emit_final_obs (implies emit_info): a step that truncates an env's episode also
         renders the observation that episode ended in into row i of ``final_obs`` ([laser, vector, image], [N, ...] each; the rows of
-        the other envs keep what they held), for a rollout that bootstraps truncated episodes."""
-        super().__init__(n_envs, 1, device, seed, n_obstacles, n_peds, max_steps, env0, emit_info, emit_final_obs)
+        the other envs keep what they held), for a rollout that bootstraps truncated episodes.  ped_model:
+        "walk", pedestrians that walk straight ahead and turn at walls and obstacles only, or "avoid", pedestrians that also give way to
+        each other and to the robot; anything else is a ValueError.  With "walk" the env calls the operators it has always called."""
+        super().__init__(n_envs, 1, device, seed, n_obstacles, n_peds, max_steps, env0, emit_info, emit_final_obs, ped_model)
 
     def reset(self, mask=None, obs_out=None):
         """A new first episode for every env, or for those with a non-zero entry in mask (uint8 [N] on the device); returns the
@@ -97,6 +109,8 @@ class DeviceNavEnv(NavArenaEnv):
         final = self._final_out(final_out)
         args = (self.state, actions, self._obs_out(obs_out), self.reward, self.done)
         kw = dict(env0=self.env0, max_steps=self.max_steps, **self._arena_kw())
+        if self.ped_model != "walk":
+            return ops.nav_env_step_model(*args, self.info, final, ped_model=self.ped_model, **kw)
         if self.emit_final_obs:
             return ops.nav_env_step_final(*args, self.info, final, **kw)[:3]
         if self.emit_info:

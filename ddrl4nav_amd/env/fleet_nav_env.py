@@ -12,18 +12,19 @@ FLEET_ENV_NAME = "DeviceNavFleet-v0"
 
 
 class FleetNavEnv(NavArenaEnv):
-    _PARAMS = ("n_worlds", "n_robots", "seed", "n_obstacles", "n_peds", "max_steps", "world0")
+    _PARAMS = ("n_worlds", "n_robots", "seed", "n_obstacles", "n_peds", "max_steps", "world0", "ped_model")
     _state_ints = staticmethod(ops.fleet_env_state_ints)
 
     def __init__(self, n_worlds, n_robots, device=None, seed=0, n_obstacles=10, n_peds=5, max_steps=500, world0=0, emit_info=False,
-                 emit_final_obs=False):
+                 emit_final_obs=False, ped_model="walk"):
         """n_worlds arenas of n_robots 1..4 robots, n_obstacles 0..10 static circles and n_peds 0..5 pedestrians each.  A robot's episode
         ends at a collision (wall, obstacle, pedestrian, another robot), at its goal or after max_steps steps; it alone respawns, the
         world stays.  world0: the global index of local world 0, as DeviceNavEnv's env0.  emit_info: every step also fills ``info``
         (int32 [N], ops.nav_info_fields; agent.NavStatus accumulates it, one status row per robot); the trajectory is the same either
         way.  emit_final_obs (implies emit_info): a step that truncates a robot's episode also renders what that
         robot saw at its end -- every robot where it is after all moves and before any respawn -- into its row of ``final_obs``
-        ([laser, vector, image], [N, ...] each; the other rows keep what they held)."""
+        ([laser, vector, image], [N, ...] each; the other rows keep what they held).  ped_model: "walk" or "avoid", as DeviceNavEnv's;
+        under "avoid" the pedestrians give way to each other and to every robot."""
         self.n_worlds, self.n_robots, self.world0 = int(n_worlds), int(n_robots), int(world0)
         if self.n_worlds < 1:
             raise ValueError("n_worlds must be at least 1, got %d" % self.n_worlds)
@@ -34,7 +35,7 @@ class FleetNavEnv(NavArenaEnv):
         if self.n_worlds * self.n_robots >= 2 ** 31:
             raise ValueError("n_worlds * n_robots must fit int32")
         super().__init__(self.n_worlds, self.n_robots, device, seed, n_obstacles, n_peds, max_steps, self.world0, emit_info,
-                         emit_final_obs)                                 # N = the rows: what device_loop compares with a rollout's N
+                         emit_final_obs, ped_model)                      # N = the rows: what device_loop compares with a rollout's N
 
     def reset(self, mask=None, obs_out=None):
         """A new world for every world, or for those with a non-zero entry in mask (uint8 [n_worlds] on the device: one byte per WORLD);
@@ -51,6 +52,8 @@ class FleetNavEnv(NavArenaEnv):
         final = self._final_out(final_out)
         args = (self.state, self.n_robots, actions, self._obs_out(obs_out), self.reward, self.done, self.info)
         kw = dict(world0=self.world0, max_steps=self.max_steps, **self._arena_kw())
+        if self.ped_model != "walk":
+            return ops.fleet_env_step_model(*args, final, ped_model=self.ped_model, **kw)
         if self.emit_final_obs:
             return ops.fleet_env_step_final(*args, final, **kw)
         return ops.fleet_env_step(*args, **kw)

@@ -4,7 +4,11 @@ The reference's imitation start (MIMIC_START, Basenn.imitation_learning) needs d
 (sh/start_dagger.sh is empty).  On the device env the expert may read the env's privileged state, so labelling every state a learner
 visits -- DAgger -- costs one small launch per step: 51 constant-(v, w) arcs are rolled ten steps ahead against the wall, the obstacles
 and the pedestrians' straight-line predictions, and the arc that gets nearest to the goal without a hit wins.  The rules are
-integer-only (tests/nav_expert_ref.py is the rule book), so labels are reproducible bit for bit from the env's state."""
+integer-only (tests/nav_expert_ref.py is the rule book), so labels are reproducible bit for bit from the env's state.
+
+The expert is the same under both pedestrian models of the env: it reads the state, which has the same words
+under "walk" and "avoid", and predicts every pedestrian straight ahead at its current heading.  Under "avoid" that prediction is wrong
+where a pedestrian turns away, which only adds margin; the expert's reach rate on the rule book's env is higher there (section 6.16)."""
 import torch
 
 from ddrl4nav_amd import ops

@@ -531,6 +531,43 @@ def nav_env_step_final(state, actions, obs, reward, done, info, final_obs, env0=
     return obs, reward, done, info, final_obs
 
 
+NAV_PED_MODELS = ("walk", "avoid")      # include/ddrl.h DDRL_PED_WALK, DDRL_PED_AVOID: the value is the index
+
+
+def nav_ped_model(ped_model):
+    """The DDRL_PED_* value of a pedestrian model given by name ("walk", "avoid") or by value (0, 1); anything else is a ValueError."""
+    if isinstance(ped_model, str):
+        if ped_model in NAV_PED_MODELS:
+            return NAV_PED_MODELS.index(ped_model)
+    elif isinstance(ped_model, int) and not isinstance(ped_model, bool) and 0 <= ped_model < len(NAV_PED_MODELS):
+        return ped_model
+    raise ValueError("ped_model must be one of %r, got %r" % (NAV_PED_MODELS, ped_model))
+
+
+def _arena_model_tail(state, state_ints, rows_per_state, rows, info, final_obs):
+    """The optional outputs of a *_env_step_model call after their checks, as the C entry points take them: info, final_* (nulls for
+    what is not given; final_obs needs info)."""
+    if info is not None or final_obs is not None:
+        _arena_info_ok(state, rows, info)
+    if final_obs is None:
+        return _p(info), c_void_p(0), c_void_p(0), c_void_p(0)
+    _arena_args(state, state_ints, rows_per_state, final_obs, what="final_obs")
+    return (_p(info),) + _p3(final_obs)
+
+
+def nav_env_step_model(state, actions, obs, reward, done, info=None, final_obs=None, ped_model="walk", env0=0, seed=0, n_obstacles=10,
+                       n_peds=5, max_steps=500):
+    """One step of every env under a pedestrian model (include/ddrl.h ddrl_op_nav_env_step_model): "walk" is
+    nav_env_step's rule 1, under "avoid" the pedestrians give way to each other and to the robot (tests/ped_avoid_ref.py).  info int32
+    [n] and final_obs = [laser, vector, image] are optional outputs, nav_env_step_info's and nav_env_step_final's (final_obs needs info).
+    With "walk" the outputs are bit-identical to the entry point that takes the same outputs.  Asynchronous on the current stream;
+    returns (obs, reward, done)."""
+    args = _nav_env_step_args(state, actions, obs, reward, done, env0, seed, n_obstacles, n_peds, max_steps)
+    tail = _arena_model_tail(state, nav_env_state_ints(), 1, args[1], info, final_obs)
+    check(_lib.load().ddrl_op_nav_env_step_model(*args[:7], nav_ped_model(ped_model), *args[7:], *tail, _st()))
+    return obs, reward, done
+
+
 def beta_threshold(beta):
     """The uint32 threshold of DAgger's mixing rate: min(2^32 - 1, floor(beta 2^32)); an env plays the expert where its draw is below."""
     beta = float(beta)
@@ -659,6 +696,17 @@ def fleet_env_step_final(state, n_robots, actions, obs, reward, done, info, fina
     args = _fleet_env_step_args(state, n_robots, actions, obs, reward, done, info, True, world0, seed, n_obstacles, n_peds, max_steps)
     _arena_args(state, fleet_env_state_ints(), int(n_robots), final_obs, what="final_obs")
     check(_lib.load().ddrl_op_fleet_env_step_final(*args, *_p3(final_obs), _st()))
+    return obs, reward, done
+
+
+def fleet_env_step_model(state, n_robots, actions, obs, reward, done, info=None, final_obs=None, ped_model="walk", world0=0, seed=0,
+                         n_obstacles=10, n_peds=5, max_steps=500):
+    """One step of every world under a pedestrian model (include/ddrl.h ddrl_op_fleet_env_step_model), as
+    nav_env_step_model: under "avoid" the pedestrians give way to each other and to every robot.  info and final_obs are optional outputs,
+    fleet_env_step's and fleet_env_step_final's (final_obs needs info).  Asynchronous on the current stream; returns (obs, reward, done)."""
+    args = _fleet_env_step_args(state, n_robots, actions, obs, reward, done, None, False, world0, seed, n_obstacles, n_peds, max_steps)
+    tail = _arena_model_tail(state, fleet_env_state_ints(), int(n_robots), state.shape[0] * int(n_robots), info, final_obs)
+    check(_lib.load().ddrl_op_fleet_env_step_model(*args[:8], nav_ped_model(ped_model), *args[8:-1], *tail, _st()))
     return obs, reward, done
 
 

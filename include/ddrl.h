@@ -901,6 +901,30 @@ int32_t ddrl_op_fleet_env_step_final(int32_t* state, int32_t n_worlds, int32_t n
                                      int32_t n_peds, int32_t max_steps, const float* actions, float* laser, float* vector, float* image,
                                      float* reward, uint8_t* done, int32_t* info, float* final_laser, float* final_vector,
                                      float* final_image, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * The pedestrian model (tests/ped_avoid_ref.py is the rule book of "avoid").  DDRL_PED_WALK is rule 1 of the
+ * entry points above: a pedestrian walks straight ahead and draws a new heading when the wall or an obstacle refuses its step.  Under
+ * DDRL_PED_AVOID it also gives way to the other pedestrians and to the robots: of its step under the heading offsets 0, +30, -30, +60,
+ * -60, +90, -90 degrees it takes the first that neither the wall nor an obstacle refuses and that does not bring it within 0.75 m of
+ * another pedestrian or a robot while coming nearer to it; the turn persists.  A refused step straight ahead, or no step left, costs one
+ * draw of a new heading, as under DDRL_PED_WALK.  No state word is added, and resets, placement, respawn and every other rule are the
+ * same.  One entry point per env takes the model and every optional output of the entry points above:
+ *   info     NULL or int32 [rows]: the info word, as ddrl_op_nav_env_step_info's
+ *   final_*  all three NULL, or all three given (then info is required): the terminal observation, as ddrl_op_*_env_step_final's
+ * With ped_model == DDRL_PED_WALK every output is bit-identical to the entry point above that takes the same outputs (the same kernels
+ * are launched).  ped_model outside the two values, final_* given in part or without info, and everything the entry points above
+ * refuse: DDRL_ERR_INVALID_ARG, decided before anything touches HIP.
+ * ------------------------------------------------------------------------------------------ */
+#define DDRL_PED_WALK 0
+#define DDRL_PED_AVOID 1
+int32_t ddrl_op_nav_env_step_model(int32_t* state, int32_t n, int64_t env0, uint32_t seed, int32_t n_obstacles, int32_t n_peds,
+                                   int32_t max_steps, int32_t ped_model, const float* actions, float* laser, float* vector, float* image,
+                                   float* reward, uint8_t* done, int32_t* info, float* final_laser, float* final_vector,
+                                   float* final_image, void* stream);
+int32_t ddrl_op_fleet_env_step_model(int32_t* state, int32_t n_worlds, int32_t n_robots, int64_t world0, uint32_t seed, int32_t n_obstacles,
+                                     int32_t n_peds, int32_t max_steps, int32_t ped_model, const float* actions, float* laser,
+                                     float* vector, float* image, float* reward, uint8_t* done, int32_t* info, float* final_laser,
+                                     float* final_vector, float* final_image, void* stream);
 /* Files the rows of flagged envs into a pool of S slots per env: for env n with (info[n] & mask) != 0 and 0 <= count[n] < S, row n of
  * every part's src (float32 [N][widths[k]]) is copied to dst[k] (float32 [S][N][widths[k]]) at [count[n]][n] and slot_out[n] = count[n];
  * a flagged env without room gets slot_out[n] = -1 and nothing is copied; either way count[n] (int32 [N], in/out) goes up by one, so an

@@ -9,7 +9,10 @@ against ddrl_op_fleet_env_step with the info word at R = 1, 2, 4, at the default
 not collide truncates in every step), and the filing launch ddrl_op_file_flagged_rows of the terminal rows into pools of depth 1.  Prints
 one JSON line.
 
-    python tools/bench_device_fleet_env.py [--rows 512] [--calls 200] [--samples 30] [--warmup 2]
+    python tools/bench_device_fleet_env.py [--rows 512] [--calls 200] [--samples 30] [--warmup 2] [--ped-model walk] [--models]
+
+--ped-model: the pedestrian model of every env above.  --models: instead of the legs above, ddrl_op_fleet_env_step
+with the info word under "walk" and under "avoid" at R = 1, 2, 4, the six legs alternating.
 """
 import argparse
 import json
@@ -31,6 +34,8 @@ def main():
     ap.add_argument("--calls", type=int, default=200, help="launches per sample")
     ap.add_argument("--samples", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ped-model", choices=("walk", "avoid"), default="walk")
+    ap.add_argument("--models", action="store_true", help="only the walk / avoid comparison")
     args = ap.parse_args()
     if args.rows < 4 or args.rows % 4:
         sys.exit("--rows must be a positive multiple of 4")
@@ -42,9 +47,13 @@ def main():
     actions = torch.rand((rows, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
     src = torch.rand((rows, OBS_FLOATS), device="cuda", generator=g)
     dst = torch.empty_like(src)
-    envs = {"nav_env_step": DeviceNavEnv(rows, device="cuda", seed=1)}
+    if args.models:
+        print(json.dumps({"tool": "bench_device_fleet_env", "rows": rows, "calls": args.calls, "device": torch.cuda.get_device_name(0),
+                          "models": model_legs(args, actions)}))
+        return
+    envs = {"nav_env_step": DeviceNavEnv(rows, device="cuda", seed=1, ped_model=args.ped_model)}
     for R in (1, 2, 4):
-        envs["fleet_env_step_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1)
+        envs["fleet_env_step_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, ped_model=args.ped_model)
     for env in envs.values():
         env.reset()
 
@@ -80,6 +89,39 @@ def main():
     print(json.dumps(out))
 
 
+def model_legs(args, actions):
+    """The step launch with the info word under both pedestrian models at R = 1, 2, 4, the six legs alternating."""
+    from ddrl4nav_amd.env import FleetNavEnv
+    rows = args.rows
+    envs = {"%s_R%d" % (model, R): FleetNavEnv(rows // R, R, device="cuda", seed=1, emit_info=True, ped_model=model)
+            for R in (1, 2, 4) for model in ("walk", "avoid")}
+    for env in envs.values():
+        env.reset()
+
+    def stepping(env):
+        def run():
+            for _ in range(args.calls):
+                env.step(actions)
+        return run
+
+    legs = {k: stepping(env) for k, env in envs.items()}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.samples):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    res = {k: summary(v, per=args.calls) for k, v in ms.items()}
+    for R in (1, 2, 4):
+        w, a = "walk_R%d" % R, "avoid_R%d" % R
+        res[w]["spread_us"] = halves_spread(ms[w], per=args.calls)
+        res[a]["over_walk"] = round(res[a]["median_us"] / res[w]["median_us"], 4)
+        res[a]["minus_walk_us"] = round(res[a]["median_us"] - res[w]["median_us"], 3)
+    return res
+
+
 def final_legs(args, actions):
     from ddrl4nav_amd import ops
     from ddrl4nav_amd.env import FleetNavEnv
@@ -87,8 +129,10 @@ def final_legs(args, actions):
     for name, max_steps in (("default_max_steps", 500), ("max_steps_1", 1)):
         envs = {}
         for R in (1, 2, 4):
-            envs["fleet_env_step_info_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_info=True)
-            envs["fleet_env_step_final_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_final_obs=True)
+            envs["fleet_env_step_info_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_info=True,
+                                                               ped_model=args.ped_model)
+            envs["fleet_env_step_final_R%d" % R] = FleetNavEnv(rows // R, R, device="cuda", seed=1, max_steps=max_steps, emit_final_obs=True,
+                                                                ped_model=args.ped_model)
         for env in envs.values():
             env.reset()
         last = envs["fleet_env_step_final_R4"]

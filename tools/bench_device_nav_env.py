@@ -22,9 +22,16 @@ legs of each measurement alternating:
   (f) bootstrap  the acting phase of (b) with the option on -- DeviceNavEnv(emit_final_obs=True), StateRollout(bootstrap_truncated=S),
                record() filing the rows -- against the same phase with it off, and finish() (with the extra forward) against finish().
 
+  (g) ped_model  the step launch under the pedestrian models "walk" and "avoid"  in the plain, info and final
+               forms, the six legs alternating, and "walk" through ddrl_op_nav_env_step_model against the entry that was there.
+
 Every leg is warmed up first; a leg reports the median, the p95 and the extremes of its samples.  Prints one JSON line.
 
     python tools/bench_device_nav_env.py [--envs 512] [--steps 256] [--calls 200] [--samples 30] [--runs 10] [--warmup 2]
+                                         [--ped-model walk] [--only LEGS]
+
+--ped-model: the pedestrian model of every env of legs (a) to (f).  --only: a comma-separated subset of kernel, info, status, final,
+acting, bootstrap, ped_model.
 """
 import argparse
 import json
@@ -69,7 +76,7 @@ def make_net(max_batch, seed=0, **config_nn):
 def kernel_legs(args):
     from ddrl4nav_amd.env import DeviceNavEnv
     N = args.envs
-    env = DeviceNavEnv(N, device="cuda", seed=1)
+    env = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1)
     env.reset()
     g = torch.Generator(device="cuda").manual_seed(0)
     actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
@@ -101,7 +108,7 @@ def kernel_legs(args):
 def info_legs(args):
     from ddrl4nav_amd.env import DeviceNavEnv
     N = args.envs
-    plain, told = DeviceNavEnv(N, device="cuda", seed=1), DeviceNavEnv(N, device="cuda", seed=1, emit_info=True)
+    plain, told = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1), DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1, emit_info=True)
     plain.reset()
     told.reset()
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -139,8 +146,8 @@ def final_legs(args):
     actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
     out = {}
     for name, max_steps in (("default_max_steps", 500), ("max_steps_1", 1)):
-        told = DeviceNavEnv(N, device="cuda", seed=1, max_steps=max_steps, emit_info=True)
-        final = DeviceNavEnv(N, device="cuda", seed=1, max_steps=max_steps, emit_final_obs=True)
+        told = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1, max_steps=max_steps, emit_info=True)
+        final = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1, max_steps=max_steps, emit_final_obs=True)
         told.reset()
         final.reset()
         pools = [torch.zeros((1,) + tuple(f.shape), device="cuda") for f in final.final_obs]
@@ -188,8 +195,8 @@ def bootstrap_legs(args):
     from ddrl4nav_amd.env import DeviceNavEnv
     N, T = args.envs, args.steps
     net = make_net(N)
-    plain = DeviceNavEnv(N, device="cuda", seed=1)
-    final = DeviceNavEnv(N, device="cuda", seed=1, emit_final_obs=True)
+    plain = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1)
+    final = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1, emit_final_obs=True)
     S = final.truncations_per_rollout(T)
     off = StateRollout(net, N, plain.state_shapes, horizon=T)
     on = StateRollout(net, N, final.state_shapes, horizon=T, bootstrap_truncated=S)
@@ -225,6 +232,52 @@ def bootstrap_legs(args):
     out["finish_on_minus_off_ms"] = round(out["finish_on"]["median_ms"] - out["finish_off"]["median_ms"], 4)
     out["S"] = S
     out["truncations_dropped"] = on.truncations_dropped()
+    return out
+
+
+def ped_model_legs(args):
+    from ddrl4nav_amd import ops
+    from ddrl4nav_amd.env import DeviceNavEnv
+    N = args.envs
+    g = torch.Generator(device="cuda").manual_seed(0)
+    actions = torch.rand((N, 2), device="cuda", generator=g) * torch.tensor([1.0, 2.0], device="cuda") - torch.tensor([0.0, 1.0], device="cuda")
+    forms = {"plain": {}, "info": dict(emit_info=True), "final": dict(emit_final_obs=True)}
+    envs = {"%s_%s" % (model, form): DeviceNavEnv(N, device="cuda", seed=1, ped_model=model, **kw)
+            for form, kw in forms.items() for model in ("walk", "avoid")}
+    for env in envs.values():
+        env.reset()
+    through = DeviceNavEnv(N, device="cuda", seed=1)       # "walk" through the entry point that takes the model
+    through.reset()
+
+    def leg(env):
+        def run():
+            for _ in range(args.calls):
+                env.step(actions)
+        return run
+
+    def walk_through_model():
+        for _ in range(args.calls):
+            ops.nav_env_step_model(through.state, actions, through.obs, through.reward, through.done, ped_model="walk", seed=1)
+
+    legs = {k: leg(env) for k, env in envs.items()}
+    legs["walk_plain_through_step_model"] = walk_through_model
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(args.samples):
+        for k, fn in legs.items():
+            ms[k].append(timed(fn))
+    out = {k: summary(v, per=args.calls) for k, v in ms.items()}
+    for form in forms:
+        w, a = "walk_%s" % form, "avoid_%s" % form
+        out[w]["spread_us"] = halves_spread(ms[w], per=args.calls)
+        out[a]["over_walk"] = round(out[a]["median_us"] / out[w]["median_us"], 4)
+        out[a]["minus_walk_us"] = round(out[a]["median_us"] - out[w]["median_us"], 3)
+    out["same_state_walk"] = bool(torch.equal(envs["walk_plain"].state, envs["walk_final"].state)
+                                  and torch.equal(envs["walk_plain"].state, through.state))
+    out["same_state_avoid"] = bool(torch.equal(envs["avoid_plain"].state, envs["avoid_final"].state))
     return out
 
 
@@ -264,7 +317,7 @@ def acting_legs(args):
     from ddrl4nav_amd.env import DeviceNavEnv
     N, T = args.envs, args.steps
     net = make_net(N)
-    env = DeviceNavEnv(N, device="cuda", seed=1)
+    env = DeviceNavEnv(N, device="cuda", ped_model=args.ped_model, seed=1)
     ro = StateRollout(net, N, env.state_shapes, horizon=T)
     env.reset(obs_out=ro.state_rows(0))
     ro.put_states_in_place(0)
@@ -312,12 +365,20 @@ def main():
     ap.add_argument("--samples", type=int, default=30)
     ap.add_argument("--runs", type=int, default=10, help="timed acting phases per leg")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ped-model", choices=("walk", "avoid"), default="walk", help="the pedestrian model of the envs of legs (a) to (f)")
+    ap.add_argument("--only", default=None, help="comma-separated legs to run (default: all)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_device_nav_env needs a GPU: there is nothing to measure without one")
-    out = {"tool": "bench_device_nav_env", "N": args.envs, "T": args.steps, "device": torch.cuda.get_device_name(0),
-           "kernel": kernel_legs(args), "info": info_legs(args), "status": status_legs(args), "final": final_legs(args),
-           "acting": acting_legs(args), "bootstrap": bootstrap_legs(args)}
+    legs = {"kernel": kernel_legs, "info": info_legs, "status": status_legs, "final": final_legs, "acting": acting_legs,
+            "bootstrap": bootstrap_legs, "ped_model": ped_model_legs}
+    only = list(legs) if args.only is None else args.only.split(",")
+    if any(k not in legs for k in only):
+        sys.exit("--only takes a comma-separated subset of %s" % ", ".join(legs))
+    out = {"tool": "bench_device_nav_env", "N": args.envs, "T": args.steps, "ped_model": args.ped_model,
+           "device": torch.cuda.get_device_name(0)}
+    for k in only:
+        out[k] = legs[k](args)
     print(json.dumps(out))
 
 

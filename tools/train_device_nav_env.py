@@ -7,7 +7,7 @@ a1 ~ U(-1, 1)) on the same env, measured first on the device over --baseline-ste
 
     python tools/train_device_nav_env.py [--envs 256] [--horizon 64] [--updates 100] [--obstacles 10] [--peds 5] [--max-steps 500]
                                          [--iters 4] [--actor-lr R] [--critic-lr R] [--normalize-obs] [--seed 0] [--out curve.json]
-                                         [--nav-status] [--robots 1] [--dagger ITERS]
+                                         [--nav-status] [--robots 1] [--dagger ITERS] [--ped-model walk]
 
 --nav-status: the env emits its info words and the rollout keeps the reference's navigation statistics on the device (agent.NavStatus;
 DESIGN.md section 6.9); reach, collision and truncation rates over the envs' latest 100 episodes are printed next to the return and
@@ -21,6 +21,9 @@ update) is printed and stored too.  --robots 1 is the single-robot env above.
 section 6.15) -- the net acts, the scripted expert (env.NavExpert) labels every visited state, GenericPPO.clone_actor fits the actor;
 beta goes from 1 to 0.  With --nav-status the net's mean action is played for --baseline-steps steps before and after, from the same
 reset, and the two reach rates are printed and stored: whether cloning helped is a measurement, not a claim.
+
+--ped-model avoid: the pedestrians give way to each other and to the robots (DESIGN.md section 6.16) instead of walking straight ahead;
+it goes with every option above.  The scripted expert of --dagger still predicts pedestrians that walk straight ahead.
 """
 import argparse
 import json
@@ -111,6 +114,8 @@ def main():
                     help="GAE goes on from the critic's value of a truncated episode's last observation (DESIGN.md section 6.12): the "
                          "env renders it, StateRollout(bootstrap_truncated=env.truncations_per_rollout(horizon)) files and evaluates it")
     ap.add_argument("--robots", type=int, default=1, help="robots per world; above 1 the env is a FleetNavEnv and --envs counts worlds")
+    ap.add_argument("--ped-model", choices=("walk", "avoid"), default="walk",
+                    help="avoid: pedestrians that give way to each other and to the robots (DESIGN.md section 6.16)")
     ap.add_argument("--dagger", type=int, default=0, help="rounds of DAgger ahead of the PPO updates (0: off)")
     ap.add_argument("--dagger-steps", type=int, default=64, help="env steps collected per round")
     ap.add_argument("--dagger-pool", type=int, default=256, help="the demonstration pool's depth in steps (rows = envs x this)")
@@ -139,7 +144,7 @@ def main():
     net = make_net(max(args.micro_batch, rows), seed=args.seed, **knobs)
     config_env = {"env_name": "DeviceNav-v0", "env_num": args.envs, "env_seed": args.seed, "env_obstacles": args.obstacles,
                   "env_peds": args.peds, "env_max_steps": args.max_steps, "env_info": args.nav_status,
-                  "env_final_obs": args.bootstrap_truncated}
+                  "env_final_obs": args.bootstrap_truncated, "env_ped_model": args.ped_model}
     if args.robots > 1:
         config_env.update(env_name="DeviceNavFleet-v0", agent_num_per_env=args.robots)
     env = make_device_env(config_env, device=net.device)
@@ -149,7 +154,7 @@ def main():
 
     per_episode, per_1000 = random_policy_return(env, args.baseline_steps, args.seed + 1)
     out = {"tool": "train_device_nav_env", "N": rows, "robots": args.robots, "T": args.horizon, "obstacles": args.obstacles, "peds": args.peds,
-           "max_steps": args.max_steps, "iters": args.iters, "normalize_obs": bool(args.normalize_obs),
+           "ped_model": args.ped_model, "max_steps": args.max_steps, "iters": args.iters, "normalize_obs": bool(args.normalize_obs),
            "bootstrap_truncated": ro.S,
            "device": torch.cuda.get_device_name(0),
            "random_policy": {"return_per_episode": per_episode, "reward_per_env_per_1000_steps": per_1000, "steps": args.baseline_steps},
