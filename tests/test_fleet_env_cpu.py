@@ -5,8 +5,6 @@ No GPU."""
 import functools
 import itertools
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,8 +12,8 @@ import pytest
 import fleet_env_ref as F
 import nav_env_ref as R
 import nav_status_ref as S
+from arena_abi import BASE, caller, common_refusals, header_declares, overlaps, refused, sizes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_fleet_env_state_ints", "ddrl_op_fleet_env_reset", "ddrl_op_fleet_env_step")
 
 
@@ -245,76 +243,34 @@ def test_nav_status_ref_counts_the_other_robot_collisions():
 
 # ---- 4. header, binding, wrappers -------------------------------------------------------------------------------------------------------------
 def test_header_declares_what_the_binding_binds():
-    from ddrl4nav_amd import _lib, ops
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        args = 0 if m.group(1).strip() == "void" else m.group(1).count(",") + 1
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == args, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [0, 12, 16]
-    assert re.search(r"#define\s+DDRL_ABI_VERSION\s+3\b", text) and _lib.ABI_VERSION == 3
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW) and lib.ddrl_abi_version() == 3
+    from ddrl4nav_amd import ops
+    _, lib = header_declares(NEW, [0, 12, 16])
     assert lib.ddrl_op_fleet_env_state_ints() == F.STATE_INTS == ops.fleet_env_state_ints() == 96
     assert ops.FLEET_ENV_MAX_ROBOTS == F.MAX_ROBOTS == 4
     assert ops.nav_env_state_ints() == 64 and ops.NAV_STATUS_SUMMARY == 22 and ops.ENV_GAMES == {"pong": 0, "catch": 1}
     assert all(hasattr(ops, k) for k in ("fleet_env_state_ints", "fleet_env_reset", "fleet_env_step"))
 
 
-NW, NR = 4, 2                                                           # the fabricated call: 4 worlds x 2 robots = 8 rows
-BYTES = dict(st=NW * 384, la=8 * 3840, ve=8 * 20, im=8 * 27648, rw=8 * 4, dn=8, info=8 * 4, act=8 * 8, mask=NW)
-ALIGN = dict(st=16, la=16, ve=4, im=16, rw=4, dn=1, info=4, act=4, mask=1)
-
-
-def _overlaps(base, names):
-    """For each pair (p, q) of `names`: q moved onto p's first byte, and onto p's last aligned unit."""
-    out = []
-    for p, q in itertools.permutations(names, 2):
-        out.append({q: base[p]})
-        if BYTES[p] > ALIGN[q] and BYTES[p] % ALIGN[q] == 0:
-            out.append({q: base[p] + BYTES[p] - ALIGN[q]})
-    return out
-
-
 def test_argument_checks_come_before_hip():
-    """Plain integers stand in for device addresses: every refusal below is decided before the first HIP call."""
+    """Plain integers stand in for device addresses: every refusal below is decided before the first HIP call.  The fabricated call:
+    4 worlds x 2 robots = 8 rows."""
     from ddrl4nav_amd import _lib
     lib = _lib.load()
-    INVALID = -1
-    a, M = 0x10000000, 0x1000000
-    base = dict(st=a, la=a + M, ve=a + 2 * M, im=a + 3 * M, rw=a + 4 * M, dn=a + 5 * M, act=a + 6 * M, mask=a + 7 * M, info=a + 8 * M)
+    size, obs = sizes("ddrl_op_fleet_env_reset"), ("st", "la", "ve", "im")
+    shapes = [dict(nw=0), dict(nr=0), dict(nr=5), dict(e0=2 ** 32 - 3), dict(nw=2 ** 30, nr=2)]
+    bad = [{p: None} for p in obs] + shapes + [dict(nw=-4), dict(nr=-1), dict(e0=-1), dict(e0=2 ** 32), dict(nobs=-1), dict(nobs=11),
+                                               dict(nped=-1), dict(nped=6), dict(nw=2 ** 29 + 1, nr=4), dict(nw=2 ** 31 - 1, nr=3)]
+    bad += [dict(st=BASE["st"] + 4), dict(la=BASE["la"] + 8), dict(la=BASE["la"] + 4), dict(im=BASE["im"] + 1), dict(im=BASE["im"] + 8),
+            dict(ve=BASE["ve"] + 2)]
+    bad += overlaps(obs, size)
+    bad += [{"mask": BASE[p]} for p in obs] + [{"mask": BASE[p] + size[p] - 1} for p in obs]
+    bad += [{"mask": BASE["st"] - 3}]                                   # a byte per world, ending inside the state
+    refused(caller(lib, "ddrl_op_fleet_env_reset"), bad)
+    step = caller(lib, "ddrl_op_fleet_env_step")
+    shapes += [dict(nw=-1), dict(nr=-2), dict(nw=2 ** 31 - 1, nr=4)]
+    refused(step, common_refusals("ddrl_op_fleet_env_step") + shapes)
+    refused(step, common_refusals("ddrl_op_fleet_env_step", without=("info",)) + shapes, info=None)    # this entry may go without it
 
-    def reset(st=base["st"], nw=NW, nr=NR, w0=0, seed=1, nobs=10, nped=5, mask=None, la=base["la"], ve=base["ve"], im=base["im"]):
-        return lib.ddrl_op_fleet_env_reset(st, nw, nr, w0, seed, nobs, nped, mask, la, ve, im, None)
-
-    bad = [dict(st=None), dict(la=None), dict(ve=None), dict(im=None), dict(nw=0), dict(nw=-4), dict(nr=0), dict(nr=5), dict(nr=-1),
-           dict(w0=-1), dict(w0=2 ** 32 - 3), dict(w0=2 ** 32), dict(nobs=-1), dict(nobs=11), dict(nped=-1), dict(nped=6),
-           dict(nw=2 ** 30, nr=2), dict(nw=2 ** 29 + 1, nr=4), dict(nw=2 ** 31 - 1, nr=3),
-           dict(st=a + 4), dict(la=a + M + 8), dict(la=a + M + 4), dict(im=a + 3 * M + 1), dict(im=a + 3 * M + 8), dict(ve=a + 2 * M + 2)]
-    bad += _overlaps(base, ("st", "la", "ve", "im"))
-    bad += [{"mask": base[p]} for p in ("st", "la", "ve", "im")] + [{"mask": base[p] + BYTES[p] - 1} for p in ("st", "la", "ve", "im")]
-    bad += [{"mask": base["st"] - (NW - 1)}]                            # ending inside the state
-    for kw in bad:
-        assert reset(**kw) == INVALID, kw
-
-    def step(st=base["st"], nw=NW, nr=NR, w0=0, seed=1, nobs=10, nped=5, ms=500, act=base["act"], la=base["la"], ve=base["ve"],
-             im=base["im"], rw=base["rw"], dn=base["dn"], info=None):
-        return lib.ddrl_op_fleet_env_step(st, nw, nr, w0, seed, nobs, nped, ms, act, la, ve, im, rw, dn, info, None)
-
-    outs = ("st", "la", "ve", "im", "rw", "dn", "info")
-    bad = [dict(st=None), dict(act=None), dict(la=None), dict(ve=None), dict(im=None), dict(rw=None), dict(dn=None), dict(nw=0),
-           dict(nw=-1), dict(nr=0), dict(nr=5), dict(nr=-2), dict(w0=-3), dict(w0=2 ** 32), dict(w0=2 ** 32 - 3), dict(nobs=-1),
-           dict(nobs=11), dict(nped=-2), dict(nped=6), dict(ms=0), dict(ms=-5), dict(nw=2 ** 30, nr=2), dict(nw=2 ** 31 - 1, nr=4),
-           dict(st=a + 8), dict(la=a + M + 4), dict(im=a + 3 * M + 12), dict(ve=a + 2 * M + 1), dict(act=a + 6 * M + 2),
-           dict(rw=a + 4 * M + 1), dict(info=a + 8 * M + 2)]
-    for kw in _overlaps(base, outs):                                    # every pair of outputs, with the info word given
-        bad.append(dict({"info": base["info"]}, **kw))
-    bad += [{"act": base[p], "info": base["info"]} for p in outs]
-    bad += [{"act": base[p] + BYTES[p] - 4, "info": base["info"]} for p in outs if BYTES[p] > 4]
-    bad += [{"act": base["dn"] - 60}]                                   # the actions' last word on the dones' first bytes
-    for kw in bad:
-        assert step(**kw) == INVALID, kw
 
 
 def test_fleet_nav_env_refuses_bad_arguments():

@@ -4,7 +4,6 @@ after every step, bit for bit; hostile and hand-built states; NavStatus fed the 
 StateRollout driven by collect_states() with in-pool rendering against a StateRollout fed by the host model through put_states -- down to
 every parameter after net.learn.  Run with `-m gpu`."""
 import functools
-import types
 
 import numpy as np
 import pytest
@@ -13,38 +12,10 @@ import torch
 import fleet_env_ref as F
 import nav_env_ref as R
 import nav_status_ref as S
+from arena_harness import (HOSTILE, LOSS_KEYS, SHAPES, assert_status_equals, assert_tape_equals, close_to, closed_loop, dev, filled, host,
+                           is_fill, make_net, play_env, record, same, tape_from)
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 0x5A5A5A5A
-SHAPES = [(1, 960), (5,), (3, 48, 48)]
-HOSTILE = np.array([[np.nan, np.nan], [np.inf, np.inf], [-np.inf, -np.inf], [1e30, 1e30], [-5.0, -5.0], [np.inf, np.nan], [1e30, -1e30]],
-                   np.float32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(a):
-    """float32 array -> its words: equality below is bitwise (a negative zero is not a zero)."""
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def close_to(got, want, rel=1e-12):
-    """Within rel of `want` entry by entry (float64 sums of a few hundred terms in another order); nan where `want` is nan."""
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    nan = np.isnan(want)
-    return bool(np.array_equal(np.isnan(got), nan) and np.all(np.abs(got[~nan] - want[~nan]) <= rel * np.abs(want[~nan])))
-
 
 # ---- 1. bit parity with the model -----------------------------------------------------------------------------------------------------------
 # (n_worlds, R, n_obstacles, n_peds, world0); the first case is the coverage tape itself (test_fleet_env_cpu.py), the others 40 steps with
@@ -55,76 +26,31 @@ SWEEP = [(1, 1, 10, 5, 2 ** 32 - 1), (1, 4, 0, 0, 3), (5, 2, 10, 0, 1000), (17, 
 
 @functools.lru_cache(maxsize=None)
 def reference(case):
-    """(model kwargs, actions [steps][rows][2], first observation, per-step states / lasers / vectors / images / rewards / dones / info
-    words stacked, event counts) of one case; never modified."""
+    """(model kwargs, the rule book's tape) of one case; never modified."""
     nw, nr, n_obs, n_peds, world0 = case
     if case == TAPE:
         kw = dict(F.COVERAGE)
-        counts, actions, first, trace = F.coverage_run()
-        assert all(counts[k] >= 3 for k in F.EVENT_NAMES), counts
+        want = record(F.FleetEnvRef(**kw), F.COVERAGE_STEPS, np.random.RandomState(0))
+        assert all(want["events"][k].sum() >= 3 for k in F.EVENT_NAMES)
     else:
         kw = dict(n_worlds=nw, n_robots=nr, seed=100 + nw, n_obstacles=n_obs, n_peds=n_peds, max_steps=15, world0=world0)
-        hostile = {t: np.resize(np.roll(HOSTILE, t, axis=0), (nw * nr, 2)) for t in (7, 23)}
-        counts, actions, first, trace = F.play(F.FleetEnvRef(**kw), 40, np.random.RandomState(nw + n_obs), hostile=hostile)
-        assert counts["trunc"] >= 1
-    stacked = (np.stack([s[0] for s in trace]),) + tuple(np.stack([s[1][k] for s in trace]) for k in range(3)) \
-        + (np.stack([s[2] for s in trace]), np.stack([s[3] for s in trace]), np.stack([s[4] for s in trace]))
-    return kw, actions, first, stacked, counts
-
-
-def guarded(rows, n):
-    """Three fp32 buffers [rows, n, ...] filled with the guard word."""
-    return [torch.full((rows, n) + s, GUARD, dtype=torch.int32, device="cuda").view(torch.float32) for s in SHAPES]
-
-
-def is_guard(t):
-    return bool((t.view(torch.int32) == GUARD).all())
+        want = record(F.FleetEnvRef(**kw), 40, np.random.RandomState(nw + n_obs), hostile={t: np.roll(HOSTILE, t, axis=0) for t in (7, 23)})
+        assert want["events"]["trunc"].sum() >= 1
+    return kw, want
 
 
 def play_on_device(kw, actions, start=None, emit_info=True):
-    """The trajectory on a fresh FleetNavEnv, every step rendered into its own row of three larger buffers (obs_out) with a guard row on
-    either side; one read-back at the end.  start: a state_dict to resume from instead of a reset."""
+    """The tape on a fresh FleetNavEnv (arena_harness.play_env) and the env.  start: a state_dict to resume from instead of a reset."""
     from ddrl4nav_amd.env import FleetNavEnv
-    steps, n = actions.shape[:2]
     env = FleetNavEnv(device="cuda", emit_info=emit_info, **kw)
-    assert env.N == n == env.n_worlds * env.n_robots and tuple(env.state.shape) == (env.n_worlds, 96)
-    env.state.fill_(-12345)                                             # reset reads nothing of what was there
-    bufs = guarded(steps + 3, n)
-    states = torch.empty((steps, env.n_worlds, 96), dtype=torch.int32, device="cuda")
-    rewards = torch.empty((steps, n), dtype=torch.float32, device="cuda")
-    dones = torch.empty((steps, n), dtype=torch.uint8, device="cuda")
-    infos = torch.zeros((steps, n), dtype=torch.int32, device="cuda")
-    acts = dev(actions)
-    if start is None:
-        out = env.reset(obs_out=[b[1] for b in bufs])
-        assert all(o.data_ptr() == b[1].data_ptr() for o, b in zip(out, bufs))
-    else:
-        env.load_state_dict(start)
-    for t in range(steps):
-        o, r, d = env.step(acts[t], obs_out=[b[t + 2] for b in bufs])
-        assert all(x.data_ptr() == b[t + 2].data_ptr() for x, b in zip(o, bufs)) and r is env.reward and d is env.done
-        states[t].copy_(env.state)
-        rewards[t].copy_(r)
-        dones[t].copy_(d)
-        if emit_info:
-            infos[t].copy_(env.info)
-    torch.cuda.synchronize()
-    assert all(is_guard(b[0]) and is_guard(b[-1]) for b in bufs)         # nothing outside the rows that were handed over
-    return [host(b) for b in bufs], host(states), host(rewards), host(dones), host(infos), env
+    assert env.N == env.n_worlds * env.n_robots and tuple(env.state.shape) == (env.n_worlds, 96)
+    return play_env(env, actions, start), env
 
 
 def check_against(case):
-    kw, actions, first, (want_s, want_l, want_v, want_i, want_r, want_d, want_w), _ = reference(case)
-    (las, vec, img), states, rewards, dones, infos, _ = play_on_device(kw, actions)
-    assert same(las[1], first[0]) and same(vec[1], first[1]) and same(img[1], first[2])
-    for t in range(len(actions)):                                       # the first step that differs, if any, names itself
-        assert np.array_equal(states[t], want_s[t]), (t, np.nonzero(states[t] != want_s[t]))
-        assert same(rewards[t], want_r[t]) and np.array_equal(dones[t], want_d[t]), t
-        assert np.array_equal(infos[t], want_w[t]), (t, np.nonzero(infos[t] != want_w[t]))
-        assert same(las[t + 2], want_l[t]), (t, np.nonzero(las[t + 2] != want_l[t]))
-        assert same(vec[t + 2], want_v[t]), t
-        assert same(img[t + 2], want_i[t]), (t, np.nonzero(img[t + 2] != want_i[t]))
-    return want_r, want_d, want_w
+    kw, want = reference(case)
+    assert_tape_equals(play_on_device(kw, want["actions"])[0], want)
+    return want["reward"], want["done"], want["info"]
 
 
 def test_the_coverage_tape_equals_the_model():
@@ -183,29 +109,27 @@ def _one_robot_against_nav(n_obs, n_peds):
 
 
 def test_repeats_are_bit_identical_and_the_info_word_changes_nothing():
-    kw, actions, _, _, _ = reference(SWEEP[3])
-    a, b, c = (play_on_device(kw, actions, emit_info=e) for e in (True, True, False))
-    for x, y, z in zip(a[0], b[0], c[0]):
-        assert same(x, y) and same(x, z)
-    for x, y, z in zip(a[1:4], b[1:4], c[1:4]):
-        assert np.array_equal(x, y) and np.array_equal(x, z)
-    assert np.array_equal(a[4], b[4]) and a[4].any() and c[5].info is None
+    kw, want = reference(SWEEP[3])
+    (a, _), (b, _), (c, env_c) = (play_on_device(kw, want["actions"], emit_info=e) for e in (True, True, False))
+    assert_tape_equals(b, a)
+    assert_tape_equals(c, a)
+    assert a["info"].any() and "info" not in c and env_c.info is None
 
 
 def test_the_env_owns_its_outputs_by_default():
     from ddrl4nav_amd.env import FleetNavEnv, make_device_env
-    kw, actions, first, (want_s, want_l, want_v, want_i, want_r, want_d, want_w), _ = reference(SWEEP[2])
+    kw, want = reference(SWEEP[2])
     env = make_device_env({"env_name": "DeviceNavFleet-v0", "env_num": kw["n_worlds"], "agent_num_per_env": kw["n_robots"],
                            "env_seed": kw["seed"], "env_obstacles": 10, "env_peds": 0, "env_max_steps": 15, "env_info": True},
                           env0=kw["world0"])
     assert isinstance(env, FleetNavEnv) and env.state_shapes == SHAPES and env.N == 10 and env.n_envs == 10 and env.world0 == 1000
     out = env.reset()
-    assert all(o is e for o, e in zip(out, env.obs)) and all(same(host(o), f) for o, f in zip(out, first))
+    assert all(o is e for o, e in zip(out, env.obs)) and all(same(host(o), f) for o, f in zip(out, want["first"]))
     for t in range(10):
-        o, r, d = env.step(dev(actions[t]))
+        o, r, d = env.step(dev(want["actions"][t]))
         assert all(x is e for x, e in zip(o, env.obs)) and r.dtype == torch.float32 and d.dtype == torch.uint8
-    assert same(host(o[0]), want_l[9]) and same(host(o[2]), want_i[9]) and np.array_equal(host(env.state), want_s[9])
-    assert np.array_equal(host(env.info), want_w[9])
+    assert same(host(o[0]), want["laser"][9]) and same(host(o[2]), want["image"][9]) and np.array_equal(host(env.state), want["state"][9])
+    assert np.array_equal(host(env.info), want["info"][9])
 
 
 def test_masked_reset_is_per_world():
@@ -226,13 +150,13 @@ def test_masked_reset_is_per_world():
     rows = np.repeat(mask != 0, nr)
     before = model.state.copy()
     want = model.reset(mask)
-    bufs = guarded(1, nw * nr)
+    bufs = filled(1, nw * nr)
     got = env.reset(mask=dev(mask), obs_out=[b[0] for b in bufs])
     torch.cuda.synchronize()
     assert np.array_equal(host(env.state), model.state) and np.array_equal(model.state[[0, 2]], before[[0, 2]])
     assert (model.state[[1, 3, 4], F.EVENTS] == 1 + 4 + 2 * nr + 3).all()
     for g, w in zip(got, want):
-        assert same(host(g)[rows], w[rows]) and is_guard(g[~torch.from_numpy(rows).cuda()])
+        assert same(host(g)[rows], w[rows]) and is_fill(g[~torch.from_numpy(rows).cuda()])
     with pytest.raises(AssertionError):
         env.reset(mask=dev(np.ones(nw * nr, np.uint8)))                 # a byte per world, not per row
     a = rng.uniform(-1, 1, (nw * nr, 2)).astype(np.float32)             # and the episodes go on for all five worlds
@@ -243,25 +167,22 @@ def test_masked_reset_is_per_world():
 
 def test_state_dict_resumes_bit_identically():
     from ddrl4nav_amd.env import FleetNavEnv
-    kw, actions, _, (want_s, want_l, want_v, want_i, want_r, want_d, want_w), _ = reference(SWEEP[3])
-    *_, env = play_on_device(kw, actions[:20])
+    kw, want = reference(SWEEP[3])
+    _, env = play_on_device(kw, want["actions"][:20])
     sd = env.state_dict()
     assert not sd["state"].is_cuda and sd["n_robots"] == 3 and sd["n_worlds"] == 17 and sd["max_steps"] == 15
-    (las, vec, img), states, rewards, dones, infos, _ = play_on_device(kw, actions[20:], start=sd)
-    assert np.array_equal(states, want_s[20:]) and same(rewards, want_r[20:]) and np.array_equal(dones, want_d[20:])
-    assert np.array_equal(infos, want_w[20:])
-    assert same(las[2:-1], want_l[20:]) and same(vec[2:-1], want_v[20:]) and same(img[2:-1], want_i[20:])
-    assert is_guard(torch.from_numpy(las[1]))                           # a resumed env renders nothing before its first step
+    got, _ = play_on_device(kw, want["actions"][20:], start=sd)         # a resumed env renders nothing before its first step: play_env
+    assert_tape_equals(got, tape_from(want, 20))
     with pytest.raises(ValueError):
         FleetNavEnv(device="cuda", **dict(kw, n_robots=2)).load_state_dict(sd)
     with pytest.raises(ValueError):
         FleetNavEnv(device="cuda", **dict(kw, max_steps=16)).load_state_dict(sd)
 
 
-def step_both(model, env, actions, obs_out=None):
+def step_both(model, env, actions):
     """One step of the model and of the device env; everything compared.  -> done."""
     o, r, d = model.step(actions)
-    go, gr, gd = env.step(dev(actions), obs_out=obs_out)
+    go, gr, gd = env.step(dev(actions))
     assert np.array_equal(host(env.state), model.state), np.nonzero(host(env.state) != model.state)
     assert all(same(host(x), y) for x, y in zip(go, o)) and same(host(gr), r) and np.array_equal(host(gd), d)
     assert np.array_equal(host(env.info), model.info)
@@ -281,17 +202,13 @@ def test_a_hostile_state_is_sanitised(nr, pops):
     for r in range(nr):                                                 # some worlds go on with their episodes
         words[3:20, 10 * r + F.STEPS] = rng.randint(0, 30, 17)
         words[3:20, 10 * r + F.X:10 * r + F.Y + 1] = rng.randint(-1500, 1500, (17, 2))
-    model, env = F.FleetEnvRef(nw, nr, **kw), FleetNavEnv(nw, nr, device="cuda", emit_info=True, **kw)
-    model.state[:] = words
-    env.state.copy_(dev(words))
-    bufs = guarded(4, nw * nr)
-    for t in range(2):
-        d = step_both(model, env, rng.uniform(-1, 1, (nw * nr, 2)).astype(np.float32), obs_out=[b[t + 1] for b in bufs])
-        assert t > 0 or (0 < d.sum() < nw * nr)
+    model = F.FleetEnvRef(nw, nr, **kw)
+    want = record(model, 2, first_state=words, actions=rng.uniform(-1, 1, (2, nw * nr, 2)).astype(np.float32))
+    assert_tape_equals(play_env(FleetNavEnv(nw, nr, device="cuda", emit_info=True, **kw), want["actions"], start=words), want)
+    assert 0 < want["done"][0].sum() < nw * nr
     kept = model.state.copy()
     model.sanitize()
     assert np.array_equal(model.state, kept)
-    assert all(is_guard(b[0]) and is_guard(b[3]) for b in bufs)
 
 
 def test_four_robots_on_one_point_respawn_one_after_the_other():
@@ -373,15 +290,13 @@ def test_nav_status_counts_the_other_robot_collisions():
     """NavStatus fed the DEVICE's info words of the coverage tape equals NavStatusRef in every per-row tensor; the fourth ring fills;
     other_robot_collision_rate() and summary() are the model's."""
     from ddrl4nav_amd.agent import NavStatus
-    kw, actions, _, stacked, _ = reference(TAPE)
-    *_, infos, _ = play_on_device(kw, actions)
-    assert np.array_equal(infos, stacked[6])
+    kw, tape = reference(TAPE)
+    infos = play_on_device(kw, tape["actions"])[0]["info"]
+    assert np.array_equal(infos, tape["info"])
     st, want = NavStatus(24, "cuda"), S.NavStatusRef(24)
     st.update(dev(infos))
     want.update(infos)
-    for name, w in want.per_env().items():
-        g = host(getattr(st, name))
-        assert g.shape == w.shape and (np.array_equal(g, w) if w.dtype == np.int32 else same(g, w)), name
+    assert_status_equals(st, want)
     assert host(st.coll_robot_num).sum() > 0
     rate, wanted = st.other_robot_collision_rate(), F.other_robot_collision_rate(want)
     print("other-robot collision rate:", rate, wanted)
@@ -394,103 +309,31 @@ def test_nav_status_counts_the_other_robot_collisions():
 NW, NR, T = 2, 2, 8
 N = NW * NR
 ENV_KW = dict(seed=31, n_obstacles=10, n_peds=5, max_steps=5)           # every robot is done every fifth step at the latest
-POOLS = ("_actions", "_logps", "values", "_dones", "_rewards", "adv", "ret")
-LOSS_KEYS = ("PpoTotalLoss", "ActorLoss", "VLoss", "EntLoss")
-
-
-def make_net(seed=13):
-    """BASELINE config 4's net (NavPreNet1D x2 + GaussionActor(2)) through create_net, hashed weights loaded; two nets made by this
-    function draw the same actions from the same observations."""
-    from ddrl4nav_amd.config import BaseConfig, ConfigNN
-    from ddrl4nav_amd.runner import create_net
-    from ddrl4nav_amd.utils.recipe import hash_weights
-    env = {"discrete_action": False, "act_dim": 2, "image_batch": 1, "ped_sim": {"total": 3}}
-    cfg = BaseConfig(types.SimpleNamespace(task="test", ip="127.0.0.1"),
-                     dict({"env_type": "gym", "env_name": "PongNoFrameskip-v4", "env_num": 8}, **env))
-    cfg.TASK_TYPE = "robot_nav"
-    cfg_nn = ConfigNN(env)
-    cfg_nn.SHARE_CNN_NET = False
-    torch.manual_seed(seed)
-    net = create_net({"config": cfg, "config_nn": cfg_nn, "config_env": env}, max_batch=N * T)
-    w = hash_weights([(k, tuple(p.shape)) for k, p in net.named_parameters()], seed)
-    net.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return net
-
-
-def learn(net, ro):
-    items = [({k: ld[k] for k in LOSS_KEYS}, ut) for ld, ut, _ in net.learn(ro.batch())]   # PpoBackUpTime is a wall clock
-    assert items
-    return items
-
-
-def snapshot(ro):
-    torch.cuda.synchronize()
-    return {k: getattr(ro, k).clone() for k in POOLS}
 
 
 def test_closed_loop_equals_the_host_driven_rollout():
-    """Variant A: StateRollout(n_envs=env.N) + FleetNavEnv through collect_states(), the observation rendered in the pool, the navigation
-    status tracked.  Variant B: an identically seeded net whose StateRollout is fed by the host model through put_states, stepped with the
-    actions read back.  Two rollouts with carry_over() between them."""
+    """arena_harness.closed_loop on a FleetNavEnv, StateRollout(n_envs=env.N), the navigation status tracked: collect_states() with
+    in-pool rendering against the host model through put_states, two rollouts with carry_over() between them."""
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.env import FleetNavEnv
     from ddrl4nav_amd.runner.device_loop import collect_states
-    net_a, net_b = make_net(), make_net()
     env = FleetNavEnv(NW, NR, device="cuda", emit_info=True, **ENV_KW)
     assert env.N == N == 4 and N * T == 32
-    ra = StateRollout(net_a, env.N, SHAPES, horizon=T, track_returns=True, track_nav_status=True)
-    rb = StateRollout(net_b, N, SHAPES, horizon=T, track_returns=True)
+    ra = StateRollout(make_net(N * T), env.N, SHAPES, horizon=T, track_returns=True, track_nav_status=True)
     with pytest.raises(ValueError):
         collect_states(ra, FleetNavEnv(NW, NR + 1, device="cuda", emit_info=True))            # 6 rows against a rollout of 4
     with pytest.raises(ValueError, match="emit_info"):
         collect_states(ra, FleetNavEnv(NW, NR, device="cuda"))
-    model = F.FleetEnvRef(NW, NR, **ENV_KW)
-    before = net_a.params.clone()
-    all_d, all_w = [], []
-    for r in range(2):
-        collect_states(ra, env)
-        if r == 0:
-            rb.put_states(0, [dev(x) for x in model.reset()])
-        for t in range(T):
-            obs, reward, done = model.step(host(rb.act(t)))
-            rb.record(t, reward, done)
-            rb.put_states(t + 1, [dev(x) for x in obs])
-            all_d.append(done)
-            all_w.append(model.info.copy())
-        rb.bootstrap()
-        rb.finish()
-        assert ra.rollouts == rb.rollouts == r + 1
-        sa, sb = snapshot(ra), snapshot(rb)
-        for k in POOLS:
-            assert torch.equal(sa[k][:T], sb[k][:T]), (r, k)
-        assert torch.equal(sa["values"], sb["values"])                   # the bootstrap row too
-        assert np.array_equal(host(ra.dones), np.stack(all_d[-T:])) and np.array_equal(host(env.state), model.state)
-        assert np.array_equal(host(ra._infos)[:T], np.stack(all_w[-T:]))
-        for pa, pb in zip(ra.states, rb.states):                          # the pool rows hold the model's observations
-            assert torch.equal(pa.view(torch.int32), pb.view(torch.int32)), r
-        items_a, items_b = learn(net_a, ra), learn(net_b, rb)
-        assert items_a == items_b
-        assert torch.equal(net_a.params, net_b.params), r
-        for (ka, pa), (kb, pb) in zip(net_a.named_parameters(), net_b.named_parameters()):
-            assert ka == kb and torch.equal(pa, pb), (r, ka)
-        ra.carry_over()
-        rb.carry_over()
-    assert not torch.equal(net_a.params, before)
-    don = np.stack(all_d)
-    assert don[:T].any() and don[T:].any() and don.sum() >= 3 * N
-    want = S.NavStatusRef(N)
-    want.update(np.stack(all_w))
-    for name, w in want.per_env().items():
-        g = host(getattr(ra.nav_status, name))
-        assert np.array_equal(g, w) if w.dtype == np.int32 else same(g, w), name
-    assert close_to([ra.nav_status.other_robot_collision_rate()], [F.other_robot_collision_rate(want)])
+    out = closed_loop(env, F.FleetEnvRef(NW, NR, **ENV_KW), T, track_nav_status=True)
+    assert out.dones[:T].any() and out.dones[T:].any() and out.dones.sum() >= 3 * N
+    assert close_to([out.ra.nav_status.other_robot_collision_rate()], [F.other_robot_collision_rate(out.status)])
 
 
 def test_train_states_runs_three_updates_on_a_fleet():
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.env import FleetNavEnv
     from ddrl4nav_amd.runner.device_loop import train_states
-    net = make_net(seed=2)
+    net = make_net(N * T, seed=2)
     net.training_iter_time = 2
     env = FleetNavEnv(NW, NR, device="cuda", seed=4, max_steps=6)
     ro = StateRollout(net, env.N, SHAPES, horizon=T, track_returns=True)

@@ -5,14 +5,13 @@ import functools
 import itertools
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
 import nav_env_ref as R
+from arena_abi import BASE, ROOT, caller, common_refusals, header_declares, overlaps, refused, sizes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_nav_env_state_ints", "ddrl_op_nav_env_trig", "ddrl_op_nav_env_reset", "ddrl_op_nav_env_step")
 
 
@@ -176,71 +175,29 @@ def test_steering_beats_random_play():
 
 # ---- 3. header, binding, wrappers -------------------------------------------------------------------------------------------------------------
 def test_header_declares_what_the_binding_binds():
-    from ddrl4nav_amd import _lib, ops
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        args = 0 if m.group(1).strip() == "void" else m.group(1).count(",") + 1
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == args, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [0, 1, 11, 14]
-    assert re.search(r"#define\s+DDRL_ABI_VERSION\s+3\b", text) and _lib.ABI_VERSION == 3
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW)
+    from ddrl4nav_amd import ops
+    _, lib = header_declares(NEW, [0, 1, 11, 14])
     assert lib.ddrl_op_nav_env_state_ints() == R.STATE_INTS == ops.nav_env_state_ints() == 64
     assert lib.ddrl_op_nav_env_trig(None) == -1
     assert ops.ENV_GAMES == {"pong": 0, "catch": 1}                    # the nav env is no third game
     assert all(hasattr(ops, k) for k in ("nav_env_state_ints", "nav_env_trig", "nav_env_reset", "nav_env_step"))
 
 
-BYTES = dict(st=8 * 256, la=8 * 3840, ve=8 * 20, im=8 * 27648, rw=8 * 4, dn=8, act=8 * 8, mask=8)   # at n = 8
-ALIGN = dict(st=16, la=16, ve=4, im=16, rw=4, dn=1, act=4, mask=1)
-
-
-def _overlaps(base, names):
-    """For each pair (p, q) of `names`: q moved onto p's first byte, and onto p's last aligned unit."""
-    out = []
-    for p, q in itertools.permutations(names, 2):
-        out.append({q: base[p]})
-        if BYTES[p] > ALIGN[q] and BYTES[p] % ALIGN[q] == 0:
-            out.append({q: base[p] + BYTES[p] - ALIGN[q]})
-    return out
-
-
 def test_argument_checks_come_before_hip():
     """Plain integers stand in for device addresses: every refusal below is decided before the first HIP call."""
     from ddrl4nav_amd import _lib
     lib = _lib.load()
-    INVALID = -1
-    a, M = 0x10000000, 0x1000000
-    base = dict(st=a, la=a + M, ve=a + 2 * M, im=a + 3 * M, rw=a + 4 * M, dn=a + 5 * M, act=a + 6 * M, mask=a + 7 * M)
+    size, obs = sizes("ddrl_op_nav_env_reset"), ("st", "la", "ve", "im")
+    bad = [{p: None} for p in obs] + [dict(n=0), dict(n=-4), dict(e0=-1), dict(e0=2 ** 32 - 7), dict(e0=2 ** 32), dict(nobs=-1),
+                                      dict(nobs=11), dict(nped=-1), dict(nped=6)]
+    bad += [dict(st=BASE["st"] + 4), dict(la=BASE["la"] + 8), dict(la=BASE["la"] + 4), dict(im=BASE["im"] + 1), dict(im=BASE["im"] + 8),
+            dict(ve=BASE["ve"] + 2)]
+    bad += overlaps(obs, size)
+    bad += [{"mask": BASE[p]} for p in obs] + [{"mask": BASE[p] + size[p] - 1} for p in obs]
+    bad += [{"mask": BASE["st"] - 7}]                                   # ending inside the state
+    refused(caller(lib, "ddrl_op_nav_env_reset"), bad)
+    refused(caller(lib, "ddrl_op_nav_env_step"), common_refusals("ddrl_op_nav_env_step") + [dict(n=0), dict(n=-1), dict(e0=2 ** 32 - 7)])
 
-    def reset(st=base["st"], n=8, env0=0, seed=1, nobs=10, nped=5, mask=None, la=base["la"], ve=base["ve"], im=base["im"]):
-        return lib.ddrl_op_nav_env_reset(st, n, env0, seed, nobs, nped, mask, la, ve, im, None)
-
-    bad = [dict(st=None), dict(la=None), dict(ve=None), dict(im=None), dict(n=0), dict(n=-4), dict(env0=-1), dict(env0=2 ** 32 - 7),
-           dict(env0=2 ** 32), dict(nobs=-1), dict(nobs=11), dict(nped=-1), dict(nped=6),
-           dict(st=a + 4), dict(la=a + M + 8), dict(la=a + M + 4), dict(im=a + 3 * M + 1), dict(im=a + 3 * M + 8), dict(ve=a + 2 * M + 2)]
-    bad += _overlaps(base, ("st", "la", "ve", "im"))
-    bad += [{"mask": base[p]} for p in ("st", "la", "ve", "im")] + [{"mask": base[p] + BYTES[p] - 1} for p in ("st", "la", "ve", "im")]
-    bad += [{"mask": base["st"] - 7}]                                   # ending inside the state
-    for kw in bad:
-        assert reset(**kw) == INVALID, kw
-
-    def step(st=base["st"], n=8, env0=0, seed=1, nobs=10, nped=5, ms=500, act=base["act"], la=base["la"], ve=base["ve"], im=base["im"],
-             rw=base["rw"], dn=base["dn"]):
-        return lib.ddrl_op_nav_env_step(st, n, env0, seed, nobs, nped, ms, act, la, ve, im, rw, dn, None)
-
-    bad = [dict(st=None), dict(act=None), dict(la=None), dict(ve=None), dict(im=None), dict(rw=None), dict(dn=None), dict(n=0), dict(n=-1),
-           dict(env0=-3), dict(env0=2 ** 32), dict(env0=2 ** 32 - 7), dict(nobs=-1), dict(nobs=11), dict(nped=-2), dict(nped=6),
-           dict(ms=0), dict(ms=-5), dict(st=a + 8), dict(la=a + M + 4), dict(im=a + 3 * M + 12), dict(ve=a + 2 * M + 1),
-           dict(act=a + 6 * M + 2), dict(rw=a + 4 * M + 1)]
-    bad += _overlaps(base, ("st", "la", "ve", "im", "rw", "dn"))
-    bad += [{"act": base[p]} for p in ("st", "la", "ve", "im", "rw", "dn")]
-    bad += [{"act": base[p] + BYTES[p] - 4} for p in ("st", "la", "ve", "im", "rw", "dn") if BYTES[p] > 4]
-    bad += [{"act": base["dn"] - 60}]                                   # the actions' last word on the dones' first bytes
-    for kw in bad:
-        assert step(**kw) == INVALID, kw
 
 
 def test_device_nav_env_refuses_bad_arguments():

@@ -2,31 +2,21 @@
 header, binding and exports, every refusal the operator decides before it touches HIP, the rule book's own claims (labels decode to the
 chosen arc, keys below 2^22, every branch taken on a seeded set of states) and the expert's quality on the rule book's env."""
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import nav_env_ref as R
 import nav_expert_ref as E
+from arena_abi import header_declares
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_nav_expert", "ddrl_op_heads_bc_mse_ws_floats", "ddrl_op_heads_bc_mse", "ddrl_op_gather_rows_f32")
 
 
 def test_header_binding_and_exports():
-    from ddrl4nav_amd import _lib, ops
+    from ddrl4nav_amd import ops
     from ddrl4nav_amd.env import NavExpert
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [12, 3, 15, 7]
-    assert re.search(r"#define\s+DDRL_ABI_VERSION\s+3\b", text) and _lib.ABI_VERSION == 3       # additive
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW)
+    header_declares(NEW, [12, 3, 15, 7])                                    # additive: the ABI version stays 3
     assert all(callable(getattr(ops, k)) for k in ("nav_expert", "beta_threshold", "heads_bc_mse", "heads_bc_mse_ws_floats",
                                                     "gather_rows_f32"))
     assert callable(NavExpert.labels) and callable(NavExpert.mix)

@@ -11,8 +11,9 @@ import pytest
 
 import nav_env_ref as R
 import nav_status_ref as S
+from arena_abi import BASE, INVALID, ROOT, caller, common_refusals, header_declares, refused
+from arena_harness import bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_nav_env_step_info", "ddrl_op_nav_status_update", "ddrl_op_nav_status_reduce")
 N, T = 24, 400
 GROUP_KEYS = tuple(k for k in S.SUMMARY_KEYS if k != "TruncationRate")   # what the reference's group_logger returns
@@ -35,11 +36,6 @@ def model_checkpoints():
         if t + 1 in g["checkpoints"]:
             out[t + 1] = m.per_env()
     return out, m
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
 
 
 # ---- 1. the model against the reference's Status --------------------------------------------------------------------------------------------
@@ -210,16 +206,8 @@ def test_info_fields_unpack_like_the_rule_book():
 # ---- 3. header, binding, argument checks, guards --------------------------------------------------------------------------------------------
 def test_header_declares_what_the_binding_binds():
     from ddrl4nav_amd import _lib, ops
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [15, 7, 6]
+    text, _ = header_declares(NEW, [15, 7, 6])
     assert len(_lib.SIGNATURES["ddrl_op_nav_env_step"][1]) == 14          # the plain entry keeps its signature
-    assert re.search(r"#define\s+DDRL_ABI_VERSION\s+3\b", text) and _lib.ABI_VERSION == 3
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW)
     for macro, value in (("ROWS", ops.NAV_STATUS_ROWS), ("RINGS", ops.NAV_STATUS_RINGS), ("WINDOW", ops.NAV_STATUS_WINDOW),
                          ("SUMMARY", ops.NAV_STATUS_SUMMARY)):
         assert re.search(r"#define\s+DDRL_NAV_STATUS_%s\s+%d\b" % (macro, value), text), macro
@@ -233,27 +221,13 @@ def test_argument_checks_come_before_hip():
     """Plain integers stand in for device addresses: every refusal below is decided before the first HIP call."""
     from ddrl4nav_amd import _lib
     lib = _lib.load()
-    INVALID, OK = -1, 0
-    a, M = 0x10000000, 0x1000000
-    base = dict(st=a, la=a + M, ve=a + 2 * M, im=a + 3 * M, rw=a + 4 * M, dn=a + 5 * M, act=a + 6 * M, inf=a + 7 * M)
-    size = dict(st=8 * 256, la=8 * 3840, ve=8 * 20, im=8 * 27648, rw=8 * 4, dn=8, act=8 * 8)       # bytes at n = 8
+    OK = 0
+    # the info word among the outputs (arena_abi.common_refusals): null, misaligned, on either end of every other argument and they on it
+    bad = common_refusals("ddrl_op_nav_env_step_info") + [dict(n=0), dict(n=-1), dict(e0=2 ** 32 - 7)]
+    bad += [dict(info=BASE["dn"] - 28), dict(dn=BASE["info"] + 31)]     # its last word on the dones' first bytes, the dones on its last byte
+    refused(caller(lib, "ddrl_op_nav_env_step_info"), bad)
 
-    def step(st=base["st"], n=8, env0=0, seed=1, nobs=10, nped=5, ms=500, act=base["act"], la=base["la"], ve=base["ve"], im=base["im"],
-             rw=base["rw"], dn=base["dn"], inf=base["inf"]):
-        return lib.ddrl_op_nav_env_step_info(st, n, env0, seed, nobs, nped, ms, act, la, ve, im, rw, dn, inf, None)
-
-    bad = [dict(inf=None), dict(inf=base["inf"] + 2), dict(inf=base["inf"] + 1), dict(st=None), dict(act=None), dict(la=None), dict(ve=None),
-           dict(im=None), dict(rw=None), dict(dn=None), dict(n=0), dict(n=-1), dict(env0=-3), dict(env0=2 ** 32 - 7), dict(nobs=11),
-           dict(nped=6), dict(ms=0), dict(st=a + 8), dict(la=a + M + 4), dict(im=a + 3 * M + 12), dict(ve=a + 2 * M + 1),
-           dict(act=a + 6 * M + 2), dict(rw=a + 4 * M + 1)]
-    for p, nbytes in size.items():                                      # the info on any other argument's first or last word ...
-        bad += [dict(inf=base[p]), dict(inf=base[p] + (nbytes - 4 if nbytes >= 4 else 0))]
-    bad += [{p: base["inf"]} for p in ("st", "la", "im", "rw", "dn", "act")]      # ... and any other argument on the info
-    bad += [dict(inf=base["dn"] - 28), dict(dn=base["inf"] + 31), dict(act=base["inf"] - 60)]
-    for kw in bad:
-        assert step(**kw) == INVALID, kw
-
-    n = 24
+    a, M, n = 0x10000000, 0x1000000, 24
     sb = dict(info=a, sums=a + M, ep=a + 2 * M, rings=a + 3 * M, out=a + 4 * M)
     nbytes = dict(info=400 * n * 4, sums=18 * n * 4, ep=n * 4, rings=5 * 100 * n * 4, out=22 * 8)
 

@@ -4,40 +4,17 @@ for bit, its reduction against the model's float64, and the closed loop -- Devic
 track_nav_status=True) through collect_states.  Run with `-m gpu`."""
 import functools
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
-import nav_env_ref as R
 import nav_status_ref as S
+from arena_harness import FILL, HOSTILE, POOLS, SHAPES, close_to, dev, host, is_fill, make_net, same
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 0x5A5A5A5A
-SHAPES = [(1, 960), (5,), (3, 48, 48)]
-HOSTILE = np.array([[np.nan, np.nan], [np.inf, np.inf], [-np.inf, -np.inf], [1e30, 1e30], [-5.0, -5.0], [np.inf, np.nan], [1e30, -1e30]],
-                   np.float32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(bits(a), bits(b))
-
 
 # ---- 1. the info word ------------------------------------------------------------------------------------------------------------------------
 STEPS = 300
@@ -100,12 +77,12 @@ def test_step_info_writes_its_words_and_nothing_around_them():
     kw, actions, _, _, _, want_i = info_reference(7, (10, 5))
     env = DeviceNavEnv(device="cuda", **kw)
     env.reset()
-    buf = torch.full((3, 7), GUARD, dtype=torch.int32, device="cuda")
+    buf = torch.full((3, 7), FILL, dtype=torch.int32, device="cuda")
     call = dict(env0=env.env0, seed=env.seed, n_obstacles=10, n_peds=5, max_steps=40)
     out = ops.nav_env_step_info(env.state, dev(actions[0]), env.obs, env.reward, env.done, buf[1], **call)
     assert len(out) == 4 and out[3].data_ptr() == buf[1].data_ptr()
     got = host(buf)
-    assert np.array_equal(got[1], want_i[0]) and (got[0] == GUARD).all() and (got[2] == GUARD).all()
+    assert np.array_equal(got[1], want_i[0]) and is_fill(got[0]) and is_fill(got[2])
     fields = ops.nav_info_fields(buf[1])
     assert fields["v"].is_cuda and np.array_equal(host(fields["v"]), S.unpack_info(want_i[0])["v"])
     with pytest.raises(AssertionError):
@@ -194,13 +171,6 @@ def test_update_refuses_what_it_cannot_take():
 
 
 # ---- 3. the reduction ------------------------------------------------------------------------------------------------------------------------
-def close_to(got, want, rel=1e-12):
-    """Within rel of `want` entry by entry; a mean that has no env to count is nan in both."""
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    nan = np.isnan(want)
-    return bool(np.array_equal(np.isnan(got), nan) and np.all(np.abs(got[~nan] - want[~nan]) <= rel * np.abs(want[~nan])))
-
-
 @pytest.mark.parametrize("columns", ["all", "one", "tiled300"])
 def test_reduce_and_summary_equal_the_model(columns):
     from ddrl4nav_amd.agent import NavStatus
@@ -246,26 +216,6 @@ def test_summary_of_partials_and_of_an_unfinished_status():
 # ---- 4. the closed loop ----------------------------------------------------------------------------------------------------------------------
 LN, LT = 8, 16
 LOOP_ENV = dict(seed=21, n_obstacles=10, n_peds=5, max_steps=12)
-POOLS = ("_actions", "_logps", "values", "_dones", "_rewards", "adv", "ret")
-
-
-def make_net(seed=13):
-    """BASELINE config 4's net (NavPreNet1D x2 + GaussionActor(2)) through create_net with hashed weights, as tests/test_nav_env_gpu.py
-    builds it: two nets made by this function draw the same actions from the same observations."""
-    from ddrl4nav_amd.config import BaseConfig, ConfigNN
-    from ddrl4nav_amd.runner import create_net
-    from ddrl4nav_amd.utils.recipe import hash_weights
-    env = {"discrete_action": False, "act_dim": 2, "image_batch": 1, "ped_sim": {"total": 3}}
-    cfg = BaseConfig(types.SimpleNamespace(task="test", ip="127.0.0.1"),
-                     dict({"env_type": "gym", "env_name": "PongNoFrameskip-v4", "env_num": 8}, **env))
-    cfg.TASK_TYPE = "robot_nav"
-    cfg_nn = ConfigNN(env)
-    cfg_nn.SHARE_CNN_NET = False
-    torch.manual_seed(seed)
-    net = create_net({"config": cfg, "config_nn": cfg_nn, "config_env": env}, max_batch=LN * LT)
-    w = hash_weights([(k, tuple(p.shape)) for k, p in net.named_parameters()], seed)
-    net.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return net
 
 
 @pytest.mark.parametrize("keep_step", [False, True])
@@ -276,7 +226,7 @@ def test_the_loop_tracks_the_status_and_changes_nothing_else(keep_step):
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.env import DeviceNavEnv
     from ddrl4nav_amd.runner.device_loop import collect_states
-    net_a, net_b = make_net(), make_net()
+    net_a, net_b = make_net(LN * LT), make_net(LN * LT)
     ra = StateRollout(net_a, LN, SHAPES, horizon=LT, track_returns=True, track_nav_status=True)
     rb = StateRollout(net_b, LN, SHAPES, horizon=LT, track_returns=True)
     assert rb.nav_status is None and ra.nav_status.N == LN and tuple(ra._infos.shape) == (LT + 1, LN)

@@ -3,7 +3,7 @@ book anchored to tests/nav_env_ref.py and tests/fleet_env_ref.py under "walk" an
 on fixed states, the two invariants, the scripted expert's quality among pedestrians that give way, the header against the binding
 table, every argument check of the two new entry points (decided before HIP) and the wrappers' knobs.  No GPU."""
 import functools
-import os
+import itertools
 import re
 
 import numpy as np
@@ -13,14 +13,10 @@ import fleet_env_ref as F
 import nav_env_ref as R
 import nav_expert_ref as E
 import ped_avoid_ref as P
+from arena_abi import caller, common_refusals, header_declares, refused
+from arena_harness import bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_nav_env_step_model", "ddrl_op_fleet_env_step_model")
-INVALID = -1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -178,16 +174,8 @@ def test_expert_reaches_its_goals_under_avoid():
 # ---- 5. header, binding, argument checks ------------------------------------------------------------------------------------------------
 def test_header_declares_what_the_binding_binds():
     from ddrl4nav_amd import _lib, ops
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [19, 20]
-    assert re.search(r"#define\s+DDRL_ABI_VERSION\s+3\b", text) and _lib.ABI_VERSION == 3       # additive
+    text, _ = header_declares(NEW, [19, 20])                                # additive: the ABI version stays 3
     assert re.search(r"#define\s+DDRL_PED_WALK\s+0\b", text) and re.search(r"#define\s+DDRL_PED_AVOID\s+1\b", text)
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW) and lib.ddrl_abi_version() == 3
     assert callable(ops.nav_env_step_model) and callable(ops.fleet_env_step_model)
     assert ops.NAV_PED_MODELS == P.MODELS and [ops.nav_ped_model(m) for m in P.MODELS] == [0, 1] == [ops.nav_ped_model(k) for k in (0, 1)]
     for bad in ("flee", "", 2, -1, None, 1.0, True):
@@ -198,53 +186,24 @@ def test_header_declares_what_the_binding_binds():
                                                  "ddrl_op_fleet_env_step", "ddrl_op_fleet_env_step_final")] == [14, 15, 18, 16, 19]
 
 
-A, M = 0x10000000, 0x1000000
-NAMES = ("st", "la", "ve", "im", "rw", "dn", "info", "act", "fl", "fv", "fi")
-BASE = {k: A + i * M for i, k in enumerate(NAMES)}
-OUTS = ("st", "la", "ve", "im", "rw", "dn", "info", "fl", "fv", "fi")
-
-
-def _refusals(step, size, extra):
-    """What tests/test_truncation_cpu.py asks of the _final entries, through the new ones, then what is new."""
-    bad = [{k: None} for k in NAMES if k not in ("info", "fl", "fv", "fi")] + extra
-    bad += [dict(nobs=-1), dict(nobs=11), dict(nped=-1), dict(nped=6), dict(ms=0), dict(ms=-3), dict(seed=1, e0=-1), dict(e0=2 ** 32)]
-    bad += [dict(st=BASE["st"] + 8), dict(la=BASE["la"] + 4), dict(im=BASE["im"] + 12), dict(ve=BASE["ve"] + 1), dict(act=BASE["act"] + 2),
-            dict(rw=BASE["rw"] + 1), dict(info=BASE["info"] + 2), dict(fl=BASE["fl"] + 4), dict(fi=BASE["fi"] + 8), dict(fv=BASE["fv"] + 2)]
-    for p in OUTS:                                                      # overlaps: every output on every other output's first byte
-        bad += [{q: BASE[p]} for q in OUTS if q != p]
-    bad += [{"act": BASE[p]} for p in OUTS] + [{"act": BASE[p] + size[p] - 4} for p in OUTS if size[p] > 4]
-    # the pedestrian model, the terminal triple in part, the terminal triple without info
-    bad += [dict(pm=2), dict(pm=-1), dict(pm=256), dict(pm=2 ** 31 - 1)]
-    bad += [dict(fl=None), dict(fv=None), dict(fi=None), dict(fl=None, fv=None), dict(fl=None, fi=None), dict(fv=None, fi=None)]
-    bad += [dict(info=None)]
-    for pm in (0, 1):
-        for kw in bad:
-            assert step(**dict(dict(pm=pm), **kw)) == INVALID, (pm, kw)
-        # and with fewer outputs: info alone, nothing
-        for kw in (dict(pm=2), dict(nped=6), dict(st=None), dict(rw=BASE["im"])):
-            assert step(**dict(dict(pm=pm, fl=None, fv=None, fi=None), **kw)) == INVALID, (pm, kw)
-            assert step(**dict(dict(pm=pm, fl=None, fv=None, fi=None, info=None), **kw)) == INVALID, (pm, kw)
+FINAL = ("fl", "fv", "fi")
 
 
 def test_argument_checks_come_before_hip():
-    """Plain integers stand in for device addresses: every refusal is decided before the first HIP call."""
+    """Plain integers stand in for device addresses: every refusal is decided before the first HIP call.  What tests/
+    test_truncation_cpu.py asks of the _final entries (arena_abi.common_refusals), through the new ones, then what is new: the pedestrian
+    model, the terminal triple in part, the terminal triple without info; and all of it with fewer outputs."""
     from ddrl4nav_amd import _lib
     lib = _lib.load()
-    b = BASE
-
-    def nav(st=b["st"], n=8, e0=0, seed=1, nobs=10, nped=5, ms=500, pm=1, act=b["act"], la=b["la"], ve=b["ve"], im=b["im"], rw=b["rw"],
-            dn=b["dn"], info=b["info"], fl=b["fl"], fv=b["fv"], fi=b["fi"]):
-        return lib.ddrl_op_nav_env_step_model(st, n, e0, seed, nobs, nped, ms, pm, act, la, ve, im, rw, dn, info, fl, fv, fi, None)
-
-    size = dict(st=8 * 256, la=8 * 3840, ve=8 * 20, im=8 * 27648, rw=32, dn=8, info=32, act=64, fl=8 * 3840, fv=8 * 20, fi=8 * 27648)
-    _refusals(nav, size, [dict(n=0), dict(n=-2), dict(e0=2 ** 32 - 3)])
-
-    def fleet(st=b["st"], nw=4, nr=2, e0=0, seed=1, nobs=10, nped=5, ms=500, pm=1, act=b["act"], la=b["la"], ve=b["ve"], im=b["im"],
-              rw=b["rw"], dn=b["dn"], info=b["info"], fl=b["fl"], fv=b["fv"], fi=b["fi"]):
-        return lib.ddrl_op_fleet_env_step_model(st, nw, nr, e0, seed, nobs, nped, ms, pm, act, la, ve, im, rw, dn, info, fl, fv, fi, None)
-
-    size["st"] = 4 * 384
-    _refusals(fleet, size, [dict(nw=0), dict(nw=-1), dict(nr=0), dict(nr=5), dict(nw=2 ** 30, nr=2), dict(e0=2 ** 32 - 3)])
+    partial = [dict.fromkeys(part) for k in (1, 2) for part in itertools.combinations(FINAL, k)] + [dict(info=None)]
+    for name, shapes in (("ddrl_op_nav_env_step_model", [dict(n=0), dict(n=-2)]),
+                         ("ddrl_op_fleet_env_step_model", [dict(nw=0), dict(nw=-1), dict(nr=0), dict(nr=5), dict(nw=2 ** 30, nr=2)])):
+        step = caller(lib, name)
+        own = shapes + [dict(pm=2), dict(pm=-1), dict(pm=256), dict(pm=2 ** 31 - 1)]
+        for pm in (0, 1):
+            refused(step, common_refusals(name) + own + partial, pm=pm)
+            refused(step, common_refusals(name, without=FINAL) + own, pm=pm, **dict.fromkeys(FINAL))           # info alone
+            refused(step, common_refusals(name, without=("info",) + FINAL) + own, pm=pm, **dict.fromkeys(("info",) + FINAL))    # none
 
 
 def test_ops_wrappers_refuse_host_tensors_and_bad_models():

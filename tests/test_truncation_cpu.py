@@ -3,9 +3,6 @@ against the oracle scan and against an analytic case in float64, the fleet's ter
 robot per world, the header against the binding table, every argument check of the four new entry points (decided before HIP), and
 truncations_per_rollout.  No GPU."""
 import ctypes
-import itertools
-import os
-import re
 import types
 
 import numpy as np
@@ -13,15 +10,11 @@ import pytest
 
 import fleet_env_ref as F
 import truncation_ref as TR
+from arena_abi import A, INVALID, M, caller, common_refusals, header_declares, refused
+from arena_harness import bits
 from oracle import ddrl_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ddrl_op_nav_env_step_final", "ddrl_op_fleet_env_step_final", "ddrl_op_file_flagged_rows", "ddrl_gae_bootstrap")
-INVALID = -1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 # ---- 1. GAE with the select -------------------------------------------------------------------------------------------------------------------
@@ -109,67 +102,20 @@ def test_one_robot_per_world_has_the_nav_terminal_observation():
 
 # ---- 3. header, binding, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_header_declares_what_the_binding_binds():
-    from ddrl4nav_amd import _lib, ops
-    text = open(os.path.join(ROOT, "include", "ddrl.h")).read()
-    for name in NEW:
-        m = re.search(r"int32_t\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == m.group(1).count(",") + 1, name
-    assert [len(_lib.SIGNATURES[n][1]) for n in NEW] == [18, 19, 11, 13]
-    lib = _lib.load()
-    assert all(hasattr(lib, name) for name in NEW) and lib.ddrl_abi_version() == 3
+    from ddrl4nav_amd import ops
+    header_declares(NEW, [18, 19, 11, 13])
     assert all(hasattr(ops, k) for k in ("nav_env_step_final", "fleet_env_step_final", "file_flagged_rows", "gae_bootstrap"))
     assert ops.NAV_INFO_TRUNCATED == TR.TRUNC_BIT == 16
 
 
-def _overlaps(base, size, align, names):
-    """For each ordered pair (p, q) of `names`: q moved onto p's first byte, and onto p's last aligned unit."""
-    out = []
-    for p, q in itertools.permutations(names, 2):
-        out.append({q: base[p]})
-        if size[p] > align[q] and size[p] % align[q] == 0:
-            out.append({q: base[p] + size[p] - align[q]})
-    return out
-
-
-A, M = 0x10000000, 0x1000000
-NAMES = ("st", "la", "ve", "im", "rw", "dn", "info", "act", "fl", "fv", "fi")
-BASE = {k: A + i * M for i, k in enumerate(NAMES)}
-ALIGN = dict(st=16, la=16, ve=4, im=16, rw=4, dn=1, info=4, act=4, fl=16, fv=4, fi=16)
-OUTS = ("st", "la", "ve", "im", "rw", "dn", "info", "fl", "fv", "fi")
-
-
-def _env_refusals(step, size, extra):
-    bad = [{k: None} for k in NAMES] + extra
-    bad += [dict(nobs=-1), dict(nobs=11), dict(nped=-1), dict(nped=6), dict(ms=0), dict(ms=-3), dict(seed=1, e0=-1), dict(e0=2 ** 32)]
-    bad += [dict(st=BASE["st"] + 8), dict(la=BASE["la"] + 4), dict(im=BASE["im"] + 12), dict(ve=BASE["ve"] + 1), dict(act=BASE["act"] + 2),
-            dict(rw=BASE["rw"] + 1), dict(info=BASE["info"] + 2), dict(fl=BASE["fl"] + 4), dict(fl=BASE["fl"] + 8), dict(fi=BASE["fi"] + 1),
-            dict(fi=BASE["fi"] + 8), dict(fv=BASE["fv"] + 2)]
-    bad += _overlaps(BASE, size, ALIGN, OUTS)                           # every pair of outputs, the terminal buffers among them
-    bad += [{"act": BASE[p]} for p in OUTS] + [{"act": BASE[p] + size[p] - 4} for p in OUTS if size[p] > 4]
-    for kw in bad:
-        assert step(**kw) == INVALID, kw
-
-
 def test_env_argument_checks_come_before_hip():
-    """Plain integers stand in for device addresses: every refusal is decided before the first HIP call."""
+    """Plain integers stand in for device addresses: every refusal is decided before the first HIP call.  arena_abi.common_refusals
+    with the terminal buffers among the outputs, then each entry's own shapes."""
     from ddrl4nav_amd import _lib
     lib = _lib.load()
-    b = BASE
-
-    def nav(st=b["st"], n=8, e0=0, seed=1, nobs=10, nped=5, ms=500, act=b["act"], la=b["la"], ve=b["ve"], im=b["im"], rw=b["rw"],
-            dn=b["dn"], info=b["info"], fl=b["fl"], fv=b["fv"], fi=b["fi"]):
-        return lib.ddrl_op_nav_env_step_final(st, n, e0, seed, nobs, nped, ms, act, la, ve, im, rw, dn, info, fl, fv, fi, None)
-
-    size = dict(st=8 * 256, la=8 * 3840, ve=8 * 20, im=8 * 27648, rw=32, dn=8, info=32, act=64, fl=8 * 3840, fv=8 * 20, fi=8 * 27648)
-    _env_refusals(nav, size, [dict(n=0), dict(n=-2), dict(e0=2 ** 32 - 3)])
-
-    def fleet(st=b["st"], nw=4, nr=2, e0=0, seed=1, nobs=10, nped=5, ms=500, act=b["act"], la=b["la"], ve=b["ve"], im=b["im"], rw=b["rw"],
-              dn=b["dn"], info=b["info"], fl=b["fl"], fv=b["fv"], fi=b["fi"]):
-        return lib.ddrl_op_fleet_env_step_final(st, nw, nr, e0, seed, nobs, nped, ms, act, la, ve, im, rw, dn, info, fl, fv, fi, None)
-
-    size["st"] = 4 * 384
-    _env_refusals(fleet, size, [dict(nw=0), dict(nw=-1), dict(nr=0), dict(nr=5), dict(nw=2 ** 30, nr=2), dict(e0=2 ** 32 - 3)])
+    refused(caller(lib, "ddrl_op_nav_env_step_final"), common_refusals("ddrl_op_nav_env_step_final") + [dict(n=0), dict(n=-2)])
+    fleet = caller(lib, "ddrl_op_fleet_env_step_final")
+    refused(fleet, common_refusals("ddrl_op_fleet_env_step_final") + [dict(nw=0), dict(nw=-1), dict(nr=0), dict(nr=5), dict(nw=2 ** 30, nr=2)])
     # the plain entry point still takes a null info; the terminal render does not
     assert fleet(info=None) == INVALID
 

@@ -4,7 +4,6 @@ pools (csrc/truncate.hip), GAE with the select (csrc/optim.hip) and the closed l
 StateRollout(bootstrap_truncated=S) through collect_states().  Everything is compared bit for bit; every tape asserts its own event
 counts.  Run with `-m gpu`."""
 import functools
-import types
 
 import numpy as np
 import pytest
@@ -13,118 +12,48 @@ import torch
 import fleet_env_ref as F
 import nav_env_ref as R
 import truncation_ref as TR
+from arena_harness import FILL, SHAPES, assert_tape_equals, dev, filled, filled_like, host, is_fill, make_net, play_ops, record, same
 from oracle import ddrl_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x7FC12345                                                   # a NaN no kernel produces
-SHAPES = [(1, 960), (5,), (3, 48, 48)]
 TRUNC = TR.TRUNC_BIT
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(a):
-    """float32 array -> its words: equality below is bitwise."""
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def sentinels(*lead):
-    """Three fp32 buffers [*lead, ...shape] filled with the sentinel."""
-    return [torch.full(tuple(lead) + s, SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32) for s in SHAPES]
-
-
-def is_sentinel(a):
-    return bool((bits(a) == SENTINEL).all())
+def check_tape(final_entry, plain_entry, want, **call):
+    """The rule book's tape through the entry that renders the terminal observations and through the one that does not
+    (arena_harness.play_ops): state, observation, reward, done and info are bit-identical between the two and the model's, the truncation
+    bit is set in the model's rows, those rows of final_obs are the model's and no other row is written at all.  -> the tape."""
+    got, plain = play_ops(final_entry, want["actions"], **call), play_ops(plain_entry, want["actions"], **call)
+    assert_tape_equals(got, dict(plain, final=None))
+    assert all(is_fill(f) for f in plain["final"])
+    assert np.array_equal((got["info"] & TRUNC) != 0, want["trunc"])
+    assert_tape_equals(got, want)
+    return got
 
 
 # ---- 1. the navigation env ----------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def nav_reference(name):
-    """(model kwargs, actions [steps][N][2], truncated [steps][N], the model's terminal observations [steps][N][...] x 3 (rows that are
-    not truncated hold whatever the snapshot held), event counts) of a tape; never modified."""
+    """(model kwargs, the tape of NavEnvFinalRef with its terminal observations, event counts) of a tape; never modified."""
     coverage = name == "coverage"
     kw = dict(R.COVERAGE) if coverage else dict(n_envs=5, seed=3, max_steps=3)
-    steps, n = (R.COVERAGE_STEPS, kw["n_envs"]) if coverage else (12, 5)
-    model = TR.NavEnvFinalRef(**kw)
-    trunc = np.zeros((steps, n), bool)
-    final = [np.zeros((steps, n) + s, np.float32) for s in SHAPES]
-    counts = dict(trunc=0, collision=0, goal=0, done=0)
-    played, plain_step = [], model.step
-
-    def step(a):                                                        # the model's step, with what it did written down
-        t = len(played)
-        out = plain_step(a)
-        ev = model.events
-        trunc[t] = model.truncated
-        counts["trunc"] += int(ev["trunc"].sum())
-        counts["goal"] += int(ev["goal"].sum())
-        counts["collision"] += int(((ev["wall_hit"] + ev["obstacle_hit"] + ev["ped_hit"]) > 0).sum())
-        counts["done"] += int(out[2].sum())
-        if trunc[t].any():
-            for f, m in zip(final, model.final):
-                f[t] = m
-        played.append(np.array(a, np.float32))
-        return out
-
-    model.step = step
     if coverage:                                                        # nav_env_ref.coverage_run, on the model that keeps the snapshots
-        R.play(model, steps, np.random.RandomState(0))
+        want = record(TR.NavEnvFinalRef(**kw), R.COVERAGE_STEPS, np.random.RandomState(0))
     else:
-        model.reset()
-        for _ in range(steps):
-            model.step(np.zeros((n, 2), np.float32))
-    actions = np.stack(played)
-    return kw, actions, trunc, final, counts
-
-
-def play_nav(kw, actions, with_final):
-    """The tape through ddrl_op_nav_env_step_final (or _step_info), every step into its own row of larger buffers; one read-back."""
-    from ddrl4nav_amd import ops
-    steps, n = actions.shape[:2]
-    env_kw = dict(env0=kw.get("env0", 0), seed=kw["seed"], n_obstacles=kw.get("n_obstacles", 10), n_peds=kw.get("n_peds", 5))
-    state = torch.zeros((n, 64), dtype=torch.int32, device="cuda")
-    states = torch.zeros((steps, n, 64), dtype=torch.int32, device="cuda")
-    obs, final = sentinels(steps + 1, n), sentinels(steps, n)
-    reward = torch.zeros((steps, n), dtype=torch.float32, device="cuda")
-    done = torch.zeros((steps, n), dtype=torch.uint8, device="cuda")
-    info = torch.zeros((steps, n), dtype=torch.int32, device="cuda")
-    acts = dev(actions)
-    ops.nav_env_reset(state, [o[0] for o in obs], **env_kw)
-    for t in range(steps):
-        out = [o[t + 1] for o in obs]
-        if with_final:
-            ops.nav_env_step_final(state, acts[t], out, reward[t], done[t], info[t], [f[t] for f in final], max_steps=kw["max_steps"], **env_kw)
-        else:
-            ops.nav_env_step_info(state, acts[t], out, reward[t], done[t], info[t], max_steps=kw["max_steps"], **env_kw)
-        states[t].copy_(state)
-    torch.cuda.synchronize()
-    return host(states), [host(o) for o in obs], host(reward), host(done), host(info), [host(f) for f in final]
+        want = record(TR.NavEnvFinalRef(**kw), 12, actions=np.zeros((12, 5, 2), np.float32))
+    ev = want["events"]
+    counts = dict(trunc=int(ev["trunc"].sum()), goal=int(ev["goal"].sum()), done=int(want["done"].sum()),
+                  collision=int(((ev["wall_hit"] + ev["obstacle_hit"] + ev["ped_hit"]) > 0).sum()))
+    return kw, want, counts
 
 
 def check_nav_tape(name):
-    kw, actions, trunc, want_final, counts = nav_reference(name)
-    plain = play_nav(kw, actions, False)
-    got = play_nav(kw, actions, True)
-    # state, observation, reward, done and info: bit-identical to ddrl_op_nav_env_step_info
-    assert np.array_equal(got[0], plain[0]) and all(same(a, b) for a, b in zip(got[1], plain[1]))
-    assert same(got[2], plain[2]) and np.array_equal(got[3], plain[3]) and np.array_equal(got[4], plain[4])
-    assert is_sentinel(np.concatenate([f.reshape(-1) for f in plain[5]]))
-    assert np.array_equal((got[4] & TRUNC) != 0, trunc) and int(got[3].sum()) == counts["done"]
-    for g, w in zip(got[5], want_final):
-        assert same(g[trunc], w[trunc]), np.nonzero(bits(g[trunc]) != bits(w[trunc]))
-        assert is_sentinel(g[~trunc])                                   # rows without bit 4 are not written at all
-    return counts, got, trunc
+    kw, want, counts = nav_reference(name)
+    call = dict(env0=kw.get("env0", 0), seed=kw["seed"], n_obstacles=kw.get("n_obstacles", 10), n_peds=kw.get("n_peds", 5))
+    got = check_tape("nav_env_step_final", "nav_env_step_info", want, max_steps=kw["max_steps"], **call)
+    assert int(got["done"].sum()) == counts["done"]
+    return counts, got, want["trunc"]
 
 
 def test_nav_coverage_tape_renders_the_terminal_observations():
@@ -132,8 +61,7 @@ def test_nav_coverage_tape_renders_the_terminal_observations():
     counts, got, trunc = check_nav_tape("coverage")
     assert counts == dict(trunc=4, collision=20, goal=10, done=34), counts
     # a terminal observation is not the next episode's first one: the vector holds the action just played
-    nxt = [o[1:] for o in got[1]]
-    assert not same(got[5][1][trunc], nxt[1][trunc])
+    assert not same(got["final"][1][trunc], got["vector"][trunc])
 
 
 def test_nav_truncation_only_tape():
@@ -147,18 +75,20 @@ def test_device_nav_env_owns_its_terminal_observations():
     """DeviceNavEnv(emit_final_obs=True): implies emit_info, owns final_obs, renders elsewhere through final_out; make_device_env reads
     env_final_obs; an env without the option refuses final_out."""
     from ddrl4nav_amd.env import DeviceNavEnv, make_device_env
-    kw, actions, trunc, want_final, _ = nav_reference("truncation_only")
+    _, want, _ = nav_reference("truncation_only")
+    actions, told = want["actions"], {t: fin for t, _, fin in want["final"]}
+    assert want["trunc"][2].all() and want["trunc"][5].all()            # told[2] and told[5] hold every row
     env = make_device_env({"env_name": "DeviceNav-v0", "env_num": 5, "env_seed": 3, "env_max_steps": 3, "env_final_obs": True})
     assert isinstance(env, DeviceNavEnv) and env.emit_final_obs and env.emit_info and env.info is not None
     assert [tuple(f.shape) for f in env.final_obs] == [(5,) + s for s in SHAPES] and env.truncations_per_rollout(7) == 3
     env.reset()
-    elsewhere = sentinels(5)
+    elsewhere = filled(5)
     for t in range(6):
         env.step(dev(actions[t]), final_out=elsewhere if t >= 3 else None)
         if t == 2:
-            assert all(same(host(f), w[2]) for f, w in zip(env.final_obs, want_final)) and trunc[2].all()
-    assert all(same(host(f), w[5]) for f, w in zip(elsewhere, want_final)) and trunc[5].all()
-    assert all(same(host(f), w[2]) for f, w in zip(env.final_obs, want_final))      # untouched since step 2
+            assert all(same(host(f), w) for f, w in zip(env.final_obs, told[2]))
+    assert all(same(host(f), w) for f, w in zip(elsewhere, told[5]))
+    assert all(same(host(f), w) for f, w in zip(env.final_obs, told[2]))            # untouched since step 2
     plain = DeviceNavEnv(5, device="cuda", seed=3, max_steps=3)
     assert plain.final_obs is None and not plain.emit_info
     with pytest.raises(ValueError, match="emit_final_obs"):
@@ -167,117 +97,66 @@ def test_device_nav_env_owns_its_terminal_observations():
 
 # ---- 2. the fleet -------------------------------------------------------------------------------------------------------------------------------------
 FLEET_KW = dict(n_worlds=3, seed=5, n_obstacles=10, n_peds=5, max_steps=9)
+FLEET_CALL = dict(world0=0, seed=5, n_obstacles=10, n_peds=5, max_steps=9)     # the same, as the ops wrappers take it
 FLEET_STEPS = 120
 
 
 @functools.lru_cache(maxsize=None)
 def fleet_reference(nr):
-    """(actions, truncated [steps][rows], terminal observations, world-steps where some but not all robots truncate, truncations)."""
-    model = F.FleetEnvRef(n_robots=nr, **FLEET_KW)
-    model.reset()
-    rows, rng = model.N, np.random.RandomState(1)
-    actions = np.zeros((FLEET_STEPS, rows, 2), np.float32)
-    trunc = np.zeros((FLEET_STEPS, rows), bool)
-    final = [np.zeros((FLEET_STEPS, rows) + s, np.float32) for s in SHAPES]
-    mixed = 0
-    for t in range(FLEET_STEPS):
-        actions[t] = rng.uniform([0.3, -1.0], [1.0, 1.0], (rows, 2)).astype(np.float32)
-        model.step(actions[t])
-        obs, trunc[t] = TR.fleet_final_obs(model)
-        assert np.array_equal(trunc[t], (model.info & TRUNC) != 0)
-        per_world = trunc[t].reshape(-1, nr)
-        mixed += int((per_world.any(axis=1) & ~per_world.all(axis=1)).sum())
-        for f, o in zip(final, obs):
-            f[t] = o
-    return actions, trunc, final, mixed, int(trunc.sum())
-
-
-def play_fleet(nr, kw, actions, with_final, start=None):
-    from ddrl4nav_amd import ops
-    steps, rows = actions.shape[:2]
-    env_kw = dict(world0=0, seed=kw["seed"], n_obstacles=kw["n_obstacles"], n_peds=kw["n_peds"])
-    state = torch.zeros((kw["n_worlds"], 96), dtype=torch.int32, device="cuda")
-    states = torch.zeros((steps,) + tuple(state.shape), dtype=torch.int32, device="cuda")
-    obs, final = sentinels(steps + 1, rows), sentinels(steps, rows)
-    reward = torch.zeros((steps, rows), dtype=torch.float32, device="cuda")
-    done = torch.zeros((steps, rows), dtype=torch.uint8, device="cuda")
-    info = torch.zeros((steps, rows), dtype=torch.int32, device="cuda")
-    acts = dev(actions)
-    if start is None:
-        ops.fleet_env_reset(state, nr, [o[0] for o in obs], **env_kw)
-    else:
-        state.copy_(dev(start))
-    for t in range(steps):
-        out = [o[t + 1] for o in obs]
-        if with_final:
-            ops.fleet_env_step_final(state, nr, acts[t], out, reward[t], done[t], info[t], [f[t] for f in final],
-                                     max_steps=kw["max_steps"], **env_kw)
-        else:
-            ops.fleet_env_step(state, nr, acts[t], out, reward[t], done[t], info=info[t], max_steps=kw["max_steps"], **env_kw)
-        states[t].copy_(state)
-    torch.cuda.synchronize()
-    return host(states), [host(o)[1:] for o in obs], host(reward), host(done), host(info), [host(f) for f in final]
-
-
-def check_fleet(got, plain, trunc, want_final):
-    assert np.array_equal(got[0], plain[0]) and all(same(a, b) for a, b in zip(got[1], plain[1]))
-    assert same(got[2], plain[2]) and np.array_equal(got[3], plain[3]) and np.array_equal(got[4], plain[4])
-    assert np.array_equal((got[4] & TRUNC) != 0, trunc)
-    for g, w in zip(got[5], want_final):
-        assert same(g[trunc], w[trunc]), np.nonzero(bits(g[trunc]) != bits(w[trunc]))
-        assert is_sentinel(g[~trunc])
+    """(the rule book's tape, world-steps where some but not all robots truncate, truncations); never modified."""
+    rng = np.random.RandomState(1)
+    actions = np.stack([rng.uniform([0.3, -1.0], [1.0, 1.0], (3 * nr, 2)).astype(np.float32) for _ in range(FLEET_STEPS)])
+    want = record(F.FleetEnvRef(n_robots=nr, **FLEET_KW), FLEET_STEPS, actions=actions)
+    assert np.array_equal(want["trunc"], (want["info"] & TRUNC) != 0)
+    per_world = want["trunc"].reshape(FLEET_STEPS, 3, nr)
+    return want, int((per_world.any(axis=2) & ~per_world.all(axis=2)).sum()), int(want["trunc"].sum())
 
 
 @pytest.mark.parametrize("nr", [1, 2, 4])
 def test_fleet_renders_the_terminal_observations(nr):
     """3 worlds x R robots, 120 steps, max_steps = 9: the terminal rows equal observe() of `played` (every robot after all moves, before
     any respawn), also where only some robots of a world truncate; nothing else is written; the other outputs are ddrl_op_fleet_env_step's."""
-    actions, trunc, want_final, mixed, total = fleet_reference(nr)
+    want, mixed, total = fleet_reference(nr)
     assert (mixed, total) == {1: (0, 39), 2: (19, 77), 4: (3, 155)}[nr], (mixed, total)
-    got, plain = play_fleet(nr, FLEET_KW, actions, True), play_fleet(nr, FLEET_KW, actions, False)
-    check_fleet(got, plain, trunc, want_final)
+    check_tape("fleet_env_step_final", "fleet_env_step", want, n_robots=nr, **FLEET_CALL)
 
 
 def test_fleet_truncation_beside_a_collision():
     """A hand-set state, 3 worlds x 2 robots: robot 0 is one step short of max_steps and stands still, robot 1 drives into the wall in
     the same step.  Row 0 of each world is rendered from `played` -- robot 1 still at the wall, not at its respawn -- and row 1 is not
     written."""
-    kw = dict(FLEET_KW, max_steps=9)
-    model = F.FleetEnvRef(n_robots=2, **kw)
+    model = F.FleetEnvRef(n_robots=2, **FLEET_KW)
     model.reset()
-    model.state[:, F.STEPS] = kw["max_steps"] - 1
+    model.state[:, F.STEPS] = FLEET_KW["max_steps"] - 1
     model.state[:, 10 + F.X], model.state[:, 10 + F.Y], model.state[:, 10 + F.H] = R.ARENA_R - R.ROBOT_R - 10, 0, 0
     start = model.state.copy()
     model.sanitize()
     assert np.array_equal(model.state, start)
     actions = np.tile(np.array([[0.0, 0.0], [1.0, 0.0]], np.float32), (3, 1))[None]
-    model.step(actions[0])
-    want, trunc = TR.fleet_final_obs(model)
+    want = record(model, 1, first_state=start, actions=actions)
     info = model.info.reshape(3, 2)
     assert (info[:, 0] & TRUNC).all() and not (info[:, 1] & TRUNC).any() and ((info[:, 1] >> 2) & 3 == 1).all() and (info[:, 1] & 64).all()
-    assert np.array_equal(trunc, np.tile([True, False], 3))
+    assert np.array_equal(want["trunc"][0], np.tile([True, False], 3))
     assert (model.played[:, 10 + F.X] > R.ARENA_R - R.ROBOT_R).all() and (np.abs(model.state[:, 10 + F.X]) <= 2 * R.CELL).all()
-    got = play_fleet(2, kw, actions, True, start=start)
-    plain = play_fleet(2, kw, actions, False, start=start)
-    check_fleet(got, plain, trunc[None], [w[None] for w in want])
-    assert np.array_equal(got[0][0], model.state)
+    check_tape("fleet_env_step_final", "fleet_env_step", want, n_robots=2, start=start, **FLEET_CALL)
 
 
 def test_fleet_nav_env_owns_its_terminal_observations():
     from ddrl4nav_amd.env import FleetNavEnv, make_device_env
-    actions, trunc, want_final, _, _ = fleet_reference(2)
+    want, _, _ = fleet_reference(2)
+    actions, trunc, told = want["actions"], want["trunc"], {t: fin for t, _, fin in want["final"]}
     env = make_device_env({"env_name": "DeviceNavFleet-v0", "env_num": 3, "agent_num_per_env": 2, "env_seed": 5, "env_max_steps": 9,
                            "env_final_obs": True})
     assert isinstance(env, FleetNavEnv) and env.emit_final_obs and env.emit_info and env.truncations_per_rollout(20) == 3
     for f in env.final_obs:
-        f.view(torch.int32).fill_(SENTINEL)
+        f.view(torch.int32).fill_(FILL)
     env.reset()
     seen = np.zeros(6, bool)
     for t in range(20):
         env.step(dev(actions[t]))
         got = [host(f) for f in env.final_obs]
         seen |= trunc[t]
-        assert all(same(g[trunc[t]], w[t][trunc[t]]) for g, w in zip(got, want_final)) and all(is_sentinel(g[~seen]) for g in got)
+        assert all(is_fill(g[~seen]) for g in got) and (t not in told or all(same(g[trunc[t]], w) for g, w in zip(got, told[t])))
     assert seen.sum() >= 4
     with pytest.raises(ValueError, match="emit_final_obs"):
         FleetNavEnv(3, 2, device="cuda").step(dev(actions[0]), final_out=env.final_obs)
@@ -300,7 +179,7 @@ def test_file_flagged_rows(n, flags):
     count = ((np.arange(n) // 2) % 4).astype(np.int32)                  # 0, 0, 1, 1, 2, 2, 3, 3: every count meets both flags
     srcs = [rng.normal(size=(n,) + s).astype(np.float32) for s in SHAPES]
     assert [s[0].size for s in srcs] == list(WIDTHS)
-    pools = sentinels(S, n)
+    pools = filled(S, n)
     want_pools, want_count = [host(p).copy() for p in pools], count.copy()
     want_slot = TR.file_rows_ref(info, srcs, want_pools, want_count)
     got_count, got_slot = dev(count), torch.full((n,), 77, dtype=torch.int32, device="cuda")
@@ -316,7 +195,7 @@ def test_file_flagged_rows(n, flags):
     # a part on bases that are not 16-byte aligned moves in 4-byte units and files the same rows
     flat = torch.zeros(n * 960 + 4, dtype=torch.float32, device="cuda")
     src = flat[1:1 + n * 960].view(n, 1, 960).copy_(dev(srcs[0]))
-    pool = sentinels(S, n)[0]
+    pool = filled(S, n)[0]
     ops.file_flagged_rows(dev(info), [(src, pool)], dev(count), got_slot)
     assert src.data_ptr() % 16 == 4 and same(host(pool), want_pools[0]) and np.array_equal(host(got_slot), want_slot)
 
@@ -336,13 +215,9 @@ def gae_case(T, N, S, seed):
 def gae_on_device(values, rewards, dones, slots, boot, gamma=0.99, landa=0.95):
     from ddrl4nav_amd import ops
     T, N = rewards.shape
-    adv, ret = sentinels_like(T, N), sentinels_like(T, N)
+    adv, ret = filled_like(T, N), filled_like(T, N)
     ops.gae_bootstrap(dev(values), dev(rewards), dev(dones), dev(slots), dev(boot), gamma, landa, adv, ret)
     return host(adv), host(ret)
-
-
-def sentinels_like(*shape):
-    return torch.full(shape, SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32)
 
 
 @pytest.mark.parametrize("N", [1, 64, 65])
@@ -380,24 +255,6 @@ def test_gae_bootstrap_equals_the_fp32_model(T, N):
 N_ENVS, T, MAX_STEPS = 6, 7, 3
 
 
-def make_net(seed=13):
-    """BASELINE config 4's net (NavPreNet1D x2 + GaussionActor(2)) through create_net, hashed weights loaded."""
-    from ddrl4nav_amd.config import BaseConfig, ConfigNN
-    from ddrl4nav_amd.runner import create_net
-    from ddrl4nav_amd.utils.recipe import hash_weights
-    env = {"discrete_action": False, "act_dim": 2, "image_batch": 1, "ped_sim": {"total": 3}}
-    cfg = BaseConfig(types.SimpleNamespace(task="test", ip="127.0.0.1"),
-                     dict({"env_type": "gym", "env_name": "PongNoFrameskip-v4", "env_num": 8}, **env))
-    cfg.TASK_TYPE = "robot_nav"
-    cfg_nn = ConfigNN(env)
-    cfg_nn.SHARE_CNN_NET = False
-    torch.manual_seed(seed)
-    net = create_net({"config": cfg, "config_nn": cfg_nn, "config_env": env}, max_batch=N_ENVS * T)
-    w = hash_weights([(k, tuple(p.shape)) for k, p in net.named_parameters()], seed)
-    net.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return net
-
-
 def make_pair(fleet):
     """(device env with emit_final_obs, host model with the same rules)."""
     from ddrl4nav_amd.env import DeviceNavEnv, FleetNavEnv
@@ -423,7 +280,7 @@ def run_closed_loop(S, fleet=False, normalize=False):
     from ddrl4nav_amd import ops
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.runner.device_loop import collect_states
-    net = make_net()
+    net = make_net(N_ENVS * T)
     env, model = make_pair(fleet)
     assert env.N == N_ENVS and env.truncations_per_rollout(T) == 3
     ro = StateRollout(net, env.N, SHAPES, horizon=T, bootstrap_truncated=S, normalize_obs=normalize or None, normalize_returns=normalize,
@@ -502,7 +359,7 @@ def test_the_loop_refuses_what_is_not_built():
     from ddrl4nav_amd.agent import StateRollout
     from ddrl4nav_amd.env import DeviceNavEnv
     from ddrl4nav_amd.runner.device_loop import collect_states
-    net = make_net()
+    net = make_net(N_ENVS * T)
     env = DeviceNavEnv(N_ENVS, device="cuda", max_steps=MAX_STEPS, emit_final_obs=True)
     ro = StateRollout(net, N_ENVS, SHAPES, horizon=T, bootstrap_truncated=2)
     with pytest.raises(ValueError, match="emit_final_obs"):
